@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — drone-steps/s of the fused Env.step()+INDI kernel on synthetic fleets.
 
-    python bench.py --gpus N --steps K --warmup W [--workload NAME]
+    python bench.py --gpus N --steps K --warmup W [--workload NAME] [--dump-outputs DIR]
 
 N > 1: when the process was not started by a launcher (WORLD_SIZE unset) bench.py starts N ranks itself —
 ``python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 bench.py ...`` as a CHILD
@@ -25,8 +25,8 @@ Workloads:
                           config's density (524 288 drones in 1024 m x 512 m = one per m^2: every rank owns a
                           128 m x 512 m slab), halo exchange of positions between neighbouring slabs
   hexa, mixed             4 194 304 hexa_6DOF / interleaved quad+hexa drones (roofline-size variants)
-The N = 1 line also carries the literal BASELINE configs 1-3 at their own sizes ("baseline_configs") and further
-variants ("also").
+The N = 1 run also measures the literal BASELINE configs 1-3 at their own sizes ("baseline_configs") and further
+variants ("also"); they go to bench_extras.json beside this file, and the line names it ("extras_file").
 """
 import argparse
 import gc
@@ -54,8 +54,13 @@ BYTES_PER_DRONE_STEP = 232      # read 13+11+10 floats, write 13+1
 # per SIMD, 1 024 SIMDs: 2.26e12 pair evaluations per second if the vector pipes did nothing else.
 VALU_PAIR_PEAK = 256 * 4 * 2.4e9 * 64 / (18 * 2.82 + 2 * 9.4)
 WATCHDOG_RC = 3                 # exit code of every rank when a collective section hangs (Watchdog)
-MIN_TIMED_S = 0.05              # the timed region is repeated (whole K-step regions) until it covers this much
+MIN_TIMED_S = 0.05              # extra entries: the timed region is repeated (whole k-step regions) until it covers this much
 SETTLE_S = 0.3                  # "also" entries of chip-filling fleets: under load for this long before the timed regions (Fleet.timed)
+DUMP_MAX_DRONES = 1 << 18       # --dump-outputs: at most this many drones (<= 34 MB of float32 for the widest path)
+DUMP_MAX_BYTES = 64 << 20
+# the entries measured beside the headline ("baseline_configs", "also") are written here, not onto the JSON line: with them
+# the line grew past 20 KB, more than a reader of the end of the output keeps
+EXTRAS_FILE = os.path.join(ROOT, "bench_extras.json")
 WORKLOADS = ["config2x1024", "config2", "config3", "config4", "config5", "hexa", "mixed", "mixed_type_major", "two_call_loop", "dyn"]
 
 
@@ -86,6 +91,10 @@ def parse(argv=None):
                         "settle ~0.1 s into a vector-heavy stretch); 0 = exactly --warmup steps, the driver's contract")
     p.add_argument("--dry-run", action="store_true",
                    help="host logic only (launcher, rendezvous, reductions, the JSON line); no device work — CPU tests")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the timed path handed its caller in its last step as DIR/<name>.npy "
+                        "(float32; rank 0; a fixed seeded sample of DUMP_MAX_DRONES drones of larger fleets).  The inputs depend on "
+                        "the arguments alone; with --settle-seconds the number of untimed steps before them depends on the clock")
     return p.parse_args(argv)
 
 
@@ -145,6 +154,7 @@ class Fleet:
         self.n_steps = n_steps
         self.graph = None
         self.loop = None
+        self.loop_out = None
         self.ctrl = None
         xyz = grid_fleet(n_fleet, replicas)
         self.n = xyz.shape[0]
@@ -221,10 +231,15 @@ class Fleet:
         yaw = np.array([0, 0, 0.4])
 
         def one():
-            obs, _, _, _ = self.env.step(state["cmd"])
-            state["cmd"], _, _ = ctrl.computeControlFromState(self.env.TIMESTEP * self.env.AGGR_PHY_STEPS, None, target_pos=tpos,
-                                                               target_rpy=yaw)
+            # the last iteration's outputs are kept for --dump-outputs, and dropped before the next one allocates: the caching
+            # allocator sees the lifetimes of a loop that keeps nothing (where these arrays lie is worth 10-15 %, placement.py)
+            for k in ("obs", "pos_e", "yaw_e"):
+                state.pop(k, None)
+            state["obs"] = self.env.step(state["cmd"])[0]
+            state["cmd"], state["pos_e"], state["yaw_e"] = ctrl.computeControlFromState(
+                self.env.TIMESTEP * self.env.AGGR_PHY_STEPS, None, target_pos=tpos, target_rpy=yaw)
         self.loop = one
+        self.loop_out = state           # what the last iteration handed its caller (--dump-outputs)
 
     def use_graph(self, steps):
         """Replay `steps` fused launches per step() call from one captured hipGraph."""
@@ -241,13 +256,14 @@ class Fleet:
         (tools/clock_probe.py, profiles/r05_clock_*.txt: five sub-steps of 4 194 304 quads 154 us -> up to 238 us -> 169.7 us
         for as long as the load lasts); a region timed right behind a short warm-up measures that episode, not the kernel."""
         torch = self.torch
+        # the collector stays off inside the timed regions (as timeit does): a collection that frees another variant's
+        # graphs or fleet in the middle of a region stalls the host for tens of milliseconds (seen: 3x wall vs device).
+        # It runs in front of the warm-up: behind it, it would leave the device idle for ~60 ms right before the timed steps
+        gc.collect()
         for _ in range(warmup):
             self.step()
         if settle_s > 0.0:
             return self._timed_settled(steps, barrier, min_s, repeat_rule, settle_s)
-        # the collector stays off inside the timed regions (as timeit does): a collection that frees another variant's
-        # graphs or fleet in the middle of a region stalls the host for tens of milliseconds (seen: 3x wall vs device)
-        gc.collect()
         torch.cuda.synchronize()
         gc_was_on = gc.isenabled()
         gc.disable()
@@ -463,6 +479,43 @@ def placement_cost(log):
     return {"placement_s": round(sum(r["seconds"] for r in rows), 3),
             "placement_peak_bytes": max([max(r.get("peak_bytes", 0), r.get("bytes", 0) if "held_bytes" in r else 0) for r in rows] + [0]),
             "placement_held_bytes": sum(r.get("held_bytes", 0) for r in (log or [])), "searches": len(rows)}
+
+
+def dump_outputs(fl, out_dir):
+    """--dump-outputs: what the timed path handed its caller in its last step, rows in the caller's numbering, for every drone
+    of fleets up to DUMP_MAX_DRONES and for a fixed seeded sample (ascending) of larger ones.  The fused step returns
+    nothing: its results are the fleet's state block (rigid state; controller memory, the command among it) and, on
+    Physics.DYN, the model's rpy rates.  The two-call loop returns observation rows from Env.step and (cmd, pos_e, yaw_e)
+    from computeControlFromState.  Returns {name: shape} of what was written."""
+    import torch
+    n = fl.n
+    idx = np.arange(n) if n <= DUMP_MAX_DRONES else np.sort(np.random.default_rng(0).choice(n, DUMP_MAX_DRONES, replace=False))
+    sel = torch.from_numpy(idx).to(fl.env.ctx.device)
+    if fl.loop_out is not None:
+        o = fl.loop_out
+        arrays = {"obs": getattr(o["obs"], "state", o["obs"]), "cmd": o["cmd"], "pos_e": o["pos_e"], "yaw_e": o["yaw_e"]}
+    else:
+        st = fl.env.state
+        arrays = {"rigid_state": st.fields(0, 13).T, "controller_memory": st.fields(13, st.n_fields - 13).T}
+        if getattr(fl.env, "_dyn_rates", None) is not None:
+            arrays["rpy_rates"] = fl.env.rpy_rates.T
+    arrays = {k: v.index_select(0, sel).float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    assert total <= DUMP_MAX_BYTES, f"--dump-outputs: {total} bytes"
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+    return {k: list(v.shape) for k, v in arrays.items()}
+
+
+def write_extras(extras):
+    """The entries measured beside the headline, as one JSON file (EXTRAS_FILE): its path, or what kept it from being written."""
+    try:
+        with open(EXTRAS_FILE, "w") as fh:
+            json.dump(extras, fh, indent=1)
+        return EXTRAS_FILE
+    except OSError as e:
+        return {"error": repr(e)[:200]}
 
 
 def two_call_child(a, kind="quad", placement=False):
@@ -912,13 +965,9 @@ def main(argv=None):
     if a.workload == "two_call_loop":
         fl.make_two_call_loop()
 
-    def repeat_rule(first_wall):
-        # the slowest rank's first region decides how many regions every rank runs
-        w, _ = sharding.reduce_step_times(dist, red_dev, first_wall, 0.0)
-        return max(1, int(np.ceil(MIN_TIMED_S / max(w, 1e-9))))
-
-    wall_local, dev_s_local, regions = fl.timed(a.steps, a.warmup, barrier, min_s=MIN_TIMED_S, repeat_rule=repeat_rule,
-                                               settle_s=a.settle_seconds)
+    # exactly --steps timed steps: one region
+    wall_local, dev_s_local, regions = fl.timed(a.steps, a.warmup, barrier, settle_s=a.settle_seconds)
+    dumped = dump_outputs(fl, a.dump_outputs) if (a.dump_outputs and rank == 0) else None
     wall, dev_s = sharding.reduce_step_times(dist, red_dev, wall_local, dev_s_local)  # MAX over ranks
     steps_timed = a.steps * regions
     value = sharding.aggregate_throughput([fl.n] * world, steps_timed, wall)
@@ -961,8 +1010,8 @@ def main(argv=None):
             "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": wall / steps_timed * 1e3,
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "steps_timed": steps_timed, "timed_regions": regions, "settle_seconds": a.settle_seconds,
-            "timing_note": f"regions of exactly --steps steps, each bracketed by barrier + device synchronisation, repeated "
-                           f"until they cover {MIN_TIMED_S * 1e3:.0f} ms; value and ms_per_step are sums over all of them",
+            "timing_note": "one region of exactly --steps steps, bracketed by barrier + device synchronisation (with "
+                           "--settle-seconds: right behind the settling load, device events only)",
             "config": {"workload": WORKLOAD_TEXT[a.workload],
                        "drones_per_gpu": fl.n, "phys_substeps": a.substeps, "layout": a.layout,
                        "noise_seed": a.noise_seed, "launches_per_step": 1, "parallelism": f"shard{world}",
@@ -1000,6 +1049,8 @@ def main(argv=None):
             out["placement_cost"] = placement_cost(fl.env.ctx.placement_log)
         if exchange is not None:
             out["exchange"] = exchange
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": a.dump_outputs, "drones": min(fl.n, DUMP_MAX_DRONES), "arrays": dumped}
         if force_dist and world == 1:
             out["rccl_selftest"] = rccl_selftest(dist, fl, red_dev)
         if a.mirror_peer:
@@ -1134,6 +1185,9 @@ def main(argv=None):
             out["also"] = also
         if world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(a.substeps)
+        extras = {k: out.pop(k) for k in ("baseline_configs", "also") if k in out}
+        if extras:
+            out["extras_file"] = write_extras(extras)
         emit(json.dumps(out))
     failed = bool(rank == 0 and world > 1 and not out.get("self_check", {}).get("ok", True))
     if dist:

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Generate the golden vectors under tests/golden/ by RUNNING the reference.
 
-TEST INFRASTRUCTURE.  Runs only in the build container (needs /root/reference);
-the GPU box and the product never import this.  Nothing from the reference is
+TEST INFRASTRUCTURE.  Runs only where a checkout of the reference package exists
+(--reference); the test suite and the product never import this.  Nothing from the reference is
 copied: this script imports the reference package from where it lies, feeds it
 seeded inputs and stores inputs + outputs as .npz (fp64).
 
@@ -23,17 +23,23 @@ What is the real reference and what is a stand-in
   stand-in's fidelity to Bullet's Euler convention, which nothing in the
   reference pins.
 
-Usage:  python tests/golden/make_goldens.py   (writes tests/golden/*.npz)
+Usage:  python tests/golden/make_goldens.py --reference CHECKOUT [dyn|env|roll]   (writes tests/golden/*.npz)
+        python tests/golden/make_goldens.py --reference CHECKOUT --check
+            (regenerates every fixture in a temporary directory; exit 0 when each is bit-identical to the stored one)
 """
+import argparse
+import glob
 import math
 import os
 import sys
+import tempfile
 import types
 
 import numpy as np
 
-REF = "/root/reference"
-OUT = os.path.dirname(os.path.abspath(__file__))
+REF = None      # the reference checkout (--reference)
+GOLDEN = os.path.dirname(os.path.abspath(__file__))
+OUT = GOLDEN
 
 
 # ----------------------------------------------------------------------------
@@ -623,15 +629,46 @@ def capture_dynamics():
     print("dynamics goldens written")
 
 
-def main():
+def main(argv=None):
+    global REF, OUT
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reference", required=True, help="checkout of enac-drones/dronesim")
+    ap.add_argument("--check", action="store_true", help="regenerate into a temporary directory and compare with tests/golden")
+    ap.add_argument("part", nargs="?", choices=["dyn", "env", "roll"], help="only the Physics.DYN / env-side / roll-sweep file")
+    a = ap.parse_args(argv)
+    REF = os.path.abspath(a.reference)
+    if a.check:
+        with tempfile.TemporaryDirectory() as d:
+            OUT = d
+            generate(None)
+            return check(GOLDEN, d)
+    generate(a.part)
+    return 0
+
+
+def check(stored_dir, fresh_dir):
+    """Every stored fixture against its regenerated twin: the same arrays, bit for bit (NaN where NaN)."""
+    files = sorted(glob.glob(os.path.join(stored_dir, "*.npz")))
+    bad = [] if len(files) == 18 else [f"{len(files)} stored fixtures, 18 expected"]
+    for f in files:
+        a, b = np.load(f, allow_pickle=True), np.load(os.path.join(fresh_dir, os.path.basename(f)), allow_pickle=True)
+        if set(a.files) != set(b.files):
+            bad.append(f"{os.path.basename(f)}: keys {sorted(set(a.files) ^ set(b.files))}")
+        bad += [f"{os.path.basename(f)}: {k}" for k in sorted(set(a.files) & set(b.files))
+                if not np.array_equal(a[k], b[k], equal_nan=a[k].dtype.kind == "f")]
+    print("\n".join(bad) if bad else f"{len(files)} fixtures regenerate bit-identically")
+    return 1 if bad else 0
+
+
+def generate(part):
     install_standins()
-    if len(sys.argv) > 1 and sys.argv[1] == "dyn":        # only the Physics.DYN file
+    if part == "dyn":        # only the Physics.DYN file
         capture_dynamics()
         return
-    if len(sys.argv) > 1 and sys.argv[1] == "env":        # only the env-side file
+    if part == "env":        # only the env-side file
         capture_env_side()
         return
-    if len(sys.argv) > 1 and sys.argv[1] == "roll":       # only the roll-sweep file
+    if part == "roll":       # only the roll-sweep file
         capture_roll_sweep()
         return
     from dronesim.control.INDIControl import INDIControl
@@ -737,4 +774,4 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    sys.exit(main())

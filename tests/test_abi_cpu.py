@@ -80,11 +80,9 @@ def test_product_does_not_import_oracle():
 
 
 @pytest.mark.parametrize("model", ["robobee", "tello"])
-def test_builtin_types_match_reference_urdf(model):
-    urdf = f"/root/reference/dronesim/assets/{model}.urdf"
-    if not os.path.exists(urdf):
-        pytest.skip("reference tree not present (GPU box)")
-    a, b = params.builtin_type(model), params.parse_urdf(urdf)
+def test_builtin_types_match_reference_urdf(model, golden_dir):
+    """tests/golden/<model>.urdf: the reference's vehicle description, stored unmodified."""
+    a, b = params.builtin_type(model), params.parse_urdf(os.path.join(golden_dir, f"{model}.urdf"))
     for f in ("kind", "n_act", "mass", "kf", "km", "kp_pos", "kd_pos", "prop_radius", "gnd_eff_coeff", "collision_radius",
               "collision_below"):
         assert getattr(a, f) == getattr(b, f), f

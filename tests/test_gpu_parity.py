@@ -2217,14 +2217,14 @@ def test_bench_launches_its_own_ranks(gpu):
     assert len(lines) == 1
     d = json.loads(lines[0])
     assert d["n_gpus"] == 2 and d["dist"]["world_size"] == 2 and d["dist"]["backend"] == "gloo"
-    assert d["config"]["drones_per_gpu"] == 65536 and d["value"] > 1e8 and d["steps_timed"] >= 10
+    assert d["config"]["drones_per_gpu"] == 65536 and d["value"] > 1e8 and d["steps_timed"] == 10
     assert d["scaling"] == "weak" and "also" not in d
 
 
 def test_bench_settled_form_times_launches_right_behind_the_settling_load(gpu):
     """`bench.py --settle-seconds S` (Fleet._timed_settled): the device is kept under the workload for S seconds, the timed
-    launches follow without a gap, device time from events in the stream; the line says so, counts whole regions of --steps
-    launches and agrees with the plain form to within what the device's clocks do to a short run."""
+    launches follow without a gap, device time from events in the stream; the line says so, times exactly --steps launches
+    and agrees with the plain form to within what the device's clocks do to a short run."""
     import json
     import subprocess
     import sys
@@ -2232,7 +2232,7 @@ def test_bench_settled_form_times_launches_right_behind_the_settling_load(gpu):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     out = {}
     for settle in ("0", "0.05"):
-        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "config4", "--substeps", "5", "--steps", "10",
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "config4", "--substeps", "5", "--steps", "4000",
                             "--warmup", "2", "--settle-seconds", settle, "--no-also", "--no-cpu-baseline"],
                            capture_output=True, text=True, timeout=600, env=env, cwd=root)
         assert r.returncode == 0, r.stderr[-3000:]
@@ -2242,9 +2242,41 @@ def test_bench_settled_form_times_launches_right_behind_the_settling_load(gpu):
     a, b = out["0"], out["0.05"]
     assert a["settle_seconds"] == 0.0 and b["settle_seconds"] == 0.05
     for d in (a, b):
-        assert d["steps"] == 10 and d["steps_timed"] == 10 * d["timed_regions"] and d["steps_timed"] * d["ms_per_step"] >= 15.0     # (the count of regions comes from the first one's duration)
+        assert d["steps"] == 4000 and d["steps_timed"] == 4000 and d["timed_regions"] == 1 and d["steps_timed"] * d["ms_per_step"] >= 15.0
         assert d["value"] > 1e8 and d["config"]["phys_substeps"] == 5 and d["config"]["drones_per_gpu"] == 65536
     assert 0.5 < a["roofline"]["launch_us"] / b["roofline"]["launch_us"] < 2.0
+
+
+@pytest.mark.parametrize("workload", ["config2", "two_call_loop"])
+def test_bench_dump_outputs_are_those_of_the_last_timed_step(gpu, tmp_path, workload):
+    """`bench.py --dump-outputs DIR` times exactly --steps steps and writes what the timed path handed its caller after them:
+    the same arrays as the same fleet stepped here 1 (set-up) + --warmup + --steps times (the fused step: state block; the
+    two-call loop: obs rows, cmd, pos_e, yaw_e), float32, one row per drone."""
+    import json
+    import subprocess
+    import sys
+    import bench
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", workload, "--replicas", "1", "--steps", "7",
+                        "--warmup", "3", "--no-also", "--no-cpu-baseline", "--dump-outputs", str(tmp_path / "bench")],
+                       capture_output=True, text=True, timeout=600, env=env, cwd=root)
+    assert r.returncode == 0, r.stderr[-3000:]
+    d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert d["steps_timed"] == 7 and d["timed_regions"] == 1 and d["config"]["drones_per_gpu"] == 4096
+    fl = bench.Fleet(4096, 1, 0, 1, "tile64", 1)
+    if workload == "two_call_loop":
+        fl.make_two_call_loop()
+    for _ in range(3 + 7):
+        fl.step()
+    shapes = bench.dump_outputs(fl, str(tmp_path / "here"))
+    fl.env.close()
+    assert d["dumped_outputs"]["arrays"] == shapes and d["dumped_outputs"]["drones"] == 4096
+    assert set(shapes) == ({"obs", "cmd", "pos_e", "yaw_e"} if workload == "two_call_loop" else {"rigid_state", "controller_memory"})
+    for name in shapes:
+        got, want = np.load(tmp_path / "bench" / f"{name}.npy"), np.load(tmp_path / "here" / f"{name}.npy")
+        assert got.dtype == np.float32 and got.shape[0] == 4096 and np.isfinite(got).all()
+        np.testing.assert_allclose(got, want, rtol=1e-6, atol=1e-6, err_msg=name)
 
 
 def test_ground_plane_watch_counts_what_pybullet_would_have_caught(gpu):

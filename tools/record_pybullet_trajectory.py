@@ -48,7 +48,7 @@ import numpy as np
 
 def main(argv=None):
     ap = argparse.ArgumentParser()
-    ap.add_argument("--reference", default="/root/reference", help="checkout of enac-drones/dronesim")
+    ap.add_argument("--reference", required=True, help="checkout of enac-drones/dronesim")
     ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
                                                   "tests", "golden", "pybullet_fly_INDI.npz"))
     ap.add_argument("--steps", type=int, default=72, help="control steps (x5 physics steps each)")
