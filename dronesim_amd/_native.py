@@ -23,7 +23,7 @@ EXPORTS = (
     "dsim_downwash_keep_workspace", "dsim_downwash_keep_ok", "dsim_downwash_keep_stats",
 )
 
-ABI_VERSION = 9
+ABI_VERSION = 10
 MAX_PEERS = 8
 HALO_HDR = 8           # header floats of a halo message (DSIM_HALO_HDR)
 DW_ALL, DW_LOCAL, DW_HALO_BIN, DW_HALO_QUERY = 0, 1, 2, 3
@@ -44,6 +44,10 @@ OPT_DYN_BODY_RATES = 1 << 17   # ... with ang_v = R(quat) rpy_rates instead of t
 # of ONE physics sub-step, the coarse one (8 + 8 bits) for a launch of several; the bits force one at any count (include/dronesim_amd.h)
 OPT_NOISE_FINE = 1 << 18
 OPT_NOISE_COARSE = 1 << 19
+# the caller asserts that the target groups of StepArgs.tgt_const_mask (bit 0 pos, 1 vel, 2 acc, 3 yaw) hold StepArgs.tgt_const for every
+# drone; the library may skip reading them (results do not depend on it; include/dronesim_amd.h)
+OPT_TGT_CONST = 1 << 20
+TGT_CONST_POS_PER_DRONE = 0xE   # the mask the kernels honour: pos per drone, vel / acc / yaw constant
 ADAPT_VELOCITY, ADAPT_RPYT = 0, 1
 QUERY_WLS_FALLBACKS, QUERY_WLS_FAILURES, QUERY_GROUND_CONTACTS, QUERY_HALO_OVERFLOW = 0, 1, 2, 3
 QUERY_DW_REUSES, QUERY_DW_MOVERS = 4, 5
@@ -86,6 +90,8 @@ class StepArgs(ctypes.Structure):
         ("bin_next", ctypes.c_void_p),
         ("drone_id", ctypes.c_void_p),
         ("dyn_rpy_rates", ctypes.c_void_p),
+        ("tgt_const_mask", ctypes.c_uint32),
+        ("tgt_const", ctypes.c_float * 10),
     ]
 
 

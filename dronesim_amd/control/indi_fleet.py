@@ -145,7 +145,7 @@ class INDIControl(BaseControl):
         real passes on candidates holding a copy of the targets (a 4 GiB walk, the fastest kept: as CtrlAviary does for the
         fused step's targets), snapshot back."""
         from .. import placement
-        st, old = self.state, self._targets.data
+        st, old = self.state, self._targets._data
         if not (self.ctx.placement and 4 * old.numel() >= placement.MIN_BYTES and not getattr(self.env, "_graph_made", False)):
             return
         snap = st.data.clone()
@@ -177,7 +177,7 @@ class INDIControl(BaseControl):
                 keep = room
                 rep["decided_by"] = "the block behind the state, in its allocation, is as fast as the walk's best: kept"
         keep.copy_(old)
-        self._targets.data = keep
+        self._targets._data = keep
         st.data.copy_(snap)
         self._cmd.copy_(outs[0]); self._pos_e.copy_(outs[1]); self._yaw_e.copy_(outs[2])
         self._plan = None
@@ -263,7 +263,7 @@ class INDIControl(BaseControl):
                 small.append(np.asarray(x, dtype=np.float32).tobytes())
             if small is not None:
                 key = (target_pos, float(control_timestep), small[0], small[1], small[2], st.data.data_ptr(),
-                       self._targets.data.data_ptr(), self._targets.version, id(getattr(self.env, "_runs", None)),
+                       self._targets._data.data_ptr(), (self._targets.version, self._targets.hint_epoch), id(getattr(self.env, "_runs", None)),
                        getattr(self.env, "_tuning", 0), self._cmd.data_ptr() if self._cmd is not None else 0)
                 plan = self._plan
                 if plan is not None and plan.matches(key):
@@ -305,7 +305,8 @@ class INDIControl(BaseControl):
         if caller_io:               # the triple comes back in the caller's numbering straight from the launch
             a.options |= nat.OPT_CALLER_IO
             a.drone_id = st.order.drone_id(st.n_pad).data_ptr()
-        if not self._outputs_placed:
+        self._targets.fill_const_hint(a)     # vel / acc / yaw the same for every drone: the kernel need not read them
+        if not self._outputs_placed:         # (so the placement trials below time the kernel the launches will run)
             self._outputs_placed = True
             if self.ctx.placement:
                 # (the trials are real passes of this law: what they add to the WLS counters is not the fleet's history)
@@ -322,7 +323,7 @@ class INDIControl(BaseControl):
             out = (self._cmd[:, :n].T, self._pos_e[:, :n].T, self._yaw_e[:n])
             if key is not None:
                 # (the key is completed with what this call settled: the buffers of the outputs and the targets' version)
-                key = key[:6] + (self._targets.data.data_ptr(), self._targets.version) + key[8:10] + (self._cmd.data_ptr(),)
+                key = key[:6] + (self._targets._data.data_ptr(), (self._targets.version, self._targets.hint_epoch)) + key[8:10] + (self._cmd.data_ptr(),)
                 self._plan = _ControlPlan(key, sview, tview, ctypes.byref(a), self._pos_e.data_ptr(), self._yaw_e.data_ptr(),
                                           self._cmd.data_ptr(), out, None, a)
             return out

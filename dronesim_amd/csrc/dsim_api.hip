@@ -338,6 +338,8 @@ int fill_stepk(dsim_ctx* ctx, int64_t n, const dsim_view& state, const dsim_view
   a->io_id = (args->options & DSIM_OPT_CALLER_IO) ? args->drone_id : nullptr;
   a->action_rows = (args->options & DSIM_OPT_ACTION_ROWS) ? 1 : 0;     // (honoured by the entry points that check it)
   a->dyn_rates = args->dyn_rpy_rates;
+  const float* c = args->tgt_const;       // (read by the TC instances only: tgt_const_honoured)
+  a->tc.pos = V3{c[0], c[1], c[2]}; a->tc.vel = V3{c[3], c[4], c[5]}; a->tc.acc = V3{c[6], c[7], c[8]}; a->tc.yaw = c[9];
   return DSIM_OK;
 }
 

@@ -301,6 +301,7 @@ struct StepK {
   unsigned hexa_types;        // bit t set: type t of the table is a morphing hexa (26 state fields in use)
   BinK bin;                   // grid of the next Env.step's downwash (k_step_mixed / k_step_run), count = null: none
   float* dyn_rates;           // Physics.DYN: BaseAviary.rpy_rates, SoA [3][n_pad] in-out (k_dyn only)
+  Target tc;                  // DSIM_OPT_TGT_CONST: vel / acc / yaw of every drone (kernel arguments: SGPRs), for the TC instances
 };
 
 // Global accesses.  NT = nontemporal (streaming) hint: each state field is read once and written
@@ -370,6 +371,19 @@ __device__ __forceinline__ void load_target(const float* ub, long long fs, unsig
   t.vel = v3(ldg<NT>(ub + 3 * fs, lo), ldg<NT>(ub + 4 * fs, lo), ldg<NT>(ub + 5 * fs, lo));
   t.acc = v3(ldg<NT>(ub + 6 * fs, lo), ldg<NT>(ub + 7 * fs, lo), ldg<NT>(ub + 8 * fs, lo));
   t.yaw = ldg<NT>(ub + 9 * fs, lo);
+}
+// TC (DSIM_OPT_TGT_CONST, mask 0xE): only the three pos fields come from the view, vel / acc / yaw are the launch's constants
+// (tgt_const_honoured): 12 instead of 40 bytes read per drone
+template <bool NT = false, bool TC = false>
+__device__ __forceinline__ void load_target(const float* ub, long long fs, unsigned lo /* bytes */, const Target& tc, Target& t) {
+  if (!TC) { load_target<NT>(ub, fs, lo, t); return; }
+  t = tc;
+  t.pos = v3(ldg<NT>(ub + 0 * fs, lo), ldg<NT>(ub + 1 * fs, lo), ldg<NT>(ub + 2 * fs, lo));
+}
+// whether a launch may take the TC instances: the hint given, on a per-drone targets view, with pos per drone and the rest constant
+static inline bool tgt_const_honoured(const dsim_step_args* args) {
+  return (args->options & DSIM_OPT_TGT_CONST) && !(args->options & DSIM_OPT_BCAST_TGT) && !args->wp_table &&
+         args->tgt_const_mask == 0xEu;
 }
 
 // Waypoint-table targets (examples/fly_INDI_TrajectoryTrack.py:242-245): row wp of the table (+ the

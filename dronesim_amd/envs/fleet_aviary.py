@@ -560,6 +560,7 @@ class CtrlAviary(PlacedFleetArrays, FleetObservation):
             tview = nat.View()
         else:
             tview = targets.view()
+            targets.fill_const_hint(args)      # vel / acc / yaw the same for every drone: the kernel need not read them
         if action is not None:
             args.action = self._action_ptr(action)
         defer = False
@@ -658,7 +659,9 @@ class CtrlAviary(PlacedFleetArrays, FleetObservation):
         if isinstance(targets, WaypointTargets):
             return (targets.table.data_ptr(), targets.counters.data_ptr(),
                     targets.offsets.data_ptr() if targets.offsets is not None else 0, targets.n_wp)
-        return (targets.data.data_ptr(), tuple(targets.data.shape))
+        # (and the hint epoch: a set() that changed what the prepared arguments carry as DSIM_OPT_TGT_CONST bumps it; a per-drone
+        # write does not, so a loop that sets new positions before every call still replays the prepared block)
+        return (targets._data.data_ptr(), tuple(targets._data.shape), getattr(targets, "hint_epoch", 0))
 
     def _action_ptr(self, action, caller_order: bool = False) -> int:
         """Device pointer of the action as SoA [n_act][n_pad].  A tensor that already IS such an array (the command

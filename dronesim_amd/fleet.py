@@ -203,16 +203,25 @@ class BlockedSoA:
             raise ValueError(layout)
         numel = n_fields * self.n_pad
         if storage is not None and storage.numel() == numel and storage.is_contiguous() and storage.device == torch.device(device):
-            self.data = storage.view(shape)
+            self._data = storage.view(shape)
         elif tail_fields > 0:
             flat = torch.zeros(numel + tail_fields * self.n_pad, dtype=torch.float32, device=device)
-            self.data, self.tail = flat[:numel].view(shape), flat[numel:]
+            self._data, self.tail = flat[:numel].view(shape), flat[numel:]
         else:
-            self.data = torch.zeros(shape, dtype=torch.float32, device=device)
+            self._data = torch.zeros(shape, dtype=torch.float32, device=device)
+
+    @property
+    def data(self) -> torch.Tensor:
+        """The device tensor of the block (layout above)."""
+        return self._data
+
+    @data.setter
+    def data(self, t: torch.Tensor) -> None:
+        self._data = t
 
     def view(self) -> nat.View:
         v = nat.View()
-        v.base = self.data.data_ptr()
+        v.base = self._data.data_ptr()
         v.n_pad = self.n_pad
         v.n_fields = self.n_fields
         if self.layout == "soa":
@@ -226,8 +235,8 @@ class BlockedSoA:
         if self.pre_access is not None:
             self.pre_access()
         if self.layout == "soa":
-            return self.data[f0:f0 + nf, : self.n]
-        return self.data[:, f0:f0 + nf, :].permute(1, 0, 2).reshape(nf, self.n_pad)[:, : self.n]
+            return self._data[f0:f0 + nf, : self.n]
+        return self._data[:, f0:f0 + nf, :].permute(1, 0, 2).reshape(nf, self.n_pad)[:, : self.n]
 
     def fields(self, f0: int, nf: int) -> torch.Tensor:
         """[nf, n] tensor of fields f0..f0+nf in the caller's numbering (with a storage order: a gathered copy)."""
@@ -240,17 +249,17 @@ class BlockedSoA:
             self.pre_access()
         self.version += 1
         nf = values.shape[0]
-        vals = values.to(self.data.device, torch.float32)
+        vals = values.to(self._data.device, torch.float32)
         if self.order is not None:
             vals = self.order.to_storage(vals, 1)
         if self.layout == "soa":
-            self.data[f0:f0 + nf, : self.n] = vals
+            self._data[f0:f0 + nf, : self.n] = vals
         elif self.n == self.n_pad:          # whole tiles: one strided copy, no staging buffer
-            self.data[:, f0:f0 + nf, :] = vals.reshape(nf, self.n_pad // self.block, self.block).permute(1, 0, 2)
+            self._data[:, f0:f0 + nf, :] = vals.reshape(nf, self.n_pad // self.block, self.block).permute(1, 0, 2)
         else:
-            full = torch.zeros((nf, self.n_pad), dtype=torch.float32, device=self.data.device)
+            full = torch.zeros((nf, self.n_pad), dtype=torch.float32, device=self._data.device)
             full[:, : self.n] = vals
-            self.data[:, f0:f0 + nf, :] = full.reshape(nf, self.n_pad // self.block, self.block).permute(1, 0, 2)
+            self._data[:, f0:f0 + nf, :] = full.reshape(nf, self.n_pad // self.block, self.block).permute(1, 0, 2)
 
 
 class FleetState(BlockedSoA):
@@ -294,13 +303,27 @@ class FleetState(BlockedSoA):
 
 
 class Targets(BlockedSoA):
-    """Per-step targets: pos3 vel3 acc3 yaw (INDIControl.computeControl arguments)."""
+    """Per-step targets: pos3 vel3 acc3 yaw (INDIControl.computeControl arguments).
+
+    The object records which field groups hold ONE constant for every drone (``set`` with a length-3 / scalar value; a fresh
+    object holds +0.0 everywhere) and hands that to the launches as ``DSIM_OPT_TGT_CONST`` (:meth:`fill_const_hint`): the
+    kernels then take vel / acc / yaw from their arguments instead of reading them (28 B per drone-step).  The fields are
+    written as before, the hint only skips reads.  Once the tensor leaves the object (``data`` read from outside, or a view
+    of it from ``fields`` / ``raw_fields``) it can be written behind ``set()``'s back, and the object offers no hint again."""
+
+    # field groups: (first field, fields, bit of dsim_step_args.tgt_const_mask)
+    GROUPS = ((0, 3, 1), (3, 3, 2), (6, 3, 4), (9, 1, 8))
 
     def __init__(self, ctx: Context, n: int, layout: str = "soa", broadcast: bool = False, pad: int = 256):
         self.broadcast = broadcast
+        # field group -> its constant as float32 BITS (a tuple of ints: what the fields hold for every drone), or a
+        # ("frozen", Frozen) key / None for per-drone data.  Zeroed storage: every group is +0.0.
+        self._const = {f0: (0,) * nf for f0, nf, _ in self.GROUPS}
+        self._hint_ok = not broadcast         # False for good once the tensor has been handed out
+        self.hint_epoch = 0                   # bumped whenever const_hint() changes: prepared launches that carry the hint key on it
         if broadcast:
             self.n, self.n_pad, self.n_fields, self.layout = 1, 64, nat.NT, "soa"
-            self.data = torch.zeros((nat.NT, 1), dtype=torch.float32, device=ctx.device)
+            self._data = torch.zeros((nat.NT, 1), dtype=torch.float32, device=ctx.device)
             self.order, self.pre_access, self.version = None, None, 0
         else:
             room, storage = getattr(ctx, "read_room", None), None
@@ -311,24 +334,77 @@ class Targets(BlockedSoA):
             self._placed = False      # CtrlAviary.step_fused may re-allocate `data` once, by trial (placement.py)
 
     @property
+    def data(self) -> torch.Tensor:
+        """The device tensor.  Reading it from outside ends the constant-group hint for this object (see the class)."""
+        self._hand_out()
+        return self._data
+
+    @data.setter
+    def data(self, t: torch.Tensor) -> None:
+        self._hand_out()
+        self._data = t
+
+    def _hand_out(self) -> None:
+        if self._hint_ok:
+            self._hint_ok = False
+            self.hint_epoch += 1
+
+    @staticmethod
+    def _is_const(key) -> bool:
+        return isinstance(key, tuple) and all(isinstance(b, int) for b in key)
+
+    def _record(self, f0: int, key) -> None:
+        old = self._const.get(f0)
+        if old != key and (self._is_const(old) or self._is_const(key)):
+            self.hint_epoch += 1
+        self._const[f0] = key
+
+    def raw_fields(self, f0: int, nf: int) -> torch.Tensor:
+        if self.layout == "soa":              # a view of the tensor (the tiled layouts gather a copy)
+            self._hand_out()
+        return super().raw_fields(f0, nf)
+
+    @property
     def behind_the_state(self) -> bool:
         """Whether the targets lie in the room behind the fleet's state block (FleetState) — asked of the tensor itself, so that a
         Targets whose data was re-allocated since (placement by trial) says no."""
-        return getattr(self, "_room_ptr", None) is not None and self.data.data_ptr() == self._room_ptr
+        return getattr(self, "_room_ptr", None) is not None and self._data.data_ptr() == self._room_ptr
 
     def view(self) -> nat.View:
         if not self.broadcast:
             return super().view()
         v = nat.View()
-        v.base = self.data.data_ptr()
+        v.base = self._data.data_ptr()
         v.n_pad, v.block, v.field_stride, v.block_stride, v.n_fields = 64, 64, 1, nat.NT, nat.NT
         return v
 
+    def const_hint(self):
+        """(mask, ten float32 bit patterns) of the groups that hold one constant for every drone, or None when the object
+        offers no hint (broadcast, handed out, or no constant group)."""
+        if not self._hint_ok:
+            return None
+        mask, bits = 0, [0] * nat.NT
+        for f0, nf, bit in self.GROUPS:
+            key = self._const.get(f0)
+            if self._is_const(key) and len(key) == nf:
+                mask |= bit
+                bits[f0:f0 + nf] = key
+        return (mask, bits) if mask else None
+
+    def fill_const_hint(self, args: nat.StepArgs) -> None:
+        """Sets DSIM_OPT_TGT_CONST, the mask and the constants (their exact bits) on ``args`` when the object offers the hint."""
+        h = self.const_hint()
+        if h is None:
+            return
+        args.options |= nat.OPT_TGT_CONST
+        args.tgt_const_mask = h[0]
+        dst = (ctypes.c_uint32 * nat.NT).from_address(ctypes.addressof(args) + nat.StepArgs.tgt_const.offset)
+        for k, b in enumerate(h[1]):
+            dst[k] = b
+
     def set(self, pos=None, vel=None, acc=None, yaw=None) -> None:
         """Each argument [3, n] / [n] (per drone) or length-3 / scalar (same for all)."""
-        dev = self.data.device
-        if not hasattr(self, "_const"):
-            self._const = {}                  # field group -> the constant it was last filled with (None: per-drone data)
+        dev = self._data.device
         for f0, val, nf in ((0, pos, 3), (3, vel, 3), (6, acc, 3), (9, yaw, 1)):
             if val is None:
                 continue
@@ -347,19 +423,23 @@ class Targets(BlockedSoA):
                 if val.ndim == 2 and val.shape[0] != nf and val.shape[1] == nf:
                     val = val.T
             elif not torch.is_tensor(val) and np.size(val) == nf:
-                key = tuple(float(x) for x in np.asarray(val, dtype=np.float32).ravel())
+                # compared by BITS: -0.0 is not +0.0 here, and a NaN is the NaN it is
+                key = tuple(int(b) for b in np.asarray(val, dtype=np.float32).ravel().view(np.uint32))
                 if self._const.get(f0) == key:
                     continue
+                val = np.asarray(key, dtype=np.uint32).view(np.float32)       # exactly the bits recorded
             t = torch.as_tensor(val, dtype=torch.float32, device=dev).reshape(nf, -1)
             if self.broadcast:
-                self.data[f0:f0 + nf, :] = t
+                self._data[f0:f0 + nf, :] = t
             else:
                 if t.shape[1] == 1:
                     t = t.expand(nf, self.n)
                 BlockedSoA.set_fields(self, f0, t)
-            self._const[f0] = key
+            self._record(f0, key)
 
     def set_fields(self, f0: int, values: torch.Tensor) -> None:
+        if any(self._is_const(k) for k in self._const.values()):
+            self.hint_epoch += 1
         self._const = {}                      # written behind set()'s back: nothing is known to be constant any more
         super().set_fields(f0, values)
 
@@ -417,6 +497,7 @@ class TrajectoryTargets(Targets):
 
     def __init__(self, ctx: Context, n: int, coeffs, TS, t0=None, offsets=None, layout: str = "soa", pad: int = 256):
         super().__init__(ctx, n, layout, pad=pad)
+        self._const, self._hint_ok = {}, False      # every field is written on the device (dsim_traj_sample)
         self.ctx = ctx
         dev = ctx.device
         self.coeffs = torch.as_tensor(np.ascontiguousarray(coeffs), dtype=torch.float64).to(dev)

@@ -292,7 +292,7 @@ class PlacedFleetArrays:
         launch has no neutral form: snapshot of the state block, real passes on candidates holding a copy of the targets,
         snapshot back."""
         targets._placed = True
-        old = targets.data
+        old = targets._data
         if not (self.ctx.placement and isinstance(targets, Targets) and not targets.broadcast and targets.order is None
                 and 4 * old.numel() >= MIN_BYTES and self._type_id is None and self.n_act == 4
                 and self._downwash is None and self._phys_options == 0 and not self._chained_enabled
@@ -302,6 +302,7 @@ class PlacedFleetArrays:
         snap, echo = self.state.data.clone(), self._last_action.clone()
         before = self.ctx.query(nat.QUERY_GROUND_CONTACTS)
         args = self.step_args(control_timestep)
+        targets.fill_const_hint(args)          # (the trials time the kernel the launches will run)
         sview, tview, ref = self.state.view(), targets.view(), ctypes.byref(args)
         filled = set()
 
@@ -326,7 +327,7 @@ class PlacedFleetArrays:
                 keep = room
                 rep["decided_by"] = "the block behind the state, in its allocation, is as fast as the walk's best: kept"
         keep.copy_(old)
-        targets.data = keep
+        targets._data = keep
         self.state.data.copy_(snap)
         self._last_action.copy_(echo)
         self._ground_trial += self.ctx.query(nat.QUERY_GROUND_CONTACTS) - before

@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define DSIM_ABI_VERSION 9
+#define DSIM_ABI_VERSION 10
 #define DSIM_MAX_ACT 6     /* actuators per vehicle (quad 4, morphing hexa 6) */
 #define DSIM_MAX_TYPES 8
 
@@ -222,6 +222,17 @@ enum {
    * Both bits: DSIM_E_ARG.                                                                                                */
   DSIM_OPT_NOISE_FINE  = 1u << 18,
   DSIM_OPT_NOISE_COARSE = 1u << 19,
+  /* -- traffic (results do not depend on it) -------------------------------------------------------------------------- */
+  DSIM_OPT_TGT_CONST   = 1u << 20,  /* The caller asserts that, for every drone, the target fields of the groups set in
+                                       dsim_step_args.tgt_const_mask (bit 0 pos, 1 vel, 2 acc, 3 yaw) hold exactly the
+                                       values of dsim_step_args.tgt_const (pos3 vel3 acc3 yaw, bit for bit).  The library
+                                       MAY take those fields from the arguments instead of reading the targets view, and
+                                       may ignore the hint; the view must hold the values either way.  Honoured, with the
+                                       mask exactly 0xE (pos per drone, vel / acc / yaw constant), by the whole-tile quad
+                                       kernels of dsim_step (plain targets: no waypoint table, n_steps 1, no explicit
+                                       action) and of dsim_control2: 7 of the 10 target floats are not read, 28 bytes less
+                                       per drone-step (232 -> 204, chained 184 -> 156, control 212 -> 184).  Every other
+                                       kernel and mask reads the view as without the bit.                               */
   /* -- scheduling (results do not depend on it) ---------------------------------------------------------------------- */
   DSIM_OPT_DEFER_FALLBACK = 1u << 11 /* dsim_step / dsim_control2 of a table with a morphing hexa do NOT launch the deferred
                                        WLS fallback pass behind the step; the caller launches dsim_wls_fallback itself —
@@ -328,6 +339,9 @@ typedef struct dsim_step_args {
    * device SoA [3][n_pad], in-out; required with DSIM_OPT_DYN, ignored otherwise: BaseAviary.rpy_rates (BaseAviary.py:670-671
    * zeroed by _housekeeping, :1785 read, :1828 written by _dynamics).  Caller-owned like every other per-drone array.  */
   float* dyn_rpy_rates;
+  /* -- constant target groups (DSIM_OPT_TGT_CONST; zeroed arguments: no hint) ---------------------------------------------- */
+  uint32_t tgt_const_mask;  /* bit 0 pos, 1 vel, 2 acc, 3 yaw: the groups whose fields hold tgt_const for every drone      */
+  float    tgt_const[10];   /* pos3 vel3 acc3 yaw; the entries of the groups outside the mask are ignored                 */
 } dsim_step_args;
 
 typedef struct dsim_ctx dsim_ctx;
