@@ -23,7 +23,7 @@ EXPORTS = (
     "dsim_downwash_keep_workspace", "dsim_downwash_keep_ok", "dsim_downwash_keep_stats",
 )
 
-ABI_VERSION = 10
+ABI_VERSION = 11
 MAX_PEERS = 8
 HALO_HDR = 8           # header floats of a halo message (DSIM_HALO_HDR)
 DW_ALL, DW_LOCAL, DW_HALO_BIN, DW_HALO_QUERY = 0, 1, 2, 3
@@ -48,6 +48,8 @@ OPT_NOISE_COARSE = 1 << 19
 # drone; the library may skip reading them (results do not depend on it; include/dronesim_amd.h)
 OPT_TGT_CONST = 1 << 20
 TGT_CONST_POS_PER_DRONE = 0xE   # the mask the kernels honour: pos per drone, vel / acc / yaw constant
+# StepArgs.tgt_period (no option bit, 0 = none): the caller asserts that every target field of drone i equals that of drone
+# i mod tgt_period; the library may read the first period only (results do not depend on it; include/dronesim_amd.h)
 ADAPT_VELOCITY, ADAPT_RPYT = 0, 1
 QUERY_WLS_FALLBACKS, QUERY_WLS_FAILURES, QUERY_GROUND_CONTACTS, QUERY_HALO_OVERFLOW = 0, 1, 2, 3
 QUERY_DW_REUSES, QUERY_DW_MOVERS = 4, 5
@@ -92,6 +94,7 @@ class StepArgs(ctypes.Structure):
         ("dyn_rpy_rates", ctypes.c_void_p),
         ("tgt_const_mask", ctypes.c_uint32),
         ("tgt_const", ctypes.c_float * 10),
+        ("tgt_period", ctypes.c_int64),
     ]
 
 

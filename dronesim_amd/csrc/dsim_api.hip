@@ -314,8 +314,10 @@ int fill_stepk(dsim_ctx* ctx, int64_t n, const dsim_view& state, const dsim_view
     rc = make_kview(*targets, DSIM_NT, &a->tg, bc);
     if (rc) return rc;
     if (!bc && targets->n_pad != state.n_pad) return DSIM_E_LAYOUT;
+    tgt_period_tiles(args, *targets, &a->tgt_tiles, &a->tgt_mask);
   } else {
     memset(&a->tg, 0, sizeof(a->tg));
+    a->tgt_tiles = a->tgt_mask = ~0u;
   }
   a->hexa_types = 0;
   for (int t = 0; t < ctx->n_types; ++t) a->hexa_types |= (ctx->h_types[t].kind != DSIM_KIND_QUAD ? 1u : 0u) << t;

@@ -302,6 +302,8 @@ struct StepK {
   BinK bin;                   // grid of the next Env.step's downwash (k_step_mixed / k_step_run), count = null: none
   float* dyn_rates;           // Physics.DYN: BaseAviary.rpy_rates, SoA [3][n_pad] in-out (k_dyn only)
   Target tc;                  // DSIM_OPT_TGT_CONST: vel / acc / yaw of every drone (kernel arguments: SGPRs), for the TC instances
+  unsigned tgt_tiles, tgt_mask;   // dsim_step_args.tgt_period: tile t of the plain k_step_fast instances reads the targets of
+                                  // tile t & tgt_mask (tgt_tiles = ~0u), or t % tgt_tiles (tgt_period_tiles)
 };
 
 // Global accesses.  NT = nontemporal (streaming) hint: each state field is read once and written
@@ -384,6 +386,21 @@ __device__ __forceinline__ void load_target(const float* ub, long long fs, unsig
 static inline bool tgt_const_honoured(const dsim_step_args* args) {
   return (args->options & DSIM_OPT_TGT_CONST) && !(args->options & DSIM_OPT_BCAST_TGT) && !args->wp_table &&
          args->tgt_const_mask == 0xEu;
+}
+
+// StepK.tgt_tiles / tgt_mask from a periodic targets view (dsim_step_args.tgt_period), honoured on a per-drone view without a
+// waypoint table when the period is a multiple of 256 and of the view's block (SoA: any), divides n_pad and is below it.  Tile t
+// then reads the targets of tile t mod (period / 256): drone i and drone i mod period sit at the same place inside their tile
+// and block, so kv_lane() is unchanged and only the wave-uniform base moves.  A power of two of tiles (the env replicas of
+// bench.py: 16) is a mask; any other count a 32-bit modulo, about 1 us more per headline launch.  Not honoured: mask ~0u.
+static inline void tgt_period_tiles(const dsim_step_args* args, const dsim_view& tv, unsigned* tiles, unsigned* mask) {
+  *tiles = ~0u; *mask = ~0u;
+  const long long p = args->tgt_period, n_pad = tv.n_pad;
+  if (p <= 0 || (args->options & DSIM_OPT_BCAST_TGT) || args->wp_table) return;
+  const long long blk = tv.block == n_pad ? 1 : tv.block;
+  if (p % 256 || blk <= 0 || p % blk || n_pad % p || p >= n_pad || p / 256 >= (long long)~0u) return;
+  const unsigned t = (unsigned)(p / 256);
+  if (t & (t - 1)) *tiles = t; else *mask = t - 1;
 }
 
 // Waypoint-table targets (examples/fly_INDI_TrajectoryTrack.py:242-245): row wp of the table (+ the

@@ -25,6 +25,11 @@
 // interleaved pairs) and it frees registers — the headline instance 62 instead of 64 VGPRs at 8 waves per SIMD, the looped noise
 // instances 66 / 69 instead of 73 / 76 VGPRs, 7 instead of 6 waves (no scratch); the branch form leaves every instance at its old count.
 // (The looped no-noise TC instances hold 8 more SGPRs for the constants: 7 waves per SIMD instead of 8.)
+// dsim_step_args.tgt_period (replicas of one task): the plain instances read the targets of the first period only, which stays in
+// L2 — 192 B/drone-step with TC (from HBM), 132.2 against 138.6 us on the headline.  A runtime base, not a template flag: it costs no
+// instance a VGPR or a wave (a few SGPRs).  The target loads keep the launch's cache policy: default-policy loads under the hint
+// measured the same (133.45 against 133.42 us, four interleaved runs).  A power of two of tiles is a mask: the 32-bit modulo
+// alone cost about 1 us per launch (133.3 against 132.2 us, profiles/r08_ab_tgt_period.txt).
 template <bool NOISE, bool NT, bool EXT, bool CH = false, int SUB = 0, bool ACT = false, bool TC = false>
 __global__ __launch_bounds__(256, EXT ? 3 : DSIM_STEP_WAVES) void k_step_fast(StepK a) {
   const DevType& T = a.types[0];
@@ -32,7 +37,10 @@ __global__ __launch_bounds__(256, EXT ? 3 : DSIM_STEP_WAVES) void k_step_fast(St
   const unsigned sl = 4u * kv_lane(a.st, threadIdx.x), tl = 4u * kv_lane(a.tg, threadIdx.x);   // bytes
   const long long i0 = (long long)blockIdx.x * 256;                   // wave-uniform
   float* const sb = a.st.base + kv_off(a.st, i0);                     // scalar bases
-  const float* const tb = a.tg.base + kv_off(a.tg, i0);
+  // the plain instances read the targets of the first period of a periodic view (tgt_period_tiles): wave-uniform, scalar
+  const unsigned bt = a.tgt_tiles == ~0u ? (blockIdx.x & a.tgt_mask) : blockIdx.x % a.tgt_tiles;
+  const long long i0t = (!EXT && !ACT) ? (long long)bt * 256 : i0;
+  const float* const tb = a.tg.base + kv_off(a.tg, i0t);
   Rigid s;
   CtrlMem<4> m;
   Target tg;

@@ -517,6 +517,7 @@ class CtrlAviary(PlacedFleetArrays, FleetObservation):
         if (action is None and plan is not None and self._downwash is None and self._chain_ok
                 and (self._chain_live or not self._chained_enabled) and plan.matches(key, targets, self._targets_ptrs(targets))):
             plan.args.step_index = self._env_steps
+            plan.args.tgt_period = self._tgt_period(targets)     # (may change with a per-drone set(), which keeps the block)
             nat.check(self.ctx.lib.dsim_step(self.ctx.handle, self.ctx.stream_ptr(), self.NUM_DRONES, plan.state_view,
                                              plan.targets_view, plan.args_ref))
             self.step_counter += self.AGGR_PHY_STEPS * n_steps
@@ -529,6 +530,7 @@ class CtrlAviary(PlacedFleetArrays, FleetObservation):
             # the grid the step kernel may fill (the Python side of a config-5 step is what paces a 65 536-drone shard)
             self._downwash.compute()
             pd.args.step_index = self._env_steps
+            pd.args.tgt_period = self._tgt_period(targets)
             pd.args.bin_next = self._downwash.bin_next_ptr()
             nat.check(self.ctx.lib.dsim_step(self.ctx.handle, self.ctx.stream_ptr(), self.NUM_DRONES, pd.state_view,
                                              pd.targets_view, pd.args_ref))
@@ -561,6 +563,7 @@ class CtrlAviary(PlacedFleetArrays, FleetObservation):
         else:
             tview = targets.view()
             targets.fill_const_hint(args)      # vel / acc / yaw the same for every drone: the kernel need not read them
+            targets.fill_period_hint(args)     # replicas of one task: the kernel need read the first period only
         if action is not None:
             args.action = self._action_ptr(action)
         defer = False
@@ -654,6 +657,10 @@ class CtrlAviary(PlacedFleetArrays, FleetObservation):
         return -1   # there is no PyBullet client; kept so example scripts keep running
 
     # ------------------------------------------------------------------ pieces
+    @staticmethod
+    def _tgt_period(targets) -> int:
+        return targets.tgt_period() if isinstance(targets, Targets) else 0
+
     @staticmethod
     def _targets_ptrs(targets):
         if isinstance(targets, WaypointTargets):

@@ -6,6 +6,7 @@ arithmetic happens in the HIP kernels behind the C-ABI.
 from __future__ import annotations
 
 import ctypes
+import math
 import os
 from typing import Optional, Sequence
 
@@ -309,7 +310,14 @@ class Targets(BlockedSoA):
     object holds +0.0 everywhere) and hands that to the launches as ``DSIM_OPT_TGT_CONST`` (:meth:`fill_const_hint`): the
     kernels then take vel / acc / yaw from their arguments instead of reading them (28 B per drone-step).  The fields are
     written as before, the hint only skips reads.  Once the tensor leaves the object (``data`` read from outside, or a view
-    of it from ``fields`` / ``raw_fields``) it can be written behind ``set()``'s back, and the object offers no hint again."""
+    of it from ``fields`` / ``raw_fields``) it can be written behind ``set()``'s back, and the object offers no hint again.
+
+    It also records, per field group, a period in drones with which the group repeats (a constant group: 1; per-drone values
+    given as a host array: found by :meth:`_host_period`; a device tensor or a ``Frozen``: none, finding one would need a
+    host sync), and hands their common multiple to the launches as ``dsim_step_args.tgt_period`` (:meth:`fill_period_hint`):
+    the plain fused-step kernels then read the targets of the first period only.  Env replicas that share one task are such
+    a fleet.  The period is given up on the same occasions as the constant hint, and does not move ``hint_epoch``: a
+    prepared launch refreshes it on every replay."""
 
     # field groups: (first field, fields, bit of dsim_step_args.tgt_const_mask)
     GROUPS = ((0, 3, 1), (3, 3, 2), (6, 3, 4), (9, 1, 8))
@@ -319,6 +327,7 @@ class Targets(BlockedSoA):
         # field group -> its constant as float32 BITS (a tuple of ints: what the fields hold for every drone), or a
         # ("frozen", Frozen) key / None for per-drone data.  Zeroed storage: every group is +0.0.
         self._const = {f0: (0,) * nf for f0, nf, _ in self.GROUPS}
+        self._period = {f0: 1 for f0, _, _ in self.GROUPS}    # field group -> drones it repeats with (None: not known to)
         self._hint_ok = not broadcast         # False for good once the tensor has been handed out
         self.hint_epoch = 0                   # bumped whenever const_hint() changes: prepared launches that carry the hint key on it
         if broadcast:
@@ -391,6 +400,38 @@ class Targets(BlockedSoA):
                 bits[f0:f0 + nf] = key
         return (mask, bits) if mask else None
 
+    def _host_period(self, b: np.ndarray) -> Optional[int]:
+        """The period of a group's per-drone values ``b`` (float32 bits [nf, n], what the fields will hold): the first column
+        that equals column 0, taken up to whole 256-drone tiles and blocks of the layout, and accepted only when every column
+        equals its counterpart in the first period.  None for a ragged or reordered fleet, or no period below n."""
+        n = self.n
+        if self.order is not None or n != self.n_pad or b.shape[1] != n:
+            return None
+        hit = np.flatnonzero((b[:, 1:] == b[:, :1]).all(0))
+        if hit.size == 0:
+            return None
+        p = math.lcm(int(hit[0]) + 1, 256, self.block or 1)
+        if n % p or p >= n or not (b.reshape(b.shape[0], n // p, p) == b[:, None, :p]).all():
+            return None
+        return p
+
+    def tgt_period(self) -> int:
+        """The period (drones) with which every target field repeats, as ``dsim_step_args.tgt_period``, or 0 for none: the
+        object offers no hint, a group is not known to repeat, or the common period does not divide the fleet below its size."""
+        if not self._hint_ok or self.order is not None or self.n != self.n_pad:
+            return 0
+        p = math.lcm(256, self.block or 1)
+        for f0, _, _ in self.GROUPS:
+            q = self._period.get(f0)
+            if q is None:
+                return 0
+            p = math.lcm(p, q)
+        return p if (self.n % p == 0 and p < self.n) else 0
+
+    def fill_period_hint(self, args: nat.StepArgs) -> None:
+        """Sets ``args.tgt_period`` (0 when the object knows no period)."""
+        args.tgt_period = self.tgt_period()
+
     def fill_const_hint(self, args: nat.StepArgs) -> None:
         """Sets DSIM_OPT_TGT_CONST, the mask and the constants (their exact bits) on ``args`` when the object offers the hint."""
         h = self.const_hint()
@@ -410,7 +451,7 @@ class Targets(BlockedSoA):
                 continue
             # the same broadcast constant as last time (e.g. the zero target_vel / target_acc of every
             # computeControl call): the fields already hold it, skip the fleet-sized fill
-            key = None
+            key, period = None, None
             if isinstance(val, Frozen):
                 # the caller's promise (see Frozen): the same OBJECT as last time means the fields already hold it — a
                 # fleet-sized copy per computeControl call is 7 % of the reference-shaped loop.  The object is held, so
@@ -428,6 +469,13 @@ class Targets(BlockedSoA):
                 if self._const.get(f0) == key:
                     continue
                 val = np.asarray(key, dtype=np.uint32).view(np.float32)       # exactly the bits recorded
+                period = 1
+            elif not self.broadcast and (not torch.is_tensor(val) or val.device.type == "cpu"):
+                # per-drone values on the host: converted here, and what the fields receive is what the period was found in
+                val = np.ascontiguousarray((val.detach().numpy() if torch.is_tensor(val) else np.asarray(val)).astype(np.float32,
+                                                                                                                     copy=False))
+                h = val.reshape(nf, -1)
+                period = 1 if h.shape[1] == 1 else self._host_period(h.view(np.uint32))
             t = torch.as_tensor(val, dtype=torch.float32, device=dev).reshape(nf, -1)
             if self.broadcast:
                 self._data[f0:f0 + nf, :] = t
@@ -436,11 +484,13 @@ class Targets(BlockedSoA):
                     t = t.expand(nf, self.n)
                 BlockedSoA.set_fields(self, f0, t)
             self._record(f0, key)
+            self._period[f0] = period
 
     def set_fields(self, f0: int, values: torch.Tensor) -> None:
         if any(self._is_const(k) for k in self._const.values()):
             self.hint_epoch += 1
         self._const = {}                      # written behind set()'s back: nothing is known to be constant any more
+        self._period = {}                     # ... or to repeat
         super().set_fields(f0, values)
 
 
@@ -497,7 +547,7 @@ class TrajectoryTargets(Targets):
 
     def __init__(self, ctx: Context, n: int, coeffs, TS, t0=None, offsets=None, layout: str = "soa", pad: int = 256):
         super().__init__(ctx, n, layout, pad=pad)
-        self._const, self._hint_ok = {}, False      # every field is written on the device (dsim_traj_sample)
+        self._const, self._period, self._hint_ok = {}, {}, False      # every field is written on the device (dsim_traj_sample)
         self.ctx = ctx
         dev = ctx.device
         self.coeffs = torch.as_tensor(np.ascontiguousarray(coeffs), dtype=torch.float64).to(dev)

@@ -303,6 +303,7 @@ class PlacedFleetArrays:
         before = self.ctx.query(nat.QUERY_GROUND_CONTACTS)
         args = self.step_args(control_timestep)
         targets.fill_const_hint(args)          # (the trials time the kernel the launches will run)
+        targets.fill_period_hint(args)
         sview, tview, ref = self.state.view(), targets.view(), ctypes.byref(args)
         filled = set()
 

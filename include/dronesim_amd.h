@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define DSIM_ABI_VERSION 10
+#define DSIM_ABI_VERSION 11
 #define DSIM_MAX_ACT 6     /* actuators per vehicle (quad 4, morphing hexa 6) */
 #define DSIM_MAX_TYPES 8
 
@@ -232,7 +232,8 @@ enum {
                                        kernels of dsim_step (plain targets: no waypoint table, n_steps 1, no explicit
                                        action) and of dsim_control2: 7 of the 10 target floats are not read, 28 bytes less
                                        per drone-step (232 -> 204, chained 184 -> 156, control 212 -> 184).  Every other
-                                       kernel and mask reads the view as without the bit.                               */
+                                       kernel and mask reads the view as without the bit.  A target view that repeats
+                                       with a period is described by dsim_step_args.tgt_period (no option bit).         */
   /* -- scheduling (results do not depend on it) ---------------------------------------------------------------------- */
   DSIM_OPT_DEFER_FALLBACK = 1u << 11 /* dsim_step / dsim_control2 of a table with a morphing hexa do NOT launch the deferred
                                        WLS fallback pass behind the step; the caller launches dsim_wls_fallback itself —
@@ -342,6 +343,17 @@ typedef struct dsim_step_args {
   /* -- constant target groups (DSIM_OPT_TGT_CONST; zeroed arguments: no hint) ---------------------------------------------- */
   uint32_t tgt_const_mask;  /* bit 0 pos, 1 vel, 2 acc, 3 yaw: the groups whose fields hold tgt_const for every drone      */
   float    tgt_const[10];   /* pos3 vel3 acc3 yaw; the entries of the groups outside the mask are ignored                 */
+  /* -- periodic targets (traffic only: results do not depend on it; zeroed arguments: no hint) ----------------------------
+   * 0: no hint.  Otherwise the caller asserts that, for every drone i < n_pad, every field of the targets view holds the
+   * value (bit for bit) the same field holds for drone i mod tgt_period: env replicas that share a task, or a constant group
+   * (a period of 1 taken up to a whole tile).  The library MAY then read the targets of the first period only, and may ignore
+   * the hint; the whole view must hold the values either way.  Honoured on a per-drone view (no DSIM_OPT_BCAST_TGT) without a
+   * waypoint table, when tgt_period is a multiple of 256 and of the view's block (no condition for plain SoA), divides n_pad
+   * and is below it; otherwise ignored, never an error.  The kernels that honour it are the whole-tile quad kernels of
+   * dsim_step with plain targets (n_steps 1, no explicit action), with or without DSIM_OPT_TGT_CONST: 12 (with it) or 40
+   * (without it) bytes per drone-step less read from HBM, the first period staying in L2.  Every other kernel — the hexa,
+   * mixed, run and general kernels, dsim_control2, dsim_physics — reads the whole view.                                 */
+  int64_t  tgt_period;
 } dsim_step_args;
 
 typedef struct dsim_ctx dsim_ctx;
