@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """bench.py — drone-steps/s of the fused Env.step()+INDI kernel on synthetic fleets.
 
-    python bench.py --gpus N --steps K --warmup W [--workload NAME] [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--workload NAME] [--dump-outputs DIR] [--full]
+
+A plain run does what its headline needs and nothing more: set-up, W warm-up steps, K timed steps, the outputs of the last
+one (--dump-outputs), the JSON line.  Everything else it can measure or check runs only with --full (see below).
 
 N > 1: when the process was not started by a launcher (WORLD_SIZE unset) bench.py starts N ranks itself —
 ``python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 bench.py ...`` as a CHILD
@@ -25,8 +28,12 @@ Workloads:
                           config's density (524 288 drones in 1024 m x 512 m = one per m^2: every rank owns a
                           128 m x 512 m slab), halo exchange of positions between neighbouring slabs
   hexa, mixed             4 194 304 hexa_6DOF / interleaved quad+hexa drones (roofline-size variants)
-The N = 1 run also measures the literal BASELINE configs 1-3 at their own sizes ("baseline_configs") and further
-variants ("also"); they go to bench_extras.json beside this file, and the line names it ("extras_file").
+--full adds what is measured or checked beside the headline.  N = 1: the literal BASELINE configs 1-3 at their own sizes
+("baseline_configs") and further variants ("also"), which go to bench_extras.json beside this file (the line names it:
+"extras_file"), and the CPU baseline ("cpu_baseline"); --no-also / --no-cpu-baseline leave them out again.  N > 1, default
+workload: config 5 on all ranks ("config5_all_ranks").  config5: the vector-pipe roofline ("roofline_valu", one rank) and the
+exchange's size and time ("exchange", N > 1 or --mirror-peer).  DSIM_BENCH_FORCE_DIST=1 at N = 1: the RCCL self-test
+("rccl_selftest").
 """
 import argparse
 import gc
@@ -73,8 +80,12 @@ def parse(argv=None):
     p.add_argument("--substeps", type=int, default=1)
     p.add_argument("--layout", default="tile64", choices=["soa", "tile64", "tile256", "tile1024", "tile4096"])
     p.add_argument("--noise-seed", type=int, default=1)
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--no-also", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="also measure and check what the headline does not need: other sizes and variants, the CPU baseline, "
+                        "config 5 on all ranks, per-workload rooflines and exchange figures, the RCCL self-test")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    p.add_argument("--no-also", action="store_true",
+                   help="with --full: leave out the other sizes and variants (baseline_configs, also, config5_all_ranks)")
     p.add_argument("--stream", choices=["auto", "on", "off"], default="auto",
                    help="nontemporal state accesses: DSIM_OPT_STREAM_ON/_OFF (A/B knob; default: the library's size rule)")
     p.add_argument("--slab-m", type=float, default=128.0,
@@ -994,7 +1005,10 @@ def main(argv=None):
     achieved = fl.n * bytes_per / launch_s / 1e9
     rank_rows = gather_ranks(dist, red_dev, [dev_s_local / steps_timed * 1e6, wall_local / steps_timed * 1e6,
                                              float(torch.cuda.current_device()), float(rank)])
-    exchange = exchange_report(fl, dist, red_dev) if (a.workload == "config5" and (world > 1 or a.mirror_peer)) else None
+    # what is measured or checked beside the headline's own figures: only with --full
+    also_on, cpu_on = a.full and not a.no_also, a.full and not a.no_cpu_baseline
+    exchange = (exchange_report(fl, dist, red_dev) if (a.full and a.workload == "config5" and (world > 1 or a.mirror_peer))
+                else None)
 
     if rank == 0:
         traffic, traffic_source = None, None
@@ -1037,7 +1051,7 @@ def main(argv=None):
                          "kernel": kernel, "bytes_per_drone_step": bytes_per,
                          "launch_us": launch_s * 1e6},
         }
-        if a.workload == "config5" and world == 1 and not a.mirror_peer:
+        if a.full and a.workload == "config5" and world == 1 and not a.mirror_peer:
             try:
                 out["roofline_valu"] = valu_roofline(torch, fl, launch_s)
             except Exception as ex:
@@ -1051,14 +1065,14 @@ def main(argv=None):
             out["exchange"] = exchange
         if dumped is not None:
             out["dumped_outputs"] = {"dir": a.dump_outputs, "drones": min(fl.n, DUMP_MAX_DRONES), "arrays": dumped}
-        if force_dist and world == 1:
+        if a.full and force_dist and world == 1:
             out["rccl_selftest"] = rccl_selftest(dist, fl, red_dev)
         if a.mirror_peer:
             out["config"]["synthetic_neighbour"] = ("--mirror-peer: ONE rank whose neighbour is its own reflection across the slab edge "
                                                     "(MirrorDist: a device-side wire); traces the exchange path, not a multi-GPU run")
     else:
         out = {}
-    if world > 1 and a.workload == "config2x1024" and not a.no_also:
+    if world > 1 and a.workload == "config2x1024" and also_on:
         with Watchdog(240, rank, out):
             try:
                 e5 = config5_all_ranks(a, local, rank, world, dist, red_dev, barrier, options)
@@ -1073,7 +1087,7 @@ def main(argv=None):
                 out["self_check"]["failed"] = sorted(k for k, v in out["self_check"]["checks"].items() if not v)
                 out["self_check"]["ok"] = not out["self_check"]["failed"]
     if rank == 0:
-        if world == 1 and not a.no_also:
+        if world == 1 and also_on:
             # ---- BASELINE.json configs 1-3 at their LITERAL sizes and example settings --------------------------------
             # (fleet, replicas, phys_substeps, waypoint table, Env.steps per launch)
             base = {}
@@ -1183,7 +1197,7 @@ def main(argv=None):
                 also["config5_shard_two_call"]["ratio_to_fused_chain"] = (
                     also["config5_shard_two_call"]["loop_us_device"] / also["config5_shard_65536_mixed_downwash"]["launch_us"])
             out["also"] = also
-        if world == 1 and not a.no_cpu_baseline:
+        if world == 1 and cpu_on:
             out["cpu_baseline"] = cpu_baseline(a.substeps)
         extras = {k: out.pop(k) for k in ("baseline_configs", "also") if k in out}
         if extras:

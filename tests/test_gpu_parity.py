@@ -2247,6 +2247,36 @@ def test_bench_settled_form_times_launches_right_behind_the_settling_load(gpu):
     assert 0.5 < a["roofline"]["launch_us"] / b["roofline"]["launch_us"] < 2.0
 
 
+def test_bench_plain_run_measures_the_headline_only(gpu):
+    """A plain `bench.py` run sets up, warms up, times exactly --steps steps and prints its line; what it can measure or check
+    beside the headline waits for --full.  Config 5 on one rank: its vector-pipe roofline (steps and a brute-force pair count
+    of its own) is in the --full line only; neither run writes the extras file when --no-also is given or implied."""
+    import json
+    import subprocess
+    import sys
+    import bench
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    extras_before = os.stat(bench.EXTRAS_FILE).st_mtime_ns if os.path.exists(bench.EXTRAS_FILE) else None
+    lines = {}
+    for mode, extra in (("plain", []), ("full", ["--full", "--no-also", "--no-cpu-baseline"])):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "config5", "--steps", "10", "--warmup", "2"]
+                           + extra, capture_output=True, text=True, timeout=600, env=env, cwd=root)
+        assert r.returncode == 0, r.stderr[-3000:]
+        out = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(out) == 1
+        lines[mode] = json.loads(out[0])
+    plain, full = lines["plain"], lines["full"]
+    for d in (plain, full):
+        assert d["steps_timed"] == 10 and d["timed_regions"] == 1 and d["value"] > 0 and d["ms_per_step"] > 0
+        assert d["unit"] == "drone-steps/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+        assert d["config"]["drones_per_gpu"] == 65536 and d["roofline"]["launch_us"] > 0
+        assert not {"also", "baseline_configs", "extras_file", "cpu_baseline", "exchange", "rccl_selftest"} & set(d)
+    assert "roofline_valu" not in plain
+    assert full["roofline_valu"]["bound"] == "valu" and full["roofline_valu"]["useful_pairs_per_step"] > 0
+    assert (os.stat(bench.EXTRAS_FILE).st_mtime_ns if os.path.exists(bench.EXTRAS_FILE) else None) == extras_before
+
+
 @pytest.mark.parametrize("workload", ["config2", "two_call_loop"])
 def test_bench_dump_outputs_are_those_of_the_last_timed_step(gpu, tmp_path, workload):
     """`bench.py --dump-outputs DIR` times exactly --steps steps and writes what the timed path handed its caller after them:

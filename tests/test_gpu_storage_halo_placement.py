@@ -593,7 +593,7 @@ def test_bench_config5_line_two_gloo_ranks(gpu):
     """bench.py --gpus 2 --workload config5 under DSIM_BENCH_BACKEND=gloo: the line carries the exchange's size and time."""
     env = dict(os.environ, DSIM_BENCH_BACKEND="gloo", PYTHONPATH=ROOT)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "config5", "--steps", "20",
-                        "--warmup", "4", "--no-also", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=600)
+                        "--warmup", "4", "--full", "--no-also", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
     line = [ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1]
     d = json.loads(line)

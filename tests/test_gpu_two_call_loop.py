@@ -442,7 +442,7 @@ def test_rccl_runs_at_world_size_one(gpu):
     env.update(DSIM_BENCH_FORCE_DIST="1", HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--workload", "config4", "--steps", "20",
-           "--warmup", "3", "--no-also", "--no-cpu-baseline"]
+           "--warmup", "3", "--full", "--no-also", "--no-cpu-baseline"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=420, env=env, cwd=ROOT)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])

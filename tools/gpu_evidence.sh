@@ -10,9 +10,9 @@ case "${1:-a}" in
 a)
   DSIM_MARGINS_OUT=$OUT/margins.json timeout -k 10 1000 python -m pytest tests -m gpu -q --no-header -p no:cacheprovider > $OUT/pytest.log 2>&1
   echo "pytest rc=$? $(tail -1 $OUT/pytest.log)"
-  timeout -k 10 600 python bench.py > $OUT/bench.json 2> $OUT/bench.err
+  timeout -k 10 600 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
   echo "bench rc=$?"; head -c 600 $OUT/bench.json; echo
-  DSIM_BENCH_FORCE_DIST=1 timeout -k 10 600 python bench.py --no-also --no-cpu-baseline > $OUT/bench_rccl_world1.json 2> $OUT/bench_rccl_world1.err
+  DSIM_BENCH_FORCE_DIST=1 timeout -k 10 600 python bench.py --full --no-also --no-cpu-baseline > $OUT/bench_rccl_world1.json 2> $OUT/bench_rccl_world1.err
   echo "bench rccl world 1 rc=$?"; tail -c 400 $OUT/bench_rccl_world1.err
   ./tools/membench 4194304 > $OUT/membench.txt 2>&1; ./tools/membench --json 4194304 >> $OUT/membench.txt 2>&1
   bash tools/profile_sq.sh r06_main
