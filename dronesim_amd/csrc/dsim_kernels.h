@@ -23,6 +23,7 @@
 #include <math.h>
 #include <string.h>
 #include <new>
+#include <type_traits>
 
 #include "../../include/dronesim_amd.h"
 #include "dsim_device.h"
@@ -747,32 +748,11 @@ static inline bool stream_policy(const dsim_step_args* a, long long n_pad, doubl
   return (double)n_pad * bytes_per_drone > 192.0 * 1024 * 1024;
 }
 
-// ... of a general kernel that serves homogeneous and mixed fleets with ONE instance per (noise, actuator count): the type waterfall
-// runs once for a homogeneous fleet (type_id null: type 0), its partition is skipped — these kernels are not on a measured path, and
-// the UNIFORM specialisation doubled their instance count (round 6: 293 -> ... instances)
-#define DSIM_LAUNCH_GEN_ANY(KERNEL, NOISE, SIX, g, a, stream)                                           \
-  do {                                                                                                  \
-    const dim3 b_(256);                                                                                 \
-    switch (((NOISE) ? 2 : 0) | ((SIX) ? 1 : 0)) {                                                      \
-      case 0: hipLaunchKernelGGL((KERNEL<false, false, 4>), g, b_, 0, stream, a); break;                \
-      case 1: hipLaunchKernelGGL((KERNEL<false, false, 6>), g, b_, 0, stream, a); break;                \
-      case 2: hipLaunchKernelGGL((KERNEL<true, false, 4>), g, b_, 0, stream, a); break;                 \
-      default: hipLaunchKernelGGL((KERNEL<true, false, 6>), g, b_, 0, stream, a); break;                \
-    }                                                                                                   \
-  } while (0)
-
-// (noise, uniform) x actuator count dispatch of a general kernel
-#define DSIM_LAUNCH_GEN(KERNEL, NOISE, UNI, SIX, g, a, stream)                                          \
-  do {                                                                                                  \
-    const dim3 b_(256);                                                                                 \
-    switch (((NOISE) ? 4 : 0) | ((UNI) ? 2 : 0) | ((SIX) ? 1 : 0)) {                                    \
-      case 0: hipLaunchKernelGGL((KERNEL<false, false, 4>), g, b_, 0, stream, a); break;                \
-      case 1: hipLaunchKernelGGL((KERNEL<false, false, 6>), g, b_, 0, stream, a); break;                \
-      case 2: hipLaunchKernelGGL((KERNEL<false, true, 4>), g, b_, 0, stream, a); break;                 \
-      case 3: hipLaunchKernelGGL((KERNEL<false, true, 6>), g, b_, 0, stream, a); break;                 \
-      case 4: hipLaunchKernelGGL((KERNEL<true, false, 4>), g, b_, 0, stream, a); break;                 \
-      case 5: hipLaunchKernelGGL((KERNEL<true, false, 6>), g, b_, 0, stream, a); break;                 \
-      case 6: hipLaunchKernelGGL((KERNEL<true, true, 4>), g, b_, 0, stream, a); break;                  \
-      default: hipLaunchKernelGGL((KERNEL<true, true, 6>), g, b_, 0, stream, a); break;                 \
-    }                                                                                                   \
-  } while (0)
+// Runtime bools -> template flags: f(std::true_type / std::false_type, ...) in the order of the bools, read as N() in a template
+// argument list.  Every combination of the flags instantiates f, and with it every kernel f names: a combination the host never
+// selects must still name an instance that exists (or be cut off with if constexpr), else it adds kernels nothing launches.
+template <class F> inline void with_flags(F&& f) { f(); }
+template <class F, class... B> inline void with_flags(F&& f, bool b, B... rest) {
+  if (b) with_flags([&](auto... t) { f(std::true_type{}, t...); }, rest...);
+  else with_flags([&](auto... t) { f(std::false_type{}, t...); }, rest...);
+}

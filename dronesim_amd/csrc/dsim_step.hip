@@ -308,28 +308,14 @@ int dsim_step(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, dsim_view
       if (blocks < 0) return blocks;
       if (blocks > 0) {
         const dim3 g((unsigned)blocks);
-#define DSIM_RUNS_CASE2(S_, A_)                                                                              \
-  do { if (noise) { if (nt) hipLaunchKernelGGL((k_step_runs<true, !A_, S_, A_>), g, b, 0, st_, a, rt);     \
-                    else hipLaunchKernelGGL((k_step_runs<true, false, S_, A_>), g, b, 0, st_, a, rt); }     \
-       else { if (nt) hipLaunchKernelGGL((k_step_runs<false, !A_, S_, A_>), g, b, 0, st_, a, rt);          \
-              else hipLaunchKernelGGL((k_step_runs<false, false, S_, A_>), g, b, 0, st_, a, rt); } } while (0)
-#define DSIM_RUNS_CASE(S_) do { if (args->action) DSIM_RUNS_CASE2(S_, true); else DSIM_RUNS_CASE2(S_, false); } while (0)
-        if (a.substeps == 1) DSIM_RUNS_CASE(true); else DSIM_RUNS_CASE(false);
-#undef DSIM_RUNS_CASE
-#undef DSIM_RUNS_CASE2
+        with_flags([&](auto N, auto NT, auto S1, auto ACT) {      // (the ACT instances: default cache policy only, see above)
+          hipLaunchKernelGGL((k_step_runs<N(), NT() && !ACT(), S1(), ACT()>), g, b, 0, st_, a, rt);
+        }, noise, nt, a.substeps == 1, args->action != nullptr);
       }
       if (any_hexa) fb_finish(ctx, a, st_);
       bin_next_commit(ctx, n, args, a);
       return (int)hipGetLastError();
     }
-#define DSIM_RUN_CASE2(H_, S_)                                                                        \
-  /* (the quad law on six actuators — hexa_6DOF_simple.urdf — with the default cache policy only: four streaming instances less) */ \
-  do { constexpr bool T_ok = (H_) != DSIM_DEV_KIND_HEXA_QUADLAW;                                                                   \
-       if (noise) { if (nt) hipLaunchKernelGGL((k_step_run<H_, true, T_ok, S_>), g, b, 0, st_, a);    \
-                    else hipLaunchKernelGGL((k_step_run<H_, true, false, S_>), g, b, 0, st_, a); }    \
-       else { if (nt) hipLaunchKernelGGL((k_step_run<H_, false, T_ok, S_>), g, b, 0, st_, a);         \
-              else hipLaunchKernelGGL((k_step_run<H_, false, false, S_>), g, b, 0, st_, a); } } while (0)
-#define DSIM_RUN_CASE(H_) do { if (a.substeps == 1) DSIM_RUN_CASE2(H_, true); else DSIM_RUN_CASE2(H_, false); } while (0)
     for (int r = 0; r < n_runs; ++r) {
       const dsim_type_run& run = runs[r];
       if (run.count == 0) continue;
@@ -338,12 +324,13 @@ int dsim_step(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, dsim_view
       a.first = run.first & ~255LL; a.lo = run.first; a.last = run.first + run.count; a.run_type = run.type;
       const dim3 g(grid_for(a.last - a.first));
       const int kind = ctx->h_types[run.type].kind;
-      if (kind == DSIM_KIND_HEXA6DOF) DSIM_RUN_CASE(DSIM_DEV_KIND_HEXA);
-      else if (kind == DSIM_KIND_HEXA_QUADLAW) DSIM_RUN_CASE(DSIM_DEV_KIND_HEXA_QUADLAW);
-      else DSIM_RUN_CASE(DSIM_DEV_KIND_QUAD);
+      with_flags([&](auto N, auto NT, auto S1) {
+        if (kind == DSIM_KIND_HEXA6DOF) hipLaunchKernelGGL((k_step_run<DSIM_DEV_KIND_HEXA, N(), NT(), S1()>), g, b, 0, st_, a);
+        // (the quad law on six actuators — hexa_6DOF_simple.urdf — with the default cache policy only: four streaming instances less)
+        else if (kind == DSIM_KIND_HEXA_QUADLAW) hipLaunchKernelGGL((k_step_run<DSIM_DEV_KIND_HEXA_QUADLAW, N(), false, S1()>), g, b, 0, st_, a);
+        else hipLaunchKernelGGL((k_step_run<DSIM_DEV_KIND_QUAD, N(), NT(), S1()>), g, b, 0, st_, a);
+      }, noise, nt, a.substeps == 1);
     }
-#undef DSIM_RUN_CASE
-#undef DSIM_RUN_CASE2
     if (any_hexa) fb_finish(ctx, a, st_);
     bin_next_commit(ctx, n, args, a);
     return (int)hipGetLastError();
@@ -358,22 +345,13 @@ int dsim_step(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, dsim_view
       const bool ext = multi;
       const bool ch = (args->options & DSIM_OPT_CHAINED) != 0;
       const bool tc = tgt_const_honoured(args);          // (the plain instances: vel / acc / yaw from the arguments)
-#define DSIM_PLAIN_CASE(N_, T_, C_)                                                                 \
-  do { if (ch && a.substeps == 1) hipLaunchKernelGGL((k_step_fast<N_, T_, false, true, 1, false, C_>), g, b, 0, st_, a); \
-       else if (ch) hipLaunchKernelGGL((k_step_fast<N_, T_, false, true, 0, false, C_>), g, b, 0, st_, a); \
-       else if (a.substeps == 1) hipLaunchKernelGGL((k_step_fast<N_, T_, false, false, 1, false, C_>), g, b, 0, st_, a); \
-       else hipLaunchKernelGGL((k_step_fast<N_, T_, false, false, 0, false, C_>), g, b, 0, st_, a); } while (0)
-#define DSIM_FAST_CASE(N_, T_)                                                                      \
-  do { if (ext) { if (ch) hipLaunchKernelGGL((k_step_fast<N_, T_, true, true>), g, b, 0, st_, a);   \
-                  else hipLaunchKernelGGL((k_step_fast<N_, T_, true, false>), g, b, 0, st_, a); }   \
-       else { if (args->action) { if (a.substeps == 1) hipLaunchKernelGGL((k_step_fast<N_, false, false, false, 1, true>), g, b, 0, st_, a); \
-                                  else hipLaunchKernelGGL((k_step_fast<N_, false, false, false, 0, true>), g, b, 0, st_, a); } \
-              else if (tc) DSIM_PLAIN_CASE(N_, T_, true);                                           \
-              else DSIM_PLAIN_CASE(N_, T_, false); } } while (0)
-      if (noise) { if (nt) DSIM_FAST_CASE(true, true); else DSIM_FAST_CASE(true, false); }
-      else { if (nt) DSIM_FAST_CASE(false, true); else DSIM_FAST_CASE(false, false); }
-#undef DSIM_FAST_CASE
-#undef DSIM_PLAIN_CASE
+      // (TC: the plain instances only.  EXT: any sub-step count.  ACT: never with EXT or CH (both kept out above), the default
+      // cache policy only, as k_step_runs)
+      with_flags([&](auto N, auto NT, auto CH, auto S1, auto TC) {
+        if (ext) hipLaunchKernelGGL((k_step_fast<N(), NT(), true, CH()>), g, b, 0, st_, a);
+        else if (args->action) hipLaunchKernelGGL((k_step_fast<N(), false, false, false, S1() ? 1 : 0, true>), g, b, 0, st_, a);
+        else hipLaunchKernelGGL((k_step_fast<N(), NT(), false, CH(), S1() ? 1 : 0, false, TC()>), g, b, 0, st_, a);
+      }, noise, nt, ch, a.substeps == 1, tc);
       first = tiles * 256;
     }
   }
@@ -387,15 +365,9 @@ int dsim_step(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, dsim_view
     a.fb.entries = ctx->d_fb;
     fb_open = true;
     const dim3 g((unsigned)tiles);
-#define DSIM_HEXA_CASE2(S_, A_)                                                                     \
-  do { if (noise) { if (nt) hipLaunchKernelGGL((k_step_hexa<true, !A_, S_, A_>), g, b, 0, st_, a);  \
-                    else hipLaunchKernelGGL((k_step_hexa<true, false, S_, A_>), g, b, 0, st_, a); }  \
-       else { if (nt) hipLaunchKernelGGL((k_step_hexa<false, !A_, S_, A_>), g, b, 0, st_, a);       \
-              else hipLaunchKernelGGL((k_step_hexa<false, false, S_, A_>), g, b, 0, st_, a); } } while (0)
-#define DSIM_HEXA_CASE(S_) do { if (args->action) DSIM_HEXA_CASE2(S_, true); else DSIM_HEXA_CASE2(S_, false); } while (0)
-    if (a.substeps == 1) DSIM_HEXA_CASE(true); else DSIM_HEXA_CASE(false);
-#undef DSIM_HEXA_CASE
-#undef DSIM_HEXA_CASE2
+    with_flags([&](auto N, auto NT, auto S1, auto ACT) {        // (the ACT instances: default cache policy only, as k_step_runs)
+      hipLaunchKernelGGL((k_step_hexa<N(), NT() && !ACT(), S1(), ACT()>), g, b, 0, st_, a);
+    }, noise, nt, a.substeps == 1, args->action != nullptr);
     first = tiles * 256;
     if (first >= a.n_pad) fb_finish(ctx, a, st_);
   }

@@ -411,7 +411,7 @@ int step_general(dsim_ctx* ctx, int64_t n, const dsim_view& state, const dsim_vi
   bool any_quadlaw6 = false;
   for (int t = 0; t < ctx->n_types; ++t) any_quadlaw6 |= ctx->h_types[t].kind == DSIM_KIND_HEXA_QUADLAW;
   a.first = first;
-  const dim3 g(grid_for(a.n_pad - first));
+  const dim3 g(grid_for(a.n_pad - first)), b(256);
   const bool lean = !args->action && !args->noise_replay && !a.wp_table && a.n_steps == 1 && !phys_opts;     // (fine_slow is a phys_opt)
   if (lean && !uni && a.tg.base && ctx->n_types <= 4 && ctx->max_act == 6 && !any_quadlaw6) {
     // a heterogeneous fleet kept in the CALLER's own order (CtrlAviary(storage="caller"); storage="auto" stores it
@@ -432,42 +432,36 @@ int step_general(dsim_ctx* ctx, int64_t n, const dsim_view& state, const dsim_vi
     if (tiled) {
       // two waves per tile, slot groups dealt round-robin (wave-tiled layout)
       const dim3 gm((unsigned)((a.n_pad - first + 127) / 128)), bm(128);
-#define DSIM_MIXED4_CASE3(S_, Y_, B_)                                                                             \
-do { if (noise) { if (nt) hipLaunchKernelGGL((k_step_mixed4<true, true, S_, Y_, B_>), gm, bm, 0, st_, a);            \
-                  else hipLaunchKernelGGL((k_step_mixed4<true, false, S_, Y_, B_>), gm, bm, 0, st_, a); }            \
-     else { if (nt) hipLaunchKernelGGL((k_step_mixed4<false, true, S_, Y_, B_>), gm, bm, 0, st_, a);                 \
-            else hipLaunchKernelGGL((k_step_mixed4<false, false, S_, Y_, B_>), gm, bm, 0, st_, a); } } while (0)
-#define DSIM_MIXED4_CASE2(S_, Y_) do { if (a.bin.count) DSIM_MIXED4_CASE3(S_, Y_, true); else DSIM_MIXED4_CASE3(S_, Y_, false); } while (0)
       // (a table of three types runs the four-type instance: an empty type has no ballots set and no slot group — sixteen
       // instances less for a storage order the host avoids by default)
-        // (round 6: and so does a table of two — 181.2 against 181.4 us for the two-type instance at 4 194 304 drones, same box:
-        // another sixteen instances less.  The three-wave form below does NOT bear it: five waves for two types 300 against 207 us.)
-#define DSIM_MIXED4_CASE(S_) DSIM_MIXED4_CASE2(S_, 4)
-      if (a.substeps == 1) DSIM_MIXED4_CASE(true); else DSIM_MIXED4_CASE(false);
-#undef DSIM_MIXED4_CASE
-#undef DSIM_MIXED4_CASE2
-#undef DSIM_MIXED4_CASE3
+      // (round 6: and so does a table of two — 181.2 against 181.4 us for the two-type instance at 4 194 304 drones, same box:
+      // another sixteen instances less.  The three-wave form below does NOT bear it: five waves for two types 300 against 207 us.)
+      with_flags([&](auto N, auto NT, auto S1, auto BIN) {
+        hipLaunchKernelGGL((k_step_mixed4<N(), NT(), S1(), 4, BIN()>), gm, bm, 0, st_, a);
+      }, noise, nt, a.substeps == 1, a.bin.count != nullptr);
     } else {
       // any other layout: one tile per workgroup, row DMAs in natural order, ballot partition
       const dim3 gm((unsigned)((a.n_pad - first + 127) / 128));
-#define DSIM_MIXED3_CASE2(W_, S_)                                                                                  \
-do { const dim3 bm(64 * W_);                                                                                    \
-     /* (default cache policy only: a fleet kept in the caller's order on a layout that is not wave-tiled is two steps off */ \
-     /*  every default — twelve streaming instances less, round 6)                                                        */ \
-     if (noise) hipLaunchKernelGGL((k_step_mixed3<true, false, W_, S_, false>), gm, bm, 0, st_, a);              \
-     else hipLaunchKernelGGL((k_step_mixed3<false, false, W_, S_, false>), gm, bm, 0, st_, a); } while (0)
-#define DSIM_MIXED3_CASE(W_) do { if (a.substeps == 1) DSIM_MIXED3_CASE2(W_, true); else DSIM_MIXED3_CASE2(W_, false); } while (0)
-      if (ctx->n_types == 2) DSIM_MIXED3_CASE(3); else if (ctx->n_types == 3) DSIM_MIXED3_CASE(4); else DSIM_MIXED3_CASE(5);
-#undef DSIM_MIXED3_CASE
-#undef DSIM_MIXED3_CASE2
+      // (default cache policy only: a fleet kept in the caller's order on a layout that is not wave-tiled is two steps off
+      //  every default — twelve streaming instances less, round 6)
+      with_flags([&](auto N, auto S1) {
+        if (ctx->n_types == 2) hipLaunchKernelGGL((k_step_mixed3<N(), false, 3, S1(), false>), gm, dim3(64 * 3), 0, st_, a);
+        else if (ctx->n_types == 3) hipLaunchKernelGGL((k_step_mixed3<N(), false, 4, S1(), false>), gm, dim3(64 * 4), 0, st_, a);
+        else hipLaunchKernelGGL((k_step_mixed3<N(), false, 5, S1(), false>), gm, dim3(64 * 5), 0, st_, a);
+      }, noise, a.substeps == 1);
     }
     if (any_hexa) fb_finish(ctx, a, st_);
     bin_next_commit(ctx, n, args, a);
     return (int)hipGetLastError();
   } else if (!six) {
-    if (lean) DSIM_LAUNCH_GEN(k_step_lean, noise, uni, false, g, a, st_);     // (fine_slow is a phys_opt: never lean)
-    else if (plane) DSIM_LAUNCH_GEN_ANY(k_step_plane, noise, false, g, a, st_);
-    else DSIM_LAUNCH_GEN_ANY(k_step_gen, noise, false, g, a, st_);
+    // (k_step_plane / k_step_gen serve homogeneous and mixed fleets with ONE instance per (noise, actuator count), UNIFORM = false:
+    // the type waterfall runs once for a homogeneous fleet (type_id null: type 0), its partition is skipped — these kernels are not
+    // on a measured path, and the UNIFORM specialisation doubled their instance count (round 6: 293 -> ... instances))
+    with_flags([&](auto N, auto UNI) {
+      if (lean) hipLaunchKernelGGL((k_step_lean<N(), UNI(), 4>), g, b, 0, st_, a);     // (fine_slow is a phys_opt: never lean)
+      else if (plane) hipLaunchKernelGGL((k_step_plane<N(), false, 4>), g, b, 0, st_, a);
+      else hipLaunchKernelGGL((k_step_gen<N(), false, 4>), g, b, 0, st_, a);
+    }, noise, uni);
   } else {
     // hexa fleets: deferred WLS fallbacks must land before the next Env.step reads cmd, so several
     // steps per call become several launches (each followed by the tiny fallback kernel)
@@ -480,9 +474,11 @@ do { const dim3 bm(64 * W_);                                                    
         a.fb.entries = ctx->d_fb;
       }
       fb_open = false;
-      if (lean && !a.action) DSIM_LAUNCH_GEN(k_step_lean, noise, uni, true, g, a, st_);
-      else if (plane) DSIM_LAUNCH_GEN_ANY(k_step_plane, noise, true, g, a, st_);
-      else DSIM_LAUNCH_GEN_ANY(k_step_gen, noise, true, g, a, st_);
+      with_flags([&](auto N, auto UNI) {        // (UNIFORM = false but for k_step_lean: as above)
+        if (lean && !a.action) hipLaunchKernelGGL((k_step_lean<N(), UNI(), 6>), g, b, 0, st_, a);
+        else if (plane) hipLaunchKernelGGL((k_step_plane<N(), false, 6>), g, b, 0, st_, a);
+        else hipLaunchKernelGGL((k_step_gen<N(), false, 6>), g, b, 0, st_, a);
+      }, noise, uni);
       fb_finish(ctx, a, st_);
       a.step_index += 1;
       a.action = nullptr;             // an explicit action applies to the first Env.step only

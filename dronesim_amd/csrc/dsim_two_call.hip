@@ -759,9 +759,9 @@ int dyn_check(const dsim_ctx* ctx, const dsim_step_args* args, const StepK& a) {
 
 int dyn_launch(bool ctrl, const StepK& a, bool nt, hipStream_t st) {
   const dim3 g(grid_for(a.n_pad)), b(256);
-  if (ctrl) { if (nt) hipLaunchKernelGGL((k_dyn<true, true>), g, b, 0, st, a); else hipLaunchKernelGGL((k_dyn<true, false>), g, b, 0, st, a); }
-  else if (a.obs_out) { if (nt) hipLaunchKernelGGL((k_dyn<false, true, true>), g, b, 0, st, a); else hipLaunchKernelGGL((k_dyn<false, false, true>), g, b, 0, st, a); }
-  else { if (nt) hipLaunchKernelGGL((k_dyn<false, true>), g, b, 0, st, a); else hipLaunchKernelGGL((k_dyn<false, false>), g, b, 0, st, a); }
+  with_flags([&](auto CTRL, auto NT, auto OBS) {       // (the observation rows: the physics half only)
+    hipLaunchKernelGGL((k_dyn<CTRL(), NT(), !CTRL() && OBS()>), g, b, 0, st, a);
+  }, ctrl, nt, a.obs_out != nullptr);
   return (int)hipGetLastError();
 }
 
@@ -804,14 +804,9 @@ int dsim_physics(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, float*
     const bool nt = stream_policy(args, state.n_pad, args->obs_out ? 216.0 : 136.0);
     const dim3 g((unsigned)(a.n_pad / 256)), b(256);
     const bool loop = a.substeps > 1 && !(noise && (a.options & DSIM_OPT_NOISE_FINE));      // (the looped instance: coarse lattice only)
-#define DSIM_PHYS_CASE(N_, T_) do {                                                                                     \
-      if (loop) { if (a.obs_out) hipLaunchKernelGGL((k_physics_fast<N_, T_, true, true>), g, b, 0, st_, a);             \
-                  else hipLaunchKernelGGL((k_physics_fast<N_, T_, false, true>), g, b, 0, st_, a); }                    \
-      else { if (a.obs_out) hipLaunchKernelGGL((k_physics_fast<N_, T_, true>), g, b, 0, st_, a);                        \
-             else hipLaunchKernelGGL((k_physics_fast<N_, T_, false>), g, b, 0, st_, a); } } while (0)
-    if (noise) { if (nt) DSIM_PHYS_CASE(true, true); else DSIM_PHYS_CASE(true, false); }
-    else { if (nt) DSIM_PHYS_CASE(false, true); else DSIM_PHYS_CASE(false, false); }
-#undef DSIM_PHYS_CASE
+    with_flags([&](auto N, auto NT, auto OBS, auto LOOP) {
+      hipLaunchKernelGGL((k_physics_fast<N(), NT(), OBS(), LOOP()>), g, b, 0, st_, a);
+    }, noise, nt, a.obs_out != nullptr, loop);
     if (args->obs_out && !obs_fused) return observe_impl(ctx, stream, n, state, last_action_out, args->obs_out, obs_w, 0);
     return (int)hipGetLastError();
   }
@@ -840,17 +835,11 @@ int dsim_physics(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, float*
       bin_next_prepare(ctx, n, args, &a, st_);
       if (blocks > 0) {
         const dim3 g((unsigned)blocks), b(256);
-#define DSIM_PRUNS_CASE2(N_, T_, S_) do {                                                                                      \
-          if (a.io_id) { const dim3 g2((unsigned)((blocks + 1) / 2) * DSIM_IO_PARTS), b2(DSIM_IO_WG);                                                 \
-                         if (a.obs_out) hipLaunchKernelGGL((k_physics_runs_io<N_, T_, true, S_>), g2, b2, 0, st_, a, rt);      \
-                         else hipLaunchKernelGGL((k_physics_runs_io<N_, T_, false, S_>), g2, b2, 0, st_, a, rt); }              \
-          else { if (a.obs_out) hipLaunchKernelGGL((k_physics_runs<N_, T_, true, S_>), g, b, 0, st_, a, rt);                  \
-                 else hipLaunchKernelGGL((k_physics_runs<N_, T_, false, S_>), g, b, 0, st_, a, rt); } } while (0)
-#define DSIM_PRUNS_CASE(N_, T_) do { if (a.substeps == 1) DSIM_PRUNS_CASE2(N_, T_, true); else DSIM_PRUNS_CASE2(N_, T_, false); } while (0)
-        if (noise) { if (nt) DSIM_PRUNS_CASE(true, true); else DSIM_PRUNS_CASE(true, false); }
-        else { if (nt) DSIM_PRUNS_CASE(false, true); else DSIM_PRUNS_CASE(false, false); }
-#undef DSIM_PRUNS_CASE
-#undef DSIM_PRUNS_CASE2
+        const dim3 g_io((unsigned)((blocks + 1) / 2) * DSIM_IO_PARTS), b_io(DSIM_IO_WG);
+        with_flags([&](auto N, auto NT, auto OBS, auto S1) {
+          if (a.io_id) hipLaunchKernelGGL((k_physics_runs_io<N(), NT(), OBS(), S1()>), g_io, b_io, 0, st_, a, rt);
+          else hipLaunchKernelGGL((k_physics_runs<N(), NT(), OBS(), S1()>), g, b, 0, st_, a, rt);
+        }, noise, nt, a.obs_out != nullptr, a.substeps == 1);
       }
       bin_next_commit(ctx, n, args, a);
       if (args->obs_out && !obs_fused) return observe_impl(ctx, stream, n, state, last_action_out, args->obs_out, obs_w, 0);
@@ -858,9 +847,11 @@ int dsim_physics(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, float*
     }
   }
   if (a.io_id) return DSIM_E_UNSUPPORTED;            // the caller's numbering is served by the run kernels only
-  const dim3 g(grid_for(a.n_pad));
-  if (args->options & DSIM_OPT_PLANE) DSIM_LAUNCH_GEN_ANY(k_physics_plane, noise, ctx->max_act == 6, g, a, st_);
-  else DSIM_LAUNCH_GEN_ANY(k_physics_gen, noise, ctx->max_act == 6, g, a, st_);
+  const dim3 g(grid_for(a.n_pad)), b(256);
+  with_flags([&](auto N, auto SIX) {         // (UNIFORM = false: one instance for homogeneous and mixed fleets, see step_general)
+    if (args->options & DSIM_OPT_PLANE) hipLaunchKernelGGL((k_physics_plane<N(), false, SIX() ? 6 : 4>), g, b, 0, st_, a);
+    else hipLaunchKernelGGL((k_physics_gen<N(), false, SIX() ? 6 : 4>), g, b, 0, st_, a);
+  }, noise, ctx->max_act == 6);
   if (args->obs_out)       // general fleets: the same rows by the observation kernel, behind the step on the stream
     return observe_impl(ctx, stream, n, state, last_action_out, args->obs_out, obs_w, 0);
   return (int)hipGetLastError();
@@ -893,23 +884,18 @@ int dsim_step_adaptor(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, c
     a.obs_out = obs_fused ? args->obs_out : nullptr;
     const bool nt = stream_policy(args, state.n_pad, args->obs_out ? 304.0 : 224.0);
     const dim3 gf((unsigned)(a.n_pad / 256));
-#define DSIM_AF2(M_, N_) do { if (nt) hipLaunchKernelGGL((k_adaptor_fast<M_, N_, true>), gf, b, 0, st_, a);                   \
-                              else hipLaunchKernelGGL((k_adaptor_fast<M_, N_, false>), gf, b, 0, st_, a); } while (0)
-#define DSIM_AF1(M_) do { if (noise) DSIM_AF2(M_, true); else DSIM_AF2(M_, false); } while (0)
-    if (mode == DSIM_ADAPT_VELOCITY) DSIM_AF1(DSIM_ADAPT_VELOCITY); else DSIM_AF1(DSIM_ADAPT_RPYT);
-#undef DSIM_AF1
-#undef DSIM_AF2
+    with_flags([&](auto N, auto NT) {
+      if (mode == DSIM_ADAPT_VELOCITY) hipLaunchKernelGGL((k_adaptor_fast<DSIM_ADAPT_VELOCITY, N(), NT()>), gf, b, 0, st_, a);
+      else hipLaunchKernelGGL((k_adaptor_fast<DSIM_ADAPT_RPYT, N(), NT()>), gf, b, 0, st_, a);
+    }, noise, nt);
     if (args->obs_out && !obs_fused) return observe_impl(ctx, stream, n, state, last_action_out, args->obs_out, 20, 0);
     return (int)hipGetLastError();
   }
   if (arows) return DSIM_E_UNSUPPORTED;               // (the general kernels take the action field-major)
-#define DSIM_ADAPT_CASE2(M_, P_)                                                                       \
-  do { if (noise) hipLaunchKernelGGL((k_adaptor<M_, true, false, P_>), g, b, 0, st_, a);                \
-       else hipLaunchKernelGGL((k_adaptor<M_, false, false, P_>), g, b, 0, st_, a); } while (0)       /* (one instance for homogeneous and mixed fleets: DSIM_LAUNCH_GEN_ANY) */
-#define DSIM_ADAPT_CASE(M_) do { if (args->options & DSIM_OPT_PLANE) DSIM_ADAPT_CASE2(M_, true); else DSIM_ADAPT_CASE2(M_, false); } while (0)
-  if (mode == DSIM_ADAPT_VELOCITY) DSIM_ADAPT_CASE(DSIM_ADAPT_VELOCITY); else DSIM_ADAPT_CASE(DSIM_ADAPT_RPYT);
-#undef DSIM_ADAPT_CASE
-#undef DSIM_ADAPT_CASE2
+  with_flags([&](auto N, auto PLANE) {         // (UNIFORM = false: one instance for homogeneous and mixed fleets, see step_general)
+    if (mode == DSIM_ADAPT_VELOCITY) hipLaunchKernelGGL((k_adaptor<DSIM_ADAPT_VELOCITY, N(), false, PLANE()>), g, b, 0, st_, a);
+    else hipLaunchKernelGGL((k_adaptor<DSIM_ADAPT_RPYT, N(), false, PLANE()>), g, b, 0, st_, a);
+  }, noise, (args->options & DSIM_OPT_PLANE) != 0);
   if (args->obs_out)       // general fleets: the rows by the observation kernel, behind the step on the stream
     return observe_impl(ctx, stream, n, state, last_action_out, args->obs_out, 20, 0);
   return (int)hipGetLastError();
@@ -935,13 +921,9 @@ int dsim_control2(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, dsim_
     const bool nt = stream_policy(args, state.n_pad, 212.0);
     const dim3 gt((unsigned)(a.n_pad / 256));
     const bool tc = tgt_const_honoured(args);
-#define DSIM_CTRL_CASE(C_)                                                                                  \
-  do { if (yaw_e_out) { if (nt) hipLaunchKernelGGL((k_control_fast<true, true, C_>), gt, b, 0, st_, a);     \
-                        else hipLaunchKernelGGL((k_control_fast<false, true, C_>), gt, b, 0, st_, a); }     \
-       else { if (nt) hipLaunchKernelGGL((k_control_fast<true, false, C_>), gt, b, 0, st_, a);              \
-              else hipLaunchKernelGGL((k_control_fast<false, false, C_>), gt, b, 0, st_, a); } } while (0)
-    if (tc) DSIM_CTRL_CASE(true); else DSIM_CTRL_CASE(false);
-#undef DSIM_CTRL_CASE
+    with_flags([&](auto NT, auto Y, auto TC) {
+      hipLaunchKernelGGL((k_control_fast<NT(), Y(), TC()>), gt, b, 0, st_, a);
+    }, nt, yaw_e_out != nullptr, tc);
     return (int)hipGetLastError();
   }
   {
@@ -967,12 +949,11 @@ int dsim_control2(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, dsim_
       const bool nt = stream_policy(args, state.n_pad, 236.0);
       if (blocks > 0) {
         const dim3 gr((unsigned)blocks);
-#define DSIM_CRUNS_CASE(T_, Y_) do {                                                                                         \
-          if (a.io_id) hipLaunchKernelGGL((k_control_runs_io<T_, Y_>), dim3((unsigned)((blocks + 1) / 2) * DSIM_IO_PARTS), dim3(DSIM_IO_WG), 0, st_, a, rt); \
-          else hipLaunchKernelGGL((k_control_runs<T_, Y_>), gr, b, 0, st_, a, rt); } while (0)
-        if (yaw_e_out) { if (nt) DSIM_CRUNS_CASE(true, true); else DSIM_CRUNS_CASE(false, true); }
-        else { if (nt) DSIM_CRUNS_CASE(true, false); else DSIM_CRUNS_CASE(false, false); }
-#undef DSIM_CRUNS_CASE
+        const dim3 g_io((unsigned)((blocks + 1) / 2) * DSIM_IO_PARTS), b_io(DSIM_IO_WG);
+        with_flags([&](auto NT, auto Y) {
+          if (a.io_id) hipLaunchKernelGGL((k_control_runs_io<NT(), Y()>), g_io, b_io, 0, st_, a, rt);
+          else hipLaunchKernelGGL((k_control_runs<NT(), Y()>), gr, b, 0, st_, a, rt);
+        }, nt, yaw_e_out != nullptr);
       }
       if (any_hexa) fb_finish(ctx, a, st_);
       return (int)hipGetLastError();
