@@ -47,6 +47,7 @@ OPT_NOISE_COARSE = 1 << 19
 # the caller asserts that the target groups of StepArgs.tgt_const_mask (bit 0 pos, 1 vel, 2 acc, 3 yaw) hold StepArgs.tgt_const for every
 # drone; the library may skip reading them (results do not depend on it; include/dronesim_amd.h)
 OPT_TGT_CONST = 1 << 20
+OPT_MEM_DERIVED = 1 << 21
 TGT_CONST_POS_PER_DRONE = 0xE   # the mask the kernels honour: pos per drone, vel / acc / yaw constant
 # StepArgs.tgt_period (no option bit, 0 = none): the caller asserts that every target field of drone i equals that of drone
 # i mod tgt_period; the library may read the first period only (results do not depend on it; include/dronesim_amd.h)

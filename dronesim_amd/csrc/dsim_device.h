@@ -100,6 +100,37 @@ __device__ __forceinline__ V3 mulT(const M3& R, V3 a) {  // R^T a
             R.m[2] * a.x + R.m[5] * a.y + R.m[8] * a.z);
 }
 
+// Body rates R(q)^T w (INDIControl.py:428-430), the value every control law stores as last_rates.  ONE definition with the
+// roundings pinned: no contraction inside, every fused multiply-add written out, so the result is a pure function of the bits
+// of q and w wherever it is inlined.  A launch under DSIM_OPT_MEM_DERIVED (and DSIM_OPT_CHAINED) recomputes the stored
+// last_rates from the stored rigid state with it and must get the very bits the law stored.  The order is the one the
+// compiler chose for the headline instance of k_step_fast before the roundings were pinned (matrix_from_quat + mulT under the
+// default contraction).  The hexa headline's outputs did not move when the helper came in; the quad headline's moved by 2e-6
+// (rigid state) / 2e-5 (commands) after 55 steps: products it shares with the law around it no longer contract THERE
+// (profiles/r09_ab_mem_derived.txt).
+__device__ __forceinline__ V3 body_rates(Q4 q, V3 w) {
+#pragma clang fp contract(off)
+  const float d = (__builtin_fmaf(q.x, q.x, q.y * q.y) + q.z * q.z) + q.w * q.w;
+  const float s = 2.0f * DSIM_RCP(d);
+  const float xs = q.x * s, ys = q.y * s, zs = q.z * s;
+  const float wx = q.w * xs, wy = q.w * ys, wz = q.w * zs;
+  const float yy = q.y * ys, zz = q.z * zs;
+  const float r0 = 1.0f - __builtin_fmaf(q.y, ys, zz), r1 = __builtin_fmaf(q.x, ys, -wz), r2 = __builtin_fmaf(q.x, zs, wy);
+  const float r3 = __builtin_fmaf(q.x, ys, wz), r4 = 1.0f - __builtin_fmaf(q.x, xs, zz), r5 = __builtin_fmaf(q.y, zs, -wx);
+  const float r6 = __builtin_fmaf(q.x, zs, -wy), r7 = __builtin_fmaf(q.y, zs, wx), r8 = 1.0f - __builtin_fmaf(q.x, xs, yy);
+  return v3(__builtin_fmaf(w.z, r6, __builtin_fmaf(w.y, r3, w.x * r0)),
+            __builtin_fmaf(w.z, r7, __builtin_fmaf(w.x, r1, w.y * r4)),
+            __builtin_fmaf(w.z, r8, __builtin_fmaf(w.x, r2, w.y * r5)));
+}
+// The same value on a quaternion the compiler cannot see through: nothing inside is shared with the caller's other uses of q.
+// For the recomputation at the top of a kernel: a product shared between the pinned code above and the physics behind it would
+// lose its permission to contract THERE, and the instance would round its physics differently from the sibling that reads the
+// fields (seen: 1e-7 after 50 steps).
+__device__ __forceinline__ V3 body_rates_apart(Q4 q, V3 w) {
+  asm("" : "+v"(q.x), "+v"(q.y), "+v"(q.z), "+v"(q.w));
+  return body_rates(q, w);
+}
+
 // p.getEulerFromQuaternion (ZYX, gimbal clamp at |sarg| >= 0.99999); C8.
 // Returns the angles the controller adds increments to (roll, pitch; yaw only when WANT_YAW)
 // and the sines/cosines of all three that the G matrix needs (INDIControl.py:301-305).  The
@@ -735,8 +766,7 @@ __device__ __forceinline__ void bullet_step_body(DT& T, float dt, RigidB& s, V3 
 template <int NACT = 4, class DT>
 __device__ __forceinline__ void indi_rate(DT& T, float inv_dt, const Rigid& s, V3 rate_sp, float thrust,
                                           CtrlMem<NACT>& m) {
-  const M3 R = matrix_from_quat(s.q);                                          // :428
-  const V3 wb = mulT(R, s.w);                                                  // :430
+  const V3 wb = body_rates(s.q, s.w);                                          // :428-430
   float v[4];
   v[0] = (rate_sp.x - wb.x) * T.krate[0] - (wb.x - m.last_rates.x) * inv_dt;   // :433-453
   v[1] = (rate_sp.y - wb.y) * T.krate[1] - (wb.y - m.last_rates.y) * inv_dt;
@@ -1034,7 +1064,7 @@ __device__ __forceinline__ void indi_hexa(DT& T, float dt, const Rigid& s, const
   const float ex0 = -s.q.x, ey0 = -s.q.y, ez = -s.q.z;
   const float ex = cps * ex0 + sps * ey0, ey = -sps * ex0 + cps * ey0;        // inv(R_psi) . att_err.xy, :549-557
   const M3 R = matrix_from_quat(s.q);                                         // :566
-  const V3 wb = mulT(R, s.w);
+  const V3 wb = body_rates(s.q, s.w);      // (what last_rates stores: the pinned form; R below serves a_e alone)
   float v[6];
   v[0] = (T.katt[0] * ex - wb.x) * T.krate[0] - (wb.x - m.last_rates.x) * inv_dt;   // :560-592
   v[1] = (T.katt[1] * ey - wb.y) * T.krate[1] - (wb.y - m.last_rates.y) * inv_dt;

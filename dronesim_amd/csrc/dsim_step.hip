@@ -30,8 +30,18 @@
 // instance a VGPR or a wave (a few SGPRs).  The target loads keep the launch's cache policy: default-policy loads under the hint
 // measured the same (133.45 against 133.42 us, four interleaved runs).  A power of two of tiles is a mask: the 32-bit modulo
 // alone cost about 1 us per launch (133.3 against 132.2 us, profiles/r08_ab_tgt_period.txt).
-template <bool NOISE, bool NT, bool EXT, bool CH = false, int SUB = 0, bool ACT = false, bool TC = false>
+// MD = DSIM_OPT_MEM_DERIVED: the six fields are recomputed on load as under CH and STORED as without it: 24 B/drone-step less
+// read (192 -> 168 with TC and a period; 144 chained), the block current after every launch.  The plain single-sub-step TC
+// instances only (NOISE x NT = 4): the looped ones are bound by vector issue, not by HBM, an explicit action is one step of a
+// loop, and the instances that read all ten target fields came out at 71 VGPRs, 7 waves per SIMD against the 64 / 8 of the
+// sibling that reads the fields (forced to 8 they spill 8-12 B): dsim_step ignores the bit there.  Headline 131.5-132.6 ->
+// 121.1-123.1 us, same box, four interleaved pairs (profiles/r09_ab_mem_derived.txt), 61 VGPRs, 8 waves like the sibling (62);
+// bit-identical to the sibling, which needs (a) ONE pinned definition of the body rates at both ends (dsim_device.h:
+// body_rates) and (b) the recomputation kept apart from the physics behind it (body_rates_apart: products shared with the
+// pinned code lose their permission to contract, and the instance then rounds its physics differently from the sibling).
+template <bool NOISE, bool NT, bool EXT, bool CH = false, int SUB = 0, bool ACT = false, bool TC = false, bool MD = false>
 __global__ __launch_bounds__(256, EXT ? 3 : DSIM_STEP_WAVES) void k_step_fast(StepK a) {
+  static_assert(!MD || (SUB == 1 && !EXT && !ACT && !CH && TC), "MD: the plain single-sub-step TC instances");
   const DevType& T = a.types[0];
   const long long sfs = a.st.field_stride, tfs = a.tg.field_stride;
   const unsigned sl = 4u * kv_lane(a.st, threadIdx.x), tl = 4u * kv_lane(a.tg, threadIdx.x);   // bytes
@@ -54,9 +64,9 @@ __global__ __launch_bounds__(256, EXT ? 3 : DSIM_STEP_WAVES) void k_step_fast(St
   // the sub-step loop of the looped instances instead of in front of it: 80 -> 74 VGPRs, still 6 waves per SIMD, 166.9 against
   // 164.6 us for five sub-steps; forced to 7 waves (72 VGPRs, 16 B of scratch) 171.5 us; issued at the top of the last sub-step
   // the compiler peels that iteration: 96 VGPRs and scratch.)
-  load_mem<4, NT, CH>(sb, sfs, sl, m);
+  load_mem<4, NT, CH || MD>(sb, sfs, sl, m);
   if (TAB) __syncthreads();
-  if (CH) { m.last_vel = s.vel; m.last_rates = mulT(matrix_from_quat(s.q), s.w); }
+  if (CH || MD) { m.last_vel = s.vel; m.last_rates = MD ? body_rates_apart(s.q, s.w) : body_rates(s.q, s.w); }
   const long long i = i0 + threadIdx.x;
   if (NOISE && a.step_index_dev) a.step_index += *a.step_index_dev;    // wave-uniform scalar load
   V3 pos_e;
@@ -104,8 +114,13 @@ __global__ __launch_bounds__(256, EXT ? 3 : DSIM_STEP_WAVES) void k_step_fast(St
 // infeasible drones queued for k_wls_fallback): whole tiles, stored cmd as the action, one Env.step per
 // launch.  Compiled apart from the mixed-fleet kernel, whose quad branch and per-lane options cost it
 // registers (177-252 VGPRs, 2 waves/SIMD).
-template <bool NOISE, bool NT, bool S1, bool ACT = false>
-__global__ __launch_bounds__(256, DSIM_HEXA_WAVES) void k_step_hexa(StepK a) {
+// MD = DSIM_OPT_MEM_DERIVED (k_step_fast): last_vel / last_rates recomputed on load, stored as usual; S1, non-ACT instances.
+// The noise-free MD instances are held to 7 waves per SIMD, what their siblings run at (69 VGPRs): left to itself the compiler
+// takes 75 VGPRs for them, 6 waves; under the bound 71, no scratch (the noise instances: 73 / 6 like their siblings' 74 / 6).
+// Measured, 4 194 304 hexas without noise, same box and library, hint on against off: profiles/r09_ab_mem_derived.txt.
+template <bool NOISE, bool NT, bool S1, bool ACT = false, bool MD = false>
+__global__ __launch_bounds__(256, (MD && !NOISE) ? 7 : DSIM_HEXA_WAVES) void k_step_hexa(StepK a) {
+  static_assert(!MD || (S1 && !ACT), "MD: the single-sub-step instances without an explicit action");
   const DevType& T = a.types[0];
   const long long sfs = a.st.field_stride, tfs = a.tg.field_stride;
   const unsigned sl = 4u * kv_lane(a.st, threadIdx.x), tl = 4u * kv_lane(a.tg, threadIdx.x);
@@ -120,8 +135,9 @@ __global__ __launch_bounds__(256, DSIM_HEXA_WAVES) void k_step_hexa(StepK a) {
   CtrlMem<6> m;
   Target tg;
   load_rigid<NT>(sb, sfs, sl, s);
-  load_mem<6, NT>(sb, sfs, sl, m);
+  load_mem<6, NT, MD>(sb, sfs, sl, m);
   load_target<NT>(tb, tfs, tl, tg);
+  if (MD) { m.last_vel = s.vel; m.last_rates = body_rates_apart(s.q, s.w); }
   if (TAB) __syncthreads();
   const long long i = i0 + threadIdx.x;
   if (NOISE && a.step_index_dev) a.step_index += *a.step_index_dev;
@@ -156,7 +172,7 @@ __global__ __launch_bounds__(256) void k_materialize(MatK a) {
   const long long fs = a.st.field_stride;
   Rigid s;
   load_rigid(p, fs, 0u, s);
-  const V3 wb = mulT(matrix_from_quat(s.q), s.w);
+  const V3 wb = body_rates(s.q, s.w);
   p[13 * fs] = s.vel.x; p[14 * fs] = s.vel.y; p[15 * fs] = s.vel.z;
   p[16 * fs] = wb.x; p[17 * fs] = wb.y; p[18 * fs] = wb.z;
 }
@@ -345,13 +361,14 @@ int dsim_step(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, dsim_view
       const bool ext = multi;
       const bool ch = (args->options & DSIM_OPT_CHAINED) != 0;
       const bool tc = tgt_const_honoured(args);          // (the plain instances: vel / acc / yaw from the arguments)
+      const bool md = (args->options & DSIM_OPT_MEM_DERIVED) != 0;     // (the plain single-sub-step TC instances, not chained)
       // (TC: the plain instances only.  EXT: any sub-step count.  ACT: never with EXT or CH (both kept out above), the default
       // cache policy only, as k_step_runs)
-      with_flags([&](auto N, auto NT, auto CH, auto S1, auto TC) {
+      with_flags([&](auto N, auto NT, auto CH, auto S1, auto TC, auto MD) {
         if (ext) hipLaunchKernelGGL((k_step_fast<N(), NT(), true, CH()>), g, b, 0, st_, a);
         else if (args->action) hipLaunchKernelGGL((k_step_fast<N(), false, false, false, S1() ? 1 : 0, true>), g, b, 0, st_, a);
-        else hipLaunchKernelGGL((k_step_fast<N(), NT(), false, CH(), S1() ? 1 : 0, false, TC()>), g, b, 0, st_, a);
-      }, noise, nt, ch, a.substeps == 1, tc);
+        else hipLaunchKernelGGL((k_step_fast<N(), NT(), false, CH(), S1() ? 1 : 0, false, TC(), MD() && S1() && !CH() && TC()>), g, b, 0, st_, a);
+      }, noise, nt, ch, a.substeps == 1, tc, md);
       first = tiles * 256;
     }
   }
@@ -365,9 +382,10 @@ int dsim_step(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, dsim_view
     a.fb.entries = ctx->d_fb;
     fb_open = true;
     const dim3 g((unsigned)tiles);
-    with_flags([&](auto N, auto NT, auto S1, auto ACT) {        // (the ACT instances: default cache policy only, as k_step_runs)
-      hipLaunchKernelGGL((k_step_hexa<N(), NT() && !ACT(), S1(), ACT()>), g, b, 0, st_, a);
-    }, noise, nt, a.substeps == 1, args->action != nullptr);
+    const bool md = (args->options & DSIM_OPT_MEM_DERIVED) != 0;     // (the single-sub-step instances without an explicit action)
+    with_flags([&](auto N, auto NT, auto S1, auto ACT, auto MD) {        // (the ACT instances: default cache policy only, as k_step_runs)
+      hipLaunchKernelGGL((k_step_hexa<N(), NT() && !ACT(), S1(), ACT(), MD() && S1() && !ACT()>), g, b, 0, st_, a);
+    }, noise, nt, a.substeps == 1, args->action != nullptr, md);
     first = tiles * 256;
     if (first >= a.n_pad) fb_finish(ctx, a, st_);
   }

@@ -75,6 +75,15 @@ class _FusedPlan:
 class CtrlAviary(PlacedFleetArrays, FleetObservation):
     """PWM-action fleet environment (reference: ``CtrlAviary``)."""
 
+    # (class-level "no hint": an env made without __init__ launches as before this option existed)
+    _mem_hint = False             # DSIM_OPT_MEM_DERIVED is offered (set by __init__)
+    _mem_handed_out = True        # ... but not to the next fused launch: the block has been handed out since the last one
+
+    @staticmethod
+    def _mem_hint_wanted(mem_hint: bool) -> bool:
+        """The constructor's argument and the environment's veto (DSIM_NO_MEM_HINT=1: A/B runs)."""
+        return bool(mem_hint) and os.environ.get("DSIM_NO_MEM_HINT", "0") == "0"
+
     def __init__(
         self,
         drone_model: Union[Sequence[str], Sequence[DroneType]] = ("tello",),
@@ -110,6 +119,7 @@ class CtrlAviary(PlacedFleetArrays, FleetObservation):
         noise: str = "auto",
         downwash_keep: Optional[int] = None,
         downwash_skin: float = 0.1,
+        mem_hint: bool = True,
     ):
         if gui or record or obstacles:
             raise NotImplementedError("gui/record/obstacles are rendering features outside the hot path")
@@ -271,6 +281,14 @@ class CtrlAviary(PlacedFleetArrays, FleetObservation):
         self._chained_enabled = chained
         self._chain_live = False          # last_vel / last_rates in HBM are stale
         self._chain_ok = False            # the previous operation was a fused step (memory consistent with the state)
+        # DSIM_OPT_MEM_DERIVED: a fused step right behind a fused step need not READ last_vel / last_rates (it still writes them:
+        # nothing is ever stale).  Given exactly when the block was left by a fused step (_chain_ok) and has not been handed to
+        # code outside the env since (_mem_handed_out: the state's accessors through pre_access, its public `data` through on_hand_out, _move_state); the launch behind
+        # such an access reads all 24 fields and makes the hint good again.  A view of the block that the caller KEEPS and writes
+        # later, behind further steps, is not seen: fetch it again after stepping.  mem_hint=False or
+        # DSIM_NO_MEM_HINT=1: never given (A/B runs; results do not depend on it).
+        self._mem_hint = self._mem_hint_wanted(mem_hint)
+        self._mem_handed_out = True
         self._fused_plan = None           # cached argument block of the repeated step_fused() call
         self._step_plan = None            # ... and of the repeated step(action) call of the reference-shaped loop
         self._fused_plan_dw = None        # ... of a downwash fleet (force, counter and the next grid are refreshed per call)
@@ -310,6 +328,7 @@ class CtrlAviary(PlacedFleetArrays, FleetObservation):
         # the host accessors of the state block (state.pos, .mem_aos(), set_fields ...) see a CONSISTENT block: a deferred
         # fallback pass joined, and the six fields a chained sequence leaves stale written back first
         self.state.pre_access = self._before_host_access
+        self.state.on_hand_out = self._mem_hand_out       # (the public `data`: the block as it lies, nothing materialised)
         self.step_counter = 0
         self._env_steps = 0
         # what the ctx owns for this fleet size is allocated now, not inside the first step
@@ -324,7 +343,20 @@ class CtrlAviary(PlacedFleetArrays, FleetObservation):
         t[:, : self.NUM_DRONES] = torch.from_numpy(np.ascontiguousarray(a.T)).float()
         return t.to(self.ctx.device)
 
+    def _mem_hint_bit(self, action=None) -> int:
+        """DSIM_OPT_MEM_DERIVED for the fused launch about to be made, or 0 (see __init__); the launch re-establishes the hint.
+        (Not on a downwash fleet: its kernels ignore the bit, and the term reads the positions through the accessors.)"""
+        ok = (self._mem_hint and self._chain_ok and not self._mem_handed_out and action is None
+              and self._downwash is None and not self._chain_live)
+        self._mem_handed_out = False
+        return nat.OPT_MEM_DERIVED if ok else 0
+
+    def _mem_hand_out(self) -> None:
+        """The state block, or a view of it, goes to code outside the env: the next fused launch reads the whole memory."""
+        self._mem_handed_out = True
+
     def _before_host_access(self) -> None:
+        self._mem_hand_out()
         self._join_fallback()
         if self._chain_live:
             self.materialize()
@@ -485,7 +517,7 @@ class CtrlAviary(PlacedFleetArrays, FleetObservation):
 
     def _step_key(self) -> tuple:
         """What a prepared Env.step launch depends on besides the action (see _StepPlan)."""
-        return (self.state.data.data_ptr(), self._obs_buf.data_ptr() if self._obs_buf is not None else 0, self._last_action.data_ptr(),
+        return (self.state._data.data_ptr(), self._obs_buf.data_ptr() if self._obs_buf is not None else 0, self._last_action.data_ptr(),
                 self._phys_options, self._tuning, self.AGGR_PHY_STEPS, id(self._runs), self._caller_io, self.noise_seed)
 
     def _is_action_rows(self, action) -> bool:
@@ -518,6 +550,13 @@ class CtrlAviary(PlacedFleetArrays, FleetObservation):
                 and (self._chain_live or not self._chained_enabled) and plan.matches(key, targets, self._targets_ptrs(targets))):
             plan.args.step_index = self._env_steps
             plan.args.tgt_period = self._tgt_period(targets)     # (may change with a per-drone set(), which keeps the block)
+            if self._mem_hint and not self._chained_enabled:
+                # (the block handed out since the last launch: this one reads the whole memory, the next is hinted again)
+                o = plan.args.options
+                want = (o & ~nat.OPT_MEM_DERIVED) if self._mem_handed_out else (o | nat.OPT_MEM_DERIVED)
+                if want != o:
+                    plan.args.options = want
+                self._mem_handed_out = False
             nat.check(self.ctx.lib.dsim_step(self.ctx.handle, self.ctx.stream_ptr(), self.NUM_DRONES, plan.state_view,
                                              plan.targets_view, plan.args_ref))
             self.step_counter += self.AGGR_PHY_STEPS * n_steps
@@ -580,6 +619,7 @@ class CtrlAviary(PlacedFleetArrays, FleetObservation):
             self._chain_live = True
         else:
             self.materialize()
+        args.options |= self._mem_hint_bit(action)
         sview = self.state.view()
         nat.check(self.ctx.lib.dsim_step(self.ctx.handle, self.ctx.stream_ptr(), self.NUM_DRONES,
                                          sview, tview, ctypes.byref(args)))
@@ -597,6 +637,8 @@ class CtrlAviary(PlacedFleetArrays, FleetObservation):
             nxt = nat.StepArgs.from_buffer_copy(args)
             if self._chained_enabled and chain:
                 nxt.options |= nat.OPT_CHAINED
+            elif self._mem_hint:
+                nxt.options |= nat.OPT_MEM_DERIVED       # (taken out for the one launch behind a host access: see the replay)
             if not self._chained_enabled or chain:
                 self._fused_plan = _FusedPlan(key, nxt, sview, tview, ctypes.byref(nxt), targets, self._targets_ptrs(targets))
 
@@ -690,8 +732,8 @@ class CtrlAviary(PlacedFleetArrays, FleetObservation):
         """The state block into another allocation (same contents).  Everything that holds its address is dropped: the
         prepared argument blocks of the fused step, the downwash and halo plans' cached views."""
         assert not self._chain_live and not self._graph_made, "the state block is pinned (chained sequence / captured graph)"
-        new_block.copy_(self.state.data)
-        self.state.data = new_block
+        new_block.copy_(self.state._data)
+        self.state.data = new_block            # (the setter ends the DSIM_OPT_MEM_DERIVED hint for the next launch)
         self._fused_plan = self._fused_plan_dw = self._step_plan = None
         dw = self._downwash
         if dw is not None:

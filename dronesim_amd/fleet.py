@@ -191,6 +191,7 @@ class BlockedSoA:
         self.version = 0            # bumped by every host-side write (set_fields): caches keyed on the contents check it
         self.order = order if (order is not None and order.n == n) else None    # StorageOrder: caller numbering <-> slots
         self.pre_access = None      # optional callable run before the block is read or written from the host side
+        self.on_hand_out = None     # optional callable run when the tensor itself leaves the object (the public `data`)
         self.tail = None
         if layout == "soa":
             self.block = 0
@@ -213,11 +214,17 @@ class BlockedSoA:
 
     @property
     def data(self) -> torch.Tensor:
-        """The device tensor of the block (layout above)."""
+        """The device tensor of the block (layout above), as it lies in memory: NOT an accessor, ``pre_access`` does not run (a
+        chained env's block is handed out stale, tests/test_gpu_parity.py::test_chained_stepping reads it so).  Whoever holds
+        it can write the block behind the object's back: ``on_hand_out`` hears of it (the object's own hot paths read ``_data``)."""
+        if self.on_hand_out is not None:
+            self.on_hand_out()
         return self._data
 
     @data.setter
     def data(self, t: torch.Tensor) -> None:
+        if self.on_hand_out is not None:
+            self.on_hand_out()
         self._data = t
 
     def view(self) -> nat.View:

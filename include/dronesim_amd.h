@@ -234,6 +234,17 @@ enum {
                                        per drone-step (232 -> 204, chained 184 -> 156, control 212 -> 184).  Every other
                                        kernel and mask reads the view as without the bit.  A target view that repeats
                                        with a period is described by dsim_step_args.tgt_period (no option bit).         */
+  DSIM_OPT_MEM_DERIVED = 1u << 21,  /* dsim_step only.  The caller asserts that in the stored block last_vel == vel and
+                                       last_rates == R(quat)^T ang_vel bit for bit, as the previous dsim_step / dsim_control
+                                       on this rigid state left them (the assertion of DSIM_OPT_CHAINED).  The library MAY
+                                       then recompute the six fields instead of reading them, and may ignore the hint; it
+                                       WRITES them as without the bit, so the block is current after every launch and
+                                       nothing needs dsim_materialize.  Honoured by the whole-tile kernels of one physics
+                                       sub-step with plain targets and no explicit action: the quad ones where
+                                       DSIM_OPT_TGT_CONST is honoured too (192 -> 168 bytes per drone-step with a period)
+                                       and the morphing-hexa ones (248 -> 224).  Every other kernel reads the fields (the
+                                       quad kernels that read all ten target fields would lose a wave per SIMD).  With DSIM_OPT_CHAINED the bit is redundant
+                                       and ignored.  Not valid behind dsim_physics or a host write of the rigid state.   */
   /* -- scheduling (results do not depend on it) ---------------------------------------------------------------------- */
   DSIM_OPT_DEFER_FALLBACK = 1u << 11 /* dsim_step / dsim_control2 of a table with a morphing hexa do NOT launch the deferred
                                        WLS fallback pass behind the step; the caller launches dsim_wls_fallback itself —
