@@ -497,11 +497,7 @@ int dsim_create(dsim_ctx** out, int device, const dsim_type_params* types, int n
   dsim_ctx* c = new (std::nothrow) dsim_ctx;
   if (!c) return (int)hipErrorOutOfMemory;
   c->device = device; c->n_types = n_types; c->max_act = max_act; c->d_types = nullptr; c->d_counters = nullptr;
-  c->d_fb = nullptr; c->fb_cap = 0; c->dw_ws = nullptr; c->dw_cells = 0; c->dw_parity = 0; c->dw_mode = 0;
-  c->n_cu = 256; c->dw_prebin = false; c->dw_prebin_valid = false; c->dw_prebin_n = 0; c->dw_prebin_off = 0;
-  c->dw_prebin_geo[0] = c->dw_prebin_geo[1] = c->dw_prebin_geo[2] = 0.0f;
-  c->dw_prebin_nx = c->dw_prebin_ny = 0; c->dw_local_m = 0; c->dw_prebin_kind = 0; c->dw_reuses = 0; c->h_keep_fb = nullptr; c->d_keep_fb = nullptr; c->dw_keep_ws = nullptr; c->dw_keep_cells = c->dw_keep_n = 0;
-  c->dw_keep_geo[0] = c->dw_keep_geo[1] = c->dw_keep_geo[2] = c->dw_keep_geo[3] = 0.0f; c->dw_keep_nx = c->dw_keep_ny = 0; c->dwh_parity = 0; c->dwh_ws = nullptr; c->dwh_cells = 0;
+  c->d_fb = nullptr; c->fb_cap = 0; c->n_cu = 256;          // (the downwash records start from their default member initialisers)
   c->d_bounds = nullptr;
   c->d_block_map = nullptr; c->h_block_map = nullptr; c->block_map_cap = 0; c->block_map_blocks = 0; c->block_map_runs = 0;
   { int v = 0; if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && v > 0) c->n_cu = v; }
@@ -597,7 +593,7 @@ int dsim_reset(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, const fl
   ResetK a;
   int rc = make_kview(state, 20 + ctx->max_act, &a.st);
   if (rc) return rc;
-  ctx->dw_prebin_valid = false;
+  ctx->prebin.valid = false;
   a.types = ctx->d_types; a.type_id = type_id;
   a.pos = init_pos; a.rpy = init_rpy; a.vel = init_vel; a.cmd = init_cmd;
   a.n_pad = state.n_pad; a.n_fields = 20 + ctx->max_act;

@@ -25,7 +25,7 @@ struct DwK {
   int max_k;
   int n_types;       // length of types[]
   unsigned long long* pairs;   // diagnostics: += pairs evaluated (dsim_downwash_args.pairs_evaluated), or null
-  int keep_mode;               // host: DSIM_DW_KEEP_* as grid_build resolved it for this call
+  int keep_mode;               // unused (the argument layout is kept): the host resolves the call's keep mode into a KeepPlan
 };
 // position component c of world entry j: from the gathered array, or (single-rank fleets, pos_all = null)
 // straight from the state block
@@ -1149,9 +1149,45 @@ __global__ __launch_bounds__(256) void k_adj_query(DwK a) {
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
-static int grid_build(dsim_ctx* ctx, hipStream_t st_, int64_t n, const dsim_view& state,
-                      const dsim_downwash_args* g, float min_cell, DwK* out, bool allow_buckets = false);
-
+// Workspace layouts.  Every caller-owned buffer is described ONCE, by a walk that places its pieces one behind the other and counts
+// the int32 words they take; without a buffer (p = null) it only counts: the exported sizes and the kernels' pointers are one walk.
+struct WsWalk {
+  char* p;
+  int64_t len;         // words so far; an aligned piece counts the 4 words of slack its alignment can cost
+  template <class T> T* take(int64_t count, bool align16 = false) {
+    if (align16) { len += 4; if (p) p = (char*)(((uintptr_t)p + 15) & ~(uintptr_t)15); }
+    T* r = (T*)p;
+    len += count * (int64_t)(sizeof(T) / sizeof(int32_t)); if (p) p += count * (int64_t)sizeof(T);
+    return r;
+  }
+};
+struct GridWs { int* count[2]; int* cursor; float4* sorted; float4* buckets; float4* overflow; WsWalk end; };
+// counting-sort form: count x2 | cursor | 16-byte aligned float4 [m]
+static GridWs sort_ws(const int32_t* ws, int64_t ncells, int64_t m) {
+  WsWalk w{(char*)ws, 0};
+  // (a braced list is evaluated left to right: the pieces in their order, then the walk as they left it)
+  return GridWs{{w.take<int>(ncells + 1), w.take<int>(ncells + 1)}, w.take<int>(ncells), w.take<float4>(m, true), nullptr, nullptr, w};
+}
+// bucket form: count x2 (the overflow length and more behind the cells: DW_CNT_EXTRA) | 16-byte aligned buckets | overflow [m].
+// With n_local >= 0 this is the halo grid of the split-phase downwash, behind a local grid whose overflow list holds n_local entries
+static GridWs bucket_ws(const int32_t* ws, int64_t ncells, int64_t m, int64_t n_local = -1) {
+  WsWalk w = n_local < 0 ? WsWalk{(char*)ws, 0} : bucket_ws(ws, ncells, n_local).end;
+  return GridWs{{w.take<int>(ncells + DW_CNT_EXTRA, n_local >= 0), w.take<int>(ncells + DW_CNT_EXTRA)}, nullptr, nullptr,
+                w.take<float4>(ncells * DW_CAP, true), w.take<float4>(m), w};
+}
+// kept lists: 16-byte aligned pbuild float4 [n_pad] | the lists | the drift ring (8-byte aligned: DW_LSTRIDE is even)
+static int64_t keep_layout(const int32_t* keep_ws, int64_t n_pad, int64_t ncells, float skin, KeepK* kp) {
+  WsWalk w{(char*)keep_ws, 0};
+  memset(kp, 0, sizeof(*kp));
+  kp->pbuild = w.take<float4>(n_pad, true); kp->lists = w.take<int>(ncells * DW_LSTRIDE);
+  kp->drift = w.take<long long>(DW_DRIFT_WORDS); kp->skin = skin;
+  return w.len;
+}
+static void bin_of(const GridWs& w, int parity, const GridGeo& geo, long long local_offset, BinK* b) {
+  memset(b, 0, sizeof(*b));
+  b->count = w.count[parity]; b->buckets = w.buckets; b->overflow = w.overflow;
+  geo.put(b, local_offset);
+}
 // ---- kept candidate lists (dsim_downwash_args.keep) ----
 static inline int dw_rings(float cell) { return cell >= DW_CUTOFF ? 1 : 2; }
 static inline bool dw_dense(int64_t m, int64_t ncells, float cell) {          // the banded two-wave query (launch_query_cell)
@@ -1171,19 +1207,15 @@ static bool keep_usable(const dsim_downwash_args* g, int64_t n, int64_t n_pad) {
          g->keep_ws_len >= dsim_downwash_keep_workspace(n_pad, g->nx, g->ny);
 }
 // ... and whether the lists of the last BUILD query are this grid's
-static bool keep_lists_valid(const dsim_ctx* ctx, const dsim_downwash_args* g, int64_t n) {
-  return ctx->dw_keep_ws && ctx->dw_keep_ws == g->keep_ws && ctx->dw_keep_cells == (long long)g->nx * g->ny && ctx->dw_keep_n == n &&
-         ctx->dw_keep_nx == g->nx && ctx->dw_keep_ny == g->ny && ctx->dw_keep_geo[0] == g->xmin && ctx->dw_keep_geo[1] == g->ymin &&
-         ctx->dw_keep_geo[2] == g->cell && ctx->dw_keep_geo[3] == g->keep_skin;
+static bool keep_lists_valid(const DwKept& k, const dsim_downwash_args* g, int64_t n) {
+  return k.ws && k.ws == g->keep_ws && k.n == n && k.geo == GridGeo(*g) && k.skin == g->keep_skin;
 }
-static void keep_layout(const dsim_downwash_args* g, int64_t n_pad, KeepK* kp) {
-  uintptr_t sp = ((uintptr_t)g->keep_ws + 15) & ~(uintptr_t)15;
-  kp->pbuild = (float4*)sp;
-  kp->lists = (int*)(kp->pbuild + n_pad);
-  kp->drift = (long long*)(kp->lists + (long long)g->nx * g->ny * DW_LSTRIDE);       // (8-byte aligned: DW_LSTRIDE is even)
-  kp->skin = g->keep_skin;
-  kp->counters = nullptr;
-  kp->feedback = nullptr; kp->seq = 0;
+// a refreshing pass (BinK.pbuild) instead of a binning one: the lists' positions, the skin, the drift ring and which refresh this is
+static void refresh_setup(const dsim_downwash_args* g, int64_t n, int64_t n_pad, BinK* b) {
+  KeepK kp;
+  keep_layout(g->keep_ws, n_pad, GridGeo(*g).ncells(), g->keep_skin, &kp);
+  b->pbuild = kp.pbuild; b->skin2 = g->keep_skin * g->keep_skin;
+  b->drift = kp.drift; b->drift_r = g->keep_age > 0 ? g->keep_age - 1 : 0; b->drift_mask = dw_drift_mask(n);
 }
 
 // dsim_step_args.bin_next: the step kernel fills the bucket grid of the next dsim_downwash call.  Only when that grid
@@ -1191,50 +1223,27 @@ static void keep_layout(const dsim_downwash_args* g, int64_t n_pad, KeepK* kp) {
 void bin_next_prepare(dsim_ctx* ctx, int64_t n, const dsim_step_args* args, StepK* a, hipStream_t st) {
   const dsim_downwash_args* g = args->bin_next;
   if (!g || !g->workspace || g->nx < 1 || g->ny < 1 || !(g->cell > 0)) return;
-  const long long ncells = (long long)g->nx * g->ny;
-  if (!dw_use_buckets(g->m, ncells) || ctx->dw_ws != g->workspace || ctx->dw_cells != ncells || ctx->dw_mode != 1 ||
+  const GridGeo geo(*g);
+  const long long ncells = geo.ncells();
+  if (!dw_use_buckets(g->m, ncells) || ctx->dw.ws != g->workspace || ctx->dw.cells != ncells || ctx->dw.mode != 1 ||
       g->local_offset < 0 || g->local_offset + n > g->m)
     return;
-  bucket_layout(g->workspace, ncells, ctx->dw_parity, &a->bin);
-  if (ctx->dw_prebin) {
+  bin_of(bucket_ws(g->workspace, ncells, g->m), ctx->dw.parity, geo, g->local_offset, &a->bin);
+  if (ctx->prebin.live) {
     // an earlier step already filled this buffer and no dsim_downwash has consumed it (two steps in a row): start over,
     // so that the buffer never holds two generations of positions
     (void)hipMemsetAsync(a->bin.count, 0, sizeof(int) * (size_t)(ncells + DW_CNT_EXTRA), st);
-    ctx->dw_prebin = false;
+    ctx->prebin.live = false;
   }
-  a->bin.xmin = g->xmin; a->bin.ymin = g->ymin; a->bin.inv_cell = 1.0f / g->cell; a->bin.nx = g->nx; a->bin.ny = g->ny;
-  a->bin.local_offset = g->local_offset;
-  // the next query re-uses kept lists: this step refreshes their positions instead of binning (BinK.pbuild)
-  bool any_quadlaw6 = false;          // (its step kernel has no refreshing form: dsim_step.hip run_body)
-  for (int t = 0; t < ctx->n_types; ++t) any_quadlaw6 |= ctx->h_types[t].kind == DSIM_KIND_HEXA_QUADLAW;
-  if (g->keep == DSIM_DW_KEEP_REUSE && !any_quadlaw6 && keep_usable(g, n, a->n_pad) && keep_lists_valid(ctx, g, n)) {
-    KeepK kp;
-    keep_layout(g, a->n_pad, &kp);
-    a->bin.pbuild = kp.pbuild; a->bin.skin2 = g->keep_skin * g->keep_skin;
-    a->bin.drift = kp.drift; a->bin.drift_r = g->keep_age > 0 ? g->keep_age - 1 : 0; a->bin.drift_mask = dw_drift_mask(n);
-  }
+  // the next query re-uses kept lists: this step refreshes their positions instead of binning (BinK.pbuild; the step kernel of
+  // DSIM_KIND_HEXA_QUADLAW has no refreshing form: dsim_step.hip run_body)
+  if (g->keep == DSIM_DW_KEEP_REUSE && !has_quadlaw6(ctx) && keep_usable(g, n, a->n_pad) && keep_lists_valid(ctx->kept, g, n))
+    refresh_setup(g, n, a->n_pad, &a->bin);
 }
 
 void bin_next_commit(dsim_ctx* ctx, int64_t n, const dsim_step_args* args, const StepK& a) {
   if (!a.bin.count) return;
-  ctx->dw_prebin = true; ctx->dw_prebin_valid = true; ctx->dw_prebin_n = n; ctx->dw_prebin_off = args->bin_next->local_offset;
-  ctx->dw_prebin_nx = args->bin_next->nx; ctx->dw_prebin_ny = args->bin_next->ny;
-  ctx->dw_prebin_geo[0] = args->bin_next->xmin; ctx->dw_prebin_geo[1] = args->bin_next->ymin;
-  ctx->dw_prebin_geo[2] = args->bin_next->cell;
-  ctx->dw_prebin_kind = a.bin.pbuild ? 1 : 0;
-}
-
-// the halo grid of the split-phase downwash sits behind the local grid (whose overflow list holds n_local entries)
-static inline void halo_layout(int32_t* ws, long long ncells, long long n_local, int parity, BinK* b) {
-  BinK loc;
-  bucket_layout(ws, ncells, 0, &loc);
-  const long long cstride = ncells + DW_CNT_EXTRA;
-  uintptr_t sp = (uintptr_t)(loc.overflow + n_local);
-  int* base = (int*)((sp + 15) & ~(uintptr_t)15);
-  b->count = base + (long long)parity * cstride;
-  sp = (uintptr_t)(base + 2 * cstride);
-  b->buckets = (float4*)((sp + 15) & ~(uintptr_t)15);
-  b->overflow = b->buckets + ncells * DW_CAP;
+  ctx->prebin = DwPrebin{true, true, n, args->bin_next->local_offset, GridGeo(*args->bin_next), a.bin.pbuild ? 1 : 0};
 }
 
 static long long halo_total(const dsim_halo_plan* h, int* off /* [DSIM_MAX_PEERS + 1] */) {     // capacities of the messages received
@@ -1246,7 +1255,6 @@ static long long halo_total(const dsim_halo_plan* h, int* off /* [DSIM_MAX_PEERS
   off[DSIM_MAX_PEERS] = (int)tot;
   return tot;
 }
-
 static int halo_check(const dsim_halo_plan* h) {
   if (!h || h->world < 1 || h->world > DSIM_MAX_PEERS || h->rank < 0 || h->rank >= h->world || h->cap < 1) return DSIM_E_ARG;
   for (int q = 0; q < h->world; ++q)
@@ -1254,7 +1262,6 @@ static int halo_check(const dsim_halo_plan* h) {
       return DSIM_E_ARG;
   return DSIM_OK;
 }
-
 static void halo_fill(const dsim_halo_plan* h, HaloK* k) {
   k->send = h->send; k->recv = h->recv; k->stride = DSIM_HALO_HDR + 3 * h->cap; k->world = h->world; k->rank = h->rank;
   k->scratch = h->scratch;
@@ -1265,8 +1272,8 @@ static void halo_fill(const dsim_halo_plan* h, HaloK* k) {
 }
 
 // the cell-centred query over (receiver grid b, candidate grid cnd)
-static void launch_query_cell(dsim_ctx* ctx, hipStream_t st_, const DwK& a, const BinK& b, const BinK& cnd, float cell,
-                              long long m_candidates, int accumulate, const KeepK* keep = nullptr) {
+static void launch_query_cell(hipStream_t st_, const DwK& a, const BinK& b, const BinK& cnd, float cell, long long m_candidates,
+                              int accumulate, const KeepK* keep = nullptr) {
   const long long ncells = (long long)a.nx * a.ny;
   // sparse worlds (mean occupancy of a neighbourhood <= 128 entries): one wave per cell and an 8 KB tile, so that a
   // CU holds ~20 cells at once; dense ones (BASELINE config 5: 625 entries per neighbourhood): two waves and 12 KB —
@@ -1282,99 +1289,168 @@ static void launch_query_cell(dsim_ctx* ctx, hipStream_t st_, const DwK& a, cons
   else hipLaunchKernelGGL((k_dw_query_cell<128, true>), gq, dim3(128), DW_TILE_DENSE_BYTES, st_, a, b, cnd, rings, DW_TILE_DENSE_BYTES / (int)sizeof(float4), accumulate, kp);
 }
 
-// counting sort of the world's positions into the xy grid (count, scan, scatter)
-static int grid_build(dsim_ctx* ctx, hipStream_t st_, int64_t n, const dsim_view& state,
-                      const dsim_downwash_args* g, float min_cell, DwK* out, bool allow_buckets) {
-  DwK& a_ = *out;
-  if (!ctx || !g || !g->workspace || n <= 0 || n > state.n_pad) return DSIM_E_ARG;
-  // pos_all = NULL: the world is this fleet (m = n, local_offset = 0) and positions are read from the state block — or,
-  // with a halo plan, this fleet plus what the plan's peers sent (checked by dsim_downwash)
-  if (!g->pos_all && !g->halo && (g->m != n || g->local_offset != 0)) return DSIM_E_ARG;
-  if (g->m < 1 || (g->pos_all && g->m_pad < g->m) || g->nx < 1 || g->ny < 1 || !(g->cell >= min_cell)) return DSIM_E_ARG;
-  if ((long long)g->nx * g->ny > (1 << 24)) return DSIM_E_ARG;
-  if (g->workspace_len < dsim_downwash_workspace(g->m, g->nx, g->ny)) return DSIM_E_ARG;
-  DwK a;
-  memset(&a, 0, sizeof(a));
-  int rc = make_kview(state, 20 + ctx->max_act, &a.st);
+struct DwCall { dsim_ctx* ctx; hipStream_t st; int64_t n; const dsim_view& state; const dsim_downwash_args* g; GridGeo geo; };   // one call
+// the one place that builds a call's DwK: the state view, the type table, the world's sizes, the grid
+static int dw_fill(const DwCall& c, DwK* a) {
+  memset(a, 0, sizeof(*a));
+  int rc = make_kview(c.state, 20 + c.ctx->max_act, &a->st);
   if (rc) return rc;
-  const long long ncells = (long long)g->nx * g->ny;
-  a.types = ctx->d_types; a.type_id = g->type_id; a.pos_all = g->pos_all; a.n_types = ctx->n_types;
-  a.pairs = (unsigned long long*)g->pairs_evaluated;
-  a.m = g->m; a.m_pad = g->m_pad; a.n = n; a.n_pad = state.n_pad; a.local_offset = g->local_offset;
-  if (g->local_offset < 0 || g->local_offset + n > g->m || g->m >= (1LL << 31)) return DSIM_E_ARG;
-  a.xmin = g->xmin; a.ymin = g->ymin; a.inv_cell = 1.0f / g->cell; a.nx = g->nx; a.ny = g->ny;
-  const bool buckets = allow_buckets && dw_use_buckets(g->m, ncells);
-  const long long cstride = ncells + (buckets ? DW_CNT_EXTRA : 1);      // the bucket form keeps the overflow length (and more) behind the cells
-  // two count buffers alternate between calls; the one for the next call is zeroed by this call's first kernel
-  const bool same = ctx->dw_ws == g->workspace && ctx->dw_cells == ncells && ctx->dw_mode == (buckets ? 1 : 0);
-  const int cur = same ? ctx->dw_parity : 0;
-  a.count = g->workspace + (long long)cur * cstride;
-  a.count_next = g->workspace + (long long)(1 - cur) * cstride;
-  if (!same) {   // first use of this workspace / grid shape / form
-    hipError_t e = hipMemsetAsync(g->workspace, 0, sizeof(int) * 2 * cstride, st_);
+  a->types = c.ctx->d_types; a->type_id = c.g->type_id; a->pos_all = c.g->pos_all; a->n_types = c.ctx->n_types;
+  a->m = c.g->m; a->m_pad = c.g->m_pad; a->n = c.n; a->n_pad = c.state.n_pad; a->pairs = (unsigned long long*)c.g->pairs_evaluated;
+  c.geo.put(a, c.g->local_offset);
+  return DSIM_OK;
+}
+// What the kept lists and the step in front make of this call (bucket form); changes nothing.  pre_live: the previous dsim_step filled
+// THIS count buffer (dsim_step_args.bin_next); pre_ok: ... with what this call needs, and the caller vouches for it
+struct KeepPlan { int mode; bool pre_live, pre_ok; };
+static KeepPlan keep_resolve(const DwCall& c) {
+  const DwPrebin& p = c.ctx->prebin;
+  KeepPlan r = {DSIM_DW_KEEP_OFF, p.live, false};
+  const bool pre = p.live && p.valid && c.g->prebinned && p.n == c.n && p.off == c.g->local_offset && p.geo == c.geo;
+  // kept lists: a REUSE needs lists of this very grid, and the step in front of it must have REFRESHED the positions (kind 1) where
+  // a BUILD or a plain query needs them BINNED (kind 0).  A step that binned in front of a REUSE makes it a BUILD (its grid is
+  // fresh: new lists cost nothing extra); a step that refreshed in front of anything else is not vouched for.
+  r.mode = keep_usable(c.g, c.n, c.state.n_pad) ? c.g->keep : DSIM_DW_KEEP_OFF;
+  if (r.mode == DSIM_DW_KEEP_REUSE && !keep_lists_valid(c.ctx->kept, c.g, c.n)) r.mode = DSIM_DW_KEEP_BUILD;
+  const bool refreshed = p.kind == 1;
+  if (r.mode == DSIM_DW_KEEP_REUSE && pre && !refreshed) r.mode = DSIM_DW_KEEP_BUILD;
+  r.pre_ok = pre && (refreshed == (r.mode == DSIM_DW_KEEP_REUSE));
+  return r;
+}
+// bucket form: refresh the kept lists' positions (REUSE) or bin the world, less what the step in front has done already
+static int bucket_fill(const DwCall& c, const DwK& a, const BinK& b, const KeepPlan& plan) {
+  if (plan.pre_live && !plan.pre_ok) {     // a step filled this buffer but not with what this call needs, or the caller does not vouch for it
+    hipError_t e = hipMemsetAsync(a.count, 0, sizeof(int) * (c.geo.ncells() + DW_CNT_EXTRA), c.st);
     if (e != hipSuccess) return (int)e;
-    ctx->dw_ws = g->workspace; ctx->dw_cells = ncells; ctx->dw_mode = buckets ? 1 : 0;
   }
-  ctx->dw_parity = 1 - cur;
-  // local entries already binned by the previous dsim_step (dsim_step_args.bin_next) into THIS count buffer?
-  const bool pre_live = same && buckets && ctx->dw_prebin;
-  const bool pre = pre_live && ctx->dw_prebin_valid && g->prebinned && ctx->dw_prebin_n == n &&
-                   ctx->dw_prebin_off == g->local_offset && ctx->dw_prebin_geo[0] == g->xmin &&
-                   ctx->dw_prebin_geo[1] == g->ymin && ctx->dw_prebin_geo[2] == g->cell && ctx->dw_prebin_nx == g->nx &&
-                   ctx->dw_prebin_ny == g->ny;
-  ctx->dw_prebin = false;
-  if (buckets) {
-    BinK b;
-    memset(&b, 0, sizeof(b));
-    bucket_layout(g->workspace, ncells, cur, &b);
-    b.xmin = a.xmin; b.ymin = a.ymin; b.inv_cell = a.inv_cell; b.nx = a.nx; b.ny = a.ny; b.local_offset = a.local_offset;
-    a.buckets = b.buckets; a.overflow = b.overflow;
-    // kept lists: a REUSE needs lists of this very grid, and the step in front of it must have REFRESHED the positions (kind 1) where
-    // a BUILD or a plain query needs them BINNED (kind 0).  A step that binned in front of a REUSE makes it a BUILD (its grid is
-    // fresh: new lists cost nothing extra); a step that refreshed in front of anything else is not vouched for.
-    int mode = keep_usable(g, n, state.n_pad) ? g->keep : DSIM_DW_KEEP_OFF;
-    if (mode == DSIM_DW_KEEP_REUSE && !keep_lists_valid(ctx, g, n)) mode = DSIM_DW_KEEP_BUILD;
-    const bool refreshed = ctx->dw_prebin_kind == 1;
-    if (mode == DSIM_DW_KEEP_REUSE && pre && !refreshed) mode = DSIM_DW_KEEP_BUILD;
-    const bool pre_ok = pre && (refreshed == (mode == DSIM_DW_KEEP_REUSE));
-    a.keep_mode = mode;
-    if (pre_live && !pre_ok) {       // a step filled this buffer but not with what this call needs, or the caller does not vouch for it
-      hipError_t e = hipMemsetAsync(a.count, 0, sizeof(int) * cstride, st_);
-      if (e != hipSuccess) return (int)e;
-    }
-    if (mode == DSIM_DW_KEEP_REUSE) {
-      if (!pre_ok) {
-        KeepK kp;
-        keep_layout(g, state.n_pad, &kp);
-        b.pbuild = kp.pbuild; b.skin2 = g->keep_skin * g->keep_skin;
-        b.drift = kp.drift; b.drift_r = g->keep_age > 0 ? g->keep_age - 1 : 0; b.drift_mask = dw_drift_mask(n);
-        // (this refresh's sums start from nothing, whatever a step that is not vouched for has left in their place)
-        hipError_t e = hipMemsetAsync(kp.drift + 4 * (b.drift_r & 3), 0, 4 * sizeof(long long), st_);
-        if (e != hipSuccess) return (int)e;
-        hipLaunchKernelGGL(k_dw_refresh, dim3(grid_for(n)), dim3(256), 0, st_, a, b);
-      }
-      a_ = a;
-      return DSIM_OK;
-    }
-    const long long m_here = g->halo ? n : a.m;         // entries this pass reads through dw_pos (the halo has its own kernel)
-    BinRange r;
-    r.j0 = 0; r.j1 = m_here; r.skip0 = r.skip1 = m_here;
-    long long todo = m_here;
-    if (pre_ok) { r.skip0 = a.local_offset; r.skip1 = a.local_offset + n; todo = m_here - n; }
-    if (todo > 0) hipLaunchKernelGGL(k_dw_bin, dim3(grid_for(todo)), dim3(256), 0, st_, a, b, r);
-    a_ = a;
+  if (plan.mode == DSIM_DW_KEEP_REUSE) {
+    if (plan.pre_ok) return DSIM_OK;
+    BinK rb = b;
+    refresh_setup(c.g, c.n, c.state.n_pad, &rb);
+    // (this refresh's sums start from nothing, whatever a step that is not vouched for has left in their place)
+    hipError_t e = hipMemsetAsync(rb.drift + 4 * (rb.drift_r & 3), 0, 4 * sizeof(long long), c.st);
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(k_dw_refresh, dim3(grid_for(c.n)), dim3(256), 0, c.st, a, rb);
     return DSIM_OK;
   }
-  a.cursor = g->workspace + 2 * (ncells + 1);
-  uintptr_t sp = (uintptr_t)(a.cursor + ncells);
-  a.sorted = (float4*)((sp + 15) & ~(uintptr_t)15);
-  hipLaunchKernelGGL(k_dw_count, dim3(grid_for(a.m > ncells + 1 ? a.m : ncells + 1)), dim3(256), 0, st_, a);
+  const long long m_here = c.g->halo ? c.n : a.m;     // entries this pass reads through dw_pos (the halo has its own kernel)
+  BinRange r = {0, m_here, m_here, m_here};
+  long long todo = m_here;
+  if (plan.pre_ok) { r.skip0 = a.local_offset; r.skip1 = a.local_offset + c.n; todo = m_here - c.n; }
+  if (todo > 0) hipLaunchKernelGGL(k_dw_bin, dim3(grid_for(todo)), dim3(256), 0, c.st, a, b, r);
+  return DSIM_OK;
+}
+// The world's positions into the xy grid.  With `b` (dsim_downwash) a world that suits it takes the bucket form: a->buckets is set,
+// *b is its grid and *plan what became of the call's keep mode.  Otherwise a counting sort: count, scan, scatter.
+static int grid_build(const DwCall& c, float min_cell, DwK* a, BinK* b = nullptr, KeepPlan* plan = nullptr) {
+  const dsim_downwash_args* g = c.g;
+  if (!c.ctx || !g->workspace || c.n <= 0 || c.n > c.state.n_pad) return DSIM_E_ARG;
+  // pos_all = NULL: the world is this fleet (m = n, local_offset = 0) and positions are read from the state block — or,
+  // with a halo plan, this fleet plus what the plan's peers sent (checked by dsim_downwash)
+  if (!g->pos_all && !g->halo && (g->m != c.n || g->local_offset != 0)) return DSIM_E_ARG;
+  if (g->m < 1 || (g->pos_all && g->m_pad < g->m) || g->nx < 1 || g->ny < 1 || !(g->cell >= min_cell)) return DSIM_E_ARG;
+  const long long ncells = c.geo.ncells();
+  if (ncells > (1 << 24) || g->workspace_len < dsim_downwash_workspace(g->m, g->nx, g->ny)) return DSIM_E_ARG;
+  int rc = dw_fill(c, a);
+  if (rc) return rc;
+  if (g->local_offset < 0 || g->local_offset + c.n > g->m || g->m >= (1LL << 31)) return DSIM_E_ARG;
+  const bool buckets = b && dw_use_buckets(g->m, ncells);
+  // Two count buffers alternate between calls; the one for the next call is zeroed by this call's first kernel.  A workspace that
+  // does not hold the last call's gets both zeroed here (they are laid out by the cell count and the form alone and are all-zero
+  // between calls: a grid of another origin or cell size takes them over as they are, so no geometry in this test)
+  DwLocal& d = c.ctx->dw;
+  if (d.ws != g->workspace || d.cells != ncells || d.mode != (buckets ? 1 : 0)) {
+    hipError_t e = hipMemsetAsync(g->workspace, 0, sizeof(int) * 2 * (ncells + (buckets ? DW_CNT_EXTRA : 1)), c.st);
+    if (e != hipSuccess) return (int)e;
+    d = DwLocal{g->workspace, ncells, 0, buckets ? 1 : 0};
+    c.ctx->prebin.live = false;          // (whatever the last dsim_step binned, it was not into these buffers)
+  }
+  const int cur = d.parity;
+  d.parity = 1 - cur;
+  const GridWs w = buckets ? bucket_ws(g->workspace, ncells, g->m) : sort_ws(g->workspace, ncells, g->m);
+  a->count = w.count[cur]; a->count_next = w.count[1 - cur];
+  a->cursor = w.cursor; a->sorted = w.sorted; a->buckets = w.buckets; a->overflow = w.overflow;
+  if (buckets) {
+    *plan = keep_resolve(c);
+    c.ctx->prebin.live = false;
+    bin_of(w, cur, c.geo, g->local_offset, b);
+    return bucket_fill(c, *a, *b, *plan);
+  }
+  c.ctx->prebin.live = false;
+  hipLaunchKernelGGL(k_dw_count, dim3(grid_for(a->m > ncells + 1 ? a->m : ncells + 1)), dim3(256), 0, c.st, *a);
   // (measured and rejected: letting the last count workgroup do the scan — the fences and the one-workgroup scan
   // behind them cost 28 us against 7 + 6.5 us for the two launches)
-  hipLaunchKernelGGL(k_dw_scan, dim3(1), dim3(1024), 0, st_, a);
-  hipLaunchKernelGGL(k_dw_scatter, dim3(grid_for(a.m)), dim3(256), 0, st_, a);
-  a_ = a;
+  hipLaunchKernelGGL(k_dw_scan, dim3(1), dim3(1024), 0, c.st, *a);
+  hipLaunchKernelGGL(k_dw_scatter, dim3(grid_for(a->m)), dim3(256), 0, c.st, *a);
   return DSIM_OK;
+}
+
+// The split phases.  The halo grid has two count buffers that alternate between steps: HALO_BIN fills the current one; HALO_QUERY
+// reads it, has its kernel zero the other for the next step, and flips.
+static int downwash_halo(const DwCall& c, const HaloK& hk, long long h_tot, float* force_out) {
+  const dsim_downwash_args* g = c.g;
+  if (c.n <= 0 || c.n > c.state.n_pad || !(g->cell >= 0.5f * DW_CUTOFF)) return DSIM_E_ARG;
+  const long long ncells = c.geo.ncells();
+  const GridWs w = bucket_ws(g->workspace, ncells, h_tot, c.n);
+  DwHalo& h = c.ctx->dwh;
+  if (h.ws != g->workspace || h.cells != ncells || h.local_m != c.n) {
+    if (g->phase == DSIM_DW_HALO_QUERY) return DSIM_E_ARG;          // HALO_BIN of this step comes first
+    hipError_t e = hipMemsetAsync(w.count[0], 0, sizeof(int) * 2 * (size_t)(ncells + DW_CNT_EXTRA), c.st);
+    if (e != hipSuccess) return (int)e;
+    h = DwHalo{g->workspace, ncells, c.n, 0};
+  }
+  BinK hb, lb;
+  bin_of(w, h.parity, c.geo, 0, &hb);
+  if (g->phase == DSIM_DW_HALO_BIN) {
+    if (h_tot > 0) hipLaunchKernelGGL(k_dw_bin_halo, dim3(grid_for(h_tot)), dim3(256), 0, c.st, hb, hk);
+    return (int)hipGetLastError();
+  }
+  // HALO_QUERY: receivers = the local grid DSIM_DW_LOCAL of this step built (the buffer before the flip)
+  if (c.ctx->dw.ws != g->workspace || c.ctx->dw.cells != ncells || c.ctx->dw.mode != 1) return DSIM_E_ARG;
+  DwK a;
+  int rc = dw_fill(c, &a);
+  if (rc) return rc;
+  bin_of(bucket_ws(g->workspace, ncells, c.n), 1 - c.ctx->dw.parity, c.geo, 0, &lb);
+  a.force_out = force_out;
+  h.parity = 1 - h.parity;
+  a.count_next = w.count[h.parity];
+  if (h_tot == 0) return DSIM_OK;                                   // nothing arrived, nothing was binned: nothing to add or clear
+  // tile shape as for the local pass of this grid (the candidates of a neighbourhood are the halo's, never more)
+  launch_query_cell(c.st, a, lb, hb, g->cell, c.n, 1);
+  return (int)hipGetLastError();
+}
+// one grid: DSIM_DW_ALL (with a halo plan: what the peers sent goes in beside the local drones) and DSIM_DW_LOCAL
+static int downwash_one_grid(const DwCall& c, const HaloK& hk, long long h_tot, float* force_out) {
+  const dsim_downwash_args* g = c.g;
+  // bucket form: cells of half the cut-off or more (two rings of neighbours below 10 m); counting-sort form: >= 10 m
+  const bool bucket_form = g->nx > 0 && g->ny > 0 && dw_use_buckets(g->m, c.geo.ncells());
+  if (g->halo && g->phase == DSIM_DW_ALL && c.ctx) c.ctx->dwh.ws = nullptr;   // (the one-grid form's overflow list may run over the halo grid's place)
+  DwK a;
+  BinK b;                             // (written in the bucket form only: a.buckets set)
+  KeepPlan plan = {};
+  int rc = grid_build(c, bucket_form ? 0.5f * DW_CUTOFF : DW_CUTOFF, &a, &b, &plan);
+  if (rc) return rc;
+  a.force_out = force_out;
+  if (!a.buckets) {
+    hipLaunchKernelGGL(k_dw_query, dim3(grid_for(a.m * DW_LPR)), dim3(256), 0, c.st, a);
+    return (int)hipGetLastError();
+  }
+  if (g->halo && g->phase == DSIM_DW_ALL && h_tot > 0)              // what the peers sent goes in beside the local drones
+    hipLaunchKernelGGL(k_dw_bin_halo, dim3(grid_for(h_tot)), dim3(256), 0, c.st, b, hk);
+  KeepK kp;
+  if (plan.mode != DSIM_DW_KEEP_OFF) keep_layout(g->keep_ws, c.state.n_pad, c.geo.ncells(), g->keep_skin, &kp);
+  if (plan.mode == DSIM_DW_KEEP_REUSE) {
+    kp.counters = c.ctx->d_counters;
+    ++c.ctx->dw_reuses;
+    kp.feedback = c.ctx->d_keep_fb; kp.seq = (int)(c.ctx->dw_reuses & 0x7fffffff);
+    hipLaunchKernelGGL((k_dw_query_kept<128>), dim3((unsigned)c.geo.ncells()), dim3(128), 0, c.st, a, b, kp);
+  }
+  else if (plan.mode == DSIM_DW_KEEP_BUILD) {
+    launch_query_cell(c.st, a, b, b, g->cell, a.m, 0, &kp);
+    c.ctx->kept = DwKept{g->keep_ws, c.n, c.geo, g->keep_skin};
+  }
+  else launch_query_cell(c.st, a, b, b, g->cell, g->phase == DSIM_DW_LOCAL ? c.n : a.m, 0);
+  return (int)hipGetLastError();
 }
 
 extern "C" {
@@ -1386,14 +1462,14 @@ int dsim_downwash_prebin_ok(int64_t m, int32_t nx, int32_t ny) {
 int64_t dsim_downwash_workspace(int64_t m, int32_t nx, int32_t ny) {
   if (m < 0 || nx < 1 || ny < 1) return -1;
   const int64_t ncells = (int64_t)nx * ny;
-  const int64_t sort_form = 2 * (ncells + 1) + ncells + 4 + 4 * m;   // count x2, cursor, 16-B alignment slack, float4[m]
-  const int64_t bucket_form = 2 * (ncells + DW_CNT_EXTRA) + 4 + 4 * ncells * DW_CAP + 4 * m;   // count x2, slack, buckets, overflow
+  const int64_t sort_form = sort_ws(nullptr, ncells, m).end.len, bucket_form = bucket_ws(nullptr, ncells, m).end.len;
   return dw_use_buckets(m, ncells) && bucket_form > sort_form ? bucket_form : sort_form;
 }
 
 int64_t dsim_downwash_keep_workspace(int64_t n_pad, int32_t nx, int32_t ny) {
   if (n_pad < 1 || nx < 1 || ny < 1) return -1;
-  return 4 + 4 * n_pad + (int64_t)nx * ny * DW_LSTRIDE + 2 * DW_DRIFT_WORDS;        // alignment slack | pbuild: float4 [n_pad] | the lists | the drift ring
+  KeepK kp;
+  return keep_layout(nullptr, n_pad, (int64_t)nx * ny, 0.0f, &kp);
 }
 
 int dsim_downwash_keep_stats(dsim_ctx* ctx, int64_t* outside_skin, int64_t* half_way, int64_t* of_query, int64_t* queries) {
@@ -1415,8 +1491,7 @@ int64_t dsim_downwash_workspace_halo(int64_t n, int64_t h, int32_t nx, int32_t n
   if (n < 1 || h < 0 || nx < 1 || ny < 1) return -1;
   const int64_t ncells = (int64_t)nx * ny;
   if (!dw_use_buckets(n + h, ncells)) return -1;
-  const int64_t local = 2 * (ncells + DW_CNT_EXTRA) + 4 + 4 * ncells * DW_CAP + 4 * n;
-  const int64_t split = local + 4 + 2 * (ncells + DW_CNT_EXTRA) + 4 + 4 * ncells * DW_CAP + 4 * h;
+  const int64_t split = bucket_ws(nullptr, ncells, h, n).end.len;
   const int64_t one = dsim_downwash_workspace(n + h, nx, ny);      // DSIM_DW_ALL on the same buffer
   return split > one ? split : one;
 }
@@ -1427,110 +1502,28 @@ int dsim_downwash(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, const
   if (!force_out && g->phase != DSIM_DW_HALO_BIN) return DSIM_E_ARG;
   if (ctx && ctx->n_types > 1 && !g->type_id && g->phase != DSIM_DW_HALO_BIN) return DSIM_E_ARG;
   if (g->phase < DSIM_DW_ALL || g->phase > DSIM_DW_HALO_QUERY || (g->phase != DSIM_DW_ALL && !g->halo)) return DSIM_E_ARG;
-  DwK a;
-  const hipStream_t st_ = (hipStream_t)stream;
-  const long long ncells = (long long)g->nx * g->ny;
-  int h_off[DSIM_MAX_PEERS + 1];
+  HaloK hk;
+  memset(&hk, 0, sizeof(hk));
   long long h_tot = 0;
   if (g->halo) {
     int rc = halo_check(g->halo);
     if (rc) return rc;
-    h_tot = halo_total(g->halo, h_off);
+    h_tot = halo_total(g->halo, hk.off);
     // the halo plan stands for the rest of the world: positions of the local drones come from the state block
     if (!ctx || g->pos_all || g->local_offset != 0 || g->m != n + h_tot || g->nx < 1 || g->ny < 1 || !g->workspace) return DSIM_E_ARG;
     if (h_tot > 0 && !g->halo->recv) return DSIM_E_ARG;
-    if (!dw_use_buckets(g->m, ncells)) return DSIM_E_UNSUPPORTED;      // the bucket form only (the caller gathers pos_all otherwise)
+    if (!dw_use_buckets(g->m, (long long)g->nx * g->ny)) return DSIM_E_UNSUPPORTED;      // the bucket form only (the caller gathers pos_all otherwise)
     if (g->phase != DSIM_DW_ALL && g->workspace_len < dsim_downwash_workspace_halo(n, h_tot, g->nx, g->ny)) return DSIM_E_ARG;
-  }
-  HaloK hk;
-  memset(&hk, 0, sizeof(hk));
-  if (g->halo) {
     halo_fill(g->halo, &hk);
     hk.index0 = n; hk.counters = ctx->d_counters;
-    for (int q = 0; q <= DSIM_MAX_PEERS; ++q) hk.off[q] = h_off[q];
   }
-  if (g->phase == DSIM_DW_HALO_BIN || g->phase == DSIM_DW_HALO_QUERY) {
-    // the halo grid: two count buffers alternate between steps; HALO_BIN fills the current one, HALO_QUERY reads it,
-    // zeroes the other for the next step and flips
-    if (n <= 0 || n > state.n_pad || !(g->cell >= 0.5f * DW_CUTOFF)) return DSIM_E_ARG;
-    BinK hb;
-    memset(&hb, 0, sizeof(hb));
-    const bool fresh = ctx->dwh_ws != g->workspace || ctx->dwh_cells != ncells || ctx->dw_local_m != n;
-    if (fresh) {
-      if (g->phase == DSIM_DW_HALO_QUERY) return DSIM_E_ARG;          // HALO_BIN of this step comes first
-      halo_layout(g->workspace, ncells, n, 0, &hb);
-      hipError_t e = hipMemsetAsync(hb.count, 0, sizeof(int) * 2 * (size_t)(ncells + DW_CNT_EXTRA), st_);
-      if (e != hipSuccess) return (int)e;
-      ctx->dwh_ws = g->workspace; ctx->dwh_cells = ncells; ctx->dw_local_m = n; ctx->dwh_parity = 0;
-    }
-    halo_layout(g->workspace, ncells, n, ctx->dwh_parity, &hb);
-    hb.xmin = g->xmin; hb.ymin = g->ymin; hb.inv_cell = 1.0f / g->cell; hb.nx = g->nx; hb.ny = g->ny; hb.local_offset = 0;
-    if (g->phase == DSIM_DW_HALO_BIN) {
-      if (h_tot > 0) hipLaunchKernelGGL(k_dw_bin_halo, dim3(grid_for(h_tot)), dim3(256), 0, st_, hb, hk);
-      return (int)hipGetLastError();
-    }
-    // HALO_QUERY: receivers = the local grid DSIM_DW_LOCAL of this step built (the buffer before the flip)
-    if (ctx->dw_ws != g->workspace || ctx->dw_cells != ncells || ctx->dw_mode != 1) return DSIM_E_ARG;
-    memset(&a, 0, sizeof(a));
-    int rc = make_kview(state, 20 + ctx->max_act, &a.st);
-    if (rc) return rc;
-    BinK lb;
-    memset(&lb, 0, sizeof(lb));
-    bucket_layout(g->workspace, ncells, 1 - ctx->dw_parity, &lb);
-    lb.xmin = g->xmin; lb.ymin = g->ymin; lb.inv_cell = hb.inv_cell; lb.nx = g->nx; lb.ny = g->ny; lb.local_offset = 0;
-    a.types = ctx->d_types; a.type_id = g->type_id; a.n_types = ctx->n_types;
-    a.pairs = (unsigned long long*)g->pairs_evaluated;
-    a.m = g->m; a.n = n; a.n_pad = state.n_pad; a.local_offset = 0;
-    a.xmin = g->xmin; a.ymin = g->ymin; a.inv_cell = hb.inv_cell; a.nx = g->nx; a.ny = g->ny;
-    a.force_out = force_out;
-    BinK nxt;
-    halo_layout(g->workspace, ncells, n, 1 - ctx->dwh_parity, &nxt);
-    a.count_next = nxt.count;
-    ctx->dwh_parity = 1 - ctx->dwh_parity;
-    if (h_tot == 0) return DSIM_OK;                                   // nothing arrived, nothing was binned: nothing to add or clear
-    // tile shape as for the local pass of this grid (the candidates of a neighbourhood are the halo's, never more)
-    launch_query_cell(ctx, st_, a, lb, hb, g->cell, n, 1);
-    return (int)hipGetLastError();
-  }
-  // bucket form: cells of half the cut-off or more (two rings of neighbours below 10 m); counting-sort form: >= 10 m
-  const bool bucket_form = g->nx > 0 && g->ny > 0 && dw_use_buckets(g->m, (int64_t)g->nx * g->ny);
-  if (g->halo && g->phase == DSIM_DW_ALL && ctx) ctx->dwh_ws = nullptr;   // (the one-grid form's overflow list may run over the halo grid's place)
-  int rc = grid_build(ctx, st_, n, state, g, bucket_form ? 0.5f * DW_CUTOFF : DW_CUTOFF, &a, true);
-  if (rc) return rc;
-  a.force_out = force_out;
-  if (a.buckets) {
-    BinK b;
-    memset(&b, 0, sizeof(b));
-    b.count = a.count; b.buckets = a.buckets; b.overflow = a.overflow;
-    b.xmin = a.xmin; b.ymin = a.ymin; b.inv_cell = a.inv_cell; b.nx = a.nx; b.ny = a.ny; b.local_offset = a.local_offset;
-    if (g->halo && g->phase == DSIM_DW_ALL && h_tot > 0)              // one grid: what the peers sent goes in beside the local drones
-      hipLaunchKernelGGL(k_dw_bin_halo, dim3(grid_for(h_tot)), dim3(256), 0, st_, b, hk);
-    if (a.keep_mode != DSIM_DW_KEEP_OFF) {
-      KeepK kp;
-      keep_layout(g, state.n_pad, &kp);
-      if (a.keep_mode == DSIM_DW_KEEP_REUSE) {
-        kp.counters = ctx->d_counters;
-        ++ctx->dw_reuses;
-        kp.feedback = ctx->d_keep_fb; kp.seq = (int)(ctx->dw_reuses & 0x7fffffff);
-        hipLaunchKernelGGL((k_dw_query_kept<128>), dim3((unsigned)ncells), dim3(128), 0, st_, a, b, kp);
-      }
-      else {
-        launch_query_cell(ctx, st_, a, b, b, g->cell, a.m, 0, &kp);
-        ctx->dw_keep_ws = g->keep_ws; ctx->dw_keep_cells = ncells; ctx->dw_keep_n = n; ctx->dw_keep_nx = g->nx; ctx->dw_keep_ny = g->ny;
-        ctx->dw_keep_geo[0] = g->xmin; ctx->dw_keep_geo[1] = g->ymin; ctx->dw_keep_geo[2] = g->cell; ctx->dw_keep_geo[3] = g->keep_skin;
-      }
-    }
-    else launch_query_cell(ctx, st_, a, b, b, g->cell, g->phase == DSIM_DW_LOCAL ? n : a.m, 0);
-  }
-  else hipLaunchKernelGGL(k_dw_query, dim3(grid_for(a.m * DW_LPR)), dim3(256), 0, st_, a);
-  return (int)hipGetLastError();
+  const DwCall c{ctx, (hipStream_t)stream, n, state, g, GridGeo(*g)};
+  return g->phase <= DSIM_DW_LOCAL ? downwash_one_grid(c, hk, h_tot, force_out) : downwash_halo(c, hk, h_tot, force_out);
 }
 
 int dsim_downwash_reset(dsim_ctx* ctx) {
   if (!ctx) return DSIM_E_ARG;
-  ctx->dw_ws = nullptr; ctx->dw_cells = 0; ctx->dw_parity = 0; ctx->dw_prebin = false; ctx->dw_prebin_valid = false;
-  ctx->dw_keep_ws = nullptr; ctx->dw_prebin_kind = 0;
-  ctx->dwh_ws = nullptr;
+  ctx->dw = DwLocal{}; ctx->prebin = DwPrebin{}; ctx->kept = DwKept{}; ctx->dwh = DwHalo{};      // (dw_reuses and the feedback words live as long as the context)
   return DSIM_OK;
 }
 
@@ -1564,10 +1557,10 @@ int dsim_halo_pack(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, cons
 
 int dsim_adjacency(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, const dsim_downwash_args* g,
                    float radius, int32_t* count_out, int32_t* list_out, int32_t max_k) {
-  if (!count_out || !(radius > 0) || (list_out && max_k < 1)) return DSIM_E_ARG;
+  if (!g || !count_out || !(radius > 0) || (list_out && max_k < 1)) return DSIM_E_ARG;
   DwK a;
   const hipStream_t st_ = (hipStream_t)stream;
-  int rc = grid_build(ctx, st_, n, state, g, radius, &a);
+  int rc = grid_build(DwCall{ctx, st_, n, state, g, GridGeo(*g)}, radius, &a);
   if (rc) return rc;
   a.radius2 = radius * radius; a.adj_count = count_out; a.adj_list = list_out; a.max_k = list_out ? max_k : 0;
   hipLaunchKernelGGL(k_adj_query, dim3(grid_for(a.m)), dim3(256), 0, st_, a);

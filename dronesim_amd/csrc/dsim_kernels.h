@@ -44,6 +44,28 @@
 #define DSIM_IO_ROWS_NT 0      // rows scattered to the caller's numbering: streaming hint or not
 #endif
 
+// ---- host-side records of the neighbour downwash (dsim_downwash.hip).  The xy grid of a call: what dsim_downwash_args says of
+// it, compared as a whole and written into kernel arguments in one place
+struct GridGeo {
+  float xmin = 0.0f, ymin = 0.0f, cell = 0.0f;
+  int nx = 0, ny = 0;
+  GridGeo() = default;
+  explicit GridGeo(const dsim_downwash_args& g) : xmin(g.xmin), ymin(g.ymin), cell(g.cell), nx(g.nx), ny(g.ny) {}
+  long long ncells() const { return (long long)nx * ny; }
+  bool operator==(const GridGeo& o) const { return xmin == o.xmin && ymin == o.ymin && cell == o.cell && nx == o.nx && ny == o.ny; }
+  template <class K> void put(K* k, long long local_offset) const {       // K: BinK or DwK (the same six fields)
+    k->xmin = xmin; k->ymin = ymin; k->inv_cell = 1.0f / cell; k->nx = nx; k->ny = ny; k->local_offset = local_offset;
+  }
+};
+// What the calls leave in the context.  The local grid's count buffers: workspace / cell count / parity, mode 0: counting sort, 1: buckets
+struct DwLocal { const int32_t* ws = nullptr; long long cells = 0; int parity = 0, mode = 0; };
+// what the last dsim_step left in the count buffer `parity` (dsim_step_args.bin_next).  live: it holds the local drones; valid: no call has moved
+// the positions since without re-binning them; kind 0: the step binned the drones, 1: it refreshed the kept lists' positions
+struct DwPrebin { bool live = false, valid = false; long long n = 0, off = 0; GridGeo geo; int kind = 0; };
+// kept candidate lists (dsim_downwash_args.keep): the buffer / fleet / grid / skin of the last BUILD query, ws null: none
+struct DwKept { const int32_t* ws = nullptr; long long n = 0; GridGeo geo; float skin = 0.0f; };
+// halo grid (split phases): the workspace / shape it was zeroed for, the overflow capacity of the local grid in front of it, parity
+struct DwHalo { const int32_t* ws = nullptr; long long cells = 0, local_m = 0; int parity = 0; };
 struct dsim_ctx {
   int device;
   int n_types;
@@ -52,28 +74,11 @@ struct dsim_ctx {
   unsigned long long* d_counters;         // [0..1] diagnostics (dsim_query), [2] fallback queue length, [3] its ticket
   FbEntry* d_fb;                          // deferred WLS fallback queue, grown to the largest fleet seen
   long long fb_cap;
-  const int32_t* dw_ws;                   // downwash grid: workspace / shape / count-buffer parity of the last call
-  long long dw_cells;
-  int dw_parity;
-  int dw_mode;                            // 0: counting sort, 1: cell buckets (which layout the count buffers hold)
+  DwLocal dw; DwPrebin prebin; DwKept kept; DwHalo dwh;   // neighbour downwash (dsim_downwash.hip): the four records above
   int n_cu;                               // compute units of the device
-  bool dw_prebin;                         // the count buffer dw_parity holds the local drones, binned by the last dsim_step
-  bool dw_prebin_valid;                   // ... and no call has moved the positions since without re-binning them
-  long long dw_prebin_n, dw_prebin_off;
-  float dw_prebin_geo[3];
-  int dw_prebin_nx, dw_prebin_ny;
-  long long dw_local_m;                   // overflow capacity of the local grid in the workspace (layout of what follows it)
-  int dw_prebin_kind;                     // what that dsim_step did: 0 binned the drones, 1 refreshed the kept lists' positions (BinK.pbuild)
-  const int32_t* dw_keep_ws;              // kept candidate lists (dsim_downwash_args.keep): the buffer / grid / fleet of the last BUILD query, null: none
-  long long dw_keep_cells, dw_keep_n;
-  float dw_keep_geo[4];                   // xmin, ymin, cell, skin
-  int dw_keep_nx, dw_keep_ny;
-  long long dw_reuses;                    // DSIM_Q_DW_REUSES
-  volatile int* h_keep_fb;                // host memory the device writes into (mapped): [0] overflow length the last finished REUSE query saw, [1] which query
-  int* d_keep_fb;                         // ... as the device addresses it (null: no feedback)
-  int dwh_parity;                         // halo grid (split-phase downwash): count-buffer parity
-  const int32_t* dwh_ws;                  // ... and the workspace / shape it was zeroed for
-  long long dwh_cells;
+  long long dw_reuses = 0;                // DSIM_Q_DW_REUSES
+  volatile int* h_keep_fb = nullptr;      // host memory the device writes into (mapped): [0] overflow length the last finished REUSE query saw, [1] which query
+  int* d_keep_fb = nullptr;               // ... as the device addresses it (null: no feedback)
   unsigned* d_bounds;                     // dsim_fleet_bounds: 5 order-preserving keys + a ticket
   int* d_block_map;                       // RunTab.block_map of the last side-by-side launch (DSIM_OPT_CALLER_IO), and what it was made for
   int* h_block_map;
@@ -81,6 +86,12 @@ struct dsim_ctx {
   dsim_type_run block_map_key[DSIM_MAX_TYPES];
   dsim_type_params h_types[DSIM_MAX_TYPES];
 };
+
+// a DSIM_KIND_HEXA_QUADLAW type in the table: served by the per-run kernels (k_step_run), whose step kernel never refreshes kept lists
+static inline bool has_quadlaw6(const dsim_ctx* ctx) {
+  for (int t = 0; t < ctx->n_types; ++t) if (ctx->h_types[t].kind == DSIM_KIND_HEXA_QUADLAW) return true;
+  return false;
+}
 
 // ---------------------------------------------------------------------------
 // blocked-SoA addressing
@@ -259,14 +270,6 @@ __device__ __forceinline__ void bin_entry(const BinK& b, float x, float y, float
 // bucket form: grids of up to 65 536 cells with at most 5/8 DW_CAP = 40 entries per cell on average (BASELINE config 5:
 // one drone per m^2 = 25 per 5 m cell); the buckets take ncells * DW_CAP * 16 bytes of the workspace (67 MB at most)
 static inline bool dw_use_buckets(int64_t m, int64_t ncells) { return ncells <= 65536 && m <= ncells * (DW_CAP * 5 / 8); }
-// where the bucket form keeps things inside the workspace (ints): count x2 | 16-byte aligned buckets | overflow
-static inline void bucket_layout(int32_t* ws, long long ncells, int parity, BinK* b) {
-  const long long cstride = ncells + DW_CNT_EXTRA;
-  b->count = ws + (long long)parity * cstride;
-  uintptr_t sp = (uintptr_t)(ws + 2 * cstride);
-  b->buckets = (float4*)((sp + 15) & ~(uintptr_t)15);
-  b->overflow = b->buckets + ncells * DW_CAP;
-}
 
 struct StepK {
   KView st, tg;

@@ -255,11 +255,11 @@ int dsim_step(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, dsim_view
     rc = dyn_check(ctx, args, a);
     if (rc) return rc;
     if (!a.tg.base) return DSIM_E_ARG;
-    ctx->dw_prebin_valid = false;
+    ctx->prebin.valid = false;
     return dyn_launch(true, a, stream_policy(args, state.n_pad, 256.0), (hipStream_t)stream);
   }
   if (args->options & DSIM_OPT_CALLER_IO) return DSIM_E_UNSUPPORTED;     // (dsim_physics / dsim_control2 only)
-  ctx->dw_prebin_valid = false;      // the positions move: a grid binned before this call is stale (bin_next_commit re-validates)
+  ctx->prebin.valid = false;      // the positions move: a grid binned before this call is stale (bin_next_commit re-validates)
   const bool noise = args->noise_seed != 0 || args->noise_replay != nullptr;
   const bool uni = args->type_id == nullptr;
   const bool six = ctx->max_act == 6;
@@ -282,8 +282,7 @@ int dsim_step(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, dsim_view
   const dsim_type_run* runs = args->runs;
   int n_runs = args->n_runs;
   dsim_type_run whole;
-  bool any_quadlaw6 = false;             // a DSIM_KIND_HEXA_QUADLAW type in the table: served by the per-run kernels (k_step_run)
-  for (int t = 0; t < ctx->n_types; ++t) any_quadlaw6 |= ctx->h_types[t].kind == DSIM_KIND_HEXA_QUADLAW;
+  const bool any_quadlaw6 = has_quadlaw6(ctx);
   if (!(runs && n_runs > 0) && uni && runs_ok && (args->ext_force || (any_quadlaw6 && !args->action))) {
     // a homogeneous fleet with an external (downwash) force, or of hexa_6DOF_simple: ONE run of its only type — the
     // single-type kernel with the force input and the fused neighbour-grid binning, instead of the general kernel

@@ -408,8 +408,7 @@ int step_general(dsim_ctx* ctx, int64_t n, const dsim_view& state, const dsim_vi
   const bool fine_slow = fine && a.substeps > 1;
   const bool phys_opts = (args->options & (DSIM_OPT_DRAG | DSIM_OPT_GROUND | DSIM_OPT_PLANE)) != 0 || fine_slow;
   const bool plane = (args->options & DSIM_OPT_PLANE) != 0;
-  bool any_quadlaw6 = false;
-  for (int t = 0; t < ctx->n_types; ++t) any_quadlaw6 |= ctx->h_types[t].kind == DSIM_KIND_HEXA_QUADLAW;
+  const bool any_quadlaw6 = has_quadlaw6(ctx);
   a.first = first;
   const dim3 g(grid_for(a.n_pad - first)), b(256);
   const bool lean = !args->action && !args->noise_replay && !a.wp_table && a.n_steps == 1 && !phys_opts;     // (fine_slow is a phys_opt)

@@ -772,7 +772,7 @@ int dsim_physics(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, float*
   StepK a;
   int rc = fill_stepk(ctx, n, state, nullptr, args, &a);
   if (rc) return rc;
-  ctx->dw_prebin_valid = false;
+  ctx->prebin.valid = false;
   a.echo = last_action_out;
   if (args->options & DSIM_OPT_DYN) {
     rc = dyn_check(ctx, args, a);
@@ -868,7 +868,7 @@ int dsim_step_adaptor(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, c
   int rc = fill_stepk(ctx, n, state, nullptr, args, &a);
   if (rc) return rc;
   if (args->options & (DSIM_OPT_CALLER_IO | DSIM_OPT_DYN)) return DSIM_E_UNSUPPORTED;   // (the adaptor envs fly Physics.PYB)
-  ctx->dw_prebin_valid = false;
+  ctx->prebin.valid = false;
   a.action = action; a.echo = last_action_out;
   const bool noise = args->noise_seed != 0, uni = args->type_id == nullptr;
   const dim3 g(grid_for(a.n_pad)), b(256);
