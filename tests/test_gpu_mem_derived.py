@@ -1,10 +1,13 @@
 """DSIM_OPT_MEM_DERIVED: a fused step that recomputes last_vel / last_rates from the rigid state it has just loaded, instead of
 reading them, leaves the state block bit for bit as the launch that reads them.  Two envs that differ only in ``mem_hint``;
 np.array_equal, no tolerance: the recomputed body rates go through the one pinned helper that also produced the stored ones
-(dsim_device.h: body_rates).  Covers every instance that honours the bit — k_step_fast with TGT_CONST: noise on / off x
-streaming on / off; k_step_hexa: noise x streaming — the quad launches without TGT_CONST, which carry the bit and whose
-kernels ignore it, and every way the env must withhold the hint for one launch.  WHICH kernel a launch ran is not visible from
-here: tools/kernel_coverage.sh lists the instances this suite launches (profiles/r09_kernels_launched_by_tests.txt)."""
+(dsim_device.h: body_rates).  An A/B test: it covers the host logic (every way the env must withhold the hint for one launch) and
+bit-identity with the sibling IN GENTLE FLIGHT, 50 steps from rest, on the instances that honour the bit — k_step_fast with
+TGT_CONST: noise on / off x streaming on / off; k_step_hexa: noise x streaming — and on the quad launches without TGT_CONST, which
+carry the bit and whose kernels ignore it.  WHICH kernel a launch ran is not visible from here: tools/kernel_coverage.sh lists
+the instances this suite launches (profiles/r09_kernels_launched_by_tests.txt).  Parity of those instances with the ORACLE,
+bit-identity over the envelope (rates at the +-100 rad/s clamp, tumbling, non-unit quaternions, tiny rates) and a witness launch
+that proves the dispatch: tests/test_gpu_hinted_vs_oracle.py."""
 import numpy as np
 import pytest
 import torch

@@ -2657,31 +2657,126 @@ def _noise_block(O, types, tid, n, seed, step_index, sub, fine=None):
     return nz
 
 
-def _sweep_case(gpu, label, types, tid, n, sub, seed, options, action=None, n_steps=1, runs=None, layout="tile64", pad=256,
-                fleet_kw=None, dt_phys=None, waypoints=False):
-    """One dsim_step launch (both streaming policies, bit-identical) against the oracle at the step bar.  fleet_kw: keywords for
-    random_fleet (envelope= ...); dt_phys: the physics period (default 1/240 s; dt_ctrl = sub x dt_phys); waypoints: the targets
-    come from a three-row waypoint table + per-drone offsets (examples/fly_INDI_TrajectoryTrack.py:242-245) — the EXT instances of
-    the fast kernel, also for a single Env.step per launch."""
-    nat, fleet = gpu
+def _body_rates_f32(rigid):
+    """f32(R(q)^T w) per drone: what a control law leaves in last_rates on this rigid state (INDIControl.py:428-430)."""
+    out = np.zeros((rigid.shape[0], 3))
+    for i in range(rigid.shape[0]):
+        R = np.array(orc.matrix_from_quat(rigid[i, 3:7])).reshape(3, 3)
+        out[i] = f32(R.T @ rigid[i, 10:13])
+    return out
+
+
+def _tgt_const_row(rng, seed):
+    """The seven constants (vel3 acc3 yaw, fp32-representable) of a DSIM_OPT_TGT_CONST case, chosen to exercise the law
+    (INDIControl.py:278-296, 341): vel within +-0.5 with one component -0.0; two acc components of opposite sign at 3.5-4, which
+    together with the position term kd (kp pos_e + ...) push the acceleration error through its +-6 clip in both directions for
+    part of a fleet whose position errors reach +-1 m and leave it inside for the rest; a yaw target within 0.2 of +-pi for odd
+    seeds, so that norm_ang of the yaw error wraps for the drones heading the other way round."""
+    vel = rng.uniform(-0.5, 0.5, 3)
+    vel[int(rng.integers(0, 3))] = -0.0
+    acc = np.array([rng.uniform(3.5, 4.0), -rng.uniform(3.5, 4.0), rng.uniform(-4.0, 4.0)])[rng.permutation(3)]
+    if seed % 2:
+        yaw = (1.0 if rng.uniform() < 0.5 else -1.0) * rng.uniform(math.pi - 0.2, math.pi - 1e-3)
+    else:
+        yaw = rng.uniform(-2.5, 2.5)
+    return f32(np.concatenate([vel, acc, [yaw]]))
+
+
+def _sweep_inputs(types, tid, n, sub, seed, derived, fleet_kw=None, tgt_const=False, tgt_period=0):
+    """(rigid, mem, tgt) of one _sweep_case, host side only (tests/test_hinted_inputs_cpu.py builds the same inputs without a
+    device).  derived: the stored last_vel / last_rates are what a control law left on this very rigid state — the precondition
+    of DSIM_OPT_CHAINED and DSIM_OPT_MEM_DERIVED."""
     na = max(t.n_act for t in types)
-    DT = float(np.float32(dt_phys)) if dt_phys is not None else globals()["DT"]
-    rigid, mem, tgt = random_fleet(np.random.default_rng(n + sub + seed), n, n_act=na, **(fleet_kw or dict(tilt=0.3, rate=1.0)))
+    rng = np.random.default_rng(n + sub + seed)
+    rigid, mem, tgt = random_fleet(rng, n, n_act=na, **(fleet_kw or dict(tilt=0.3, rate=1.0)))
     if tid is not None:
         for k, t in enumerate(types):
             mem[tid == k, 7 + t.n_act:13] = 0.0
     elif na == 4:
         mem[:, 11:13] = 0.0
-    if options & nat.OPT_CHAINED:
-        # the chained form does not READ last_vel / last_rates: it takes them to be what a previous step left — the
+    if derived:
+        # these forms do not READ last_vel / last_rates: they take them to be what a previous step left — the
         # velocity and the body rates of the stored state (computeControl stores them at the end of every call)
         mem[:, 0:3] = rigid[:, 7:10]
-        for i in range(n):
-            R = np.array(orc.matrix_from_quat(rigid[i, 3:7])).reshape(3, 3)
-            mem[i, 3:6] = f32(R.T @ rigid[i, 10:13])
+        mem[:, 3:6] = _body_rates_f32(rigid)
         mem = f32(mem)
+    if tgt_period:
+        # env replicas of one task: the target rows repeat with the period, the states do not
+        assert tgt_period % 256 == 0 and tgt_period < n and n % tgt_period == 0, (n, tgt_period)
+        tgt = np.tile(tgt[:tgt_period], (n // tgt_period, 1))
+    if tgt_const:
+        tgt = tgt.copy()
+        tgt[:, 3:10] = _tgt_const_row(rng, seed)[None, :]
+    return rigid, mem, tgt
+
+
+def _prime_on_device(gpu, types, n, layout, pad, rigid, mem, tgt, sub, DT, dtc, seed, step_index):
+    """(r0, m0) behind ONE plain dsim_step (no hint) from (rigid, mem): a state in which last_vel / last_rates are what the
+    device's own control law stored — last_vel == vel is asserted bit for bit."""
+    nat, fleet = gpu
+    ctx = fleet.Context(types)
+    st, tg = fleet.FleetState(ctx, n, layout, pad), fleet.Targets(ctx, n, layout, pad=pad)
+    st.load_aos(rigid, mem)
+    tg.set_fields(0, torch.from_numpy(np.ascontiguousarray(tgt.T)))
+    a = _args(nat, sub, DT, dtc, seed=seed, step_index=step_index)
+    nat.check(ctx.lib.dsim_step(ctx.handle, _stream(ctx), n, st.view(), tg.view(), ctypes.byref(a)))
+    r0, m0 = st.rigid_aos(), st.mem_aos()
+    ctx.close()
+    assert np.isfinite(r0).all() and np.isfinite(m0).all()
+    np.testing.assert_array_equal(m0[:, 0:3], r0[:, 7:10])
+    return r0, m0
+
+
+def _fill_tgt_const(nat, a, row10):
+    """DSIM_OPT_TGT_CONST with pos per drone on the args, the exact bits of row10[3:10] (fleet.Targets.fill_const_hint)."""
+    a.options |= nat.OPT_TGT_CONST
+    a.tgt_const_mask = 0xE
+    dst = (ctypes.c_uint32 * nat.NT).from_address(ctypes.addressof(a) + nat.StepArgs.tgt_const.offset)
+    for k, b in enumerate(np.asarray(row10, dtype=np.float32).view(np.uint32)):
+        dst[k] = int(b) if k >= 3 else 0
+
+
+def _poison(block, f0, f1, first_drone, last_drone):
+    """NaN into fields [f0, f1) of drones [first_drone, last_drone) of a BlockedSoA's device array (whole blocks of the layout)."""
+    nan = float("nan")
+    if block.layout == "soa":
+        block._data[f0:f1, first_drone:last_drone] = nan
+    else:
+        assert first_drone % block.block == 0 and last_drone % block.block == 0
+        block._data[first_drone // block.block:last_drone // block.block, f0:f1, :] = nan
+
+
+def _sweep_case(gpu, label, types, tid, n, sub, seed, options, action=None, n_steps=1, runs=None, layout="tile64", pad=256,
+                fleet_kw=None, dt_phys=None, waypoints=False, tgt_const=False, tgt_period=0, mem_derived=False, witness=False,
+                prime=False):
+    """One dsim_step launch (both streaming policies, bit-identical) against the oracle at the step bar.  fleet_kw: keywords for
+    random_fleet (envelope= ...); dt_phys: the physics period (default 1/240 s; dt_ctrl = sub x dt_phys); waypoints: the targets
+    come from a three-row waypoint table + per-drone offsets (examples/fly_INDI_TrajectoryTrack.py:242-245) — the EXT instances of
+    the fast kernel, also for a single Env.step per launch.
+    The traffic hints (include/dronesim_amd.h), all off by default: tgt_const — vel / acc / yaw hold ONE row of constants
+    (_tgt_const_row), in the view and in the arguments (DSIM_OPT_TGT_CONST, mask 0xE); tgt_period — the target rows repeat with
+    that many drones (dsim_step_args.tgt_period; use a small spread= in fleet_kw, so that the position errors of the replicas lie
+    on both sides of the clip); mem_derived — the stored last_vel / last_rates are those of the rigid state and the launch carries
+    DSIM_OPT_MEM_DERIVED (it stores the six fields: rigid and mem are judged in full, nothing is materialised).  The oracle gets
+    the full [n, 10] array and the full memory either way.  witness: a second launch from the same state and arguments with NaN in
+    every device field the hinted instance must not read; it must return finite, identical bits — which proves that the hinted
+    instance, not the sibling that reads the fields, produced the judged result.  For instances the header documents as
+    honouring the hint only.  prime (with mem_derived): the precondition is not built on the host (f32 of the fp64 body rates,
+    which the oracle then reads while the kernel recomputes its own fp32 ones) but by one un-hinted dsim_step on the device from
+    the constructed state; launch and oracle are judged from the state (r0, m0) read back behind it, in which the stored fields
+    are the device's own."""
+    nat, fleet = gpu
+    na = max(t.n_act for t in types)
+    DT = float(np.float32(dt_phys)) if dt_phys is not None else globals()["DT"]
     dtc = float(np.float32(sub / 240)) if dt_phys is None else float(np.float32(sub * DT))
     sidx = 4
+    rigid, mem, tgt = _sweep_inputs(types, tid, n, sub, seed, (bool(options & nat.OPT_CHAINED) or mem_derived) and not prime, fleet_kw,
+                                    tgt_const, tgt_period)
+    if prime:
+        assert mem_derived and tid is None and action is None and not waypoints
+        rigid, mem = _prime_on_device(gpu, types, n, layout, pad, rigid, mem, tgt, sub, DT, dtc, seed, sidx - 1)
+    if mem_derived:
+        options |= nat.OPT_MEM_DERIVED
     got = {}
     wp_rows = wp_cnt = wp_off = None
     if waypoints:
@@ -2692,34 +2787,70 @@ def _sweep_case(gpu, label, types, tid, n, sub, seed, options, action=None, n_st
         wp_off = (tgt[:, 0:3].astype(np.float32) - wp_rows[wp_cnt, 0:3]).astype(np.float32)
         tgt = np.concatenate([(wp_rows[wp_cnt, 0:3] + wp_off).astype(np.float64), wp_rows[wp_cnt, 3:10].astype(np.float64)], 1)   # (fp32 sum, as the kernel forms it)
     for pol in (nat.OPT_STREAM_ON, nat.OPT_STREAM_OFF):
-        ctx = fleet.Context(types)
-        st, tg = fleet.FleetState(ctx, n, layout, pad), fleet.Targets(ctx, n, layout, pad=pad)
-        st.load_aos(rigid, mem)
-        tg.set_fields(0, torch.from_numpy(np.ascontiguousarray(tgt.T)))
-        tdev = None
-        if tid is not None:
-            tdev = torch.zeros(st.n_pad, dtype=torch.uint8, device=ctx.device); tdev[:n] = torch.from_numpy(tid)
-        adev = None
-        if action is not None:
-            adev = torch.zeros((na, st.n_pad), device=ctx.device); adev[:, :n] = torch.from_numpy(np.ascontiguousarray(action.T)).float()
-        a = _args(nat, sub, DT, dtc, options=options | pol, seed=seed, step_index=sidx, type_id=tdev, action=adev)
-        a.n_steps = n_steps
-        if waypoints:
-            wp = fleet.WaypointTargets(ctx, n, wp_rows[:, 0:3], wp_rows[:, 3:6], wp_rows[:, 6:9], wp_rows[:, 9], wp_counters=wp_cnt, offsets=wp_off, pad=pad)
-            wp.fill(a)
-        arr = None
-        if runs is not None:
-            arr = (nat.TypeRun * len(runs))()
-            for k, (f, c, ty) in enumerate(runs):
-                arr[k].first, arr[k].count, arr[k].type = f, c, ty
-            a.runs, a.n_runs = ctypes.addressof(arr), len(runs)
-        nat.check(ctx.lib.dsim_step(ctx.handle, _stream(ctx), n, st.view(), tg.view(), ctypes.byref(a)))
-        if options & nat.OPT_CHAINED:
-            nat.check(ctx.lib.dsim_materialize(ctx.handle, _stream(ctx), n, st.view()))
-        got[pol] = (st.rigid_aos(), st.mem_aos())
-        ctx.close()
+        for poisoned in ((False, True) if witness else (False,)):
+            ctx = fleet.Context(types)
+            st, tg = fleet.FleetState(ctx, n, layout, pad), fleet.Targets(ctx, n, layout, pad=pad)
+            st.load_aos(rigid, mem)
+            tg.set_fields(0, torch.from_numpy(np.ascontiguousarray(tgt.T)))
+            tdev = None
+            if tid is not None:
+                tdev = torch.zeros(st.n_pad, dtype=torch.uint8, device=ctx.device); tdev[:n] = torch.from_numpy(tid)
+            adev = None
+            if action is not None:
+                adev = torch.zeros((na, st.n_pad), device=ctx.device); adev[:, :n] = torch.from_numpy(np.ascontiguousarray(action.T)).float()
+            a = _args(nat, sub, DT, dtc, options=options | pol, seed=seed, step_index=sidx, type_id=tdev, action=adev)
+            a.n_steps = n_steps
+            if tgt_const:
+                _fill_tgt_const(nat, a, tgt[0])
+            if tgt_period:
+                assert st.n_pad == n, (n, st.n_pad)          # the period is a statement about every drone of the padded view
+                a.tgt_period = tgt_period
+            if poisoned:
+                # This launch knowingly BREAKS the caller's side of the contract (the view and the block must hold the values
+                # whether or not the library reads them), in order to pin dispatch: only the whole 256-drone tiles are served
+                # by the hinted instances, so only they are poisoned (a ragged tail goes to the general kernel, which reads)
+                assert tgt_const or tgt_period or mem_derived, "witness: no hint to witness"
+                whole = (st.n_pad // 256) * 256
+                if tgt_const:
+                    _poison(tg, 3, 10, 0, whole)
+                if tgt_period:
+                    _poison(tg, 0, 10, tgt_period, whole)
+                if mem_derived:
+                    _poison(st, 13, 19, 0, whole)
+            if waypoints:
+                wp = fleet.WaypointTargets(ctx, n, wp_rows[:, 0:3], wp_rows[:, 3:6], wp_rows[:, 6:9], wp_rows[:, 9], wp_counters=wp_cnt, offsets=wp_off, pad=pad)
+                wp.fill(a)
+            arr = None
+            if runs is not None:
+                arr = (nat.TypeRun * len(runs))()
+                for k, (f, c, ty) in enumerate(runs):
+                    arr[k].first, arr[k].count, arr[k].type = f, c, ty
+                a.runs, a.n_runs = ctypes.addressof(arr), len(runs)
+            nat.check(ctx.lib.dsim_step(ctx.handle, _stream(ctx), n, st.view(), tg.view(), ctypes.byref(a)))
+            if options & nat.OPT_CHAINED:
+                nat.check(ctx.lib.dsim_materialize(ctx.handle, _stream(ctx), n, st.view()))
+            res = (st.rigid_aos(), st.mem_aos())
+            ctx.close()
+            if poisoned:
+                assert np.isfinite(res[0]).all() and np.isfinite(res[1]).all(), f"{label}: the launch read a field its hint covers"
+                np.testing.assert_array_equal(res[0], got[pol][0], err_msg=label + " (witness)")
+                np.testing.assert_array_equal(res[1], got[pol][1], err_msg=label + " (witness)")
+            else:
+                got[pol] = res
     np.testing.assert_array_equal(got[nat.OPT_STREAM_ON][0], got[nat.OPT_STREAM_OFF][0], err_msg=label)
     np.testing.assert_array_equal(got[nat.OPT_STREAM_ON][1], got[nat.OPT_STREAM_OFF][1], err_msg=label)
+    r, m, r0, m0 = _sweep_oracle(nat, types, tid, n, sub, seed, options, rigid, mem, tgt, DT, dtc, action, n_steps, sidx)
+    if n_steps == 1:
+        assert_step_parity(label, types, tid, rigid, mem, tgt, got[nat.OPT_STREAM_OFF][0], got[nat.OPT_STREAM_OFF][1], r, m,
+                           DT, dtc, sub, action=action, noise=bool(seed))
+    else:      # several Env.steps in one launch: the bar of the LAST step from the oracle's previous state, widened by the count
+        assert_step_parity(label, types, tid, r0, m0, tgt, got[nat.OPT_STREAM_OFF][0], got[nat.OPT_STREAM_OFF][1], r, m,
+                           DT, dtc, sub, k=K_ULP * sub * 4 * n_steps)
+
+
+def _sweep_oracle(nat, types, tid, n, sub, seed, options, rigid, mem, tgt, DT, dtc, action=None, n_steps=1, sidx=4):
+    """The oracle's n_steps fused steps from (rigid, mem): (rigid, mem) after the last one and before it."""
+    na = max(t.n_act for t in types)
     O = orc.Oracle(types)
     r, m = rigid.copy(), mem.copy()
     for k in range(n_steps):
@@ -2729,12 +2860,7 @@ def _sweep_case(gpu, label, types, tid, n, sub, seed, options, action=None, n_st
         if action is not None and k == 0:
             a6 = np.zeros((n, 6)); a6[:, :na] = action
         assert O.step(r, m, tgt, sub, DT, dtc, noise=nz, type_id=tid, action=a6, options=options & (nat.OPT_DRAG | nat.OPT_GROUND)) == 0
-    if n_steps == 1:
-        assert_step_parity(label, types, tid, rigid, mem, tgt, got[nat.OPT_STREAM_OFF][0], got[nat.OPT_STREAM_OFF][1], r, m,
-                           DT, dtc, sub, action=action, noise=bool(seed))
-    else:      # several Env.steps in one launch: the bar of the LAST step from the oracle's previous state, widened by the count
-        assert_step_parity(label, types, tid, r0, m0, tgt, got[nat.OPT_STREAM_OFF][0], got[nat.OPT_STREAM_OFF][1], r, m,
-                           DT, dtc, sub, k=K_ULP * sub * 4 * n_steps)
+    return r, m, r0, m0
 
 
 @pytest.mark.parametrize("seed", [0, 7])

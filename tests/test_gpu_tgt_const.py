@@ -1,7 +1,9 @@
 """DSIM_OPT_TGT_CONST: a fleet whose Targets hand vel / acc / yaw to the kernels as constants steps exactly — torch.equal on the
 state block — as an identical fleet whose kernels read those fields (its Targets were handed out, so it never offers the hint).
-Covers every instance that honours the hint: k_step_fast with noise on / off, streaming on / off, chained on / off, one and five
-sub-steps, and k_control_fast with and without the yaw error, streaming on / off."""
+An A/B test: it covers the host logic (when the env offers the hint, re-keys a prepared launch, withdraws it for good) and
+bit-identity with the sibling IN GENTLE FLIGHT on the instances that honour the hint — k_step_fast with noise on / off, streaming
+on / off, chained on / off, one and five sub-steps, k_control_fast with and without the yaw error, streaming on / off.  Parity of
+those instances with the ORACLE, constants that exercise the law, and the envelope: tests/test_gpu_hinted_vs_oracle.py."""
 import ctypes
 
 import numpy as np

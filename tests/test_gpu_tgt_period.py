@@ -1,8 +1,10 @@
 """dsim_step_args.tgt_period: a fleet of replicas that share one task (the targets repeat with a period) steps exactly — torch.equal
 on the state block — as an identical fleet whose kernels read every target (its Targets were handed out, so it offers no hint).
-Covers every k_step_fast instance that honours the period: noise on / off, streaming on / off, chained on / off, one and five
-sub-steps, with DSIM_OPT_TGT_CONST (vel / acc / yaw constant) and without it (vel per drone, periodic).  A launch through the C ABI
-with NaN in every target beyond the first period proves that those instances read the first period only."""
+An A/B test: it covers the host logic (which period a Targets finds and hands to a prepared launch, when it gives it up) and
+bit-identity with the sibling IN GENTLE FLIGHT on the k_step_fast instances that honour the period: noise on / off, streaming
+on / off, chained on / off, one and five sub-steps, with DSIM_OPT_TGT_CONST (vel / acc / yaw constant) and without it (vel per
+drone, periodic).  A launch through the C ABI with NaN in every target beyond the first period proves that those instances read
+the first period only.  Parity of those instances with the ORACLE and the envelope: tests/test_gpu_hinted_vs_oracle.py."""
 import ctypes
 
 import numpy as np
