@@ -21,9 +21,11 @@ EXPORTS = (
     "dsim_downwash_workspace", "dsim_downwash_prebin_ok", "dsim_downwash_reset", "dsim_adjacency", "dsim_wls_fallback", "dsim_fleet_bounds",
     "dsim_halo_pack", "dsim_downwash_workspace_halo", "dsim_dev_alloc", "dsim_dev_free", "dsim_noise_draw",
     "dsim_downwash_keep_workspace", "dsim_downwash_keep_ok", "dsim_downwash_keep_stats",
+    "dsim_clearance", "dsim_clearance_workspace", "dsim_abi_minor",
 )
 
 ABI_VERSION = 11
+ABI_MINOR = 1            # DSIM_ABI_MINOR: dsim_type_params ends with collision_sphere; dsim_clearance
 MAX_PEERS = 8
 HALO_HDR = 8           # header floats of a halo message (DSIM_HALO_HDR)
 DW_ALL, DW_LOCAL, DW_HALO_BIN, DW_HALO_QUERY = 0, 1, 2, 3
@@ -54,6 +56,7 @@ TGT_CONST_POS_PER_DRONE = 0xE   # the mask the kernels honour: pos per drone, ve
 ADAPT_VELOCITY, ADAPT_RPYT = 0, 1
 QUERY_WLS_FALLBACKS, QUERY_WLS_FAILURES, QUERY_GROUND_CONTACTS, QUERY_HALO_OVERFLOW = 0, 1, 2, 3
 QUERY_DW_REUSES, QUERY_DW_MOVERS = 4, 5
+QUERY_DRONE_CONTACTS = 6     # pairs of drones x dsim_clearance calls whose bounding spheres overlapped
 
 
 class View(ctypes.Structure):
@@ -202,8 +205,12 @@ def load(path: str = None) -> ctypes.CDLL:
     lib.dsim_downwash_keep_workspace.argtypes = [i64, i32, i32]
     lib.dsim_downwash_keep_ok.argtypes = [i64, i32, i32, ctypes.c_float, ctypes.c_float]
     lib.dsim_downwash_keep_stats.argtypes = [vp] + [ctypes.POINTER(ctypes.c_int64)] * 4
-    if lib.dsim_abi_version() != ABI_VERSION:
-        raise ImportError(f"libdronesim_amd.so ABI {lib.dsim_abi_version()} != binding {ABI_VERSION}")
+    lib.dsim_clearance_workspace.restype = ctypes.c_int64
+    lib.dsim_clearance_workspace.argtypes = [i64, i32, i32]
+    lib.dsim_clearance.argtypes = [vp, vp, i64, View, ctypes.POINTER(DownwashArgs), vp, ctypes.c_float, vp, vp, vp]
+    lib.dsim_abi_minor.restype = ctypes.c_int
+    if lib.dsim_abi_version() != ABI_VERSION or lib.dsim_abi_minor() != ABI_MINOR:
+        raise ImportError(f"libdronesim_amd.so ABI {lib.dsim_abi_version()}.{lib.dsim_abi_minor()} != binding {ABI_VERSION}.{ABI_MINOR}")
     _lib = lib
     return lib
 

@@ -266,6 +266,7 @@ static void to_dev(const dsim_type_params& p, DevType* d) {
   if (p.kind == DSIM_KIND_HEXA6DOF) { d->reset_thrust = 0.3f; d->reset_cmd = 0.5f; }   // INDIControl_6DOF.py:232-234
   d->speed_limit = (float)(p.max_speed_kmh * (1000.0 / 3600.0));
   d->coll_r = (float)p.collision_radius; d->coll_below = (float)p.collision_below;
+  d->coll_sphere = (float)p.collision_sphere;
   d->mu_plane = (float)p.contact_friction;
   for (int k = 0; k < 3; ++k) d->base_off[k] = (float)p.base_offset[k];
   d->watch_below = (float)(p.collision_below + p.base_offset[2]);    // (the offset of the shipped hexa is along body z)
@@ -463,6 +464,7 @@ int observe_impl(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, const 
 extern "C" {
 
 int dsim_abi_version(void) { return DSIM_ABI_VERSION; }
+int dsim_abi_minor(void) { return DSIM_ABI_MINOR; }
 
 const char* dsim_strerror(int code) {
   switch (code) {
@@ -508,8 +510,8 @@ int dsim_create(dsim_ctx** out, int device, const dsim_type_params* types, int n
   for (int t = 0; t < n_types; ++t) { c->h_types[t] = types[t]; to_dev(types[t], &h[t]); }
   e = hipMalloc((void**)&c->d_types, sizeof(DevType) * DSIM_MAX_TYPES);
   if (e == hipSuccess) e = hipMemcpy(c->d_types, h, sizeof(DevType) * DSIM_MAX_TYPES, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMalloc((void**)&c->d_counters, sizeof(unsigned long long) * (8 + DSIM_GROUND_SHARDS));
-  if (e == hipSuccess) e = hipMemset(c->d_counters, 0, sizeof(unsigned long long) * (8 + DSIM_GROUND_SHARDS));
+  if (e == hipSuccess) e = hipMalloc((void**)&c->d_counters, sizeof(unsigned long long) * DSIM_N_COUNTERS);
+  if (e == hipSuccess) e = hipMemset(c->d_counters, 0, sizeof(unsigned long long) * DSIM_N_COUNTERS);
   if (e == hipSuccess) e = hipMalloc((void**)&c->d_bounds, sizeof(unsigned) * 8);
   if (e == hipSuccess) {
     // two ints of host memory the REUSE queries of the neighbour downwash report into (dsim_downwash_keep_stats): best effort —
@@ -565,14 +567,18 @@ int dsim_dev_free(dsim_ctx* ctx, void* ptr) {
 }
 
 int dsim_query(dsim_ctx* ctx, void* stream, int32_t what, int64_t* value_out) {
-  if (!ctx || !value_out || what < 0 || what > DSIM_Q_DW_MOVERS) return DSIM_E_ARG;
-  unsigned long long h[8 + DSIM_GROUND_SHARDS];
+  if (!ctx || !value_out || what < 0 || what > DSIM_Q_DRONE_CONTACTS) return DSIM_E_ARG;
+  unsigned long long h[DSIM_N_COUNTERS];
   hipError_t e = hipMemcpyAsync(h, ctx->d_counters, sizeof(h), hipMemcpyDeviceToHost, (hipStream_t)stream);
   if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
   if (e != hipSuccess) return (int)e;
   if (what == DSIM_Q_GROUND_CONTACTS) {
     unsigned long long sum = 0;
     for (int k = 0; k < DSIM_GROUND_SHARDS; ++k) sum += h[8 + k];
+    *value_out = (int64_t)sum;
+  } else if (what == DSIM_Q_DRONE_CONTACTS) {
+    unsigned long long sum = 0;
+    for (int k = 0; k < DSIM_DRONE_SHARDS; ++k) sum += h[8 + DSIM_GROUND_SHARDS + k];
     *value_out = (int64_t)sum;
   } else if (what == DSIM_Q_HALO_OVERFLOW) {
     *value_out = (int64_t)h[4];

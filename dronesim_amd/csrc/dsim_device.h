@@ -51,6 +51,8 @@ struct DevType {
   // (at the end: in the middle of the table they moved every offset behind them, and four instances of k_step_runs came back
   // with a 36-byte scratch reservation)
   double raxis64[DSIM_MAX_ACT][3], rxa64[DSIM_MAX_ACT][3];   // (double)raxis, (double)rxa — the fp32 values, widened (hexa_wrench_base)
+  float coll_sphere;                          // bounding sphere of the collision shapes about the COM (drone-drone contact watch)
+  float _pad_sphere;
 };
 
 // The table is written once (dsim_create) and only read by kernels, which read it through the CONSTANT address space.  A
@@ -366,6 +368,8 @@ struct Target { V3 pos, vel, acc; float yaw; };
 // model the plane (DSIM_OPT_PLANE does, in its own kernel instances), so an Env.step that ends with the vehicle's
 // collision cylinder at or below z = 0 is COUNTED: one atomic per wave that holds such a drone, on one of 64 counter shards (dsim_query sums them).
 #define DSIM_GROUND_SHARDS 64
+#define DSIM_DRONE_SHARDS 64      // the drone-drone contact watch (k_clearance_query) counts on shards of its own, behind the ground watch's
+#define DSIM_N_COUNTERS (8 + DSIM_GROUND_SHARDS + DSIM_DRONE_SHARDS)
 template <class DT>
 __device__ __forceinline__ void ground_watch(DT& T, const Rigid& s, unsigned long long* counters, bool live = true) {
   const float r22 = 1.0f - 2.0f * (s.q.x * s.q.x + s.q.y * s.q.y);                     // body z . world z (unit q)

@@ -1146,6 +1146,76 @@ __global__ __launch_bounds__(256) void k_adj_query(DwK a) {
   if (a.adj_list) for (int k = cnt; k < a.max_k; ++k) a.adj_list[(long long)k * a.n_pad + i] = -1;
 }
 
+// ---- drone-drone contact watch (dsim_clearance): clearance between the vehicles' bounding spheres, same grid ------------------
+// The sorted entry of this query is (x, y, z, R): the candidate's radius arrives with its position, in the one 16-byte load
+// per pair the adjacency pass makes, and the world index — needed for the own entry, for the nearest neighbour at the end
+// and under the rare overlap — lies beside it in sidx[], at the same sorted slot.
+struct ClrK {
+  const float* radius_all;     // [m_pad] radius of every world entry (the pos_all form), or null: the type table
+  int* sidx;                   // [m] sorted slot -> world index
+  float margin;
+  float* clearance;            // [n_pad]
+  int* nearest;                // [n_pad] or null
+  unsigned long long* counters;   // the ctx's (DSIM_Q_DRONE_CONTACTS: DSIM_DRONE_SHARDS shards behind the ground watch's)
+  unsigned long long* pairs_out;  // nullable device counter
+};
+__global__ __launch_bounds__(256) void k_clr_scatter(DwK a, ClrK c) {
+  const long long j = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (j >= a.m) return;
+  const float x = dw_pos(a, j, 0), y = dw_pos(a, j, 1), z = dw_pos(a, j, 2);
+  const float r = c.radius_all ? c.radius_all[j] : a.types[a.type_id ? min((int)a.type_id[j], a.n_types - 1) : 0].coll_sphere;
+  int cx, cy;
+  const int slot = atomicAdd(&a.cursor[dw_cell(a, x, y, cx, cy)], 1);
+  a.sorted[slot] = make_float4(x, y, z, r);
+  c.sidx[slot] = (int)j;
+}
+// Receivers in grid order, one lane each, 3 x 3 cells.  Cells are 2 R_max + margin or more, so a pair with c_ij < margin is
+// less than one cell apart in x and in y: unclamped, its two cell indices differ by at most one per axis, and clamping a drone
+// from outside the box into a border cell is monotone — it never moves two indices further apart — so the pair is still
+// found in adjacent cells.  (The cell index is rounded in fp32: a pair whose distance along one axis is within that rounding of
+// a whole cell has c_ij within the same rounding of margin, where the answer min(margin, .) is margin either way.)
+// The lane keeps key = |p_i - p_j| - R_j against margin + R_i; overlap is key < R_i.  Pairs are counted by the lower world
+// index, summed over the wave by shuffles, one atomic per wave that has something to add (as ground_watch).
+__global__ __launch_bounds__(256) void k_clearance_query(DwK a, ClrK c) {
+  const long long s = (long long)blockIdx.x * 256 + threadIdx.x;
+  bool live = s < a.m;
+  const float4 me = live ? a.sorted[s] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  const int jme = live ? c.sidx[s] : -1;
+  const long long i = (long long)jme - a.local_offset;
+  live = live && i >= 0 && i < a.n;                             // (another rank's drone: a candidate only)
+  float best = c.margin + me.w;
+  int bslot = -1;
+  unsigned pairs = 0;
+  if (live && me.w > 0.0f) {
+    int cx, cy;
+    dw_cell(a, me.x, me.y, cx, cy);
+    for (int yy = max(cy - 1, 0); yy <= min(cy + 1, a.ny - 1); ++yy) {
+      const int c0 = yy * a.nx + max(cx - 1, 0), c1 = yy * a.nx + min(cx + 1, a.nx - 1);
+      for (int s2 = a.count[c0]; s2 < a.count[c1 + 1]; ++s2) {
+        const float4 p = a.sorted[s2];
+        const float dx = p.x - me.x, dy = p.y - me.y, dz = p.z - me.z;
+        const float key = DSIM_SQRT(dx * dx + dy * dy + dz * dz) - p.w;
+        const bool seen = s2 != (int)s && p.w > 0.0f;
+        if (seen && key < me.w && c.sidx[s2] > jme) ++pairs;
+        const bool better = seen && key < best;
+        best = better ? key : best;
+        bslot = better ? s2 : bslot;
+      }
+    }
+  }
+  if (live) {
+    c.clearance[i] = bslot >= 0 ? best - me.w : c.margin;
+    if (c.nearest) c.nearest[i] = bslot >= 0 ? c.sidx[bslot] : -1;
+  }
+  if (__ballot(pairs != 0u) == 0ULL) return;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) pairs += __shfl_xor(pairs, off);
+  if ((threadIdx.x & 63u) == 0u) {
+    atomicAdd(&c.counters[8 + DSIM_GROUND_SHARDS + (blockIdx.x & (DSIM_DRONE_SHARDS - 1))], (unsigned long long)pairs);
+    if (c.pairs_out) atomicAdd(c.pairs_out, (unsigned long long)pairs);
+  }
+}
+
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
@@ -1342,7 +1412,8 @@ static int bucket_fill(const DwCall& c, const DwK& a, const BinK& b, const KeepP
 }
 // The world's positions into the xy grid.  With `b` (dsim_downwash) a world that suits it takes the bucket form: a->buckets is set,
 // *b is its grid and *plan what became of the call's keep mode.  Otherwise a counting sort: count, scan, scatter.
-static int grid_build(const DwCall& c, float min_cell, DwK* a, BinK* b = nullptr, KeepPlan* plan = nullptr) {
+// scatter = false (counting-sort form): the caller scatters into a->sorted itself, with entries of its own (dsim_clearance).
+static int grid_build(const DwCall& c, float min_cell, DwK* a, BinK* b = nullptr, KeepPlan* plan = nullptr, bool scatter = true) {
   const dsim_downwash_args* g = c.g;
   if (!c.ctx || !g->workspace || c.n <= 0 || c.n > c.state.n_pad) return DSIM_E_ARG;
   // pos_all = NULL: the world is this fleet (m = n, local_offset = 0) and positions are read from the state block — or,
@@ -1381,7 +1452,7 @@ static int grid_build(const DwCall& c, float min_cell, DwK* a, BinK* b = nullptr
   // (measured and rejected: letting the last count workgroup do the scan — the fences and the one-workgroup scan
   // behind them cost 28 us against 7 + 6.5 us for the two launches)
   hipLaunchKernelGGL(k_dw_scan, dim3(1), dim3(1024), 0, c.st, *a);
-  hipLaunchKernelGGL(k_dw_scatter, dim3(grid_for(a->m)), dim3(256), 0, c.st, *a);
+  if (scatter) hipLaunchKernelGGL(k_dw_scatter, dim3(grid_for(a->m)), dim3(256), 0, c.st, *a);
   return DSIM_OK;
 }
 
@@ -1564,6 +1635,35 @@ int dsim_adjacency(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, cons
   if (rc) return rc;
   a.radius2 = radius * radius; a.adj_count = count_out; a.adj_list = list_out; a.max_k = list_out ? max_k : 0;
   hipLaunchKernelGGL(k_adj_query, dim3(grid_for(a.m)), dim3(256), 0, st_, a);
+  return (int)hipGetLastError();
+}
+
+// counting-sort form + the world index of every sorted slot behind it
+int64_t dsim_clearance_workspace(int64_t m, int32_t nx, int32_t ny) {
+  const int64_t base = dsim_downwash_workspace(m, nx, ny);
+  if (base < 0) return -1;
+  WsWalk w = sort_ws(nullptr, (int64_t)nx * ny, m).end;
+  w.take<int>(m);
+  return w.len > base ? w.len : base;
+}
+
+int dsim_clearance(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, const dsim_downwash_args* g,
+                   const float* radius_all, float margin, float* clearance_out, int32_t* nearest_out, uint64_t* pairs_out) {
+  if (!ctx || !g || !clearance_out || !(margin > 0)) return DSIM_E_ARG;
+  if (g->halo) return DSIM_E_UNSUPPORTED;
+  if ((g->pos_all != nullptr) != (radius_all != nullptr)) return DSIM_E_ARG;     // the world's radii travel with its positions
+  if (ctx->n_types > 1 && !g->type_id && !radius_all) return DSIM_E_ARG;
+  float r_max = 0.0f;
+  for (int t = 0; t < ctx->n_types; ++t) r_max = fmaxf(r_max, (float)ctx->h_types[t].collision_sphere);
+  if (g->nx < 1 || g->ny < 1 || g->m < 1 || g->workspace_len < dsim_clearance_workspace(g->m, g->nx, g->ny)) return DSIM_E_ARG;
+  DwK a;
+  const hipStream_t st_ = (hipStream_t)stream;
+  int rc = grid_build(DwCall{ctx, st_, n, state, g, GridGeo(*g)}, 2.0f * r_max + margin, &a, nullptr, nullptr, false);
+  if (rc) return rc;
+  WsWalk w = sort_ws(g->workspace, GridGeo(*g).ncells(), g->m).end;
+  ClrK c = {radius_all, w.take<int>(g->m), margin, clearance_out, nearest_out, ctx->d_counters, (unsigned long long*)pairs_out};
+  hipLaunchKernelGGL(k_clr_scatter, dim3(grid_for(a.m)), dim3(256), 0, st_, a, c);
+  hipLaunchKernelGGL(k_clearance_query, dim3(grid_for(a.m)), dim3(256), 0, st_, a, c);
   return (int)hipGetLastError();
 }
 

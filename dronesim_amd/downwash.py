@@ -28,6 +28,26 @@ from . import _native as nat
 
 CUTOFF = 10.0     # BaseAviary.py:1752: "Ignore drones more than 10 meters away"
 KEEP_RUN_AHEAD = 8    # kept candidate lists: list-served queries the host may be ahead of the device (Downwash._keep_next)
+CLEARANCE_CELLS_PER_DRONE = 4     # Downwash.clearance: its grid has at most this many cells per drone of the world (clearance_grid) ...
+CLEARANCE_MAX_CELLS = 1 << 22     # ... and never more than this (as Downwash._grid_box)
+
+
+def clearance_grid(lo, hi, r_max: float, margin: float, m: int):
+    """The grid of Downwash.clearance for a world of ``m`` drones whose xy bounding box is ``lo`` .. ``hi``:
+    (cell, xmin, ymin, nx, ny).  Two bounds: the cell is at least 2 r_max + margin (what dsim_clearance needs to find every
+    pair closer than ``margin`` in adjacent cells; a thousandth more, so that fp32 rounding of the sum cannot undercut it), and
+    it is doubled until nx ny <= max(CLEARANCE_CELLS_PER_DRONE m, 16) and <= CLEARANCE_MAX_CELLS — a sparse fleet spread over kilometres gets a few
+    large cells, not a count array far larger than the fleet (3 x 3 cells, the least a box with its one-cell margin takes,
+    always pass)."""
+    cell = (2.0 * float(r_max) + float(margin)) * (1.0 + 2.0 ** -10)
+    limit = min(max(CLEARANCE_CELLS_PER_DRONE * int(m), 16), CLEARANCE_MAX_CELLS)
+    while True:
+        xmin, ymin = float(lo[0]) - cell, float(lo[1]) - cell
+        nx = max(1, int(math.floor((float(hi[0]) + cell - xmin) / cell)) + 1)
+        ny = max(1, int(math.floor((float(hi[1]) + cell - ymin) / cell)) + 1)
+        if nx * ny <= limit:
+            return cell, xmin, ymin, nx, ny
+        cell *= 2.0
 
 
 def shard_counts(n_local: int, dist=None):
@@ -656,3 +676,49 @@ class Downwash:
                                               float(radius), count.data_ptr(), lst.data_ptr() if lst is not None else None,
                                               max_k))
         return count[: st.n], (lst[:, : st.n] if lst is not None else None)
+
+    def clearance(self, margin: float, world_pos: Optional[torch.Tensor] = None, world_radius: Optional[torch.Tensor] = None,
+                  local_offset: Optional[int] = None, pairs_out: Optional[torch.Tensor] = None, box=None):
+        """Drone-drone contact watch (dsim_clearance): per local drone the clearance min(margin, min_j |p_i - p_j| - R_i - R_j)
+        between the vehicles' bounding spheres (DroneType.collision_sphere) and the world index of the drone that attains
+        it (-1: none closer than ``margin``), as (clearance [n] float32, nearest [n] int32).  Pairs whose spheres overlap
+        are counted into the context (nat.QUERY_DRONE_CONTACTS) and, when given, added to ``pairs_out`` (int64 [1] on the
+        device).  ``world_pos`` [3, m] with ``world_radius`` [m]: the positions and radii of every drone of the world, this
+        block's drones at ``local_offset``; neither: the world is this block.  The call chooses its own grid
+        (clearance_grid) over the fleet's bounding box, re-measured every ``box_refresh`` calls like the downwash's (one
+        host sync), or over ``box`` = (xmin, ymin, xmax, ymax) when the caller knows the arena: drones outside the box are
+        clamped to its border cells, which costs search efficiency, never a pair."""
+        st, lib = self.state, self.ctx.lib
+        if (world_pos is None) != (world_radius is None):
+            raise ValueError("clearance: world_pos and world_radius come together (the radii of the remote drones travel with "
+                             "their positions)")
+        if world_pos is None and self.dist is not None and self.dist.is_initialized() and self.dist.get_world_size() > 1:
+            raise NotImplementedError("clearance on a sharded fleet: pass the gathered world_pos / world_radius")
+        margin = float(margin)
+        rad = None
+        if world_pos is not None:
+            world_pos = world_pos.to(torch.float32).contiguous()
+            rad = world_radius.to(device=self.ctx.device, dtype=torch.float32).contiguous()
+        key = (margin, None if world_pos is None else int(world_pos.shape[1]), None if box is None else tuple(float(v) for v in box))
+        if self._box is None or (box is None and self._box_age >= self._box_refresh) or getattr(self, "_clr_key", None) != key:
+            if box is not None:
+                lo, hi = key[2][:2], key[2][2:]
+            else:
+                src = st.raw_fields(0, 2) if world_pos is None else world_pos[:2]
+                lo, hi = src.min(dim=1).values.cpu(), src.max(dim=1).values.cpu()
+            r_max = max(float(t.collision_sphere) for t in self.ctx.types)
+            if rad is not None and rad.numel():
+                r_max = max(r_max, float(rad.max()))
+            self.cell, *grid = clearance_grid(lo, hi, r_max, margin, st.n if world_pos is None else world_pos.shape[1])
+            self._box, self._box_age, self._clr_key = tuple(grid), 0, key
+        self._auto_cell = False
+        self._prebin_version = None
+        a = self._grid_args(world_pos, local_offset)
+        self._workspace(a, lib.dsim_clearance_workspace(a.m, a.nx, a.ny))
+        clr = torch.empty((st.n_pad,), dtype=torch.float32, device=self.ctx.device)
+        near = torch.empty((st.n_pad,), dtype=torch.int32, device=self.ctx.device)
+        self._keep_radius, self._clr_args = rad, a     # (the kernels read the radii asynchronously on the stream)
+        nat.check(lib.dsim_clearance(self.ctx.handle, self.ctx.stream_ptr(), st.n, st.view(), ctypes.byref(a),
+                                     rad.data_ptr() if rad is not None else None, margin, clr.data_ptr(), near.data_ptr(),
+                                     pairs_out.data_ptr() if pairs_out is not None else None))
+        return clr[: st.n], near[: st.n]

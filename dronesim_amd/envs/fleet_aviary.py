@@ -78,6 +78,7 @@ class CtrlAviary(PlacedFleetArrays, FleetObservation):
     # (class-level "no hint": an env made without __init__ launches as before this option existed)
     _mem_hint = False             # DSIM_OPT_MEM_DERIVED is offered (set by __init__)
     _mem_handed_out = True        # ... but not to the next fused launch: the block has been handed out since the last one
+    _drone_watch = False          # the drone-drone contact watch behind every step (set by __init__)
 
     @staticmethod
     def _mem_hint_wanted(mem_hint: bool) -> bool:
@@ -120,9 +121,23 @@ class CtrlAviary(PlacedFleetArrays, FleetObservation):
         downwash_keep: Optional[int] = None,
         downwash_skin: float = 0.1,
         mem_hint: bool = True,
+        drone_watch: bool = False,
+        drone_watch_margin: float = 1.0,
     ):
         if gui or record or obstacles:
             raise NotImplementedError("gui/record/obstacles are rendering features outside the hot path")
+        # The reference's Bullet world lets the vehicles' collision shapes act on each other; here every drone is integrated
+        # alone.  drone_watch=True: every step / step_fused / adaptor step is followed, on the env's stream, by one
+        # dsim_clearance on the state it left (once per Env.step, like the ground watch): drone_contacts() reports how many
+        # pairs of bounding spheres overlapped so far, last_clearance holds (clearance, nearest) of the last step
+        # (drone_clearance()).  Off by default: nothing is launched.
+        if drone_watch and dist is not None and dist.is_initialized() and dist.get_world_size() > 1:
+            raise NotImplementedError("drone_watch on a sharded fleet: the radii of the other ranks' drones would have to travel "
+                                      "with their positions (Downwash.clearance takes world_pos / world_radius)")
+        self._drone_watch, self._drone_watch_margin = bool(drone_watch), float(drone_watch_margin)
+        self.last_clearance = None
+        self._clearance = None    # grid for drone_clearance(), built on first use
+        self._clr_on_demand = None    # int64 [1]: pairs the on-demand queries counted (not Env.steps: drone_contacts() leaves them out)
         # the add-on terms of the PYB_* modes (dead code in the reference fork, intended formulas); Physics.DYN: the
         # reference's own explicit model, BaseAviary._dynamics (BaseAviary.py:1767-1828; DSIM_OPT_DYN)
         self._phys_options = {Physics.PYB: 0, Physics.PYB_DW: 0, Physics.PYB_GND: nat.OPT_GROUND,
@@ -469,6 +484,7 @@ class CtrlAviary(PlacedFleetArrays, FleetObservation):
             self._use_last_action = True
             self.step_counter += self.AGGR_PHY_STEPS
             self._env_steps += 1
+            self._watch_drones()
             return plan.out, self._computeReward(), self._computeDone(), plan.info
         # The neighbour-downwash term is evaluated per PHYSICS SUB-STEP, as the reference loops it (BaseAviary.py:510-536:
         # with AGGR_PHY_STEPS > 1 the positions are refreshed and _downwash applied inside the sub-step loop): one
@@ -504,6 +520,7 @@ class CtrlAviary(PlacedFleetArrays, FleetObservation):
         self._use_last_action = True
         self.step_counter += self.AGGR_PHY_STEPS
         self._env_steps += 1
+        self._watch_drones()
         out = self._computeObs(obs if self._caller_io else self._rows_to_caller(obs))
         self._step_plan = None
         if (passes == 1 and self._downwash is None and out is obs and torch.is_tensor(action) and action.is_cuda
@@ -561,6 +578,7 @@ class CtrlAviary(PlacedFleetArrays, FleetObservation):
                                              plan.targets_view, plan.args_ref))
             self.step_counter += self.AGGR_PHY_STEPS * n_steps
             self._env_steps += n_steps
+            self._watch_drones()
             return
         pd = self._fused_plan_dw
         if (action is None and pd is not None and self._downwash is not None and not self._dw_substepped()
@@ -575,6 +593,7 @@ class CtrlAviary(PlacedFleetArrays, FleetObservation):
                                              pd.targets_view, pd.args_ref))
             self.step_counter += self.AGGR_PHY_STEPS
             self._env_steps += 1
+            self._watch_drones()
             return
         wp = isinstance(targets, WaypointTargets)
         if self._dw_substepped():
@@ -641,6 +660,7 @@ class CtrlAviary(PlacedFleetArrays, FleetObservation):
                 nxt.options |= nat.OPT_MEM_DERIVED       # (taken out for the one launch behind a host access: see the replay)
             if not self._chained_enabled or chain:
                 self._fused_plan = _FusedPlan(key, nxt, sview, tview, ctypes.byref(nxt), targets, self._targets_ptrs(targets))
+        self._watch_drones()       # (once per call: with n_steps > 1 the states in between never leave the registers)
 
     def capture_fused(self, targets, steps: int, control_timestep: Optional[float] = None):
         """Captures ``steps`` consecutive :meth:`step_fused` launches into ONE hipGraph and returns a
@@ -653,6 +673,9 @@ class CtrlAviary(PlacedFleetArrays, FleetObservation):
         query -> step (which fills the next query's grid) -> fallback, and the grid's box is the one measured at capture
         time — drones that leave it are clamped to its border cells, which costs search efficiency,
         never exactness (``Downwash._grid_box``); capture again after the fleet has moved far."""
+        if self._drone_watch:
+            raise NotImplementedError("graph capture with drone_watch: the watch re-measures its grid's box on the host from "
+                                      "time to time, which a captured sequence cannot")
         dw = self._downwash
         if dw is not None:
             world = dw.dist.get_world_size() if (dw.dist is not None and dw.dist.is_initialized()) else 1
@@ -691,6 +714,21 @@ class CtrlAviary(PlacedFleetArrays, FleetObservation):
         which trajectories are comparable with the reference; with ``ground_plane=True`` (the default for
         reference-sized fleets) the product-defined contact model of DSIM_OPT_PLANE acts there instead."""
         return self.ctx.query(nat.QUERY_GROUND_CONTACTS) - self._ground_trial
+
+    def _watch_drones(self) -> None:
+        """drone_watch=True: one dsim_clearance on the state the step just left, on the env's stream."""
+        if self._drone_watch:
+            self.last_clearance = self._drone_query(self._drone_watch_margin, None)
+
+    def drone_contacts(self) -> int:
+        """Pairs of drones x Env.steps so far whose bounding spheres (DroneType.collision_sphere) overlapped behind a step
+        of a ``drone_watch=True`` env (cumulative over this env's context; synchronises the stream).  The reference's
+        Bullet world lets the vehicles' collision shapes act on each other; here contact between drones is not modelled,
+        and a non-zero count means part of the flight lies outside the domain in which trajectories are comparable with
+        the reference.  One-sided: 0 certifies that no two vehicles touched; overlapping spheres need not be touching
+        shapes.  On-demand drone_clearance() calls are not Env.steps and are left out."""
+        seen = self.ctx.query(nat.QUERY_DRONE_CONTACTS)
+        return seen - (int(self._clr_on_demand.item()) if self._clr_on_demand is not None else 0)
 
     def close(self):
         self.ctx.close()

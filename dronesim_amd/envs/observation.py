@@ -75,6 +75,28 @@ class FleetObservation:
                 lst = torch.where(lst >= 0, self.order.drone[lst.clamp(min=0)], lst).to(torch.int32)
         return cnt, lst
 
+    def drone_clearance(self, margin: float = 1.0):
+        """Per-drone clearance of the CURRENT state between the vehicles' bounding spheres (dsim_clearance; no counterpart in
+        the reference, whose Bullet world makes the vehicles collide instead): (clearance [N] float32, nearest [N] int32) in
+        the caller's numbering — clearance[i] = min(margin, min_j |p_i - p_j| - R_i - R_j), nearest[i] = the drone that
+        attains it, -1 when none is closer than ``margin``.  Negative clearance: the two spheres overlap."""
+        if self._clr_on_demand is None:
+            self._clr_on_demand = torch.zeros((1,), dtype=torch.int64, device=self.ctx.device)
+        return self._drone_query(float(margin), self._clr_on_demand)
+
+    def _drone_query(self, margin: float, pairs_out):
+        from ..downwash import Downwash
+        if self._clearance is None:
+            self._clearance = Downwash(self.ctx, self.state, self._type_id, None)
+        if self._downwash is not None:
+            self._downwash.invalidate_prebin()            # the clearance pass re-uses the ctx's grid bookkeeping
+        clr, near = self._clearance.clearance(margin, pairs_out=pairs_out)
+        if self.order is not None:              # per-slot results of slot indices -> per-drone results of drone indices
+            clr = self.order.to_caller(clr, 0)
+            near = self.order.to_caller(near, 0).long()
+            near = torch.where(near >= 0, self.order.drone[near.clamp(min=0)], near).to(torch.int32)
+        return clr, near
+
     def _getAdjacencyMatrix(self, pos: np.ndarray) -> np.ndarray:
         """BaseAviary.py:901-921 — O(N^2), only produced in dict mode (small fleets)."""
         d = np.linalg.norm(pos[:, None, :] - pos[None, :, :], axis=2)

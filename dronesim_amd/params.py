@@ -80,6 +80,7 @@ class TypeParamsC(ctypes.Structure):
         ("arm", ctypes.c_double),
         ("dyn_mixer", ctypes.c_int32),
         ("_pad_dyn", ctypes.c_int32),
+        ("collision_sphere", ctypes.c_double),
     ]
 
 
@@ -120,6 +121,7 @@ class DroneType:
     max_speed_kmh: float = 30.0      # URDF properties max_speed_kmh (all shipped types: 30)
     collision_radius: float = 0.0    # bounding cylinder of the <collision> shapes about body z: radius ...
     collision_below: float = 0.0     # ... and extent below the COM (ground-plane watch; 0 = none)
+    collision_sphere: float = 0.0    # bounding sphere of the same shapes about the COM (drone-drone contact watch; 0 = takes no part)
     contact_friction: float = 0.5    # DSIM_OPT_PLANE: plane.urdf lateral_friction 1.0 x PyBullet's default 0.5 for the vehicle
     base_offset: Sequence[float] = (0.0, 0.0, 0.0)   # integrated COM -> the point PyBullet reports (base link COM), body frame
     arm: float = 0.0                 # URDF <properties arm=...> (BaseAviary.py:2058): the lever L of Physics.DYN's mixer
@@ -213,6 +215,7 @@ class DroneType:
         c.gnd_eff_h_clip = self.gnd_eff_h_clip
         c.max_speed_kmh = self.max_speed_kmh
         c.collision_radius, c.collision_below = self.collision_radius, self.collision_below
+        c.collision_sphere = self.collision_sphere
         c.contact_friction = self.contact_friction
         for j in range(3):
             c.base_offset[j] = float(self.base_offset[j])
@@ -260,6 +263,7 @@ def _robobee() -> DroneType:
                      [-7.0, 7.0, -7.0, 7.0], [1.7, 1.7, 1.7, 1.7]]),
         kp_pos=1.0, kd_pos=2.2, att_gain=(7.0, 7.0, 5.0), rate_gain=(18.0, 18.0, 10.0),
         prop_radius=3.31348e-2, collision_radius=0.15, collision_below=0.05, arm=0.0635, **_AERO,      # robobee.urdf:72-77, 31
+        collision_sphere=0.15811388300841897,     # robobee.urdf:72-77: the rim of the 0.15 m x 0.1 m cylinder, hypot(0.15, 0.05)
     )
 
 
@@ -278,6 +282,7 @@ def _tello() -> DroneType:
                      [-5.0, 5.0, -5.0, 5.0], [1.7, 1.7, 1.7, 1.7]]),
         kp_pos=1.7, kd_pos=2.5, att_gain=(10.0, 10.0, 4.0), rate_gain=(12.0, 12.0, 7.0),
         prop_radius=3.31348e-2, collision_radius=0.0475, collision_below=0.0205, arm=0.0635, **_AERO,   # tello.urdf:68-73, 27
+        collision_sphere=0.05173490117899134,     # tello.urdf:68-73: the rim of its cylinder, hypot(0.0475, 0.0205)
     )
 
 
@@ -312,6 +317,7 @@ def _hexa_6dof() -> DroneType:
         kp_pos=1.7, kd_pos=2.5, att_gain=(10.0, 10.0, 5.0), rate_gain=(18.0, 18.0, 12.0),
         prop_radius=6.7e-2, reset_thrust=0.3, reset_cmd=0.5, arm=1.0635,
         collision_radius=0.18986507827381124, collision_below=0.06903716345121234,   # all links' <collision> shapes
+        collision_sphere=0.2020269236644212,   # the lower rim of that cylinder (the farthest point of a shape itself: 0.1952 m)
         base_offset=(-1.1106382076676865e-05, -1.111343640005967e-06, 0.010962836548787658),   # mainbody COM - composite COM
         **_AERO,
     )
@@ -331,7 +337,8 @@ def _hexa_6dof_simple() -> DroneType:
                      [-5.0, 5.0, -5.0, 5.0, -5.0, 5.0], [1.7, 1.7, 1.7, 1.7, 1.7, 1.7]]),
         kp_pos=t.kp_pos, kd_pos=t.kd_pos, att_gain=t.att_gain, rate_gain=t.rate_gain,
         prop_radius=t.prop_radius, reset_thrust=0.0, reset_cmd=0.0, arm=t.arm,
-        collision_radius=t.collision_radius, collision_below=t.collision_below, base_offset=t.base_offset, **_AERO,
+        collision_radius=t.collision_radius, collision_below=t.collision_below, collision_sphere=t.collision_sphere,
+        base_offset=t.base_offset, **_AERO,
     )
 
 
@@ -477,9 +484,11 @@ def parse_urdf(path: str) -> DroneType:
         kind, rt, rc = KIND_QUAD, 0.0, 0.0
 
     # bounding cylinder (about the body z axis through the COM) of every <collision> shape of every link, with the
-    # links in their URDF rest pose: radius and extent below the COM
+    # links in their URDF rest pose: radius and extent below the COM; and the bounding sphere about the COM: the farthest
+    # point of any shape (`far`, exact for the three shapes read here) or the lower rim of that cylinder, whichever is farther —
+    # the rim carries the contact points of the product's own plane model (DSIM_OPT_PLANE), so the sphere holds them too
     com_ref = C if is_hexa else com0
-    coll_r = coll_below = 0.0
+    coll_r = coll_below = coll_sphere = 0.0
     for ln in [base] + order:
         for col in links[ln].findall("collision"):
             geo = col.find("geometry")
@@ -490,15 +499,21 @@ def parse_urdf(path: str) -> DroneType:
                 r, h = float(geo.find("cylinder").attrib["radius"]), 0.5 * float(geo.find("cylinder").attrib["length"])
                 az = abs(Rs[2, 2])
                 down, out = h * az + r * math.sqrt(max(0.0, 1 - az * az)), r * az + h * math.sqrt(max(0.0, 1 - az * az))
+                along = float(ctr @ Rs[:, 2])          # the centre along / across the cylinder's axis: the farthest rim point
+                across = math.sqrt(max(0.0, float(ctr @ ctr) - along * along))
+                far = math.hypot(abs(along) + h, across + r)
             elif geo.find("sphere") is not None:
                 down = out = float(geo.find("sphere").attrib["radius"])
+                far = float(np.linalg.norm(ctr)) + down
             elif geo.find("box") is not None:
                 half = 0.5 * np.array(_floats(geo.find("box").attrib["size"]))
                 down, out = float(np.abs(Rs[2]) @ half), float(np.linalg.norm((np.abs(Rs[:2]) @ half)))
+                far = float(np.linalg.norm(np.abs(Rs.T @ ctr) + half))     # the farthest corner, in the box's own frame
             else:
                 continue        # meshes: not used by the shipped vehicles' collision shapes
             coll_below = max(coll_below, down - ctr[2])
             coll_r = max(coll_r, float(np.linalg.norm(ctr[:2])) + out)
+            coll_sphere = max(coll_sphere, far)
 
     return DroneType(
         name=name, kind=kind, n_act=n_act, mass=mass, ctrl_mass=m0, inertia=inertia,
@@ -515,5 +530,6 @@ def parse_urdf(path: str) -> DroneType:
         max_speed_kmh=float(prop["max_speed_kmh"]), arm=float(prop["arm"]),
         reset_thrust=rt, reset_cmd=rc,
         collision_radius=coll_r, collision_below=coll_below,
+        collision_sphere=max(coll_sphere, math.hypot(coll_r, coll_below)) if coll_r > 0.0 else 0.0,
         base_offset=tuple(float(x) for x in (com0 - C)) if is_hexa else (0.0, 0.0, 0.0),
     )

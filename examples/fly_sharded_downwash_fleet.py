@@ -60,8 +60,10 @@ def main(argv=None):
     r = env.state.rigid_aos()
     drift = np.linalg.norm(r[:, 0:3] - xyz, axis=1)
     halo = env._downwash.halo
+    # (single rank: the drone-drone contact watch on the final state — drones whose bounding sphere overlaps another's)
+    touching = f"; drones in sphere contact {int((env.drone_clearance(1.0)[0] < 0).sum())}" if world == 1 else ""
     sys.stdout.write(f"rank {rank}/{world}: {n} drones x {A.steps} env steps in {el:.2f} s ({n * A.steps / el:.3g} drone-steps/s); "
-          f"median drift from the hold point {np.median(drift):.3f} m; ground contacts {env.ground_contacts()}; WLS failures "
+          f"median drift from the hold point {np.median(drift):.3f} m; ground contacts {env.ground_contacts()}{touching}; WLS failures "
           f"{env.ctx.query(nat.QUERY_WLS_FAILURES)}"
           + (f"; ships {halo.sent_per_step} positions per step to {len(halo.messages())} neighbour(s), overflow {halo.overflow()}"
              if halo is not None else "") + "\n")

@@ -38,6 +38,8 @@ extern "C" {
 #endif
 
 #define DSIM_ABI_VERSION 11
+#define DSIM_ABI_MINOR 1   /* 1: dsim_type_params ends with collision_sphere (callers built against minor 0 must be rebuilt: the
+                              type table's stride grew); dsim_clearance, DSIM_Q_DRONE_CONTACTS */
 #define DSIM_MAX_ACT 6     /* actuators per vehicle (quad 4, morphing hexa 6) */
 #define DSIM_MAX_TYPES 8
 
@@ -140,6 +142,16 @@ typedef struct dsim_type_params {
   int32_t dyn_mixer;                  /* DSIM_DYN_MIXER_X: (f0+f1-f2-f3, -f0+f1+f2-f3) L/sqrt 2 (DroneModel.CF2X, :1794-1800);
                                          DSIM_DYN_MIXER_PLUS: (f1-f3, -f0+f2) L (CF2P / HB, :1801-1803)                    */
   int32_t _pad_dyn;
+  /* Bounding sphere of the vehicle's collision shapes: the radius, about the integrated centre of mass, of the smallest sphere
+   * the builder can certify to contain every <collision> shape of every link in the URDF rest pose (and the lower rim of the
+   * bounding cylinder above, which carries the contact points of DSIM_OPT_PLANE).  The reference flies in a Bullet world where
+   * the vehicles' collision shapes act on each other (BaseAviary.py:681-694 loads every vehicle with collisions on); this
+   * library integrates every drone alone, and every pair of drones whose spheres overlap is counted instead
+   * (dsim_clearance, DSIM_Q_DRONE_CONTACTS), so that a caller knows when a flight has left the domain in which results are
+   * comparable.  The test is one-sided in the useful direction: where no two spheres overlap, Bullet's narrow phase would
+   * have found no drone-drone contact either; an overlap of spheres need not be one of shapes.  0 = the type takes no part in
+   * the watch.  (At the END of the struct: DSIM_ABI_MINOR 1 appended it.) */
+  double  collision_sphere;
 } dsim_type_params;
 enum { DSIM_DYN_MIXER_X = 0, DSIM_DYN_MIXER_PLUS = 1 };
 
@@ -371,6 +383,7 @@ typedef struct dsim_ctx dsim_ctx;
 
 /* library / build info */
 int         dsim_abi_version(void);
+int         dsim_abi_minor(void);
 const char* dsim_strerror(int code);
 
 /* ctx: uploads the type table to `device`.  Replaces the per-instance parsing in
@@ -617,6 +630,30 @@ int dsim_downwash_reset(dsim_ctx* ctx);
 int dsim_adjacency(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, const dsim_downwash_args* args,
                    float radius, int32_t* count_out, int32_t* list_out, int32_t max_k);
 
+/* Drone-drone contact watch: per-drone clearance between the bounding spheres of the vehicles (dsim_type_params.collision_sphere)
+ * on the same uniform grid.  No counterpart in the reference, whose Bullet world lets the vehicles' collision shapes act on each
+ * other; this library models no such contact and reports where it would have mattered.  For local drone i, over every other
+ * drone j of the world,
+ *     c_ij = |p_i - p_j| - R_i - R_j   (3-D),      clearance_out[i] = min(margin, min_j c_ij)       [n_pad]
+ *     nearest_out[i] = the j that attains the minimum, as an index into the world (pos_all), -1 when no c_ij < margin
+ *                      (nullable; [n_pad])
+ * A drone with R = 0 neither receives nor is seen: clearance = margin, nearest = -1.  Every unordered pair with c_ij < 0 is
+ * counted once per world, by the rank that owns the lower world index (i local, j > i + local_offset): into the cumulative
+ * counter DSIM_Q_DRONE_CONTACTS and, when pairs_out is given, *pairs_out += the count (a device counter).  One-sided like the
+ * ground watch: a count of 0 certifies that Bullet's narrow phase would have found no drone-drone contact; a pair that is
+ * counted has overlapping SPHERES, which the shapes inside them need not.
+ * R of a local drone comes from the type table (args->type_id with more than one type).  With args->pos_all the radius of every
+ * world entry — the remote drones' too — is radius_all [m_pad] (device; the local entries must agree with the table), and
+ * without pos_all radius_all must be NULL.  args->cell must be >= 2 R_max + margin (R_max over the type table, and the caller
+ * vouches for it over radius_all): every pair with c_ij < margin is then less than one cell apart in x and in y, so its two
+ * drones lie in the same or adjacent cells — also when one of them is clamped into a border cell from outside the box, because
+ * clamping never moves two cell indices further apart.  The grid takes the counting-sort form; workspace: at least
+ * dsim_clearance_workspace(m, nx, ny) int32 entries.  A halo plan: DSIM_E_UNSUPPORTED.  margin > 0. */
+int64_t dsim_clearance_workspace(int64_t m, int32_t nx, int32_t ny);
+int dsim_clearance(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, const dsim_downwash_args* grid,
+                   const float* radius_all, float margin,
+                   float* clearance_out, int32_t* nearest_out, uint64_t* pairs_out);
+
 /* The rotor-noise normals the step kernels draw (diagnostics / distribution studies; no counterpart in the reference, whose
  * draws come from numpy's global generator): for drones [0, n) and the physics sub-steps [0, substeps) of Env.step number
  * step_index, out [substeps][2 * n_act][n_pad] (device) receives the UNIT-variance normals — n_act = 4: rows 0 .. 3 the force noise,
@@ -638,9 +675,11 @@ int dsim_noise_draw(dsim_ctx* ctx, void* stream, int64_t n, int64_t n_pad, int32
  *                         headers that announced more than recv_cap: the force of that step may have missed pairs
  *   DSIM_Q_DW_REUSES      dsim_downwash calls answered from kept candidate lists (dsim_downwash_args.keep)
  *   DSIM_Q_DW_MOVERS      overflow-list entries those calls found, summed: drones that had left the lists' skin (performance
- *                         only — results do not depend on it; / DSIM_Q_DW_REUSES = the mean length every receiver scanned)      */
+ *                         only — results do not depend on it; / DSIM_Q_DW_REUSES = the mean length every receiver scanned)
+ *   DSIM_Q_DRONE_CONTACTS pairs of drones x dsim_clearance calls whose bounding spheres overlapped, where Bullet's world might have
+ *                         made the two vehicles collide (see dsim_type_params.collision_sphere; each pair once per call)        */
 enum { DSIM_Q_WLS_FALLBACKS = 0, DSIM_Q_WLS_FAILURES = 1, DSIM_Q_GROUND_CONTACTS = 2, DSIM_Q_HALO_OVERFLOW = 3,
-       DSIM_Q_DW_REUSES = 4, DSIM_Q_DW_MOVERS = 5 };
+       DSIM_Q_DW_REUSES = 4, DSIM_Q_DW_MOVERS = 5, DSIM_Q_DRONE_CONTACTS = 6 };
 int dsim_query(dsim_ctx* ctx, void* stream, int32_t what, int64_t* value_out);
 
 /* error codes */
