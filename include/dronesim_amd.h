@@ -477,7 +477,9 @@ int dsim_observe(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, const 
  * sampling (the example samples at 1/control_freq).  yaw_state: device SoA [3][n_pad] fp64 in-out
  * (yaw, heading_x, heading_y), zero-initialised like trajGenerator; fp64 because the rule integrates
  * acos() of nearly parallel unit headings, whose error is sqrt(eps) per step.  offset: nullable fp32
- * SoA [3][n_pad] added to the sampled position.  Polynomials (degree 9, t up to ~7 s) in fp64. */
+ * SoA [3][n_pad] added to the sampled position.  Polynomials (degree 9, t up to ~7 s) in fp64.
+ * At zero horizontal velocity the reference's heading is 0/0 and its yaw NaN from that sample on
+ * (np.sign of a NaN cross product): so is this one's — yaw_state[0] and the yaw target become NaN and stay. */
 int dsim_traj_sample(dsim_ctx* ctx, void* stream, int64_t n, const double* coeffs, const double* ts,
                      int32_t n_seg, double* t, double dt_advance, double* yaw_state, const float* offset,
                      dsim_view targets_out);
@@ -625,8 +627,11 @@ int dsim_downwash_reset(dsim_ctx* ctx);
  * i != j are neighbours when |pos_i - pos_j| < neighbourhood_radius).  The reference returns the dense
  * O(N^2) matrix row in every observation; here the same uniform grid as the downwash gives, per local
  * drone, the neighbour count and (optionally) up to max_k neighbour indices into pos_all in ascending
- * grid order (count_out [n_pad]; list_out [max_k][n_pad] nullable, unused slots -1).  args->cell must be
- * >= radius; pos_all / workspace / local_offset as for dsim_downwash (type_id is ignored). */
+ * grid order: the cell index cy * nx + cx of the listed neighbours never decreases along a list, and a
+ * list cut at max_k holds the neighbours of the lowest cells; the order inside one cell is unspecified
+ * (count_out [n_pad], exact whatever max_k; list_out [max_k][n_pad] nullable, unused slots -1).
+ * args->cell must be >= radius (DSIM_E_ARG otherwise, nothing is written); pos_all / workspace /
+ * local_offset as for dsim_downwash (type_id is ignored). */
 int dsim_adjacency(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, const dsim_downwash_args* args,
                    float radius, int32_t* count_out, int32_t* list_out, int32_t max_k);
 

@@ -1143,7 +1143,9 @@ void orc_traj_sample(const double* coeffs, const double* TS, int n_seg, double t
   cosine = fmax(-1.0, fmin(cosine, 1.0));
   const double dyaw = acos(cosine);
   const double cr = yaw_state[1] * cy - yaw_state[2] * cx;        /* np.cross of 2-vectors */
-  yaw_state[0] += (cr > 0 ? 1.0 : (cr < 0 ? -1.0 : 0.0)) * dyaw;
+  /* np.sign keeps a NaN: at zero horizontal velocity the heading is 0/0, the cross product NaN, and the reference's yaw is NaN
+   * from that sample on (fmin above drops the NaN of the cosine, so dyaw alone would hide it) */
+  yaw_state[0] += (cr > 0 ? 1.0 : (cr < 0 ? -1.0 : cr)) * dyaw;
   if (yaw_state[0] > ORC_PI) yaw_state[0] -= 2 * ORC_PI;
   if (yaw_state[0] < -ORC_PI) yaw_state[0] += 2 * ORC_PI;
   yaw_state[1] = cx; yaw_state[2] = cy;

@@ -23,7 +23,7 @@ What is the real reference and what is a stand-in
   stand-in's fidelity to Bullet's Euler convention, which nothing in the
   reference pins.
 
-Usage:  python tests/golden/make_goldens.py --reference CHECKOUT [dyn|env|roll]   (writes tests/golden/*.npz)
+Usage:  python tests/golden/make_goldens.py --reference CHECKOUT [dyn|env|roll|traj]   (writes tests/golden/*.npz)
         python tests/golden/make_goldens.py --reference CHECKOUT --check
             (regenerates every fixture in a temporary directory; exit 0 when each is bit-identical to the stored one)
 """
@@ -629,12 +629,58 @@ def capture_dynamics():
     print("dynamics goldens written")
 
 
+def capture_traj_edges():
+    """trajGenerator.get_des_state at ZERO horizontal velocity (trajGen.py:128-143): the heading is vel / 0, the cross product NaN,
+    np.sign(NaN) NaN, and the yaw NaN from that sample on.  The min-snap fit never yields such coefficients exactly (its rest
+    conditions hold to rounding), so the sampler runs on hand-made ones: the generator object is made without its optimiser
+    (object.__new__) and given TS, coeffs and the memory its __init__ would set; get_des_state / get_yaw are the reference's own.
+      climb   x and y constant: a purely vertical climb, zero horizontal velocity at every t
+      launch  horizontal velocity zero at t = 0 only (x, y start with a t^2 term)
+    Per set two samplers: one started on the zero (`*_t`), one started where the velocity is not zero (`*_t_late`; on `climb`
+    there is no such time: its late sampler shows that the NaN does not depend on the start).  Rows: pos3 vel3 acc3 yaw."""
+    from dronesim.utils.trajGen import trajGenerator
+
+    def coeffs(n_seg, polys):
+        """polys[seg][axis] = ascending coefficients -> [n_seg * 10, 3] as trajGenerator.coeffs"""
+        c = np.zeros((n_seg * 10, 3))
+        for s_ in range(n_seg):
+            for d in range(3):
+                p = polys[s_][d]
+                c[s_ * 10: s_ * 10 + len(p), d] = p
+        return c
+
+    def run(co, TS, ts):
+        g = object.__new__(trajGenerator)
+        g.TS, g.coeffs, g.order, g.yaw, g.heading = TS, co, 10, 0, np.zeros(2)
+        rows = []
+        with np.errstate(all="ignore"):
+            for ti in ts:
+                st = g.get_des_state(ti)
+                rows.append(np.concatenate([st.pos, st.vel, st.acc, [st.yaw]]))
+        return np.array(rows)
+
+    TS = np.array([0.0, 2.0, 4.0])
+    # (the second segment continues the first: position, velocity and acceleration agree at t = 2)
+    climb = coeffs(2, [[[1.5], [-0.5], [0.5, 0.4, 0.05]], [[1.5], [-0.5], [1.5, 0.6, 0.05]]])
+    launch = coeffs(2, [[[0.0, 0.0, 0.3, -0.02], [1.0, 0.0, -0.2, 0.05], [0.5, 0.1]],
+                        [[1.04, 0.96, 0.18, -0.02], [0.6, -0.2, 0.1, 0.05], [0.7, 0.1]]])
+    t0 = np.arange(0, 24) / 96.0
+    t_late = 1.0 / 96.0 + np.arange(0, 24) / 96.0
+    t_climb_late = np.concatenate([1.5 + np.arange(0, 12) / 96.0, [2.0, 3.999, 4.5]])     # across the boundary, into the clamp
+    # (t == TS[-1] exactly is not recorded: the reference indexes one segment past the end there and raises)
+    np.savez(os.path.join(OUT, "traj_edges.npz"), TS=TS, climb_coeffs=climb, launch_coeffs=launch,
+             climb_t=t0, climb_rows=run(climb, TS, t0), climb_t_late=t_climb_late, climb_rows_late=run(climb, TS, t_climb_late),
+             launch_t=t0, launch_rows=run(launch, TS, t0), launch_t_late=t_late, launch_rows_late=run(launch, TS, t_late))
+    print("trajectory edge goldens written")
+
+
 def main(argv=None):
     global REF, OUT
     ap = argparse.ArgumentParser()
     ap.add_argument("--reference", required=True, help="checkout of enac-drones/dronesim")
     ap.add_argument("--check", action="store_true", help="regenerate into a temporary directory and compare with tests/golden")
-    ap.add_argument("part", nargs="?", choices=["dyn", "env", "roll"], help="only the Physics.DYN / env-side / roll-sweep file")
+    ap.add_argument("part", nargs="?", choices=["dyn", "env", "roll", "traj"],
+                    help="only the Physics.DYN / env-side / roll-sweep / trajectory-edge file")
     a = ap.parse_args(argv)
     REF = os.path.abspath(a.reference)
     if a.check:
@@ -649,7 +695,7 @@ def main(argv=None):
 def check(stored_dir, fresh_dir):
     """Every stored fixture against its regenerated twin: the same arrays, bit for bit (NaN where NaN)."""
     files = sorted(glob.glob(os.path.join(stored_dir, "*.npz")))
-    bad = [] if len(files) == 18 else [f"{len(files)} stored fixtures, 18 expected"]
+    bad = [] if len(files) == 19 else [f"{len(files)} stored fixtures, 19 expected"]
     for f in files:
         a, b = np.load(f, allow_pickle=True), np.load(os.path.join(fresh_dir, os.path.basename(f)), allow_pickle=True)
         if set(a.files) != set(b.files):
@@ -670,6 +716,9 @@ def generate(part):
         return
     if part == "roll":       # only the roll-sweep file
         capture_roll_sweep()
+        return
+    if part == "traj":       # only the trajectory-edge file
+        capture_traj_edges()
         return
     from dronesim.control.INDIControl import INDIControl
     from dronesim.control.INDIControl_6DOF import INDIControl as INDIControl_6DOF  # same class name in both modules
@@ -767,6 +816,7 @@ def generate(part):
     np.savez(os.path.join(OUT, "traj_track_waypoints.npz"), TS=traj.TS, coeffs=traj.coeffs,
              t=ts, target_pos=np.array(P), target_vel=np.array(V), target_acc=np.array(Ac),
              target_yaw=np.array(Y), gates=gates)
+    capture_traj_edges()
     capture_env_side()
     capture_roll_sweep()
     capture_dynamics()

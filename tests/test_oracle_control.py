@@ -182,6 +182,27 @@ def test_trajectory_sampler_matches_reference_table(golden_dir):
         assert abs(o[9] - g["target_yaw"][k]) < 1e-5, k   # yaw integrates acos() of nearly parallel headings (ill-conditioned)
 
 
+@pytest.mark.parametrize("run", ["climb", "climb_late", "launch", "launch_late"])
+def test_trajectory_sampler_at_zero_horizontal_velocity_matches_reference(golden_dir, run):
+    """trajGen.get_yaw (trajGen.py:128-143) divides the velocity by its norm: at zero horizontal velocity the heading is 0/0, the
+    cross product NaN, np.sign(NaN) NaN, and the reference's yaw is NaN from that sample on — whatever comes later.  Rows recorded
+    from the reference's own get_des_state on hand-made coefficients (make_goldens.py:capture_traj_edges): a purely vertical climb,
+    and a launch whose horizontal velocity is zero at t = 0 only, each with a sampler started on the zero and one started later.
+    Where the reference's yaw is NaN the oracle's is NaN, where it is finite (launch_late) the two agree."""
+    g = _load(golden_dir, "traj_edges.npz")
+    name, late = run.split("_")[0], run.endswith("_late")
+    ts, rows = g[f"{name}_t_late" if late else f"{name}_t"], g[f"{name}_rows_late" if late else f"{name}_rows"]
+    assert np.isnan(rows[:, 9]).all() == (run != "launch_late") and np.isnan(rows[:, 9]).any() == (run != "launch_late")
+    ys = np.zeros(3)
+    for k, t in enumerate(ts):
+        o = orc.traj_sample(g[f"{name}_coeffs"], g["TS"], t, ys)
+        np.testing.assert_allclose(o[0:9], rows[k, 0:9], rtol=0, atol=1e-12)
+        assert np.isnan(o[9]) == np.isnan(rows[k, 9]), (k, o[9], rows[k, 9])
+        assert np.isnan(ys[0]) == np.isnan(rows[k, 9])                      # ... and the memory carries it to the next sample
+        if not np.isnan(rows[k, 9]):
+            assert abs(o[9] - rows[k, 9]) < 1e-9, k
+
+
 def test_euler_and_matrix_conventions_match_scipy():
     """Row C8: the three PyBullet math helpers are restated (nothing of Bullet is available here).  Their
     convention — quaternion xyzw, roll-pitch-yaw = rotations about the FIXED x, y, z axes in that order

@@ -477,3 +477,243 @@ def assert_downwash(label, got, ref, types, type_id, recv_pos, world_pos):
     WORST[label] = max(WORST.get(label, 0.0), worst)
     assert worst <= 1.0, (label, worst, int(ratio.argmax()), float(got[ratio.argmax()]), float(ref[ratio.argmax()]))
     return worst
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the service kernels (dsim_reset, dsim_traj_sample, dsim_adjacency, dsim_fleet_bounds): seeded inputs, built once here for
+# tests/test_gpu_service_kernels.py (the device) and tests/test_service_inputs_cpu.py (the properties the device tests rely on)
+# ---------------------------------------------------------------------------------------------------------------------
+PI32, HPI32 = float(np.float32(math.pi)), float(np.float32(math.pi / 2))       # the fp32 images: what a caller can hand over
+# rpy rows every reset fleet starts with (a fleet of one takes the first): +-pi roll and yaw, +-pi/2 pitch (the Euler gimbal
+# point), 0, and angles of 1e-4 (sin(h) ~ h: the small end of the half-angle products)
+RESET_ANGLE_TABLE = np.array([
+    [PI32, HPI32, 1e-4], [0, 0, 0], [0, HPI32, 0], [0, -HPI32, 0], [PI32, 0, 0], [-PI32, 0, 0], [0, 0, PI32], [0, 0, -PI32],
+    [1e-4, 1e-4, 1e-4], [1e-4, 0, 0], [0, -1e-4, 0], [0, 0, 1e-4], [-PI32, -HPI32, PI32], [HPI32, 0, HPI32], [PI32, HPI32, -PI32]])
+EULER_CLAMP = 0.99999       # p.getEulerFromQuaternion's gimbal threshold on |sin(pitch)| (attitude_zoo): discontinuous there
+
+
+def reset_inputs(n, mixed, seed=4242):
+    """What dsim_reset is handed, fp32-representable: pos [n,3], rpy [n,3] (RESET_ANGLE_TABLE, then a seeded spread over
+    (-pi, pi]^3), vel [n,3], cmd [n, 4 or 6] and tid [n] uint8 (mixed: even lanes type 0 = quad, odd lanes type 1 = hexa) or None.
+    A spread attitude within 1e-4 of the Euler clamp is redrawn: there the helper the controller calls is discontinuous, and
+    the step that follows the reset would compare the two branches (tests/util.py:attitude_zoo)."""
+    rng = np.random.default_rng(seed + 7 * n + int(mixed))
+    pos = np.concatenate([rng.uniform(-50, 50, (n, 2)), rng.uniform(0.5, 20.0, (n, 1))], 1)
+    rpy = -rng.uniform(-math.pi, math.pi, (n, 3))                         # (-pi, pi]
+    for _ in range(100):
+        bad = np.abs(np.abs(np.sin(f32(rpy[:, 1]))) - EULER_CLAMP) < 1e-4
+        if not bad.any():
+            break
+        rpy[bad, 1] = -rng.uniform(-math.pi, math.pi, int(bad.sum()))
+    k = min(n, len(RESET_ANGLE_TABLE))
+    rpy[:k] = RESET_ANGLE_TABLE[:k]
+    vel = rng.uniform(-2, 2, (n, 3))
+    na = 6 if mixed else 4
+    cmd = rng.uniform(0.3, 0.7, (n, na))
+    tid = None
+    if mixed:
+        tid = (np.arange(n) % 2).astype(np.uint8)
+        cmd[tid == 0, 4:6] = 0.0                                           # a quad's block holds 0 behind its four actuators
+    return dict(pos=f32(pos), rpy=f32(rpy), vel=f32(vel), cmd=f32(cmd), tid=tid)
+
+
+def reset_expected(types, inp, vel_given, cmd_given):
+    """The fp64 definition of reset() (BaseAviary.py:640-714, INDIControl.py:109-146) on reset_inputs: rigid [n,13] with the
+    quaternion of orc.quat_from_euler, mem [n,13] = Oracle.reset_mem rounded to fp32, or the given command."""
+    n = inp["pos"].shape[0]
+    rigid = np.zeros((n, 13))
+    rigid[:, 0:3] = inp["pos"]
+    rigid[:, 3:7] = np.stack([orc.quat_from_euler(r) for r in inp["rpy"]])
+    if vel_given:
+        rigid[:, 7:10] = inp["vel"]
+    mem = f32(orc.Oracle(types).reset_mem(n, inp["tid"]))
+    if cmd_given:
+        mem[:, 7:7 + inp["cmd"].shape[1]] = inp["cmd"]
+    return rigid, mem
+
+
+TRAJ_N, TRAJ_SAMPLES, TRAJ_DT, TRAJ_WRAPPERS = 600, 20, 1.0 / 96, 24
+
+
+def traj_service_fleet(coeffs, TS, n=TRAJ_N, seed=99):
+    """Per-drone start times, yaw memories and offsets of the sampler test.  t0: every TS[k] exactly and one fp64 ulp either
+    side, TS[-1] + 1e-9, TS[-1] + 5 (the clamp t_end - 0.001), 0, then a seeded spread over [0, TS[-1]).  The last TRAJ_WRAPPERS
+    drones start mid-flight where the yaw turns, with the heading the sampler would hold there and a yaw memory placed so that the
+    yaw passes +-pi half way through the TRAJ_SAMPLES samples (found with the oracle) or, every other one, passes the other end
+    at the first sample; everybody else starts as trajGenerator
+    does, with zeros.  Returns t0 [n], yaw_state [3, n], offsets [n, 3] (fp32-representable)."""
+    TS = np.asarray(TS, dtype=np.float64)
+    rng = np.random.default_rng(seed)
+    edge = []
+    for tk in TS:
+        edge += [tk, np.nextafter(tk, -np.inf), np.nextafter(tk, np.inf)]
+    edge += [TS[-1] + 1e-9, TS[-1] + 5.0, 0.0]
+    t0 = np.concatenate([edge, rng.uniform(0.0, TS[-1], n - len(edge))])
+    ys = np.zeros((3, n))
+    span = TRAJ_SAMPLES * TRAJ_DT
+    for j, i in enumerate(range(n - TRAJ_WRAPPERS, n)):
+        # spread over the flight, away from its ends (there the vehicle is at rest and the heading is rounding noise)
+        t0[i] = TS[-1] * (0.1 + 0.8 * j / TRAJ_WRAPPERS)
+        y = np.zeros(3)
+        orc.traj_sample(coeffs, TS, t0[i] - TRAJ_DT, y)                  # the heading one sample earlier
+        h = y.copy()
+        y[0] = 0.0
+        for k in range(TRAJ_SAMPLES // 2):                               # the turn of the first half of the samples ...
+            orc.traj_sample(coeffs, TS, t0[i] + k * TRAJ_DT, y)
+        turn = y[0]
+        orc.traj_sample(coeffs, TS, t0[i] + (TRAJ_SAMPLES // 2) * TRAJ_DT, y)
+        turn = 0.5 * (turn + y[0])                                       # ... and half of the next: +-pi falls BETWEEN two samples
+        ys[:, i] = [(math.pi if turn > 0 else -math.pi) - turn, h[1], h[2]]
+        if j % 2:
+            # this trajectory turns one way only: every other drone remembers a heading half a radian to the right of its course,
+            # turns left by that much at its first sample and passes the OTHER end, +pi (or -pi on a left-turning trajectory)
+            s_ = -0.5 if turn < 0 else 0.5
+            ys[:, i] = [(math.pi if turn < 0 else -math.pi) + 0.5 * s_, h[1] * math.cos(s_) - h[2] * math.sin(s_),
+                        h[1] * math.sin(s_) + h[2] * math.cos(s_)]
+    assert span > 0
+    # (offsets that keep |position| below 16 m: one fp32 ulp there is 9.5e-7 m, under the 2e-6 m bar of the position)
+    off = f32(np.concatenate([rng.uniform(-6, 6, (n, 2)), rng.uniform(0, 5, (n, 1))], 1))
+    return t0, ys, off
+
+
+def traj_oracle_run(coeffs, TS, t0, ys0, samples=TRAJ_SAMPLES, dt=TRAJ_DT):
+    """The oracle's sampler per drone, advanced as the kernel advances it (t += dt after every sample): rows
+    [samples, n, 10], t [samples, n] AFTER the advance, yaw_state [samples, 3, n] after each sample."""
+    n = len(t0)
+    t, ys = np.array(t0, dtype=np.float64), np.array(ys0, dtype=np.float64)
+    rows, tt, yy = np.zeros((samples, n, 10)), np.zeros((samples, n)), np.zeros((samples, 3, n))
+    for k in range(samples):
+        for i in range(n):
+            y = ys[:, i].copy()
+            rows[k, i] = orc.traj_sample(coeffs, TS, t[i], y)
+            ys[:, i] = y
+        t = t + dt
+        tt[k], yy[k] = t, ys
+    return rows, tt, yy
+
+
+# ---- adjacency: positions on the 1/8 m lattice below 256 m ----------------------------------------------------------------
+# Every coordinate is k / 8 with 0 <= k < 2048, so every difference is k / 8 with |k| < 2048, every square k / 64 with
+# k < 2^22 and every three-term sum k / 64 with k < 3 x 2^22 < 2^24: exact in fp32 whichever way the compiler rounds (two
+# roundings or a fused multiply-add, any order of the sum).  A numpy brute force in fp32 IS the answer, pair by pair.
+ADJ_RADIUS = 7.5
+ADJ_EXACT_OFFSETS = np.array([[4.5, 6, 0], [6, 4.5, 0], [0, 4.5, 6], [6, 0, 4.5], [7.5, 0, 0], [0, 7.5, 0], [0, 0, 7.5], [2.5, 5, 5]])
+ADJ_NEAR_OFFSETS = np.array([[7.375, 0, 0], [7.625, 0, 0], [0, 7.375, 0], [0, 7.625, 0], [0, 0, 7.375], [0, 0, 7.625]])
+
+
+def _lattice(rng, n, lo, hi, zhi=16.0):
+    """n points on the 1/8 m lattice, x and y in [lo, hi), z in [0, zhi)"""
+    return np.concatenate([rng.integers(int(lo * 8), int(hi * 8), (n, 2)), rng.integers(0, int(zhi * 8), (n, 1))], 1) / 8.0
+
+
+def adjacency_case(name):
+    """dict(pos [m,3] float32 — the WORLD —, lo, hi: the receivers are pos[lo:hi], radius, cell, xmin, ymin, nx, ny, max_k).
+      strict     cell = radius = 7.5: 100 seeds, each with partners at exactly 7.5 m (ADJ_EXACT_OFFSETS) and at 7.5 -+ 1/8 m
+      borders    cell 8: a third of the drones with x or y (or both) a whole multiple of the cell, a grid over the whole box
+      middle     the same drones, the grid over [16, 240)^2 only: a quarter of them lie outside and are clamped into border cells
+      world      1 500 world entries, the receivers are the middle 500 (pos_all + local_offset)
+      one_cell_N N = 1, 2, 65, 700 drones inside ONE cell of a 3 x 3 grid, eight of them (from N = 65) on one point
+      overflow   300 drones in one cell (well over 20 neighbours each) and 300 spread thin (fewer than 8), lists of max_k = 8"""
+    rng = np.random.default_rng(sum(map(ord, "borders" if name == "middle" else name)))
+    c = dict(radius=ADJ_RADIUS, cell=8.0, xmin=0.0, ymin=0.0, nx=32, ny=32, max_k=64)
+    if name == "strict":
+        seeds = _lattice(rng, 100, 16, 232)
+        pos = np.concatenate([seeds] + [seeds + o for o in ADJ_EXACT_OFFSETS] + [seeds + o for o in ADJ_NEAR_OFFSETS])
+        c.update(cell=7.5, nx=35, ny=35)
+    elif name in ("borders", "middle"):
+        pos = _lattice(rng, 2000, 0, 256)
+        k = np.arange(2000)
+        pos[k % 3 == 0, 0] = np.floor(pos[k % 3 == 0, 0] / 8) * 8
+        pos[k % 6 == 0, 1] = np.floor(pos[k % 6 == 0, 1] / 8) * 8
+        pos[k % 9 == 1, 1] = np.floor(pos[k % 9 == 1, 1] / 8) * 8
+        if name == "middle":
+            c.update(xmin=16.0, ymin=16.0, nx=28, ny=28)
+    elif name == "world":
+        pos = _lattice(rng, 1500, 64, 192)
+        c.update(lo=500, hi=1000)
+    elif name.startswith("one_cell_"):
+        n = int(name.rsplit("_", 1)[1])
+        pos = _lattice(rng, n, 8, 16, 8.0)
+        if n >= 8:
+            pos[10:18] = pos[10] if n > 18 else pos[0]
+        c.update(nx=3, ny=3)
+    elif name == "overflow":
+        pos = np.concatenate([_lattice(rng, 300, 40, 48, 8.0), _lattice(rng, 300, 64, 256)])
+        c.update(max_k=8)
+    else:
+        raise ValueError(name)
+    assert pos.min() >= 0 and pos.max() < 256 and np.array_equal(pos * 8, np.round(pos * 8))
+    c.setdefault("lo", 0)
+    c.setdefault("hi", pos.shape[0])
+    c["pos"] = pos.astype(np.float32)
+    return c
+
+
+ADJACENCY_CASES = ("strict", "borders", "middle", "world", "one_cell_1", "one_cell_2", "one_cell_65", "one_cell_700", "overflow")
+
+
+def adjacency_d2(pos, lo, hi, dtype=np.float32):
+    """[hi - lo, m] squared distances receiver x world entry, every operation in `dtype`"""
+    p = pos.astype(dtype)
+    d = p[lo:hi, None, :] - p[None, :, :]
+    return (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]
+
+
+def adjacency_brute(c):
+    """The exact answer: bool [receivers, m], True where |p_i - p_j| < radius (strictly) and j is not i itself."""
+    nb = adjacency_d2(c["pos"], c["lo"], c["hi"]) < np.float32(c["radius"]) ** 2
+    nb[np.arange(c["hi"] - c["lo"]), np.arange(c["lo"], c["hi"])] = False
+    return nb
+
+
+def adjacency_cells(c):
+    """The cell index cy nx + cx of every world entry as the kernels compute it (dsim_downwash.hip:dw_cell: fp32, clamped)."""
+    inv = np.float32(1.0) / np.float32(c["cell"])
+    cx = np.clip(np.floor((c["pos"][:, 0] - np.float32(c["xmin"])) * inv).astype(np.int64), 0, c["nx"] - 1)
+    cy = np.clip(np.floor((c["pos"][:, 1] - np.float32(c["ymin"])) * inv).astype(np.int64), 0, c["ny"] - 1)
+    return cy * c["nx"] + cx
+
+
+# ---- fleet bounds ---------------------------------------------------------------------------------------------------------
+BOUNDS_KINDS = ("negative", "straddle", "zeros", "magnitudes", "nan_x")
+BOUNDS_SIZES = (1, 63, 64, 65, 5000)
+
+
+def bounds_fleet(kind, n, seed=0):
+    """rigid [n,13], mem [n,13] (fp32-representable) for dsim_fleet_bounds.
+      negative    x, y in [-900, -1): only the ~u branch of the keys runs; every velocity component negative
+      straddle    x, y in [-40, 60)
+      zeros       x negative but for one -0.0 and (from n = 3 on) one +0.0: the maximum is a zero of either sign; y positive but
+                  for the same two zeros: the minimum is
+      magnitudes  |x|, |y| = 10^u, u in [-30, 6), both signs; velocities likewise up to 1e2
+      nan_x       straddle with one drone's x NaN (from n = 2 on; fminf / fmaxf drop it)"""
+    rng = np.random.default_rng(1000 * BOUNDS_KINDS.index(kind) + n + seed)
+    rigid, mem, _ = random_fleet(rng, n)
+    sign = lambda k: np.where(rng.uniform(size=k) < 0.5, -1.0, 1.0)
+    if kind == "negative":
+        rigid[:, 0:2] = -rng.uniform(1, 900, (n, 2))
+        rigid[:, 7:10] = -rng.uniform(0.01, 3, (n, 3))
+    elif kind in ("straddle", "nan_x"):
+        rigid[:, 0:2] = rng.uniform(-40, 60, (n, 2))
+        if n >= 2:
+            rigid[0, 0:2], rigid[1, 0:2] = (-3.0, 2.0), (4.0, -1.0)      # both signs even in a fleet of two
+        if kind == "nan_x" and n >= 2:
+            rigid[n // 2, 0] = np.nan
+    elif kind == "zeros":
+        rigid[:, 0] = -rng.uniform(1, 5, n)
+        rigid[:, 1] = rng.uniform(1, 5, n)
+        rigid[n // 2, 0:2] = -0.0
+        if n >= 3:
+            rigid[n // 3, 0:2] = 0.0
+    elif kind == "magnitudes":
+        rigid[:, 0:2] = sign((n, 2)) * 10.0 ** rng.uniform(-30, 6, (n, 2))
+        rigid[:, 7:10] = sign((n, 3)) * 10.0 ** rng.uniform(-30, 2, (n, 3))
+    return f32(rigid), mem
+
+
+def bounds_expected(rigid):
+    """numpy's fp32 answer: xmin, ymin, xmax, ymax, max |coordinate velocity| (NaN positions dropped, as fminf / fmaxf do)"""
+    r = rigid.astype(np.float32)
+    with np.errstate(all="ignore"):
+        return np.array([np.nanmin(r[:, 0]), np.nanmin(r[:, 1]), np.nanmax(r[:, 0]), np.nanmax(r[:, 1]), np.abs(r[:, 7:10]).max()],
+                        dtype=np.float32)
