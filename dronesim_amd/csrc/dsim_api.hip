@@ -353,9 +353,28 @@ int fill_stepk(dsim_ctx* ctx, int64_t n, const dsim_view& state, const dsim_view
   return DSIM_OK;
 }
 
+// What the launchers route on (StepCall, dsim_kernels.h), from the StepK fill_stepk just filled: every entry point asks once.
+StepCall classify_step(const dsim_ctx* ctx, const dsim_step_args* args, const StepK& a) {
+  StepCall c;
+  c.replay = args->noise_replay != nullptr;
+  c.noise = args->noise_seed != 0 || c.replay;
+  c.uni = args->type_id == nullptr;
+  c.six = ctx->max_act == 6;
+  // the fine noise lattice (resolved by fill_stepk): carried by every instance but the looped fast ones (quad_substeps)
+  c.fine = c.noise && !c.replay && (a.options & DSIM_OPT_NOISE_FINE) != 0;
+  c.fine_slow = c.fine && a.substeps > 1;        // several sub-steps per launch on the fine lattice: the general kernels
+  c.addon = (args->options & (DSIM_OPT_DRAG | DSIM_OPT_GROUND | DSIM_OPT_PLANE)) != 0;
+  c.plane = (args->options & DSIM_OPT_PLANE) != 0;
+  c.off_fast_path = c.addon || c.fine_slow;
+  c.multi = a.wp_table != nullptr || a.n_steps > 1;
+  c.any_quadlaw6 = has_quadlaw6(ctx);
+  c.whole_tiles = (a.n_pad % 256) == 0;
+  return c;
+}
+
 // The deferred-fallback queue is the one ctx-owned buffer that depends on the fleet size: it is
 // (re)allocated when a larger hexa fleet is first seen, never per call afterwards.
-int fb_prepare(dsim_ctx* ctx, long long n_pad, hipStream_t st) {
+static int fb_prepare(dsim_ctx* ctx, long long n_pad, hipStream_t st) {
   if (ctx->max_act != 6) return DSIM_OK;
   if (ctx->fb_cap < n_pad) {
     hipError_t e = hipStreamSynchronize(st);
@@ -367,6 +386,15 @@ int fb_prepare(dsim_ctx* ctx, long long n_pad, hipStream_t st) {
     ctx->fb_cap = n_pad;
   }
   return DSIM_OK;   // the queue length is reset by k_wls_fallback itself
+}
+
+// Opens the queue for a launch that may defer WLS fallbacks: room for the fleet, and the launch's view of the entries
+// (StepK.fb was filled before a possible reallocation).  One queue serves one step: fb_finish works it off.
+int fb_open_queue(dsim_ctx* ctx, StepK* a, hipStream_t st) {
+  const int rc = fb_prepare(ctx, a->n_pad, st);
+  if (rc) return rc;
+  a->fb.entries = ctx->d_fb;
+  return DSIM_OK;
 }
 
 void fb_finish(dsim_ctx* ctx, const StepK& a, hipStream_t st) {
@@ -394,7 +422,7 @@ int make_runtab(const dsim_ctx* ctx, long long n_pad, const dsim_type_run* runs,
     rt->blk0[r] = blocks;
     if (r >= n_runs) continue;
     const dsim_type_run& run = runs[r];
-    if (run.first < 0 || run.count < 0 || run.first + run.count > n_pad || run.type < 0 || run.type >= ctx->n_types) return DSIM_E_ARG;
+    if (!run_valid(ctx, n_pad, run)) return DSIM_E_ARG;
     rt->first[r] = run.first & ~255LL; rt->lo[r] = run.first; rt->last[r] = run.first + run.count; rt->type[r] = run.type;
     const int kind = ctx->h_types[run.type].kind;
     if (kind != DSIM_KIND_QUAD) rt->hexa_mask |= 1u << r;
@@ -627,10 +655,10 @@ int dsim_wls_fallback(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, c
   memset(&a, 0, sizeof(a));
   int rc = make_kview(state, 20 + ctx->max_act, &a.st);
   if (rc) return rc;
-  rc = fb_prepare(ctx, state.n_pad, (hipStream_t)stream);
-  if (rc) return rc;
   a.types = ctx->d_types; a.type_id = type_id; a.n_pad = state.n_pad; a.cmd_out = cmd_out;
-  a.fb.entries = ctx->d_fb; a.fb.count = ctx->d_counters + 2; a.fb.counters = ctx->d_counters;
+  a.fb.count = ctx->d_counters + 2; a.fb.counters = ctx->d_counters;
+  rc = fb_open_queue(ctx, &a, (hipStream_t)stream);
+  if (rc) return rc;
   fb_finish(ctx, a, (hipStream_t)stream);
   return (int)hipGetLastError();
 }

@@ -19,6 +19,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <limits.h>
 #include <stdlib.h>
 #include <math.h>
 #include <string.h>
@@ -716,10 +717,26 @@ struct RunOf { long long i0, lo, last; int type; bool hexa, quadlaw6; };
 // ---------------------------------------------------------------------------
 // host side: helpers shared by the entry points (defined in dsim_api.hip unless noted; not exported)
 // ---------------------------------------------------------------------------
+// What the step launchers route on, derived ONCE per call from ctx, the arguments and the filled StepK (classify_step, right
+// behind fill_stepk): dsim_step hands the record to step_general, dsim_physics / dsim_step_adaptor / dsim_control2 read theirs.
+struct StepCall {
+  bool noise, replay;        // rotor noise drawn (a seed, or a replayed stream) / replayed (dsim_step_args.noise_replay)
+  bool uni, six;             // no per-drone type_id: a homogeneous fleet / a six-actuator type in the table
+  bool fine;                 // noise drawn on the fine lattice (resolved by fill_stepk; a replayed stream has none)
+  bool fine_slow;            // ... over several sub-steps per launch: no looped fast instance carries that (quad_substeps)
+  bool addon, plane;         // any of DSIM_OPT_DRAG | GROUND | PLANE / DSIM_OPT_PLANE
+  bool off_fast_path;        // addon || fine_slow: what dsim_step's fast forms do not serve.  (dsim_physics routes on the two
+                             // apart: k_physics_fast carries both lattices, its run kernels do not)
+  bool multi;                // waypoint-table targets and / or several Env.steps per launch
+  bool any_quadlaw6;         // a DSIM_KIND_HEXA_QUADLAW type in the table
+  bool whole_tiles;          // the block is whole 256-drone tiles
+};
+
 #pragma GCC visibility push(hidden)
 int make_kview(const dsim_view& v, int need_fields, KView* k, bool bcast = false);
 int fill_stepk(dsim_ctx* ctx, int64_t n, const dsim_view& state, const dsim_view* targets, const dsim_step_args* args, StepK* a);
-int fb_prepare(dsim_ctx* ctx, long long n_pad, hipStream_t st);
+StepCall classify_step(const dsim_ctx* ctx, const dsim_step_args* args, const StepK& a);
+int fb_open_queue(dsim_ctx* ctx, StepK* a, hipStream_t st);
 void fb_finish(dsim_ctx* ctx, const StepK& a, hipStream_t st);
 int make_runtab(const dsim_ctx* ctx, long long n_pad, const dsim_type_run* runs, int n_runs, RunTab* rt, bool* any_hexa);
 int side_by_side_map(dsim_ctx* ctx, hipStream_t st, const dsim_type_run* runs, int n_runs, RunTab* rt);
@@ -729,10 +746,24 @@ void bin_next_prepare(dsim_ctx* ctx, int64_t n, const dsim_step_args* args, Step
 void bin_next_commit(dsim_ctx* ctx, int64_t n, const dsim_step_args* args, const StepK& a);                 // dsim_downwash.hip
 int dyn_check(const dsim_ctx* ctx, const dsim_step_args* args, const StepK& a);                             // dsim_two_call.hip
 int dyn_launch(bool ctrl, const StepK& a, bool nt, hipStream_t st);                                         // dsim_two_call.hip
-int step_general(dsim_ctx* ctx, int64_t n, const dsim_view& state, const dsim_view& targets, const dsim_step_args* args, StepK& a,
-                 long long first, bool fb_open, hipStream_t st_);                                           // dsim_step_mixed.hip
+int step_general(dsim_ctx* ctx, int64_t n, const dsim_view& state, const dsim_view& targets, const dsim_step_args* args,
+                 const StepCall& c, StepK& a, long long first, bool fb_open, hipStream_t st_);              // dsim_step_mixed.hip
 #pragma GCC visibility pop
 
+// a run of dsim_step_args.runs lies inside the block and names a type of the table (make_runtab, dsim_step's per-run launches)
+static inline bool run_valid(const dsim_ctx* ctx, long long n_pad, const dsim_type_run& run) {
+  return run.first >= 0 && run.count >= 0 && run.first + run.count <= n_pad && run.type >= 0 && run.type < ctx->n_types;
+}
+
+// The runs the single-type bodies serve for a call: the caller's (dsim_step_args.runs, at most max_runs of them), else — where
+// the caller admits it — a homogeneous fleet as ONE run of its only type (kept in `whole`); else none (n_runs 0).
+struct CallRuns { const dsim_type_run* runs; int n_runs; };
+static inline CallRuns call_runs(const dsim_step_args* args, long long n_pad, int max_runs, bool admit_whole, dsim_type_run& whole) {
+  if (args->runs && args->n_runs > 0 && args->n_runs <= max_runs) return CallRuns{args->runs, args->n_runs};
+  if (!admit_whole) return CallRuns{nullptr, 0};
+  whole.first = 0; whole.count = n_pad; whole.type = 0; whole._pad = 0;
+  return CallRuns{&whole, 1};
+}
 
 static inline unsigned grid_for(long long n) { return (unsigned)((n + 255) / 256); }
 // Which lattice a launch's rotor noise is drawn on (include/dronesim_amd.h: DSIM_OPT_NOISE_FINE / _COARSE): resolved ONCE per

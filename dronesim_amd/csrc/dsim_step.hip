@@ -1,5 +1,7 @@
 // dsim_step.hip — dsim_step: Env.step + computeControl in ONE launch (the hot path of examples/fly_INDI.py:217-245), every
-// kernel family that serves it (gfx950 only).
+// kernel family that serves it (gfx950 only).  Host side, at the end: the call is classified once (StepCall, classify_step);
+// dsim_step refuses what it does not serve and tries its routes in order, one function each — step_dyn, step_runs,
+// step_quad_tiles, step_hexa_tiles, then step_general (dsim_step_mixed.hip) for the ragged tail and everything else.
 #include "dsim_kernels.h"
 
 // ---- fused Env.step + computeControl (the hot path) -----------------------
@@ -244,93 +246,57 @@ __global__ __launch_bounds__(256, 3) void k_step_runs(StepK a, RunTab rt) {
   else run_body<DSIM_DEV_KIND_QUAD, NOISE, NT, S1, ACT>(a, ro.i0, ro.lo, ro.last, ro.type, ntab);
 }
 
-extern "C" {
-
-int dsim_step(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, dsim_view targets,
-              const dsim_step_args* args) {
-  StepK a;
-  int rc = fill_stepk(ctx, n, state, &targets, args, &a);
+// ---------------------------------------------------------------------------
+// host side: one function per route of dsim_step, tried in dsim_step's order; what they route on is the call's StepCall
+// (classify_step).  The general remainder — ragged tails, and every configuration none of these serves — is step_general
+// (dsim_step_mixed.hip).
+// ---------------------------------------------------------------------------
+// Physics.DYN (DSIM_OPT_DYN): k_dyn with the control law (dsim_two_call.hip); what the mode does not combine with is refused
+static int step_dyn(dsim_ctx* ctx, const dsim_step_args* args, const StepK& a, hipStream_t st_) {
+  const int rc = dyn_check(ctx, args, a);
   if (rc) return rc;
-  if (args->options & DSIM_OPT_DYN) {
-    rc = dyn_check(ctx, args, a);
-    if (rc) return rc;
-    if (!a.tg.base) return DSIM_E_ARG;
-    ctx->prebin.valid = false;
-    return dyn_launch(true, a, stream_policy(args, state.n_pad, 256.0), (hipStream_t)stream);
-  }
-  if (args->options & DSIM_OPT_CALLER_IO) return DSIM_E_UNSUPPORTED;     // (dsim_physics / dsim_control2 only)
-  ctx->prebin.valid = false;      // the positions move: a grid binned before this call is stale (bin_next_commit re-validates)
-  const bool noise = args->noise_seed != 0 || args->noise_replay != nullptr;
-  const bool uni = args->type_id == nullptr;
-  const bool six = ctx->max_act == 6;
-  const hipStream_t st_ = (hipStream_t)stream;
+  if (!a.tg.base) return DSIM_E_ARG;
+  ctx->prebin.valid = false;
+  return dyn_launch(true, a, stream_policy(args, a.n_pad, 256.0), st_);
+}
+
+// Type-major storage (dsim_step_args.runs, or a homogeneous fleet as one run): the single-type bodies, all runs in one launch
+// (k_step_runs) or one launch per run (k_step_run); the downwash force in, the next neighbour grid out.
+static int step_runs(dsim_ctx* ctx, int64_t n, const dsim_step_args* args, const StepCall& c, StepK& a,
+                     const dsim_type_run* runs, int n_runs, hipStream_t st_) {
   const dim3 b(256);
-  long long first = 0;
-  // the fine noise lattice (resolved by fill_stepk): carried by every instance but the looped fast ones (quad_substeps)
-  const bool fine = noise && !args->noise_replay && (a.options & DSIM_OPT_NOISE_FINE) != 0;
-  const bool fine_slow = fine && a.substeps > 1;        // several sub-steps per launch on the fine lattice: the general kernels
-  const bool phys_opts = (args->options & (DSIM_OPT_DRAG | DSIM_OPT_GROUND | DSIM_OPT_PLANE)) != 0 || fine_slow;
-  const bool plane = (args->options & DSIM_OPT_PLANE) != 0;
-  if ((args->options & (DSIM_OPT_DRAG | DSIM_OPT_GROUND)) && six)
-    return DSIM_E_UNSUPPORTED;                          // the add-on formulas are written for the four-rotor links
-  if ((args->options & DSIM_OPT_CHAINED) && (!uni || six || args->action || args->noise_replay || args->ext_force ||
-                                             phys_opts || (state.n_pad % 256)))
-    return DSIM_E_UNSUPPORTED;                          // chained stepping is a fast-path-only mode
-  const bool runs_ok = !args->noise_replay && !a.wp_table && a.n_steps == 1 && !phys_opts && a.tg.base &&
-                       !(args->options & DSIM_OPT_CHAINED);
-  const bool plain = runs_ok && !args->action;
-  const dsim_type_run* runs = args->runs;
-  int n_runs = args->n_runs;
-  dsim_type_run whole;
-  const bool any_quadlaw6 = has_quadlaw6(ctx);
-  if (!(runs && n_runs > 0) && uni && runs_ok && (args->ext_force || (any_quadlaw6 && !args->action))) {
-    // a homogeneous fleet with an external (downwash) force, or of hexa_6DOF_simple: ONE run of its only type — the
-    // single-type kernel with the force input and the fused neighbour-grid binning, instead of the general kernel
-    whole.first = 0; whole.count = a.n_pad; whole.type = 0; whole._pad = 0;
-    runs = &whole; n_runs = 1;
+  const bool nt = stream_policy(args, a.n_pad, 240.0);
+  bool any_hexa = false;
+  bin_next_prepare(ctx, n, args, &a, st_);
+  for (int r = 0; r < n_runs; ++r) {
+    if (!run_valid(ctx, a.n_pad, runs[r])) return DSIM_E_ARG;
+    any_hexa |= ctx->h_types[runs[r].type].kind == DSIM_KIND_HEXA6DOF;
   }
-  // (an explicit action — the first iteration of the example loop, fly_INDI.py:214 — is served by the ACT instances of the
-  // one-launch form; beyond DSIM_MAX_TYPES runs it goes to the general kernel.  The ACT instances exist with the default cache
-  // policy only: an explicit action is ONE step of a loop, the streaming hint would buy it nothing and cost twelve instances)
-  if (runs && n_runs > 0 && runs_ok && (!args->action || (n_runs <= DSIM_MAX_TYPES && !any_quadlaw6))) {
-    // type-major storage: one single-type launch per run
-    const bool nt = stream_policy(args, state.n_pad, 240.0);
-    bool any_hexa = false;
-    bin_next_prepare(ctx, n, args, &a, st_);
-    for (int r = 0; r < n_runs; ++r) {
-      const dsim_type_run& run = runs[r];
-      if (run.first < 0 || run.count < 0 || run.first + run.count > a.n_pad || run.type < 0 || run.type >= ctx->n_types)
-        return DSIM_E_ARG;
-      any_hexa |= ctx->h_types[run.type].kind == DSIM_KIND_HEXA6DOF;
+  if (any_hexa) {
+    const int rc = fb_open_queue(ctx, &a, st_);
+    if (rc) return rc;
+  }
+  // (measured on MI355X, 50 % quads + 50 % hexas: 65 536 drones 12.0 us against 9.5 + 9.0 us for two dependent launches;
+  // 4 194 304 drones 160.1 against 165.2 us — the launch boundary between the runs costs more than the registers the
+  // second law adds (83 VGPRs, 5 waves per SIMD, against 74 and 6): one launch is the default at every size for ONE sub-step.
+  // With several sub-steps the launch is bound by vector issue and the looped instances differ more: k_step_runs 102 VGPRs, 4 waves
+  // per SIMD, against 76 / 6 (quads) and 89 / 5 (hexas) for the single-law k_step_run — a fleet that fills the chip then takes
+  // one launch per run (round 6: 4 194 304 interleaved quads + hexas x 5 sub-steps))
+  const bool per_run_pays = a.substeps > 1 && a.n_pad >= (1LL << 20) && !args->action;
+  const bool one_launch = !c.any_quadlaw6 && !per_run_pays;
+  if (n_runs <= DSIM_MAX_TYPES && (n_runs >= 2 || args->action) && one_launch) {
+    // several runs (or an explicit action): one launch for all of them (k_step_runs)
+    RunTab rt;
+    const int blocks = make_runtab(ctx, a.n_pad, runs, n_runs, &rt, &any_hexa);
+    if (blocks < 0) return blocks;
+    if (blocks > 0) {
+      const dim3 g((unsigned)blocks);
+      with_flags([&](auto N, auto NT, auto S1, auto ACT) {      // (the ACT instances: default cache policy only, see dsim_step)
+        hipLaunchKernelGGL((k_step_runs<N(), NT() && !ACT(), S1(), ACT()>), g, b, 0, st_, a, rt);
+      }, c.noise, nt, a.substeps == 1, args->action != nullptr);
     }
-    if (any_hexa) {
-      rc = fb_prepare(ctx, a.n_pad, st_);
-      if (rc) return rc;
-      a.fb.entries = ctx->d_fb;
-    }
-    // (measured on MI355X, 50 % quads + 50 % hexas: 65 536 drones 12.0 us against 9.5 + 9.0 us for two dependent launches;
-    // 4 194 304 drones 160.1 against 165.2 us — the launch boundary between the runs costs more than the registers the
-    // second law adds (83 VGPRs, 5 waves per SIMD, against 74 and 6): one launch is the default at every size for ONE sub-step.
-    // With several sub-steps the launch is bound by vector issue and the looped instances differ more: k_step_runs 102 VGPRs, 4 waves
-    // per SIMD, against 76 / 6 (quads) and 89 / 5 (hexas) for the single-law k_step_run — a fleet that fills the chip then takes
-    // one launch per run (round 6: 4 194 304 interleaved quads + hexas x 5 sub-steps))
-    const bool per_run_pays = a.substeps > 1 && a.n_pad >= (1LL << 20) && !args->action;
-    const bool one_launch = !any_quadlaw6 && !per_run_pays;
-    if (n_runs <= DSIM_MAX_TYPES && (n_runs >= 2 || args->action) && one_launch) {
-      // several runs (or an explicit action): one launch for all of them (k_step_runs)
-      RunTab rt;
-      const int blocks = make_runtab(ctx, a.n_pad, runs, n_runs, &rt, &any_hexa);
-      if (blocks < 0) return blocks;
-      if (blocks > 0) {
-        const dim3 g((unsigned)blocks);
-        with_flags([&](auto N, auto NT, auto S1, auto ACT) {      // (the ACT instances: default cache policy only, see above)
-          hipLaunchKernelGGL((k_step_runs<N(), NT() && !ACT(), S1(), ACT()>), g, b, 0, st_, a, rt);
-        }, noise, nt, a.substeps == 1, args->action != nullptr);
-      }
-      if (any_hexa) fb_finish(ctx, a, st_);
-      bin_next_commit(ctx, n, args, a);
-      return (int)hipGetLastError();
-    }
+  } else {
+    // one single-type launch per run
     for (int r = 0; r < n_runs; ++r) {
       const dsim_type_run& run = runs[r];
       if (run.count == 0) continue;
@@ -344,52 +310,96 @@ int dsim_step(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, dsim_view
         // (the quad law on six actuators — hexa_6DOF_simple.urdf — with the default cache policy only: four streaming instances less)
         else if (kind == DSIM_KIND_HEXA_QUADLAW) hipLaunchKernelGGL((k_step_run<DSIM_DEV_KIND_HEXA_QUADLAW, N(), false, S1()>), g, b, 0, st_, a);
         else hipLaunchKernelGGL((k_step_run<DSIM_DEV_KIND_QUAD, N(), NT(), S1()>), g, b, 0, st_, a);
-      }, noise, nt, a.substeps == 1);
-    }
-    if (any_hexa) fb_finish(ctx, a, st_);
-    bin_next_commit(ctx, n, args, a);
-    return (int)hipGetLastError();
-  }
-  const bool multi = a.wp_table != nullptr || a.n_steps > 1;
-  if (uni && !six && !(args->action && multi) && !args->noise_replay && !args->ext_force && !phys_opts) {      // (fine_slow is a phys_opt: a fine launch that comes here has ONE sub-step)
-    // fast path over the whole 256-drone tiles (an explicit action: the ACT instances of the plain form)
-    const bool nt = stream_policy(args, state.n_pad, 232.0);
-    const long long tiles = a.n_pad / 256;
-    if (tiles > 0) {
-      const dim3 g((unsigned)tiles);
-      const bool ext = multi;
-      const bool ch = (args->options & DSIM_OPT_CHAINED) != 0;
-      const bool tc = tgt_const_honoured(args);          // (the plain instances: vel / acc / yaw from the arguments)
-      const bool md = (args->options & DSIM_OPT_MEM_DERIVED) != 0;     // (the plain single-sub-step TC instances, not chained)
-      // (TC: the plain instances only.  EXT: any sub-step count.  ACT: never with EXT or CH (both kept out above), the default
-      // cache policy only, as k_step_runs)
-      with_flags([&](auto N, auto NT, auto CH, auto S1, auto TC, auto MD) {
-        if (ext) hipLaunchKernelGGL((k_step_fast<N(), NT(), true, CH()>), g, b, 0, st_, a);
-        else if (args->action) hipLaunchKernelGGL((k_step_fast<N(), false, false, false, S1() ? 1 : 0, true>), g, b, 0, st_, a);
-        else hipLaunchKernelGGL((k_step_fast<N(), NT(), false, CH(), S1() ? 1 : 0, false, TC(), MD() && S1() && !CH() && TC()>), g, b, 0, st_, a);
-      }, noise, nt, ch, a.substeps == 1, tc, md);
-      first = tiles * 256;
+      }, c.noise, nt, a.substeps == 1);
     }
   }
+  if (any_hexa) fb_finish(ctx, a, st_);
+  bin_next_commit(ctx, n, args, a);
+  return (int)hipGetLastError();
+}
+
+// Homogeneous quad fleet: k_step_fast over the whole 256-drone tiles (an explicit action: the ACT instances of the plain form).
+// Returns the first drone it left for the tail.
+static long long step_quad_tiles(const dsim_step_args* args, const StepCall& c, const StepK& a, hipStream_t st_) {
+  const bool nt = stream_policy(args, a.n_pad, 232.0);
+  const long long tiles = a.n_pad / 256;
+  if (tiles == 0) return 0;
+  const dim3 g((unsigned)tiles), b(256);
+  const bool ext = c.multi;
+  const bool ch = (args->options & DSIM_OPT_CHAINED) != 0;
+  const bool tc = tgt_const_honoured(args);          // (the plain instances: vel / acc / yaw from the arguments)
+  const bool md = (args->options & DSIM_OPT_MEM_DERIVED) != 0;     // (the plain single-sub-step TC instances, not chained)
+  // (TC: the plain instances only.  EXT: any sub-step count.  ACT: never with EXT or CH (both kept out by dsim_step), the default
+  // cache policy only, as k_step_runs)
+  with_flags([&](auto N, auto NT, auto CH, auto S1, auto TC, auto MD) {
+    if (ext) hipLaunchKernelGGL((k_step_fast<N(), NT(), true, CH()>), g, b, 0, st_, a);
+    else if (args->action) hipLaunchKernelGGL((k_step_fast<N(), false, false, false, S1() ? 1 : 0, true>), g, b, 0, st_, a);
+    else hipLaunchKernelGGL((k_step_fast<N(), NT(), false, CH(), S1() ? 1 : 0, false, TC(), MD() && S1() && !CH() && TC()>), g, b, 0, st_, a);
+  }, c.noise, nt, ch, a.substeps == 1, tc, md);
+  return tiles * 256;
+}
+
+// Homogeneous morphing-hexa fleet: k_step_hexa over the whole tiles.  Opens the WLS fallback queue and leaves it OPEN for a
+// ragged tail (*first < n_pad): one queue serves one step, step_general's launch finds it prepared and closes it.
+static int step_hexa_tiles(dsim_ctx* ctx, const dsim_step_args* args, const StepCall& c, StepK& a, hipStream_t st_, long long* first) {
+  const long long tiles = a.n_pad / 256;
+  const bool nt = stream_policy(args, a.n_pad, 248.0);
+  const int rc = fb_open_queue(ctx, &a, st_);
+  if (rc) return rc;
+  const dim3 g((unsigned)tiles), b(256);
+  const bool md = (args->options & DSIM_OPT_MEM_DERIVED) != 0;     // (the single-sub-step instances without an explicit action)
+  with_flags([&](auto N, auto NT, auto S1, auto ACT, auto MD) {        // (the ACT instances: default cache policy only, as k_step_runs)
+    hipLaunchKernelGGL((k_step_hexa<N(), NT() && !ACT(), S1(), ACT(), MD() && S1() && !ACT()>), g, b, 0, st_, a);
+  }, c.noise, nt, a.substeps == 1, args->action != nullptr, md);
+  *first = tiles * 256;
+  if (*first >= a.n_pad) fb_finish(ctx, a, st_);
+  return DSIM_OK;
+}
+
+extern "C" {
+
+int dsim_step(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, dsim_view targets,
+              const dsim_step_args* args) {
+  StepK a;
+  int rc = fill_stepk(ctx, n, state, &targets, args, &a);
+  if (rc) return rc;
+  const StepCall c = classify_step(ctx, args, a);
+  const hipStream_t st_ = (hipStream_t)stream;
+  if (args->options & DSIM_OPT_DYN) return step_dyn(ctx, args, a, st_);
+  // ---- the refusals
+  if (args->options & DSIM_OPT_CALLER_IO) return DSIM_E_UNSUPPORTED;     // (dsim_physics / dsim_control2 only)
+  ctx->prebin.valid = false;      // the positions move: a grid binned before this call is stale (bin_next_commit re-validates)
+  if ((args->options & (DSIM_OPT_DRAG | DSIM_OPT_GROUND)) && c.six)
+    return DSIM_E_UNSUPPORTED;                          // the add-on formulas are written for the four-rotor links
+  if ((args->options & DSIM_OPT_CHAINED) && (!c.uni || c.six || args->action || c.replay || args->ext_force ||
+                                             c.off_fast_path || !c.whole_tiles))
+    return DSIM_E_UNSUPPORTED;                          // chained stepping is a fast-path-only mode
+  // ---- the routes, in order: the first that serves the call launches it
+  // 1. runs of one type each.  A homogeneous fleet with an external (downwash) force, or of hexa_6DOF_simple, is ONE run of its
+  // only type: the single-type kernel with the force input and the fused neighbour-grid binning, instead of the general kernel.
+  // (An explicit action — the first iteration of the example loop, fly_INDI.py:214 — is served by the ACT instances of the
+  // one-launch form; beyond DSIM_MAX_TYPES runs it goes to the general kernel.  The ACT instances exist with the default cache
+  // policy only: an explicit action is ONE step of a loop, the streaming hint would buy it nothing and cost twelve instances)
+  const bool runs_ok = !c.replay && !c.multi && !c.off_fast_path && a.tg.base && !(args->options & DSIM_OPT_CHAINED);
+  dsim_type_run whole;
+  const bool whole_as_run = c.uni && runs_ok && (args->ext_force || (c.any_quadlaw6 && !args->action));
+  const CallRuns cr = call_runs(args, a.n_pad, INT_MAX, whole_as_run, whole);
+  if (cr.n_runs > 0 && runs_ok && (!args->action || (cr.n_runs <= DSIM_MAX_TYPES && !c.any_quadlaw6)))
+    return step_runs(ctx, n, args, c, a, cr.runs, cr.n_runs, st_);
+  // 2. / 3. a homogeneous fleet's whole tiles on the fast forms (fine_slow is off the fast path: a fine launch that comes here
+  // has ONE sub-step); what they leave, or everything when neither applies, goes to 4.
+  long long first = 0;
   bool fb_open = false;
-  if (uni && six && ctx->h_types[0].kind == DSIM_KIND_HEXA6DOF && !args->noise_replay && !args->ext_force &&
-      !a.wp_table && a.n_steps == 1 && a.n_pad >= 256 && !phys_opts) {
-    const long long tiles = a.n_pad / 256;
-    const bool nt = stream_policy(args, state.n_pad, 248.0);
-    rc = fb_prepare(ctx, a.n_pad, st_);
+  if (c.uni && !c.six && !(args->action && c.multi) && !c.replay && !args->ext_force && !c.off_fast_path)
+    first = step_quad_tiles(args, c, a, st_);
+  if (c.uni && c.six && ctx->h_types[0].kind == DSIM_KIND_HEXA6DOF && !c.replay && !args->ext_force && !c.multi &&
+      a.n_pad >= 256 && !c.off_fast_path) {
+    rc = step_hexa_tiles(ctx, args, c, a, st_, &first);
     if (rc) return rc;
-    a.fb.entries = ctx->d_fb;
     fb_open = true;
-    const dim3 g((unsigned)tiles);
-    const bool md = (args->options & DSIM_OPT_MEM_DERIVED) != 0;     // (the single-sub-step instances without an explicit action)
-    with_flags([&](auto N, auto NT, auto S1, auto ACT, auto MD) {        // (the ACT instances: default cache policy only, as k_step_runs)
-      hipLaunchKernelGGL((k_step_hexa<N(), NT() && !ACT(), S1(), ACT(), MD() && S1() && !ACT()>), g, b, 0, st_, a);
-    }, noise, nt, a.substeps == 1, args->action != nullptr, md);
-    first = tiles * 256;
-    if (first >= a.n_pad) fb_finish(ctx, a, st_);
   }
-  if (first < a.n_pad)     // ragged tail, or everything when the fast path does not apply (dsim_step_mixed.hip)
-    return step_general(ctx, n, state, targets, args, a, first, fb_open, st_);
+  // 4. ragged tail, or everything when no fast form applies: the general kernels (dsim_step_mixed.hip)
+  if (first < a.n_pad) return step_general(ctx, n, state, targets, args, c, a, first, fb_open, st_);
   return (int)hipGetLastError();
 }
 

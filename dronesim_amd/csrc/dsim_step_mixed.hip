@@ -1,6 +1,6 @@
 // dsim_step_mixed.hip — the part of dsim_step that no single-type fast path serves: the general kernels (ragged tails, options,
 // replayed noise, more than four types per lane) and the LDS-staged kernels of mixed fleets kept in the caller's own order
-// (gfx950 only).
+// (gfx950 only).  Host side: step_general, the last route of dsim_step, which hands it the call as it classified it (StepCall).
 #include "dsim_kernels.h"
 
 // FULL = false: the lean form for plain stepping of mixed fleets (stored cmd as the action, no
@@ -397,31 +397,24 @@ __global__ __launch_bounds__(128, S1 ? 4 : 3) void k_step_mixed4(StepK a) {
 // ---------------------------------------------------------------------------
 // dsim_step's ragged tail, or the whole fleet when no single-type fast path applies (called by dsim_step, dsim_step.hip): the
 // general kernels (k_step_gen / _lean / _plane) and the LDS-staged kernels of mixed fleets kept in the caller's own order.
-// first: first drone of this part (a multiple of 256); fb_open: the WLS fallback queue is already prepared for this step.
-int step_general(dsim_ctx* ctx, int64_t n, const dsim_view& state, const dsim_view& targets, const dsim_step_args* args, StepK& a,
-                 long long first, bool fb_open, hipStream_t st_) {
+// c: the call as dsim_step classified it; first: first drone of this part (a multiple of 256); fb_open: the WLS fallback queue is
+// already open for this step (the tiles went through k_step_hexa).
+int step_general(dsim_ctx* ctx, int64_t n, const dsim_view& state, const dsim_view& targets, const dsim_step_args* args,
+                 const StepCall& c, StepK& a, long long first, bool fb_open, hipStream_t st_) {
   int rc = DSIM_OK;
-  const bool noise = args->noise_seed != 0 || args->noise_replay != nullptr;
-  const bool uni = args->type_id == nullptr;
-  const bool six = ctx->max_act == 6;
-  const bool fine = noise && !args->noise_replay && (a.options & DSIM_OPT_NOISE_FINE) != 0;
-  const bool fine_slow = fine && a.substeps > 1;
-  const bool phys_opts = (args->options & (DSIM_OPT_DRAG | DSIM_OPT_GROUND | DSIM_OPT_PLANE)) != 0 || fine_slow;
-  const bool plane = (args->options & DSIM_OPT_PLANE) != 0;
-  const bool any_quadlaw6 = has_quadlaw6(ctx);
+  const bool plane = c.plane;       // (the name the launch lambdas read)
   a.first = first;
   const dim3 g(grid_for(a.n_pad - first)), b(256);
-  const bool lean = !args->action && !args->noise_replay && !a.wp_table && a.n_steps == 1 && !phys_opts;     // (fine_slow is a phys_opt)
-  if (lean && !uni && a.tg.base && ctx->n_types <= 4 && ctx->max_act == 6 && !any_quadlaw6) {
+  const bool lean = !args->action && !c.replay && !c.multi && !c.off_fast_path;     // (fine_slow is off the fast path)
+  if (lean && !c.uni && a.tg.base && ctx->n_types <= 4 && c.six && !c.any_quadlaw6) {
     // a heterogeneous fleet kept in the CALLER's own order (CtrlAviary(storage="caller"); storage="auto" stores it
     // type-major and never comes here): the LDS-staged kernels, which partition every tile by type
     const bool nt = stream_policy(args, state.n_pad, 240.0);
     bool any_hexa = false;
     for (int t = 0; t < ctx->n_types; ++t) any_hexa |= ctx->h_types[t].kind == DSIM_KIND_HEXA6DOF;
     if (any_hexa && !fb_open) {
-      rc = fb_prepare(ctx, a.n_pad, st_);
+      rc = fb_open_queue(ctx, &a, st_);
       if (rc) return rc;
-      a.fb.entries = ctx->d_fb;
     }
     if (first == 0) bin_next_prepare(ctx, n, args, &a, st_);      // (the whole fleet goes through this kernel)
     // LDS-DMA of whole 1 KB row groups needs the wave-tiled layout [n/64][F][64] for the state (26 fields: a table with
@@ -437,7 +430,7 @@ int step_general(dsim_ctx* ctx, int64_t n, const dsim_view& state, const dsim_vi
       // another sixteen instances less.  The three-wave form below does NOT bear it: five waves for two types 300 against 207 us.)
       with_flags([&](auto N, auto NT, auto S1, auto BIN) {
         hipLaunchKernelGGL((k_step_mixed4<N(), NT(), S1(), 4, BIN()>), gm, bm, 0, st_, a);
-      }, noise, nt, a.substeps == 1, a.bin.count != nullptr);
+      }, c.noise, nt, a.substeps == 1, a.bin.count != nullptr);
     } else {
       // any other layout: one tile per workgroup, row DMAs in natural order, ballot partition
       const dim3 gm((unsigned)((a.n_pad - first + 127) / 128));
@@ -447,20 +440,20 @@ int step_general(dsim_ctx* ctx, int64_t n, const dsim_view& state, const dsim_vi
         if (ctx->n_types == 2) hipLaunchKernelGGL((k_step_mixed3<N(), false, 3, S1(), false>), gm, dim3(64 * 3), 0, st_, a);
         else if (ctx->n_types == 3) hipLaunchKernelGGL((k_step_mixed3<N(), false, 4, S1(), false>), gm, dim3(64 * 4), 0, st_, a);
         else hipLaunchKernelGGL((k_step_mixed3<N(), false, 5, S1(), false>), gm, dim3(64 * 5), 0, st_, a);
-      }, noise, a.substeps == 1);
+      }, c.noise, a.substeps == 1);
     }
     if (any_hexa) fb_finish(ctx, a, st_);
     bin_next_commit(ctx, n, args, a);
     return (int)hipGetLastError();
-  } else if (!six) {
+  } else if (!c.six) {
     // (k_step_plane / k_step_gen serve homogeneous and mixed fleets with ONE instance per (noise, actuator count), UNIFORM = false:
     // the type waterfall runs once for a homogeneous fleet (type_id null: type 0), its partition is skipped — these kernels are not
     // on a measured path, and the UNIFORM specialisation doubled their instance count (round 6: 293 -> ... instances))
     with_flags([&](auto N, auto UNI) {
-      if (lean) hipLaunchKernelGGL((k_step_lean<N(), UNI(), 4>), g, b, 0, st_, a);     // (fine_slow is a phys_opt: never lean)
+      if (lean) hipLaunchKernelGGL((k_step_lean<N(), UNI(), 4>), g, b, 0, st_, a);     // (fine_slow is off the fast path: never lean)
       else if (plane) hipLaunchKernelGGL((k_step_plane<N(), false, 4>), g, b, 0, st_, a);
       else hipLaunchKernelGGL((k_step_gen<N(), false, 4>), g, b, 0, st_, a);
-    }, noise, uni);
+    }, c.noise, c.uni);
   } else {
     // hexa fleets: deferred WLS fallbacks must land before the next Env.step reads cmd, so several
     // steps per call become several launches (each followed by the tiny fallback kernel)
@@ -468,16 +461,15 @@ int step_general(dsim_ctx* ctx, int64_t n, const dsim_view& state, const dsim_vi
     a.n_steps = 1;
     for (int k = 0; k < steps; ++k) {
       if (!fb_open) {                 // (open already when the tiles went through k_step_hexa: one queue, one fallback pass)
-        rc = fb_prepare(ctx, a.n_pad, st_);
+        rc = fb_open_queue(ctx, &a, st_);
         if (rc) return rc;
-        a.fb.entries = ctx->d_fb;
       }
       fb_open = false;
       with_flags([&](auto N, auto UNI) {        // (UNIFORM = false but for k_step_lean: as above)
         if (lean && !a.action) hipLaunchKernelGGL((k_step_lean<N(), UNI(), 6>), g, b, 0, st_, a);
         else if (plane) hipLaunchKernelGGL((k_step_plane<N(), false, 6>), g, b, 0, st_, a);
         else hipLaunchKernelGGL((k_step_gen<N(), false, 6>), g, b, 0, st_, a);
-      }, noise, uni);
+      }, c.noise, c.uni);
       fb_finish(ctx, a, st_);
       a.step_index += 1;
       a.action = nullptr;             // an explicit action applies to the first Env.step only

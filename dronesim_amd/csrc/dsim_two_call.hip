@@ -1,5 +1,7 @@
 // dsim_two_call.hip — the reference-shaped two-call loop: dsim_physics (Env.step), dsim_control / dsim_control2 (computeControl),
-// dsim_step_adaptor (VelocityAviary / RPYTAviary), Physics.DYN (gfx950 only).
+// dsim_step_adaptor (VelocityAviary / RPYTAviary), Physics.DYN (gfx950 only).  Host side, at the end: every entry point
+// classifies its call once (StepCall, classify_step) and routes on that record; the observation-row rule (obs_fuse / obs_finish),
+// the whole fleet as one run (call_runs) and the fallback queue's opening (fb_open_queue) are written once.
 #include "dsim_kernels.h"
 
 // ---- Env.step only ---------------------------------------------------------
@@ -765,6 +767,21 @@ int dyn_launch(bool ctrl, const StepK& a, bool nt, hipStream_t st) {
   return (int)hipGetLastError();
 }
 
+// The observation rows of a physics launch (dsim_step_args.obs_out).  The rule: FUSED into the launch when the caller's buffer
+// is aligned for the pieces the kernel stores them in (align bytes: any torch allocation is aligned far beyond that), else
+// written by the observation kernel BEHIND the launch on the stream.  obs_fuse decides and sets StepK.obs_out in front of the
+// launch; obs_finish, behind it, returns the call's result.  (The general kernels never fuse: obs_finish with fused = false.)
+static bool obs_fuse(const dsim_step_args* args, unsigned align, StepK* a) {
+  const bool fused = args->obs_out && ((uintptr_t)args->obs_out & (align - 1u)) == 0;
+  a->obs_out = fused ? args->obs_out : nullptr;
+  return fused;
+}
+static int obs_finish(dsim_ctx* ctx, void* stream, int64_t n, const dsim_view& state, const float* last_action,
+                      const dsim_step_args* args, int width, bool fused) {
+  if (args->obs_out && !fused) return observe_impl(ctx, stream, n, state, last_action, args->obs_out, width, 0);
+  return (int)hipGetLastError();
+}
+
 extern "C" {
 
 int dsim_physics(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, float* last_action_out,
@@ -772,65 +789,53 @@ int dsim_physics(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, float*
   StepK a;
   int rc = fill_stepk(ctx, n, state, nullptr, args, &a);
   if (rc) return rc;
+  const StepCall c = classify_step(ctx, args, a);
   ctx->prebin.valid = false;
   a.echo = last_action_out;
   if (args->options & DSIM_OPT_DYN) {
     rc = dyn_check(ctx, args, a);
     if (rc) return rc;
     if (args->obs_out && args->obs_width != 20) return DSIM_E_ARG;
-    const bool obs_fused = args->obs_out && ((uintptr_t)args->obs_out & 15u) == 0;       // (16-byte stores of the rows)
-    a.obs_out = obs_fused ? args->obs_out : nullptr;
+    const bool obs_fused = obs_fuse(args, 16, &a);       // (16-byte stores of the rows)
     rc = dyn_launch(false, a, stream_policy(args, state.n_pad, args->obs_out ? 240.0 : 160.0), (hipStream_t)stream);
     if (rc) return rc;
-    if (args->obs_out && !obs_fused) return observe_impl(ctx, stream, n, state, last_action_out, args->obs_out, 20, 0);
-    return DSIM_OK;
+    return obs_finish(ctx, stream, n, state, last_action_out, args, 20, obs_fused);
   }
-  const bool fine_slow = (args->noise_seed != 0 && !args->noise_replay && (a.options & DSIM_OPT_NOISE_FINE) && a.substeps > 1);
-  const bool phys_opts = (args->options & (DSIM_OPT_DRAG | DSIM_OPT_GROUND | DSIM_OPT_PLANE)) != 0;
-  if ((args->options & (DSIM_OPT_DRAG | DSIM_OPT_GROUND)) && ctx->max_act == 6) return DSIM_E_UNSUPPORTED;
+  if ((args->options & (DSIM_OPT_DRAG | DSIM_OPT_GROUND)) && c.six) return DSIM_E_UNSUPPORTED;
   const int obs_w = 16 + ctx->max_act;
   if (args->obs_out && args->obs_width != obs_w) return DSIM_E_ARG;
-  const bool noise = args->noise_seed != 0 || args->noise_replay != nullptr;
   const hipStream_t st_ = (hipStream_t)stream;
   if ((args->options & DSIM_OPT_CALLER_IO) && !args->drone_id) return DSIM_E_ARG;
   const bool arows = (args->options & DSIM_OPT_ACTION_ROWS) != 0;
   if (arows && (!args->action || ((uintptr_t)args->action & 15u))) return DSIM_E_ARG;
-  if (args->type_id == nullptr && ctx->max_act == 4 && !args->noise_replay && !args->ext_force && !phys_opts &&
-      (a.n_pad % 256) == 0 && !args->bin_next && !args->drone_id && !(args->options & DSIM_OPT_CALLER_IO)) {
-    // homogeneous quad fleet in whole tiles: the fast form, observation fused (16-byte stores: any torch allocation is
-    // aligned far beyond that; a misaligned caller buffer gets the rows from the observation kernel behind the step)
-    const bool obs_fused = args->obs_out && ((uintptr_t)args->obs_out & 15u) == 0;
-    a.obs_out = obs_fused ? args->obs_out : nullptr;
+  if (c.uni && ctx->max_act == 4 && !c.replay && !args->ext_force && !c.addon &&
+      c.whole_tiles && !args->bin_next && !args->drone_id && !(args->options & DSIM_OPT_CALLER_IO)) {
+    // homogeneous quad fleet in whole tiles: the fast form, the observation rows in 16-byte stores.  (fine_slow is served
+    // here: k_physics_fast carries both lattices at any sub-step count)
+    const bool obs_fused = obs_fuse(args, 16, &a);
     const bool nt = stream_policy(args, state.n_pad, args->obs_out ? 216.0 : 136.0);
     const dim3 g((unsigned)(a.n_pad / 256)), b(256);
-    const bool loop = a.substeps > 1 && !(noise && (a.options & DSIM_OPT_NOISE_FINE));      // (the looped instance: coarse lattice only)
+    const bool loop = a.substeps > 1 && !(c.noise && (a.options & DSIM_OPT_NOISE_FINE));      // (the looped instance: coarse lattice only)
     with_flags([&](auto N, auto NT, auto OBS, auto LOOP) {
       hipLaunchKernelGGL((k_physics_fast<N(), NT(), OBS(), LOOP()>), g, b, 0, st_, a);
-    }, noise, nt, a.obs_out != nullptr, loop);
-    if (args->obs_out && !obs_fused) return observe_impl(ctx, stream, n, state, last_action_out, args->obs_out, obs_w, 0);
-    return (int)hipGetLastError();
+    }, c.noise, nt, a.obs_out != nullptr, loop);
+    return obs_finish(ctx, stream, n, state, last_action_out, args, obs_w, obs_fused);
   }
   if (arows) return DSIM_E_UNSUPPORTED;               // (every other kernel takes the action field-major)
   // Every other fleet kind on the fast form: runs of one type (dsim_step_args.runs), or a homogeneous fleet as ONE run —
   // morphing hexas, type-major quad + hexa fleets, fleets with the downwash force, ragged tails.  The observation rows are
   // written by the same launch; the new positions may fill the next neighbour grid (bin_next).
   {
-    const dsim_type_run* runs = args->runs;
-    int n_runs = args->n_runs;
     dsim_type_run whole;
-    if (!(runs && n_runs > 0 && n_runs <= DSIM_MAX_TYPES) && args->type_id == nullptr) {
-      whole.first = 0; whole.count = a.n_pad; whole.type = 0; whole._pad = 0;
-      runs = &whole; n_runs = 1;
-    }
-    if (runs && n_runs > 0 && n_runs <= DSIM_MAX_TYPES && !args->noise_replay && !phys_opts && !fine_slow) {   // (k_physics_fast above carries
-      RunTab rt;                                                                                              //  both lattices at any count)
+    const CallRuns cr = call_runs(args, a.n_pad, DSIM_MAX_TYPES, c.uni, whole);
+    if (cr.n_runs > 0 && !c.replay && !c.addon && !c.fine_slow) {      // (the run kernels' looped form: the coarse lattice only)
+      RunTab rt;
       bool any_hexa = false;
-      const int blocks = make_runtab(ctx, a.n_pad, runs, n_runs, &rt, &any_hexa);
+      const int blocks = make_runtab(ctx, a.n_pad, cr.runs, cr.n_runs, &rt, &any_hexa);
       if (blocks < 0) return blocks;
-      if (a.io_id) { rc = side_by_side_map(ctx, st_, runs, n_runs, &rt); if (rc) return rc; }
+      if (a.io_id) { rc = side_by_side_map(ctx, st_, cr.runs, cr.n_runs, &rt); if (rc) return rc; }
       if (a.io_id && args->obs_out && ((uintptr_t)args->obs_out & 15u)) return DSIM_E_ARG;   // (the window's 16-byte pieces)
-      const bool obs_fused = args->obs_out && ((uintptr_t)args->obs_out & 7u) == 0;     // (8-byte pieces of the rows)
-      a.obs_out = obs_fused ? args->obs_out : nullptr;
+      const bool obs_fused = obs_fuse(args, 8, &a);     // (8-byte pieces of the rows)
       const bool nt = stream_policy(args, state.n_pad, args->obs_out ? 240.0 : 152.0);
       bin_next_prepare(ctx, n, args, &a, st_);
       if (blocks > 0) {
@@ -839,11 +844,10 @@ int dsim_physics(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, float*
         with_flags([&](auto N, auto NT, auto OBS, auto S1) {
           if (a.io_id) hipLaunchKernelGGL((k_physics_runs_io<N(), NT(), OBS(), S1()>), g_io, b_io, 0, st_, a, rt);
           else hipLaunchKernelGGL((k_physics_runs<N(), NT(), OBS(), S1()>), g, b, 0, st_, a, rt);
-        }, noise, nt, a.obs_out != nullptr, a.substeps == 1);
+        }, c.noise, nt, a.obs_out != nullptr, a.substeps == 1);
       }
       bin_next_commit(ctx, n, args, a);
-      if (args->obs_out && !obs_fused) return observe_impl(ctx, stream, n, state, last_action_out, args->obs_out, obs_w, 0);
-      return (int)hipGetLastError();
+      return obs_finish(ctx, stream, n, state, last_action_out, args, obs_w, obs_fused);
     }
   }
   if (a.io_id) return DSIM_E_UNSUPPORTED;            // the caller's numbering is served by the run kernels only
@@ -851,10 +855,8 @@ int dsim_physics(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, float*
   with_flags([&](auto N, auto SIX) {         // (UNIFORM = false: one instance for homogeneous and mixed fleets, see step_general)
     if (args->options & DSIM_OPT_PLANE) hipLaunchKernelGGL((k_physics_plane<N(), false, SIX() ? 6 : 4>), g, b, 0, st_, a);
     else hipLaunchKernelGGL((k_physics_gen<N(), false, SIX() ? 6 : 4>), g, b, 0, st_, a);
-  }, noise, ctx->max_act == 6);
-  if (args->obs_out)       // general fleets: the same rows by the observation kernel, behind the step on the stream
-    return observe_impl(ctx, stream, n, state, last_action_out, args->obs_out, obs_w, 0);
-  return (int)hipGetLastError();
+  }, c.noise, c.six);
+  return obs_finish(ctx, stream, n, state, last_action_out, args, obs_w, false);     // (general fleets: the rows behind the step)
 }
 
 int dsim_step_adaptor(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, const float* action,
@@ -870,35 +872,29 @@ int dsim_step_adaptor(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, c
   if (args->options & (DSIM_OPT_CALLER_IO | DSIM_OPT_DYN)) return DSIM_E_UNSUPPORTED;   // (the adaptor envs fly Physics.PYB)
   ctx->prebin.valid = false;
   a.action = action; a.echo = last_action_out;
-  const bool noise = args->noise_seed != 0, uni = args->type_id == nullptr;
+  const StepCall c = classify_step(ctx, args, a);       // (c.noise is noise_seed != 0 here: a replayed stream is refused above)
   const dim3 g(grid_for(a.n_pad)), b(256);
   const hipStream_t st_ = (hipStream_t)stream;
   const bool arows = (args->options & DSIM_OPT_ACTION_ROWS) != 0;
   if (args->obs_out && args->obs_width != 20) return DSIM_E_ARG;
   // (k_adaptor_fast carries both noise lattices: its sub-step loop is the non-looped form, dsim_kernels.h:quad_substeps)
-  if (uni && (a.n_pad % 256) == 0 && !(args->options & DSIM_OPT_PLANE) && !args->drone_id &&
-      (!arows || ((uintptr_t)action & 15u) == 0)) {
-    // homogeneous quad fleet in whole tiles: ONE launch, the observation rows fused (16-byte stores; a misaligned caller
-    // buffer gets them from the observation kernel behind the step), the action in either layout
-    const bool obs_fused = args->obs_out && ((uintptr_t)args->obs_out & 15u) == 0;
-    a.obs_out = obs_fused ? args->obs_out : nullptr;
+  if (c.uni && c.whole_tiles && !c.plane && !args->drone_id && (!arows || ((uintptr_t)action & 15u) == 0)) {
+    // homogeneous quad fleet in whole tiles: ONE launch, the observation rows in 16-byte stores, the action in either layout
+    const bool obs_fused = obs_fuse(args, 16, &a);
     const bool nt = stream_policy(args, state.n_pad, args->obs_out ? 304.0 : 224.0);
     const dim3 gf((unsigned)(a.n_pad / 256));
     with_flags([&](auto N, auto NT) {
       if (mode == DSIM_ADAPT_VELOCITY) hipLaunchKernelGGL((k_adaptor_fast<DSIM_ADAPT_VELOCITY, N(), NT()>), gf, b, 0, st_, a);
       else hipLaunchKernelGGL((k_adaptor_fast<DSIM_ADAPT_RPYT, N(), NT()>), gf, b, 0, st_, a);
-    }, noise, nt);
-    if (args->obs_out && !obs_fused) return observe_impl(ctx, stream, n, state, last_action_out, args->obs_out, 20, 0);
-    return (int)hipGetLastError();
+    }, c.noise, nt);
+    return obs_finish(ctx, stream, n, state, last_action_out, args, 20, obs_fused);
   }
   if (arows) return DSIM_E_UNSUPPORTED;               // (the general kernels take the action field-major)
   with_flags([&](auto N, auto PLANE) {         // (UNIFORM = false: one instance for homogeneous and mixed fleets, see step_general)
     if (mode == DSIM_ADAPT_VELOCITY) hipLaunchKernelGGL((k_adaptor<DSIM_ADAPT_VELOCITY, N(), false, PLANE()>), g, b, 0, st_, a);
     else hipLaunchKernelGGL((k_adaptor<DSIM_ADAPT_RPYT, N(), false, PLANE()>), g, b, 0, st_, a);
-  }, noise, (args->options & DSIM_OPT_PLANE) != 0);
-  if (args->obs_out)       // general fleets: the rows by the observation kernel, behind the step on the stream
-    return observe_impl(ctx, stream, n, state, last_action_out, args->obs_out, 20, 0);
-  return (int)hipGetLastError();
+  }, c.noise, c.plane);
+  return obs_finish(ctx, stream, n, state, last_action_out, args, 20, false);        // (general fleets: the rows behind the step)
 }
 
 int dsim_control(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, dsim_view targets,
@@ -915,9 +911,9 @@ int dsim_control2(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, dsim_
   a.pos_e_out = pos_e_out; a.yaw_e_out = yaw_e_out; a.cmd_out = cmd_out;
   const dim3 g(grid_for(a.n_pad)), b(256);
   const hipStream_t st_ = (hipStream_t)stream;
-  const bool uni = args->type_id == nullptr;
+  const StepCall c = classify_step(ctx, args, a);
   if ((args->options & DSIM_OPT_CALLER_IO) && !args->drone_id) return DSIM_E_ARG;
-  if (uni && ctx->max_act == 4 && (a.n_pad % 256) == 0 && a.tg.base && !a.io_id) {
+  if (c.uni && ctx->max_act == 4 && c.whole_tiles && a.tg.base && !a.io_id) {
     const bool nt = stream_policy(args, state.n_pad, 212.0);
     const dim3 gt((unsigned)(a.n_pad / 256));
     const bool tc = tgt_const_honoured(args);
@@ -928,24 +924,18 @@ int dsim_control2(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, dsim_
   }
   {
     // every other fleet kind: runs of one type (or a homogeneous fleet as one run) on the single-type bodies (k_control_runs)
-    const dsim_type_run* runs = args->runs;
-    int n_runs = args->n_runs;
     dsim_type_run whole;
-    if (!(runs && n_runs > 0 && n_runs <= DSIM_MAX_TYPES) && uni) {
-      whole.first = 0; whole.count = a.n_pad; whole.type = 0; whole._pad = 0;
-      runs = &whole; n_runs = 1;
-    }
-    if (runs && n_runs > 0 && n_runs <= DSIM_MAX_TYPES) {
+    const CallRuns cr = call_runs(args, a.n_pad, DSIM_MAX_TYPES, c.uni, whole);
+    if (cr.n_runs > 0) {
       RunTab rt;
       bool any_hexa = false;
-      const int blocks = make_runtab(ctx, a.n_pad, runs, n_runs, &rt, &any_hexa);
+      const int blocks = make_runtab(ctx, a.n_pad, cr.runs, cr.n_runs, &rt, &any_hexa);
       if (blocks < 0) return blocks;
       if (any_hexa) {
-        rc = fb_prepare(ctx, a.n_pad, st_);
+        rc = fb_open_queue(ctx, &a, st_);
         if (rc) return rc;
-        a.fb.entries = ctx->d_fb;
       }
-      if (a.io_id) { rc = side_by_side_map(ctx, st_, runs, n_runs, &rt); if (rc) return rc; }
+      if (a.io_id) { rc = side_by_side_map(ctx, st_, cr.runs, cr.n_runs, &rt); if (rc) return rc; }
       const bool nt = stream_policy(args, state.n_pad, 236.0);
       if (blocks > 0) {
         const dim3 gr((unsigned)blocks);
@@ -961,10 +951,9 @@ int dsim_control2(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, dsim_
   }
   // what is left: per-lane types without usable runs (the caller's own order of a heterogeneous fleet)
   if (a.io_id) return DSIM_E_UNSUPPORTED;
-  if (ctx->max_act == 6) {
-    rc = fb_prepare(ctx, a.n_pad, st_);
+  if (c.six) {
+    rc = fb_open_queue(ctx, &a, st_);
     if (rc) return rc;
-    a.fb.entries = ctx->d_fb;
     hipLaunchKernelGGL((k_control_gen<6>), g, b, 0, st_, a);
     fb_finish(ctx, a, st_);
   }
