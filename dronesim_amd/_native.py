@@ -22,6 +22,7 @@ EXPORTS = (
     "dsim_halo_pack", "dsim_downwash_workspace_halo", "dsim_dev_alloc", "dsim_dev_free", "dsim_noise_draw",
     "dsim_downwash_keep_workspace", "dsim_downwash_keep_ok", "dsim_downwash_keep_stats",
     "dsim_clearance", "dsim_clearance_workspace", "dsim_abi_minor",
+    "dsim_obstacle_grid_plan", "dsim_obstacle_grid_build", "dsim_obstacles_create", "dsim_obstacles_destroy", "dsim_obstacle_clearance",
 )
 
 ABI_VERSION = 11
@@ -57,6 +58,22 @@ ADAPT_VELOCITY, ADAPT_RPYT = 0, 1
 QUERY_WLS_FALLBACKS, QUERY_WLS_FAILURES, QUERY_GROUND_CONTACTS, QUERY_HALO_OVERFLOW = 0, 1, 2, 3
 QUERY_DW_REUSES, QUERY_DW_MOVERS = 4, 5
 QUERY_DRONE_CONTACTS = 6     # pairs of drones x dsim_clearance calls whose bounding spheres overlapped
+QUERY_OBSTACLE_CONTACTS = 7  # drones x dsim_obstacle_clearance calls whose bounding sphere overlapped a triangle of the set
+
+
+class ObstacleGrid(ctypes.Structure):
+    """dsim_obstacle_grid: the uniform 3-D grid around a triangle soup (dsim_obstacle_grid_plan)."""
+    _fields_ = [
+        ("origin", ctypes.c_float * 3),
+        ("cell", ctypes.c_float),
+        ("nx", ctypes.c_int32),
+        ("ny", ctypes.c_int32),
+        ("nz", ctypes.c_int32),
+        ("reach", ctypes.c_float),
+        ("list_len", ctypes.c_int64),
+        ("lo", ctypes.c_float * 3),
+        ("hi", ctypes.c_float * 3),
+    ]
 
 
 class View(ctypes.Structure):
@@ -209,6 +226,11 @@ def load(path: str = None) -> ctypes.CDLL:
     lib.dsim_clearance_workspace.argtypes = [i64, i32, i32]
     lib.dsim_clearance.argtypes = [vp, vp, i64, View, ctypes.POINTER(DownwashArgs), vp, ctypes.c_float, vp, vp, vp]
     lib.dsim_abi_minor.restype = ctypes.c_int
+    lib.dsim_obstacle_grid_plan.argtypes = [vp, i64, ctypes.c_float, ctypes.POINTER(ObstacleGrid)]
+    lib.dsim_obstacle_grid_build.argtypes = [vp, i64, ctypes.POINTER(ObstacleGrid), vp, vp]
+    lib.dsim_obstacles_create.argtypes = [vp, vp, vp, i64, ctypes.c_float, ctypes.POINTER(vp)]
+    lib.dsim_obstacles_destroy.argtypes = [vp, vp]
+    lib.dsim_obstacle_clearance.argtypes = [vp, vp, i64, View, vp, vp, vp, ctypes.c_float, vp, vp, vp]
     if lib.dsim_abi_version() != ABI_VERSION or lib.dsim_abi_minor() != ABI_MINOR:
         raise ImportError(f"libdronesim_amd.so ABI {lib.dsim_abi_version()}.{lib.dsim_abi_minor()} != binding {ABI_VERSION}.{ABI_MINOR}")
     _lib = lib

@@ -602,7 +602,7 @@ int dsim_dev_free(dsim_ctx* ctx, void* ptr) {
 }
 
 int dsim_query(dsim_ctx* ctx, void* stream, int32_t what, int64_t* value_out) {
-  if (!ctx || !value_out || what < 0 || what > DSIM_Q_DRONE_CONTACTS) return DSIM_E_ARG;
+  if (!ctx || !value_out || what < 0 || what > DSIM_Q_OBSTACLE_CONTACTS) return DSIM_E_ARG;
   unsigned long long h[DSIM_N_COUNTERS];
   hipError_t e = hipMemcpyAsync(h, ctx->d_counters, sizeof(h), hipMemcpyDeviceToHost, (hipStream_t)stream);
   if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
@@ -614,6 +614,10 @@ int dsim_query(dsim_ctx* ctx, void* stream, int32_t what, int64_t* value_out) {
   } else if (what == DSIM_Q_DRONE_CONTACTS) {
     unsigned long long sum = 0;
     for (int k = 0; k < DSIM_DRONE_SHARDS; ++k) sum += h[8 + DSIM_GROUND_SHARDS + k];
+    *value_out = (int64_t)sum;
+  } else if (what == DSIM_Q_OBSTACLE_CONTACTS) {
+    unsigned long long sum = 0;
+    for (int k = 0; k < DSIM_OBST_SHARDS; ++k) sum += h[8 + DSIM_GROUND_SHARDS + DSIM_DRONE_SHARDS + k];
     *value_out = (int64_t)sum;
   } else if (what == DSIM_Q_HALO_OVERFLOW) {
     *value_out = (int64_t)h[4];

@@ -369,7 +369,8 @@ struct Target { V3 pos, vel, acc; float yaw; };
 // collision cylinder at or below z = 0 is COUNTED: one atomic per wave that holds such a drone, on one of 64 counter shards (dsim_query sums them).
 #define DSIM_GROUND_SHARDS 64
 #define DSIM_DRONE_SHARDS 64      // the drone-drone contact watch (k_clearance_query) counts on shards of its own, behind the ground watch's
-#define DSIM_N_COUNTERS (8 + DSIM_GROUND_SHARDS + DSIM_DRONE_SHARDS)
+#define DSIM_OBST_SHARDS 64       // ... and the static-obstacle watch (k_obstacle_clearance) behind the drone watch's
+#define DSIM_N_COUNTERS (8 + DSIM_GROUND_SHARDS + DSIM_DRONE_SHARDS + DSIM_OBST_SHARDS)
 template <class DT>
 __device__ __forceinline__ void ground_watch(DT& T, const Rigid& s, unsigned long long* counters, bool live = true) {
   const float r22 = 1.0f - 2.0f * (s.q.x * s.q.x + s.q.y * s.q.y);                     // body z . world z (unit q)

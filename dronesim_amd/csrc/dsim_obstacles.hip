@@ -1,0 +1,223 @@
+// Static-obstacle watch (dsim_obstacle_clearance): per-drone clearance between the vehicle's bounding sphere and a static soup
+// of triangles, on a uniform 3-D grid of per-cell triangle lists (include/dronesim_amd.h).  Point against triangle soup; the
+// drone-drone watch (dsim_downwash.hip, k_clearance_query) is point against points.
+#include <hip/hip_runtime.h>
+
+#include <new>
+#include <vector>
+
+#include "dsim_kernels.h"
+#include "dsim_obstacle_grid.h"
+
+#define OBS_LDS_TRI 512          // sets up to this many triangles (32 KiB of records) are staged in LDS once per workgroup
+#define OBS_MAX_BLOCKS 2048      // workgroups walk tiles of 256 drones grid-stride, so one staging serves many tiles
+
+struct dsim_obstacles {
+  float4* rec;                   // [n_tri][4]  (dsim_obs::records)
+  int* cell_start;               // [cells + 1]
+  int* cell_tri;                 // [list_len]
+  int n_tri;
+  dsim_obstacle_grid grid;
+};
+
+struct ObsK {
+  KView st;
+  long long n, n_pad, tiles;
+  const float* offset;           // SoA [3][n_pad] or null
+  const uint8_t* type_id;        // or null: type 0
+  const DevType* types;
+  int n_types;
+  const float4* rec;
+  const int* cell_start;
+  const int* cell_tri;
+  int n_tri;
+  float ox, oy, oz, inv_cell;
+  int nx, ny, nz;
+  float lox, loy, loz, hix, hiy, hiz;     // the grown box: outside it no triangle is within reach
+  float margin;
+  float* clearance;              // [n_pad]
+  int* nearest;                  // [n_pad] or null
+  unsigned long long* counters;  // the ctx's (DSIM_Q_OBSTACLE_CONTACTS: DSIM_OBST_SHARDS shards behind the drone watch's)
+  unsigned long long* contacts_out;
+};
+
+// Squared distance from q to one triangle record (Ericson, Real-Time Collision Detection 5.1.5, without branches: every lane of a
+// wave meets another region).  The vertex and edge regions give barycentric (v, w) of the closest point and the distance to it;
+// in the face region the distance is |n . ap| with the record's unit normal, which does not lose digits in the quotient
+// vb / (va + vb + vc) of a thin triangle.  A point that fp32 rounding puts on the wrong side of a region border gets the
+// neighbouring region's formula, which agrees with its own to second order in the distance from the border.
+__device__ __forceinline__ float tri_dist2(const float4 r0, const float4 r1, const float4 r2, const float4 r3, float qx, float qy,
+                                           float qz) {
+  const float ax = r0.x, ay = r0.y, az = r0.z, abx = r0.w, aby = r1.x, abz = r1.y, acx = r1.z, acy = r1.w, acz = r2.x;
+  const float nx = r2.y, ny = r2.z, nz = r2.w, e00 = r3.x, e01 = r3.y, e11 = r3.z;
+  const float px = qx - ax, py = qy - ay, pz = qz - az;
+  const float d1 = abx * px + aby * py + abz * pz, d2 = acx * px + acy * py + acz * pz;
+  const float d3 = d1 - e00, d4 = d2 - e01, d5 = d1 - e01, d6 = d2 - e11;
+  const float vc = d1 * d4 - d3 * d2, vb = d5 * d2 - d1 * d6, va = d3 * d6 - d5 * d4;
+  const float d43 = d4 - d3, d56 = d5 - d6;
+  const bool rA = d1 <= 0.0f && d2 <= 0.0f;
+  const bool rB = d3 >= 0.0f && d4 <= d3;
+  const bool rAB = vc <= 0.0f && d1 >= 0.0f && d3 <= 0.0f;
+  const bool rC = d6 >= 0.0f && d5 <= d6;
+  const bool rAC = vb <= 0.0f && d2 >= 0.0f && d6 <= 0.0f;
+  const bool rBC = va <= 0.0f && d43 >= 0.0f && d56 >= 0.0f;
+  // in the order of the book: the first region that holds decides
+  float num = 0.0f, den = 1.0f;        // the one quotient: AB d1 / (d1 - d3), AC d2 / (d2 - d6), BC (d4 - d3) / ((d4 - d3) + (d5 - d6))
+  int mode = 6;                        // 0 A, 1 B, 2 AB, 3 C, 4 AC, 5 BC, 6 face
+  if (rBC) { mode = 5; num = d43; den = d43 + d56; }
+  if (rAC) { mode = 4; num = d2; den = d2 - d6; }
+  if (rC) mode = 3;
+  if (rAB) { mode = 2; num = d1; den = d1 - d3; }
+  if (rB) mode = 1;
+  if (rA) mode = 0;
+  const float t = den > 0.0f ? num * DSIM_RCP(den) : 0.0f;
+  const float v = mode == 1 ? 1.0f : (mode == 2 ? t : (mode == 5 ? 1.0f - t : 0.0f));
+  const float w = mode == 3 ? 1.0f : (mode == 4 || mode == 5 ? t : 0.0f);
+  const float ex = px - v * abx - w * acx, ey = py - v * aby - w * acy, ez = pz - v * abz - w * acz;
+  const float h = nx * px + ny * py + nz * pz;
+  return mode == 6 ? h * h : ex * ex + ey * ey + ez * ez;
+}
+
+// One drone per lane, tiles of 256 drones grid-stride.  A tile none of whose drones lies in the grown box reads its positions
+// (and offsets) and writes (margin, -1); of a tile that has some, the waves that have none do the same.  The others look up
+// their cell and walk its list: the records come from LDS when the whole set fits (staged by the workgroup before its first
+// tile that needs them), else through L2 — the set is read-only and small next to the fleet.
+template <bool LDS>
+__global__ __launch_bounds__(256) void k_obstacle_clearance(ObsK a) {
+  extern __shared__ float4 s_rec[];
+  bool staged = false;
+  for (long long tile = blockIdx.x; tile < a.tiles; tile += gridDim.x) {
+    const long long i = tile * 256 + threadIdx.x;
+    const bool live = i < a.n;
+    float qx = 0.0f, qy = 0.0f, qz = 0.0f, R = 0.0f;
+    if (live) {
+      const long long o = kv_off(a.st, i);
+      qx = a.st.base[o]; qy = a.st.base[o + a.st.field_stride]; qz = a.st.base[o + 2 * a.st.field_stride];
+      if (a.offset) { qx -= a.offset[i]; qy -= a.offset[a.n_pad + i]; qz -= a.offset[2 * a.n_pad + i]; }
+      R = a.types[a.type_id ? min((int)a.type_id[i], a.n_types - 1) : 0].coll_sphere;
+    }
+    // (a NaN position fails every comparison: not in the box, clearance = margin)
+    const bool inbox = live && R > 0.0f && qx >= a.lox && qx <= a.hix && qy >= a.loy && qy <= a.hiy && qz >= a.loz && qz <= a.hiz;
+    if (LDS) {
+      if (!staged && __syncthreads_or(inbox ? 1 : 0)) {
+        for (int k = threadIdx.x; k < 4 * a.n_tri; k += 256) s_rec[k] = a.rec[k];
+        __syncthreads();
+        staged = true;
+      }
+    }
+    float best = INFINITY;
+    int body = -1;
+    if (inbox) {                       // (a wave with no such lane skips the block: the per-wave reject)
+      const int cx = min(max((int)floorf((qx - a.ox) * a.inv_cell), 0), a.nx - 1);
+      const int cy = min(max((int)floorf((qy - a.oy) * a.inv_cell), 0), a.ny - 1);
+      const int cz = min(max((int)floorf((qz - a.oz) * a.inv_cell), 0), a.nz - 1);
+      const int c = (cz * a.ny + cy) * a.nx + cx;
+      const int end = a.cell_start[c + 1];
+      for (int k = a.cell_start[c]; k < end; ++k) {
+        const int t = a.cell_tri[k];
+        const float4* r = (LDS ? s_rec : a.rec) + 4 * t;
+        const float4 r0 = r[0], r1 = r[1], r2 = r[2], r3 = r[3];
+        const float d2 = tri_dist2(r0, r1, r2, r3, qx, qy, qz);
+        const bool better = d2 < best;
+        best = better ? d2 : best;
+        body = better ? __float_as_int(r3.w) : body;
+      }
+    }
+    const float c_i = DSIM_SQRT(best) - R;
+    const bool in = inbox && c_i < a.margin;
+    if (live) {
+      a.clearance[i] = in ? c_i : a.margin;
+      if (a.nearest) a.nearest[i] = in ? body : -1;
+    }
+    const unsigned long long hit = __ballot(in && c_i < 0.0f);
+    if (hit != 0ULL && (threadIdx.x & 63u) == 0u) {
+      const unsigned long long cnt = (unsigned long long)__popcll(hit);
+      atomicAdd(&a.counters[8 + DSIM_GROUND_SHARDS + DSIM_DRONE_SHARDS + (tile & (DSIM_OBST_SHARDS - 1))], cnt);
+      if (a.contacts_out) atomicAdd(a.contacts_out, cnt);
+    }
+  }
+}
+
+extern "C" {
+
+int dsim_obstacle_grid_plan(const float* tri, int64_t n_tri, float reach, dsim_obstacle_grid* out) {
+  return dsim_obs::plan(tri, n_tri, reach, out);
+}
+
+int dsim_obstacle_grid_build(const float* tri, int64_t n_tri, const dsim_obstacle_grid* g, int32_t* cell_start, int32_t* cell_tri) {
+  return dsim_obs::build(tri, n_tri, g, cell_start, cell_tri);
+}
+
+int dsim_obstacles_create(dsim_ctx* ctx, const float* tri_host, const int32_t* body_host, int64_t n_tri, float reach,
+                          dsim_obstacles** out) {
+  if (!ctx || !out) return DSIM_E_ARG;
+  dsim_obstacle_grid g;
+  int rc = dsim_obs::plan(tri_host, n_tri, reach, &g);
+  if (rc) return rc;
+  if (body_host) for (int64_t t = 0; t < n_tri; ++t) if (body_host[t] < 0) return DSIM_E_ARG;
+  const int64_t cells = (int64_t)g.nx * g.ny * g.nz;
+  std::vector<int32_t> start, list;
+  std::vector<float> rec;
+  try {
+    start.resize(cells + 1); list.resize(g.list_len > 0 ? g.list_len : 1); rec.resize(DSIM_OBS_REC_FLOATS * n_tri);
+  } catch (const std::bad_alloc&) { return (int)hipErrorOutOfMemory; }
+  rc = dsim_obs::build(tri_host, n_tri, &g, start.data(), list.data());
+  if (rc) return rc;
+  dsim_obs::records(tri_host, body_host, n_tri, rec.data());
+  dsim_obstacles* s = new (std::nothrow) dsim_obstacles();
+  if (!s) return (int)hipErrorOutOfMemory;
+  s->rec = nullptr; s->cell_start = nullptr; s->cell_tri = nullptr; s->n_tri = (int)n_tri; s->grid = g;
+  hipError_t e = hipSetDevice(ctx->device);           // (as dsim_dev_alloc: the set lives where the ctx's streams run)
+  if (e == hipSuccess) e = hipMalloc((void**)&s->rec, rec.size() * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc((void**)&s->cell_start, start.size() * sizeof(int32_t));
+  if (e == hipSuccess) e = hipMalloc((void**)&s->cell_tri, list.size() * sizeof(int32_t));
+  if (e == hipSuccess) e = hipMemcpy(s->rec, rec.data(), rec.size() * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(s->cell_start, start.data(), start.size() * sizeof(int32_t), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(s->cell_tri, list.data(), list.size() * sizeof(int32_t), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e != hipSuccess) { (void)dsim_obstacles_destroy(ctx, s); return (int)e; }
+  *out = s;
+  return DSIM_OK;
+}
+
+int dsim_obstacles_destroy(dsim_ctx* ctx, dsim_obstacles* set) {
+  (void)ctx;                                          // (may be NULL: a set may outlive the ctx it was made through)
+  if (!set) return DSIM_OK;
+  hipError_t e = hipSuccess, f;                       // (hipFree waits for the work that may still read the set)
+  if (set->rec && (f = hipFree(set->rec)) != hipSuccess) e = f;
+  if (set->cell_start && (f = hipFree(set->cell_start)) != hipSuccess) e = f;
+  if (set->cell_tri && (f = hipFree(set->cell_tri)) != hipSuccess) e = f;
+  delete set;
+  return (int)e;
+}
+
+int dsim_obstacle_clearance(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, const dsim_obstacles* set,
+                            const float* offset, const uint8_t* type_id, float margin,
+                            float* clearance_out, int32_t* nearest_out, uint64_t* contacts_out) {
+  if (!ctx || !set || !clearance_out || !(margin > 0.0f) || n <= 0 || n > state.n_pad) return DSIM_E_ARG;
+  if (ctx->n_types > 1 && !type_id) return DSIM_E_ARG;
+  float r_max = 0.0f;
+  for (int t = 0; t < ctx->n_types; ++t) r_max = fmaxf(r_max, (float)ctx->h_types[t].collision_sphere);
+  if ((double)r_max + (double)margin > (double)set->grid.reach) return DSIM_E_ARG;
+  ObsK a;
+  const int rc = make_kview(state, 3, &a.st);
+  if (rc) return rc;
+  const dsim_obstacle_grid& g = set->grid;
+  a.n = n; a.n_pad = state.n_pad; a.tiles = (n + 255) / 256;
+  a.offset = offset; a.type_id = type_id; a.types = ctx->d_types; a.n_types = ctx->n_types;
+  a.rec = set->rec; a.cell_start = set->cell_start; a.cell_tri = set->cell_tri; a.n_tri = set->n_tri;
+  a.ox = g.origin[0]; a.oy = g.origin[1]; a.oz = g.origin[2]; a.inv_cell = 1.0f / g.cell;
+  a.nx = g.nx; a.ny = g.ny; a.nz = g.nz;
+  a.lox = g.lo[0]; a.loy = g.lo[1]; a.loz = g.lo[2]; a.hix = g.hi[0]; a.hiy = g.hi[1]; a.hiz = g.hi[2];
+  a.margin = margin; a.clearance = clearance_out; a.nearest = nearest_out;
+  a.counters = ctx->d_counters; a.contacts_out = (unsigned long long*)contacts_out;
+  const unsigned blocks = (unsigned)(a.tiles < OBS_MAX_BLOCKS ? a.tiles : OBS_MAX_BLOCKS);
+  const hipStream_t st_ = (hipStream_t)stream;
+  if (set->n_tri <= OBS_LDS_TRI)
+    hipLaunchKernelGGL((k_obstacle_clearance<true>), dim3(blocks), dim3(256), (size_t)set->n_tri * 64, st_, a);
+  else
+    hipLaunchKernelGGL((k_obstacle_clearance<false>), dim3(blocks), dim3(256), 0, st_, a);
+  return (int)hipGetLastError();
+}
+
+}  // extern "C"

@@ -40,7 +40,7 @@ class _AdaptorAviary(CtrlAviary):
             self._use_last_action = True
             self.step_counter += self.AGGR_PHY_STEPS
             self._env_steps += 1
-            self._watch_drones()
+            self._watch_after_step()
             return plan.out, self._computeReward(), self._computeDone(), plan.info
         args = self.step_args(self.AGGR_PHY_STEPS * self.TIMESTEP)
         # A homogeneous fleet in whole tiles steps in ONE launch that takes the action as the caller holds it ([N, 4] rows
@@ -66,7 +66,7 @@ class _AdaptorAviary(CtrlAviary):
         self._use_last_action = True
         self.step_counter += self.AGGR_PHY_STEPS
         self._env_steps += 1
-        self._watch_drones()
+        self._watch_after_step()
         out = self._computeObs(obs)
         self._step_plan = None
         if rows_in and out is obs:

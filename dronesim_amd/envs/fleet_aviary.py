@@ -79,6 +79,7 @@ class CtrlAviary(PlacedFleetArrays, FleetObservation):
     _mem_hint = False             # DSIM_OPT_MEM_DERIVED is offered (set by __init__)
     _mem_handed_out = True        # ... but not to the next fused launch: the block has been handed out since the last one
     _drone_watch = False          # the drone-drone contact watch behind every step (set by __init__)
+    _obst = None                  # the static-obstacle watch's device set (set by __init__)
 
     @staticmethod
     def _mem_hint_wanted(mem_hint: bool) -> bool:
@@ -123,6 +124,9 @@ class CtrlAviary(PlacedFleetArrays, FleetObservation):
         mem_hint: bool = True,
         drone_watch: bool = False,
         drone_watch_margin: float = 1.0,
+        obstacle_watch=None,
+        obstacle_margin: float = 1.0,
+        obstacle_offsets=None,
     ):
         if gui or record or obstacles:
             raise NotImplementedError("gui/record/obstacles are rendering features outside the hot path")
@@ -138,6 +142,13 @@ class CtrlAviary(PlacedFleetArrays, FleetObservation):
         self.last_clearance = None
         self._clearance = None    # grid for drone_clearance(), built on first use
         self._clr_on_demand = None    # int64 [1]: pairs the on-demand queries counted (not Env.steps: drone_contacts() leaves them out)
+        # The reference's Bullet world also holds static bodies (p.loadURDF of a gate); here they act on nothing.
+        # obstacle_watch=ObstacleSet: every step / step_fused / adaptor step is followed, on the env's stream, by one
+        # dsim_obstacle_clearance on the state it left (once per LAUNCH: a step_fused with n_steps > 1 is sampled once, at its end);
+        # obstacle_contacts() reports the drone x Env.step count, last_obstacle_clearance the tensors of the last step.
+        # obstacle_offsets [N, 3] (the caller's numbering): the set lies in the frame of each drone's task, p_i - offset_i.
+        # Set up at the end of __init__ (_obstacle_setup), when the context and the storage order exist.
+        self._obst_set, self._obst_margin, self._obst = obstacle_watch, float(obstacle_margin), None
         # the add-on terms of the PYB_* modes (dead code in the reference fork, intended formulas); Physics.DYN: the
         # reference's own explicit model, BaseAviary._dynamics (BaseAviary.py:1767-1828; DSIM_OPT_DYN)
         self._phys_options = {Physics.PYB: 0, Physics.PYB_DW: 0, Physics.PYB_GND: nat.OPT_GROUND,
@@ -349,6 +360,7 @@ class CtrlAviary(PlacedFleetArrays, FleetObservation):
         # what the ctx owns for this fleet size is allocated now, not inside the first step
         nat.check(self.ctx.lib.dsim_reserve(self.ctx.handle, self.ctx.stream_ptr(), self.state.n_pad))
         self._housekeeping()
+        self._obstacle_setup(obstacle_offsets)
 
     # ------------------------------------------------------------------ helpers
     def _soa3(self, a: np.ndarray) -> torch.Tensor:
@@ -484,7 +496,7 @@ class CtrlAviary(PlacedFleetArrays, FleetObservation):
             self._use_last_action = True
             self.step_counter += self.AGGR_PHY_STEPS
             self._env_steps += 1
-            self._watch_drones()
+            self._watch_after_step()
             return plan.out, self._computeReward(), self._computeDone(), plan.info
         # The neighbour-downwash term is evaluated per PHYSICS SUB-STEP, as the reference loops it (BaseAviary.py:510-536:
         # with AGGR_PHY_STEPS > 1 the positions are refreshed and _downwash applied inside the sub-step loop): one
@@ -520,7 +532,7 @@ class CtrlAviary(PlacedFleetArrays, FleetObservation):
         self._use_last_action = True
         self.step_counter += self.AGGR_PHY_STEPS
         self._env_steps += 1
-        self._watch_drones()
+        self._watch_after_step()
         out = self._computeObs(obs if self._caller_io else self._rows_to_caller(obs))
         self._step_plan = None
         if (passes == 1 and self._downwash is None and out is obs and torch.is_tensor(action) and action.is_cuda
@@ -578,7 +590,7 @@ class CtrlAviary(PlacedFleetArrays, FleetObservation):
                                              plan.targets_view, plan.args_ref))
             self.step_counter += self.AGGR_PHY_STEPS * n_steps
             self._env_steps += n_steps
-            self._watch_drones()
+            self._watch_after_step()
             return
         pd = self._fused_plan_dw
         if (action is None and pd is not None and self._downwash is not None and not self._dw_substepped()
@@ -593,7 +605,7 @@ class CtrlAviary(PlacedFleetArrays, FleetObservation):
                                              pd.targets_view, pd.args_ref))
             self.step_counter += self.AGGR_PHY_STEPS
             self._env_steps += 1
-            self._watch_drones()
+            self._watch_after_step()
             return
         wp = isinstance(targets, WaypointTargets)
         if self._dw_substepped():
@@ -660,7 +672,7 @@ class CtrlAviary(PlacedFleetArrays, FleetObservation):
                 nxt.options |= nat.OPT_MEM_DERIVED       # (taken out for the one launch behind a host access: see the replay)
             if not self._chained_enabled or chain:
                 self._fused_plan = _FusedPlan(key, nxt, sview, tview, ctypes.byref(nxt), targets, self._targets_ptrs(targets))
-        self._watch_drones()       # (once per call: with n_steps > 1 the states in between never leave the registers)
+        self._watch_after_step()       # (once per call: with n_steps > 1 the states in between never leave the registers)
 
     def capture_fused(self, targets, steps: int, control_timestep: Optional[float] = None):
         """Captures ``steps`` consecutive :meth:`step_fused` launches into ONE hipGraph and returns a
@@ -672,7 +684,8 @@ class CtrlAviary(PlacedFleetArrays, FleetObservation):
         composition, plain or waypoint targets.  With the neighbour-downwash term (single rank): every captured step is
         query -> step (which fills the next query's grid) -> fallback, and the grid's box is the one measured at capture
         time — drones that leave it are clamped to its border cells, which costs search efficiency,
-        never exactness (``Downwash._grid_box``); capture again after the fleet has moved far."""
+        never exactness (``Downwash._grid_box``); capture again after the fleet has moved far.  With ``obstacle_watch`` every
+        captured step is followed by its query, as in eager mode: nothing of it runs on the host."""
         if self._drone_watch:
             raise NotImplementedError("graph capture with drone_watch: the watch re-measures its grid's box on the host from "
                                       "time to time, which a captured sequence cannot")
@@ -692,6 +705,8 @@ class CtrlAviary(PlacedFleetArrays, FleetObservation):
             if dw.keep_lists > 1:
                 dw.keep_lists = 0
                 dw.invalidate_prebin()
+        if self._obst is not None:
+            self.obstacle_clearance()     # (eager, not an Env.step: the watch's kernel is loaded before the capture starts)
         # nothing may allocate under capture: the fallback queue of hexa fleets is reserved up front
         nat.check(self.ctx.lib.dsim_reserve(self.ctx.handle, self.ctx.stream_ptr(), self.state.n_pad))
         self._graph_made = True
@@ -715,10 +730,84 @@ class CtrlAviary(PlacedFleetArrays, FleetObservation):
         reference-sized fleets) the product-defined contact model of DSIM_OPT_PLANE acts there instead."""
         return self.ctx.query(nat.QUERY_GROUND_CONTACTS) - self._ground_trial
 
-    def _watch_drones(self) -> None:
-        """drone_watch=True: one dsim_clearance on the state the step just left, on the env's stream."""
+    def _watch_after_step(self) -> None:
+        """The watches behind a step, on the state it just left and on the env's stream: one dsim_clearance with
+        drone_watch=True, one dsim_obstacle_clearance with obstacle_watch (the adaptor envs' steps come through here too)."""
         if self._drone_watch:
             self.last_clearance = self._drone_query(self._drone_watch_margin, None)
+        if self._obst is not None:
+            self._watch_obstacles()
+
+    def _obstacle_setup(self, offsets) -> None:
+        """obstacle_watch: the device set for reach = R_max + margin, the offsets in storage order and the tensors every
+        per-step query writes (fixed addresses: a captured sequence holds them)."""
+        if self._obst_set is None:
+            if offsets is not None:
+                raise ValueError("obstacle_offsets without obstacle_watch")
+            return
+        from .. import obstacles as obs
+        if not isinstance(self._obst_set, obs.ObstacleSet):
+            raise TypeError("obstacle_watch takes an ObstacleSet")
+        if not self._obst_margin > 0.0:
+            raise ValueError("obstacle_margin must be positive")
+        dev, n_pad = self.ctx.device, self.state.n_pad
+        self._obst_off = None
+        if offsets is not None:
+            offsets = np.asarray(offsets, dtype=np.float64)
+            if offsets.shape != (self.NUM_DRONES, 3):
+                raise ValueError(f"obstacle_offsets must be [{self.NUM_DRONES}, 3]")
+            self._obst_off = self._soa3(offsets)
+        self._obst = self._obst_set.to_device(self.ctx, obs.watch_reach(self.ctx.types, self._obst_margin))
+        self._obst_clr = torch.empty((n_pad,), dtype=torch.float32, device=dev)
+        self._obst_near = torch.empty((n_pad,), dtype=torch.int32, device=dev)
+        self._obst_on_demand = torch.zeros((1,), dtype=torch.int64, device=dev)    # what on-demand queries counted
+        self._obst_sampled = False
+
+    def _watch_obstacles(self) -> None:
+        """One dsim_obstacle_clearance on the state the step just left, on the env's stream (also under capture)."""
+        from .. import obstacles as obs
+        obs.query(self.ctx, self.state, self._obst, self._obst_margin, self._obst_clr, self._obst_near, self._obst_off,
+                  self._type_id)
+        self._obst_sampled = True
+
+    @property
+    def last_obstacle_clearance(self):
+        """(clearance [N] float32, nearest body [N] int32) behind the last step of an ``obstacle_watch`` env, in the
+        caller's numbering; None before the first step."""
+        if self._obst is None or not self._obst_sampled:
+            return None
+        return self._obst_to_caller(self._obst_clr, self._obst_near)
+
+    def _obst_to_caller(self, clr, near):
+        clr, near = clr[: self.NUM_DRONES], near[: self.NUM_DRONES]
+        if self.order is not None:
+            clr, near = self.order.to_caller(clr, 0), self.order.to_caller(near, 0)
+        return clr, near
+
+    def obstacle_contacts(self) -> int:
+        """Drones x sampled Env.steps so far whose bounding sphere (DroneType.collision_sphere) overlapped a triangle of the
+        ``obstacle_watch`` set (cumulative over this env's context; synchronises the stream).  The reference's Bullet world
+        makes a vehicle collide with the static bodies loaded into it; here they act on nothing, and a non-zero count means
+        part of the flight lies outside the domain in which trajectories are comparable with the reference.  One-sided:
+        0 certifies that no bounding sphere touched a triangle at the sampled states; an overlapping sphere need not be a
+        touching shape.  A step_fused launch with n_steps > 1 is sampled once, at its end.  On-demand
+        obstacle_clearance() calls are not Env.steps and are left out."""
+        seen = self.ctx.query(nat.QUERY_OBSTACLE_CONTACTS)
+        return seen - (int(self._obst_on_demand.item()) if self._obst is not None else 0)
+
+    def obstacle_clearance(self, margin: Optional[float] = None):
+        """Per-drone clearance of the CURRENT state to the ``obstacle_watch`` set (dsim_obstacle_clearance): (clearance [N]
+        float32, nearest [N] int32) in the caller's numbering — clearance[i] = min(margin, min_t dist(p_i - offset_i,
+        triangle t) - R_i), nearest[i] = the body of the triangle that attains it, -1 when none is closer than ``margin``
+        (default: the env's obstacle_margin, which is also the largest the device set serves).  Not counted as an Env.step."""
+        if self._obst is None:
+            raise ValueError("obstacle_clearance() needs an env made with obstacle_watch=ObstacleSet")
+        from .. import obstacles as obs
+        margin = self._obst_margin if margin is None else float(margin)
+        clr = torch.empty((self.state.n_pad,), dtype=torch.float32, device=self.ctx.device)
+        near = torch.empty((self.state.n_pad,), dtype=torch.int32, device=self.ctx.device)
+        obs.query(self.ctx, self.state, self._obst, margin, clr, near, self._obst_off, self._type_id, self._obst_on_demand)
+        return self._obst_to_caller(clr, near)
 
     def drone_contacts(self) -> int:
         """Pairs of drones x Env.steps so far whose bounding spheres (DroneType.collision_sphere) overlapped behind a step
@@ -731,6 +820,8 @@ class CtrlAviary(PlacedFleetArrays, FleetObservation):
         return seen - (int(self._clr_on_demand.item()) if self._clr_on_demand is not None else 0)
 
     def close(self):
+        if self._obst is not None:
+            self._obst.close()
         self.ctx.close()
 
     def getPyBulletClient(self):

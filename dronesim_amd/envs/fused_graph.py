@@ -56,6 +56,8 @@ class FusedGraph:
                             self._args.ext_force = dw.compute().data_ptr()
                             self._args.bin_next = dw.bin_next_ptr() if i + 1 < steps else None
                         nat.check(lib.dsim_step(h, sp, n, self._sview, self._tview, ctypes.byref(self._args)))
+                        if env._obst is not None:          # the static-obstacle watch: one query behind every step, as in eager mode
+                            env._watch_obstacles()
                 finally:
                     if dw is not None:
                         dw._box_refresh = refresh

@@ -1,0 +1,216 @@
+"""Static obstacles of the world as triangle soups: the input of the static-obstacle watch (dsim_obstacle_clearance).
+
+The reference flies in a Bullet world into which static bodies are loaded (``p.loadURDF`` of a gate:
+examples/fly_INDI_TrajectoryTrack.py:216-221); a body marked ``concave="yes"`` collides against its triangles.  An
+:class:`ObstacleSet` holds such bodies as fp32 triangles, each with the index of the body it belongs to; nothing here needs a
+device until :meth:`ObstacleSet.to_device`.
+"""
+from __future__ import annotations
+
+import ctypes
+import os
+import xml.etree.ElementTree as etxml
+
+import numpy as np
+
+from . import _native as nat
+
+
+def _rot(rpy) -> np.ndarray:
+    """URDF / Bullet fixed-axis roll-pitch-yaw: R = Rz(yaw) Ry(pitch) Rx(roll)."""
+    r, p, y = (float(v) for v in rpy)
+    cr, sr, cp, sp, cy, sy = np.cos(r), np.sin(r), np.cos(p), np.sin(p), np.cos(y), np.sin(y)
+    return np.array([[cy * cp, cy * sp * sr - sy * cr, cy * sp * cr + sy * sr],
+                     [sy * cp, sy * sp * sr + cy * cr, sy * sp * cr - cy * sr],
+                     [-sp, cp * sr, cp * cr]])
+
+
+def _vec(text, n=3) -> np.ndarray:
+    v = np.array([float(s) for s in str(text).split()], dtype=np.float64)
+    if v.size != n:
+        raise ValueError(f"expected {n} numbers, got {text!r}")
+    return v
+
+
+def read_obj(path: str):
+    """The ``v`` and ``f`` lines of a Wavefront file: (vertices [V, 3] float64, faces [F, 3] int64, 0-based).  ``f`` entries
+    of the forms i, i/j, i//k and i/j/k; negative indices count from the end; polygons are fanned from their first vertex."""
+    verts, faces = [], []
+    with open(path) as fh:
+        for ln in fh:
+            tok = ln.split()
+            if not tok:
+                continue
+            if tok[0] == "v":
+                verts.append([float(x) for x in tok[1:4]])
+            elif tok[0] == "f":
+                idx = [int(t.split("/")[0]) for t in tok[1:]]
+                idx = [i - 1 if i > 0 else len(verts) + i for i in idx]
+                if len(idx) < 3:
+                    raise ValueError(f"{path}: face with {len(idx)} vertices")
+                faces.extend([idx[0], idx[k], idx[k + 1]] for k in range(1, len(idx) - 1))
+    v, f = np.array(verts, dtype=np.float64).reshape(-1, 3), np.array(faces, dtype=np.int64).reshape(-1, 3)
+    if f.size and (f.min() < 0 or f.max() >= len(v)):
+        raise ValueError(f"{path}: face index out of range")
+    return v, f
+
+
+_BOX_FACES = np.array([[0, 2, 1], [1, 2, 3], [4, 5, 6], [5, 7, 6], [0, 1, 4], [1, 5, 4],
+                       [2, 6, 3], [3, 6, 7], [0, 4, 2], [2, 4, 6], [1, 3, 5], [3, 7, 5]], dtype=np.int64)
+
+
+class DeviceObstacles:
+    """The library's device copy of a set (dsim_obstacles_create): records, grid and cell lists for one ``reach``."""
+
+    def __init__(self, ctx, tri: np.ndarray, body: np.ndarray, reach: float):
+        self.ctx, self.reach, self.n_tri = ctx, float(np.float32(reach)), int(tri.shape[0])
+        self._tri = np.ascontiguousarray(tri, dtype=np.float32).reshape(-1, 9)
+        self._body = np.ascontiguousarray(body, dtype=np.int32)
+        self._h = ctypes.c_void_p()
+        nat.check(ctx.lib.dsim_obstacles_create(ctx.handle, self._tri.ctypes.data, self._body.ctypes.data, self.n_tri,
+                                                self.reach, ctypes.byref(self._h)))
+
+    @property
+    def handle(self):
+        return self._h
+
+    def close(self) -> None:
+        if self._h:
+            self.ctx.lib.dsim_obstacles_destroy(None, self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class ObstacleSet:
+    """Triangles [T, 3, 3] (float32, world frame of the drone's task) and the body index [T] of each."""
+
+    def __init__(self, triangles, body):
+        self.triangles = np.ascontiguousarray(np.asarray(triangles, dtype=np.float32).reshape(-1, 3, 3))
+        self.body = np.ascontiguousarray(np.broadcast_to(np.asarray(body, dtype=np.int32), (self.triangles.shape[0],)))
+        if self.triangles.shape[0] == 0:
+            raise ValueError("an obstacle set needs at least one triangle")
+        if not np.isfinite(self.triangles).all():
+            raise ValueError("non-finite vertex coordinate")
+        if self.body.min() < 0:
+            raise ValueError("body indices are >= 0")
+        t = self.triangles.astype(np.float64)
+        area = 0.5 * np.linalg.norm(np.cross(t[:, 1] - t[:, 0], t[:, 2] - t[:, 0]), axis=1)
+        if area.min() < 1e-12:
+            raise ValueError(f"triangle {int(area.argmin())} has area {area.min():.3e} m^2 (below 1e-12)")
+
+    # ---- constructors ---------------------------------------------------------------------------------------------------
+    @classmethod
+    def from_triangles(cls, vertices, faces, body=0) -> "ObstacleSet":
+        v, f = np.asarray(vertices, dtype=np.float64).reshape(-1, 3), np.asarray(faces, dtype=np.int64).reshape(-1, 3)
+        if f.size and (f.min() < 0 or f.max() >= len(v)):
+            raise ValueError("face index out of range")
+        return cls(v[f], body)
+
+    @classmethod
+    def box(cls, centre, size, rpy=(0, 0, 0)) -> "ObstacleSet":
+        """A box of full edge lengths ``size`` about ``centre``: 12 triangles."""
+        h = 0.5 * np.asarray(size, dtype=np.float64).reshape(3)
+        corners = np.array([[sx, sy, sz] for sz in (-1, 1) for sy in (-1, 1) for sx in (-1, 1)], dtype=np.float64) * h
+        v = corners @ _rot(rpy).T + np.asarray(centre, dtype=np.float64)
+        return cls.from_triangles(v, _BOX_FACES)
+
+    @classmethod
+    def from_obj(cls, path, scale=(1, 1, 1), position=(0, 0, 0), rpy=(0, 0, 0)) -> "ObstacleSet":
+        v, f = read_obj(path)
+        v = (v * np.asarray(scale, dtype=np.float64)) @ _rot(rpy).T + np.asarray(position, dtype=np.float64)
+        return cls.from_triangles(v, f)
+
+    @classmethod
+    def from_urdf(cls, path, position=(0, 0, 0), rpy=(0, 0, 0)) -> "ObstacleSet":
+        """Every ``<collision>`` of every link of a static body, placed at ``position`` / ``rpy`` (what p.loadURDF takes): one
+        body.  A ``<mesh>`` only when its link or its collision says ``concave="yes"`` — without the flag Bullet collides
+        against the mesh's convex hull, which the triangles are not; ``<box>``; any other shape is a ValueError.  So is a file
+        with a ``<joint>`` or more than one ``<link>``: joint origins are not composed, and the links would be misplaced."""
+        root = etxml.parse(path).getroot()
+        n_links, n_joints = len(list(root.iter("link"))), len(list(root.iter("joint")))
+        if n_links != 1 or n_joints:
+            raise ValueError(f"{path}: {n_links} links and {n_joints} joints: only a static body of one link is supported")
+        base_r, base_t = _rot(rpy), np.asarray(position, dtype=np.float64)
+        tris = []
+        for link in root.iter("link"):
+            for col in link.findall("collision"):
+                org = col.find("origin")
+                o_t = _vec(org.attrib.get("xyz", "0 0 0")) if org is not None else np.zeros(3)
+                o_r = _rot(_vec(org.attrib.get("rpy", "0 0 0"))) if org is not None else np.eye(3)
+                geo = col.find("geometry")
+                shape = geo[0] if geo is not None and len(geo) else None
+                if shape is None:
+                    raise ValueError(f"{path}: <collision> of link {link.attrib.get('name')!r} has no geometry")
+                if shape.tag == "mesh":
+                    if "yes" not in (link.attrib.get("concave", "no"), col.attrib.get("concave", "no")):
+                        raise ValueError(f"{path}: the <mesh> of link {link.attrib.get('name')!r} is not concave=\"yes\": Bullet "
+                                         "would collide against its convex hull, which its triangles are not")
+                    v, f = read_obj(os.path.join(os.path.dirname(os.path.abspath(path)), shape.attrib["filename"]))
+                    local = (v * _vec(shape.attrib.get("scale", "1 1 1")))[f]
+                elif shape.tag == "box":
+                    local = cls.box((0, 0, 0), _vec(shape.attrib["size"])).triangles.astype(np.float64)
+                else:
+                    raise ValueError(f"{path}: collision shape <{shape.tag}> is not supported (a concave <mesh> or a <box>)")
+                tris.append((local @ o_r.T + o_t) @ base_r.T + base_t)
+        if not tris:
+            raise ValueError(f"{path}: no <collision>")
+        return cls(np.concatenate(tris), 0)
+
+    # ---- the set ----------------------------------------------------------------------------------------------------------
+    def __add__(self, other: "ObstacleSet") -> "ObstacleSet":
+        """Both sets' triangles; the bodies of ``other`` are numbered behind this set's."""
+        if not isinstance(other, ObstacleSet):
+            return NotImplemented
+        return ObstacleSet(np.concatenate([self.triangles, other.triangles]),
+                           np.concatenate([self.body, other.body + self.n_bodies]))
+
+    @property
+    def n_tri(self) -> int:
+        return int(self.triangles.shape[0])
+
+    @property
+    def n_bodies(self) -> int:
+        return int(self.body.max()) + 1
+
+    @property
+    def aabb(self):
+        """(lo [3], hi [3]) of the vertices, float32."""
+        v = self.triangles.reshape(-1, 3)
+        return v.min(0), v.max(0)
+
+    def grid(self, reach: float):
+        """The host-side grid of this set for ``reach`` (dsim_obstacle_grid_plan / _build; needs no device):
+        (nat.ObstacleGrid, cell_start int32 [cells + 1], cell_tri int32 [list_len])."""
+        lib = nat.load()
+        tri = np.ascontiguousarray(self.triangles.reshape(-1, 9))
+        g = nat.ObstacleGrid()
+        nat.check(lib.dsim_obstacle_grid_plan(tri.ctypes.data, self.n_tri, float(reach), ctypes.byref(g)))
+        start = np.zeros(g.nx * g.ny * g.nz + 1, dtype=np.int32)
+        lst = np.zeros(max(int(g.list_len), 1), dtype=np.int32)
+        nat.check(lib.dsim_obstacle_grid_build(tri.ctypes.data, self.n_tri, ctypes.byref(g), start.ctypes.data, lst.ctypes.data))
+        return g, start, lst[: int(g.list_len)]
+
+    def to_device(self, ctx, reach: float) -> DeviceObstacles:
+        """The library's device set for queries with R_max + margin <= ``reach`` (allocates, uploads, synchronises: not
+        inside a graph capture)."""
+        return DeviceObstacles(ctx, self.triangles, self.body, reach)
+
+
+def watch_reach(types, margin: float) -> float:
+    """The least ``reach`` a query of ``margin`` over these drone types accepts: fp32(R_max) + fp32(margin), a thousandth more so
+    that no rounding of the sum undercuts it."""
+    r_max = max(float(np.float32(t.collision_sphere)) for t in types)
+    return float(np.float32((r_max + float(np.float32(margin))) * (1.0 + 2.0 ** -10)))
+
+
+def query(ctx, state, dev: DeviceObstacles, margin: float, clearance, nearest, offset=None, type_id=None, contacts_out=None) -> None:
+    """dsim_obstacle_clearance on the current stream into the given tensors ([n_pad] float32 / int32)."""
+    nat.check(ctx.lib.dsim_obstacle_clearance(
+        ctx.handle, ctx.stream_ptr(), state.n, state.view(), dev.handle, offset.data_ptr() if offset is not None else None,
+        type_id.data_ptr() if type_id is not None else None, float(margin), clearance.data_ptr(),
+        nearest.data_ptr() if nearest is not None else None, contacts_out.data_ptr() if contacts_out is not None else None))

@@ -39,7 +39,11 @@ extern "C" {
 
 #define DSIM_ABI_VERSION 11
 #define DSIM_ABI_MINOR 1   /* 1: dsim_type_params ends with collision_sphere (callers built against minor 0 must be rebuilt: the
-                              type table's stride grew); dsim_clearance, DSIM_Q_DRONE_CONTACTS */
+                              type table's stride grew); dsim_clearance, DSIM_Q_DRONE_CONTACTS.
+                              Added since, without a new number because a caller built against 11.1 never sees them (new functions,
+                              a new struct, a new enum value; nothing that existed changed size, layout or meaning): the
+                              static-obstacle watch, dsim_obstacle_grid_plan / _build, dsim_obstacles_create / _destroy,
+                              dsim_obstacle_clearance, dsim_obstacle_grid, DSIM_Q_OBSTACLE_CONTACTS */
 #define DSIM_MAX_ACT 6     /* actuators per vehicle (quad 4, morphing hexa 6) */
 #define DSIM_MAX_TYPES 8
 
@@ -659,6 +663,70 @@ int dsim_clearance(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, cons
                    const float* radius_all, float margin,
                    float* clearance_out, int32_t* nearest_out, uint64_t* pairs_out);
 
+/* Static-obstacle watch: per-drone clearance to world triangle meshes.  The third thing a Bullet world does to a vehicle besides
+ * the ground plane and the other vehicles is collide it with the static bodies loaded into the world (p.loadURDF of a gate, a
+ * wall; a body marked concave="yes" collides against its triangles).  This library models no such contact and reports where it
+ * would have mattered, in the drone watch's terms:
+ *   - The watch is one-sided.  A count of 0 certifies that, at the sampled states, no vehicle's bounding sphere
+ *     (dsim_type_params.collision_sphere) touched a triangle, and hence that Bullet's narrow phase had nothing to report at
+ *     those states.
+ *   - A counted drone has an overlapping SPHERE, which its shapes need not.
+ *   - The watch samples the end of an Env.step, as the other two watches do.
+ *   - A meshed solid is its surface.  A sphere wholly inside a closed body is not seen, but it crossed the surface on the way in.
+ *
+ * An obstacle set is a soup of triangles in fp32 (tri [n_tri][9]: vertices a, b, c), each carrying the index of the BODY it belongs
+ * to; it is static for its lifetime.  Around it lies a uniform 3-D grid over the soup's bounding box grown by `reach`; the list of
+ * a cell holds every triangle whose distance to any point of that cell can be below `reach` (and may hold more: over-inclusion is
+ * allowed, omission is not).  The cell of a point q is (clamp(floor((q - origin) / cell), 0, n - 1)) per axis, index
+ * (cz * ny + cy) * nx + cx; the lists carry a slack of a hundredth of a cell, so a point within fp32 rounding of a cell face may be
+ * looked up in either cell.  A point outside the grown box [lo, hi] has no triangle within `reach`.
+ *
+ * The two grid functions are host-only: no ctx, no device, callable on a machine without a GPU.
+ *   dsim_obstacle_grid_plan   chooses the grid (the cell edge starts at reach / 2 and is doubled until there are at most 2^18 cells,
+ *                             4096 along an axis, and 2^26 list entries) and counts the lists: *out is complete, list_len included.
+ *   dsim_obstacle_grid_build  fills cell_start [cells + 1] (cells = nx ny nz; cell_start[cells] = list_len) and cell_tri [list_len]
+ *                             (triangle indices, ascending inside a cell) for the grid `g` the plan returned for the same soup.
+ * DSIM_E_ARG, with nothing written: n_tri < 1 or > 65536, a null pointer, reach <= 0 or not finite, a non-finite coordinate, a
+ * triangle with area below 1e-12 m^2, a grid that needs more than 2^18 cells at any list budget, or (build) a `g` that is not the
+ * plan of this soup. */
+typedef struct dsim_obstacle_grid {
+  float   origin[3];      /* corner of cell (0, 0, 0) = lo                                                      */
+  float   cell;           /* cell edge [m]                                                                      */
+  int32_t nx, ny, nz;
+  float   reach;          /* what the lists were made for                                                       */
+  int64_t list_len;       /* entries of cell_tri                                                                */
+  float   lo[3], hi[3];   /* the soup's bounding box grown by reach                                             */
+} dsim_obstacle_grid;
+int dsim_obstacle_grid_plan(const float* tri, int64_t n_tri, float reach, dsim_obstacle_grid* out);
+int dsim_obstacle_grid_build(const float* tri, int64_t n_tri, const dsim_obstacle_grid* g, int32_t* cell_start, int32_t* cell_tri);
+
+/* The device set, owned by the library: dsim_obstacles_create plans and builds the grid on the host, prepares one 64-byte record
+ * per triangle (a, ab, ac, the unit normal, the three dot products of the region test, the body index), allocates, uploads and
+ * SYNCHRONISES.  It must not sit inside a stream capture (like the run table of DSIM_OPT_CALLER_IO, it is made before capture
+ * starts); neither must dsim_obstacles_destroy, which waits for the work that may still read the set.  tri_host [n_tri][9] and
+ * body_host [n_tri] (>= 0; NULL: every triangle is body 0) are host memory, read during the call only.  Errors as the grid plan's. */
+typedef struct dsim_obstacles dsim_obstacles;
+int dsim_obstacles_create(dsim_ctx* ctx, const float* tri_host, const int32_t* body_host, int64_t n_tri, float reach,
+                          dsim_obstacles** out);
+int dsim_obstacles_destroy(dsim_ctx* ctx, dsim_obstacles* set);
+
+/* The query: stream-ordered, allocates nothing, never synchronises (it may be captured).  For drone i of `state`,
+ *     q_i = p_i - offset_i       offset: SoA [3][n_pad] (device) or NULL = 0.  The set lives in the frame of the drone's TASK, which
+ *                                is what dsim_step_args.wp_offset means for waypoint tables: every replica has its own gate.
+ *     R_i = collision_sphere of its type (type_id [n_pad], required with more than one type)
+ *     c_i = min_t dist(q_i, triangle t) - R_i       exact Euclidean point-triangle distance (face, edge and vertex regions)
+ *     clearance_out[i] = min(margin, c_i)                                                                  [n_pad]
+ *     nearest_out[i]   = the BODY index of the triangle that attains the minimum, -1 when c_i >= margin      [n_pad], nullable
+ *                        (not the triangle: a closest point on a shared edge belongs to two triangles)
+ * A type with R = 0 takes no part: its drones get clearance = margin, nearest = -1 and are never counted.  Every drone with
+ * c_i < 0 adds one to the cumulative counter DSIM_Q_OBSTACLE_CONTACTS and, when contacts_out is given, to *contacts_out (a device
+ * counter); one atomic per wave and counter at most.  DSIM_E_ARG, nothing written: a null ctx / set / clearance_out, margin <= 0,
+ * or R_max + margin > reach of the set (R_max over the type table), because a cell list then no longer holds every triangle
+ * that matters.  A wave none of whose drones lies in the grown box reads its positions and nothing else. */
+int dsim_obstacle_clearance(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, const dsim_obstacles* set,
+                            const float* offset, const uint8_t* type_id, float margin,
+                            float* clearance_out, int32_t* nearest_out, uint64_t* contacts_out);
+
 /* The rotor-noise normals the step kernels draw (diagnostics / distribution studies; no counterpart in the reference, whose
  * draws come from numpy's global generator): for drones [0, n) and the physics sub-steps [0, substeps) of Env.step number
  * step_index, out [substeps][2 * n_act][n_pad] (device) receives the UNIT-variance normals — n_act = 4: rows 0 .. 3 the force noise,
@@ -682,9 +750,11 @@ int dsim_noise_draw(dsim_ctx* ctx, void* stream, int64_t n, int64_t n_pad, int32
  *   DSIM_Q_DW_MOVERS      overflow-list entries those calls found, summed: drones that had left the lists' skin (performance
  *                         only — results do not depend on it; / DSIM_Q_DW_REUSES = the mean length every receiver scanned)
  *   DSIM_Q_DRONE_CONTACTS pairs of drones x dsim_clearance calls whose bounding spheres overlapped, where Bullet's world might have
- *                         made the two vehicles collide (see dsim_type_params.collision_sphere; each pair once per call)        */
+ *                         made the two vehicles collide (see dsim_type_params.collision_sphere; each pair once per call)
+ *   DSIM_Q_OBSTACLE_CONTACTS  drones x dsim_obstacle_clearance calls whose bounding sphere overlapped a triangle of the obstacle
+ *                         set, where Bullet's world might have made the vehicle collide with a static body                     */
 enum { DSIM_Q_WLS_FALLBACKS = 0, DSIM_Q_WLS_FAILURES = 1, DSIM_Q_GROUND_CONTACTS = 2, DSIM_Q_HALO_OVERFLOW = 3,
-       DSIM_Q_DW_REUSES = 4, DSIM_Q_DW_MOVERS = 5, DSIM_Q_DRONE_CONTACTS = 6 };
+       DSIM_Q_DW_REUSES = 4, DSIM_Q_DW_MOVERS = 5, DSIM_Q_DRONE_CONTACTS = 6, DSIM_Q_OBSTACLE_CONTACTS = 7 };
 int dsim_query(dsim_ctx* ctx, void* stream, int32_t what, int64_t* value_out);
 
 /* error codes */
