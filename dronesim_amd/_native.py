@@ -23,6 +23,7 @@ EXPORTS = (
     "dsim_downwash_keep_workspace", "dsim_downwash_keep_ok", "dsim_downwash_keep_stats",
     "dsim_clearance", "dsim_clearance_workspace", "dsim_abi_minor",
     "dsim_obstacle_grid_plan", "dsim_obstacle_grid_build", "dsim_obstacles_create", "dsim_obstacles_destroy", "dsim_obstacle_clearance",
+    "dsim_obstacle_ray_grid_plan", "dsim_obstacle_ray_grid_build", "dsim_obstacles_enable_rays", "dsim_depth_image",
 )
 
 ABI_VERSION = 11
@@ -59,6 +60,22 @@ QUERY_WLS_FALLBACKS, QUERY_WLS_FAILURES, QUERY_GROUND_CONTACTS, QUERY_HALO_OVERF
 QUERY_DW_REUSES, QUERY_DW_MOVERS = 4, 5
 QUERY_DRONE_CONTACTS = 6     # pairs of drones x dsim_clearance calls whose bounding spheres overlapped
 QUERY_OBSTACLE_CONTACTS = 7  # drones x dsim_obstacle_clearance calls whose bounding sphere overlapped a triangle of the set
+
+
+CAM_METRIC, CAM_GROUND = 1, 2    # dsim_camera_params.flags
+SEG_GROUND = -2                  # DSIM_SEG_GROUND: the plane z = 0 in a segmentation image
+
+
+class CameraParams(ctypes.Structure):
+    """dsim_camera_params (dsim_depth_image)."""
+    _fields_ = [
+        ("width", ctypes.c_int32),
+        ("height", ctypes.c_int32),
+        ("fov_deg", ctypes.c_float),
+        ("aspect", ctypes.c_float),
+        ("far", ctypes.c_float),
+        ("flags", ctypes.c_uint32),
+    ]
 
 
 class ObstacleGrid(ctypes.Structure):
@@ -231,6 +248,10 @@ def load(path: str = None) -> ctypes.CDLL:
     lib.dsim_obstacles_create.argtypes = [vp, vp, vp, i64, ctypes.c_float, ctypes.POINTER(vp)]
     lib.dsim_obstacles_destroy.argtypes = [vp, vp]
     lib.dsim_obstacle_clearance.argtypes = [vp, vp, i64, View, vp, vp, vp, ctypes.c_float, vp, vp, vp]
+    lib.dsim_obstacle_ray_grid_plan.argtypes = [vp, i64, ctypes.POINTER(ObstacleGrid)]
+    lib.dsim_obstacle_ray_grid_build.argtypes = [vp, i64, ctypes.POINTER(ObstacleGrid), vp, vp]
+    lib.dsim_obstacles_enable_rays.argtypes = [vp, vp]
+    lib.dsim_depth_image.argtypes = [vp, vp, View, vp, ctypes.POINTER(CameraParams), i64, vp, vp, vp, vp, vp]
     if lib.dsim_abi_version() != ABI_VERSION or lib.dsim_abi_minor() != ABI_MINOR:
         raise ImportError(f"libdronesim_amd.so ABI {lib.dsim_abi_version()}.{lib.dsim_abi_minor()} != binding {ABI_VERSION}.{ABI_MINOR}")
     _lib = lib

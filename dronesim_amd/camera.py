@@ -1,0 +1,98 @@
+"""Depth camera: per-drone depth and segmentation images of a static obstacle set (dsim_depth_image).
+
+The reference's envs keep, with ``vision_attributes=True``, an image triple per drone from ``p.getCameraImage``
+(BaseAviary._getDroneImages, BaseAviary.py:794-853).  Depth and segmentation of the static world are geometry: one ray per pixel
+against the set's triangles gives them exactly.  Two deviations from Bullet's renderer: the other drones are not drawn, and there
+is no RGB (shading is not reproducible).  The camera model is in include/dronesim_amd.h.
+"""
+from __future__ import annotations
+
+import ctypes
+
+import numpy as np
+import torch
+
+from . import _native as nat
+from .obstacles import DeviceObstacles, ObstacleSet
+
+
+def camera_reach(types) -> float:
+    """The reach a device set made for the camera alone is given (the watch grid still has to be planned): that of a watch
+    with margin 1 m."""
+    from .obstacles import watch_reach
+    return watch_reach(types, 1.0)
+
+
+class DepthCamera:
+    """``cameras``: the drones that carry a camera, in the CALLER's numbering and in the order of the output images (None:
+    every drone); ``offsets`` [N, 3] (the caller's numbering): the set lies in the frame p_i - offset_i of each drone's task;
+    ``type_id``: uint8 device tensor [n_pad] in storage order, required with several types.  ``obstacle_set``: an
+    :class:`ObstacleSet` (a device set is made for it) or a :class:`DeviceObstacles` to share.  The camera owns its outputs:
+    ``dep`` float32 [n_cam, H, W] (row 0 at the top, as PyBullet returns it; the depth-buffer value, or metres with
+    ``metric=True``) and ``seg`` int32 (body index, -1 nothing, -2 the ground plane)."""
+
+    def __init__(self, ctx, state, obstacle_set, res=(64, 48), fov=60.0, aspect=1.0, far=1000.0, ground=False, metric=False,
+                 cameras=None, offsets=None, type_id=None):
+        w, h = (int(v) for v in res)
+        if not (1 <= w <= 1024 and 1 <= h <= 1024):
+            raise ValueError(f"res must be (width, height) with 1 <= each <= 1024, got {res!r}")
+        if not (0.0 < float(fov) < 180.0):
+            raise ValueError("fov must lie in (0, 180) degrees")
+        if not (float(aspect) > 0.0 and np.isfinite(aspect)):
+            raise ValueError("aspect must be positive")
+        if not (float(far) > 0.0 and np.isfinite(far)):
+            raise ValueError("far must be positive and finite")
+        if any(not float(t.arm) > 0.0 for t in ctx.types):
+            raise ValueError("every drone type needs arm > 0: it is the camera's height above the drone and its near plane")
+        if len(ctx.types) > 1 and type_id is None:
+            raise ValueError("type_id is required with several drone types")
+        self.ctx, self.state = ctx, state
+        self._owns_set = isinstance(obstacle_set, ObstacleSet)
+        if self._owns_set:
+            obstacle_set = obstacle_set.to_device(ctx, camera_reach(ctx.types))
+        if not isinstance(obstacle_set, DeviceObstacles):
+            raise TypeError("obstacle_set takes an ObstacleSet or a DeviceObstacles")
+        self.set = obstacle_set.enable_rays()
+        order = getattr(state, "order", None) or getattr(ctx, "order", None)
+        n, dev = state.n, ctx.device
+        self._index = None
+        if cameras is None:
+            n_cam = n
+            if order is not None:                  # image k belongs to drone k of the caller: its storage slot
+                self._index = torch.from_numpy(order.slot_np.astype(np.int32)).to(dev)
+        else:
+            cams = np.asarray(cameras, dtype=np.int64).ravel()
+            if cams.size < 1 or cams.min() < 0 or cams.max() >= n:
+                raise ValueError(f"cameras must name drones in [0, {n})")
+            n_cam = int(cams.size)
+            self._index = torch.from_numpy((order.slot_np[cams] if order is not None else cams).astype(np.int32)).to(dev)
+        self.n_cam = n_cam
+        self._off = None
+        if offsets is not None:
+            off = np.asarray(offsets, dtype=np.float64)
+            if off.shape != (n, 3):
+                raise ValueError(f"offsets must be [{n}, 3]")
+            if order is not None:
+                off = order.to_storage_np(off)
+            t = torch.zeros((3, state.n_pad), dtype=torch.float32)
+            t[:, :n] = torch.from_numpy(np.ascontiguousarray(off.T)).float()
+            self._off = t.to(dev)
+        self._type_id = type_id
+        self.params = nat.CameraParams(w, h, float(fov), float(aspect), float(far),
+                                       (nat.CAM_GROUND if ground else 0) | (nat.CAM_METRIC if metric else 0))
+        self.dep = torch.empty((n_cam, h, w), dtype=torch.float32, device=dev)
+        self.seg = torch.empty((n_cam, h, w), dtype=torch.int32, device=dev)
+
+    def capture(self, seg: bool = True):
+        """Enqueues one dsim_depth_image on the current stream (it may be captured into a graph) and returns (dep, seg): the
+        camera's own tensors, overwritten by the next capture.  ``seg=False`` leaves the segmentation image unwritten."""
+        nat.check(self.ctx.lib.dsim_depth_image(
+            self.ctx.handle, self.ctx.stream_ptr(), self.state.view(), self.set.handle, ctypes.byref(self.params), self.n_cam,
+            self._index.data_ptr() if self._index is not None else None, self._off.data_ptr() if self._off is not None else None,
+            self._type_id.data_ptr() if self._type_id is not None else None, self.dep.data_ptr(),
+            self.seg.data_ptr() if seg else None))
+        return self.dep, (self.seg if seg else None)
+
+    def close(self) -> None:
+        if self._owns_set:
+            self.set.close()

@@ -274,6 +274,7 @@ static void to_dev(const dsim_type_params& p, DevType* d) {
   d->speed_limit = (float)(p.max_speed_kmh * (1000.0 / 3600.0));
   d->coll_r = (float)p.collision_radius; d->coll_below = (float)p.collision_below;
   d->coll_sphere = (float)p.collision_sphere;
+  d->arm = (float)p.arm;
   d->mu_plane = (float)p.contact_friction;
   for (int k = 0; k < 3; ++k) d->base_off[k] = (float)p.base_offset[k];
   d->watch_below = (float)(p.collision_below + p.base_offset[2]);    // (the offset of the shipped hexa is along body z)

@@ -1,0 +1,279 @@
+// Depth camera (dsim_depth_image): per-drone depth and segmentation images of the static obstacle set, one ray per pixel against
+// the set's RAY grid (dsim_obstacle_grid.h: ray_plan; include/dronesim_amd.h has the camera model).  Compiled as part of
+// dsim_obstacles.hip, which includes this file: it reads the set's private record (struct dsim_obstacles) and shares OBS_LDS_TRI.
+#pragma once
+
+#include <stdlib.h>
+
+#define CAM_TILE 8                 // a wave is an 8 x 8 pixel tile; a workgroup the 2 x 2 tiles of a 16 x 16 pixel block
+
+struct CamK {
+  KView st;
+  long long n_pad;
+  const int* cam_index;            // [n_cam] drone indices in storage order, or null: the camera's own number
+  const float* offset;             // SoA [3][n_pad] or null
+  const uint8_t* type_id;          // or null: type 0
+  const DevType* types;
+  int n_types;
+  const float4* rec;
+  const int* cell_start;
+  const int* cell_tri;
+  int n_tri;
+  float ox, oy, oz, cell, inv_cell;       // the ray grid
+  int nx, ny, nz;
+  float hix, hiy, hiz;                    // its box is [o, hi]
+  int W, H, bx;                           // image size; 16 x 16 blocks per image row
+  unsigned blocks_per_cam;
+  float inv_w, inv_h, th, tha, far;       // 1 / W, 1 / H, tan(fov / 2), ... x aspect
+  unsigned flags;
+  float* depth;                           // [n_cam][H][W]
+  int* seg;                               // same shape, or null
+#ifdef DSIM_CAM_COUNT
+  unsigned long long* tests;              // triangle tests, summed over every ray (a measuring build: tools/bench_camera.py)
+#endif
+};
+
+// One lane per pixel.  The pose and the basis are the same for the whole workgroup: the drone's index comes from blockIdx, its
+// position and quaternion are read through the view with that uniform index, and f, s, u and the eye stay in scalar registers.
+// A lane slab-clips its ray against the grid's box, walks the cells by 3-D DDA (Amanatides & Woo, three named scalars per
+// quantity and selects: an array indexed by the stepping axis would live in scratch), tests the list of every cell with
+// Moller-Trumbore from the records (a, ab, ac; body in r3.w) and stops as soon as its best t is not beyond the cell's exit.
+template <bool LDS, bool SEG>
+__global__ __launch_bounds__(256) void k_depth_image(CamK a) {
+  extern __shared__ float4 s_cam_rec[];
+  const unsigned cam = blockIdx.x / a.blocks_per_cam, blk = blockIdx.x - cam * a.blocks_per_cam;
+  const unsigned wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+  const int by = (int)(blk / (unsigned)a.bx), bxi = (int)(blk - (unsigned)by * (unsigned)a.bx);
+  const int col = bxi * 16 + (int)(wave & 1u) * CAM_TILE + (int)(lane & 7u);
+  const int row = by * 16 + (int)(wave >> 1) * CAM_TILE + (int)(lane >> 3);
+  const bool live = col < a.W && row < a.H;                   // tiles at the right and bottom edge are masked
+  const bool metric = (a.flags & DSIM_CAM_METRIC) != 0u;
+  const float miss = metric ? INFINITY : 1.0f;
+  const size_t out = ((size_t)cam * (size_t)a.H + (size_t)row) * (size_t)a.W + (size_t)col;
+
+  // ---- the camera (uniform) -------------------------------------------------------------------------------------------------
+  const long long i = a.cam_index ? (long long)a.cam_index[cam] : (long long)cam;
+  bool defined = i >= 0 && i < a.n_pad;
+  float ex = 0.0f, ey = 0.0f, ez = 0.0f, fx = 1.0f, fy = 0.0f, fz = 0.0f, sx = 0.0f, sy = 0.0f, near = 1.0f;
+  if (defined) {
+    const long long o = kv_off(a.st, i);
+    const float* p = a.st.base + o;
+    const long long fs = a.st.field_stride;
+    float px = p[0], py = p[fs], pz = p[2 * fs];
+    Q4 q;
+    q.x = p[3 * fs]; q.y = p[4 * fs]; q.z = p[5 * fs]; q.w = p[6 * fs];
+    if (a.offset) { px -= a.offset[i]; py -= a.offset[a.n_pad + i]; pz -= a.offset[2 * a.n_pad + i]; }
+    near = dev_type(a.types, a.type_id ? min((int)a.type_id[i], a.n_types - 1) : 0).arm;
+    const float qq = q.x * q.x + q.y * q.y + q.z * q.z + q.w * q.w;
+    const float s2 = 2.0f / qq;
+    const float xs = q.x * s2, ys = q.y * s2, zs = q.z * s2;
+    const float r0 = 1.0f - (q.y * ys + q.z * zs), r3 = q.x * ys + q.w * zs, r6 = q.x * zs - q.w * ys;   // R(q) (1, 0, 0)
+    fx = 1000.0f * r0; fy = 1000.0f * r3; fz = 1000.0f * r6 - near;                                       // target - eye
+    const float fi = 1.0f / sqrtf(fx * fx + fy * fy + fz * fz);
+    fx *= fi; fy *= fi; fz *= fi;
+    const float ss = fx * fx + fy * fy;                        // |f x up|^2 with up = (0, 0, 1): f x up = (fy, -fx, 0)
+    const float si = 1.0f / sqrtf(ss);
+    sx = fy * si; sy = -fx * si;
+    ex = px; ey = py; ez = pz + near;
+    // (a NaN anywhere fails a comparison here: |x| <= FLT_MAX holds for finite x only)
+    defined = fabsf(ex) <= 3.0e38f && fabsf(ey) <= 3.0e38f && fabsf(ez) <= 3.0e38f && fabsf(fx) <= 2.0f && fabsf(fy) <= 2.0f &&
+              fabsf(fz) <= 2.0f && ss >= 1e-12f && fabsf(sx) <= 2.0f && fabsf(sy) <= 2.0f && near > 0.0f;
+  }
+  if (!defined) {                                              // no defined image: background everywhere (a uniform branch)
+    if (live) {
+      a.depth[out] = miss;
+      if (SEG) a.seg[out] = -1;
+    }
+    return;
+  }
+  const float ux = sy * fz, uy = -(sx * fz), uz = sx * fy - sy * fx;        // u = s x f, s = (sx, sy, 0)
+  if (LDS) {                                                   // the whole set's records, once per workgroup (as the watch does)
+    for (int k = threadIdx.x; k < 4 * a.n_tri; k += 256) s_cam_rec[k] = a.rec[k];
+    __syncthreads();
+  }
+
+  // ---- the ray of this pixel -------------------------------------------------------------------------------------------------
+  const float ca = (2.0f * ((float)col + 0.5f) * a.inv_w - 1.0f) * a.tha;
+  const float cb = (1.0f - 2.0f * ((float)row + 0.5f) * a.inv_h) * a.th;
+  const float dx = fx + ca * sx + cb * ux, dy = fy + ca * sy + cb * uy, dz = fz + cb * uz;
+  float best = INFINITY;
+  int body = -1;
+  if ((a.flags & DSIM_CAM_GROUND) != 0u) {                     // the plane z = 0: analytic, also for rays that miss the box
+    const float tg = -ez / dz;                                 // (dz = 0: +-inf or NaN, which fail the test)
+    if (tg >= near && tg <= a.far) { best = tg; body = DSIM_SEG_GROUND; }
+  }
+  // slab clip against [o, hi]; a zero component gives +-inf (or NaN at a face, which fminf / fmaxf drop)
+  const float ix_ = 1.0f / dx, iy_ = 1.0f / dy, iz_ = 1.0f / dz;
+  const float x0 = (a.ox - ex) * ix_, x1 = (a.hix - ex) * ix_;
+  const float y0 = (a.oy - ey) * iy_, y1 = (a.hiy - ey) * iy_;
+  const float z0 = (a.oz - ez) * iz_, z1 = (a.hiz - ez) * iz_;
+  const float t_in = fmaxf(fmaxf(fminf(x0, x1), fminf(y0, y1)), fmaxf(fminf(z0, z1), near));
+  const float t_out = fminf(fminf(fmaxf(x0, x1), fmaxf(y0, y1)), fminf(fmaxf(z0, z1), fminf(a.far, best)));
+  const bool inside_x = dx != 0.0f || (ex >= a.ox && ex <= a.hix);          // a ray parallel to a slab and outside it misses
+  const bool inside_y = dy != 0.0f || (ey >= a.oy && ey <= a.hiy);
+  const bool inside_z = dz != 0.0f || (ez >= a.oz && ez <= a.hiz);
+#ifdef DSIM_CAM_COUNT
+  unsigned n_tests = 0u;
+#endif
+  if (live && t_in <= t_out && inside_x && inside_y && inside_z) {
+    // the cell of the entry point, clamped; per axis the direction of travel, t at the next face and t per cell
+    const float qx = ex + t_in * dx, qy = ey + t_in * dy, qz = ez + t_in * dz;
+    int cx = min(max((int)floorf((qx - a.ox) * a.inv_cell), 0), a.nx - 1);
+    int cy = min(max((int)floorf((qy - a.oy) * a.inv_cell), 0), a.ny - 1);
+    int cz = min(max((int)floorf((qz - a.oz) * a.inv_cell), 0), a.nz - 1);
+    const int stx = dx > 0.0f ? 1 : -1, sty = dy > 0.0f ? 1 : -1, stz = dz > 0.0f ? 1 : -1;
+    const float dtx = dx != 0.0f ? a.cell * fabsf(ix_) : INFINITY;
+    const float dty = dy != 0.0f ? a.cell * fabsf(iy_) : INFINITY;
+    const float dtz = dz != 0.0f ? a.cell * fabsf(iz_) : INFINITY;
+    float tmx = dx != 0.0f ? (a.ox + (float)(cx + (dx > 0.0f ? 1 : 0)) * a.cell - ex) * ix_ : INFINITY;
+    float tmy = dy != 0.0f ? (a.oy + (float)(cy + (dy > 0.0f ? 1 : 0)) * a.cell - ey) * iy_ : INFINITY;
+    float tmz = dz != 0.0f ? (a.oz + (float)(cz + (dz > 0.0f ? 1 : 0)) * a.cell - ez) * iz_ : INFINITY;
+    const int max_cells = a.nx + a.ny + a.nz;                  // a walk visits fewer: every step moves one cell along one axis
+    for (int it = 0; it < max_cells; ++it) {
+      const int c = (cz * a.ny + cy) * a.nx + cx;
+      const int end = a.cell_start[c + 1];
+      for (int k = a.cell_start[c]; k < end; ++k) {
+        const float4* r = (LDS ? s_cam_rec : a.rec) + 4 * a.cell_tri[k];
+        const float4 r0 = r[0], r1 = r[1];
+        const float acz = r[2].x;
+        const int rb = __float_as_int(r[3].w);
+        const float ax = r0.x, ay = r0.y, az = r0.z, abx = r0.w, aby = r1.x, abz = r1.y, acx = r1.z, acy = r1.w;
+        const float pvx = dy * acz - dz * acy, pvy = dz * acx - dx * acz, pvz = dx * acy - dy * acx;      // d x ac
+        const float det = abx * pvx + aby * pvy + abz * pvz;
+        const float tx = ex - ax, ty = ey - ay, tz = ez - az;
+        const float idet = DSIM_RCP(det);                      // (det = 0, a ray in the triangle's plane: inf, nothing passes)
+        const float u = (tx * pvx + ty * pvy + tz * pvz) * idet;
+        const float qvx = ty * abz - tz * aby, qvy = tz * abx - tx * abz, qvz = tx * aby - ty * abx;      // (e - a) x ab
+        const float v = (dx * qvx + dy * qvy + dz * qvz) * idet;
+        const float t = (acx * qvx + acy * qvy + acz * qvz) * idet;
+        const bool hit = u >= 0.0f && v >= 0.0f && u + v <= 1.0f && t >= near && t <= a.far && t < best;
+        best = hit ? t : best;
+        body = hit ? rb : body;
+#ifdef DSIM_CAM_COUNT
+        ++n_tests;
+#endif
+      }
+      const float t_exit = fminf(tmx, fminf(tmy, tmz));
+      if (best <= t_exit || t_exit >= t_out) break;            // nothing nearer can lie in a later cell / the ray leaves the box
+      const bool gx = tmx <= tmy && tmx <= tmz;
+      const bool gy = !gx && tmy <= tmz;
+      const bool gz = !gx && !gy;
+      cx += gx ? stx : 0; cy += gy ? sty : 0; cz += gz ? stz : 0;
+      tmx += gx ? dtx : 0.0f; tmy += gy ? dty : 0.0f; tmz += gz ? dtz : 0.0f;
+      if (cx < 0 || cx >= a.nx || cy < 0 || cy >= a.ny || cz < 0 || cz >= a.nz) break;
+    }
+  }
+  if (live) {
+    const bool got = best < INFINITY;
+    a.depth[out] = metric ? best : (got ? a.far * (best - near) * DSIM_RCP(best * (a.far - near)) : 1.0f);
+    if (SEG) a.seg[out] = got ? body : -1;
+  }
+#ifdef DSIM_CAM_COUNT
+  if (a.tests && n_tests) atomicAdd(a.tests, (unsigned long long)n_tests);
+#endif
+}
+
+#ifdef DSIM_CAM_COUNT
+static unsigned long long* g_cam_tests = nullptr;              // device counter of the measuring build
+#endif
+
+extern "C" {
+
+int dsim_obstacle_ray_grid_plan(const float* tri, int64_t n_tri, dsim_obstacle_grid* out) {
+  return dsim_obs::ray_plan(tri, n_tri, false, out);
+}
+
+int dsim_obstacle_ray_grid_build(const float* tri, int64_t n_tri, const dsim_obstacle_grid* g, int32_t* cell_start, int32_t* cell_tri) {
+  return dsim_obs::ray_build(tri, n_tri, false, g, cell_start, cell_tri);
+}
+
+int dsim_obstacles_enable_rays(dsim_ctx* ctx, dsim_obstacles* set) {
+  if (!ctx || !set) return DSIM_E_ARG;
+  if (set->ray_start) return DSIM_OK;
+  // DSIM_RAY_ONE_CELL=1: the whole box as one cell that lists every triangle, the brute-force caster a measurement compares
+  // the grid against (tools/bench_camera.py); results do not depend on it
+  const char* env = getenv("DSIM_RAY_ONE_CELL");
+  const bool one_cell = env && env[0] == '1';
+  const float* tri = set->tri_host.data();
+  dsim_obstacle_grid g;
+  int rc = dsim_obs::ray_plan(tri, set->n_tri, one_cell, &g);
+  if (rc) return rc;
+  const int64_t cells = (int64_t)g.nx * g.ny * g.nz;
+  std::vector<int32_t> start, list;
+  try {
+    start.resize(cells + 1); list.resize(g.list_len > 0 ? g.list_len : 1);
+  } catch (const std::bad_alloc&) { return (int)hipErrorOutOfMemory; }
+  rc = dsim_obs::ray_build(tri, set->n_tri, one_cell, &g, start.data(), list.data());
+  if (rc) return rc;
+  int *d_start = nullptr, *d_list = nullptr;
+  hipError_t e = hipSetDevice(ctx->device);
+  if (e == hipSuccess) e = hipMalloc((void**)&d_start, start.size() * sizeof(int32_t));
+  if (e == hipSuccess) e = hipMalloc((void**)&d_list, list.size() * sizeof(int32_t));
+  if (e == hipSuccess) e = hipMemcpy(d_start, start.data(), start.size() * sizeof(int32_t), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_list, list.data(), list.size() * sizeof(int32_t), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e != hipSuccess) {
+    if (d_start) (void)hipFree(d_start);
+    if (d_list) (void)hipFree(d_list);
+    return (int)e;
+  }
+  set->ray_start = d_start; set->ray_tri = d_list; set->ray_grid = g;
+  return DSIM_OK;
+}
+
+int dsim_depth_image(dsim_ctx* ctx, void* stream, dsim_view state, const dsim_obstacles* set, const dsim_camera_params* params,
+                     int64_t n_cam, const int32_t* cam_index, const float* offset, const uint8_t* type_id, float* depth_out,
+                     int32_t* seg_out) {
+  if (!ctx || !set || !params || !depth_out || !set->ray_start || n_cam < 1) return DSIM_E_ARG;
+  const dsim_camera_params& p = *params;
+  if (p.width < 1 || p.width > 1024 || p.height < 1 || p.height > 1024) return DSIM_E_ARG;
+  if (!(p.far > 0.0f) || !isfinite(p.far) || !(p.fov_deg > 0.0f) || !(p.fov_deg < 180.0f) || !(p.aspect > 0.0f) || !isfinite(p.aspect))
+    return DSIM_E_ARG;
+  if (ctx->n_types > 1 && !type_id) return DSIM_E_ARG;
+  for (int t = 0; t < ctx->n_types; ++t) if (!((float)ctx->h_types[t].arm > 0.0f)) return DSIM_E_ARG;
+  if (!cam_index && n_cam > state.n_pad) return DSIM_E_ARG;
+  CamK a;
+  const int rc = make_kview(state, 7, &a.st);
+  if (rc) return rc;
+  const dsim_obstacle_grid& g = set->ray_grid;
+  a.n_pad = state.n_pad; a.cam_index = cam_index; a.offset = offset; a.type_id = type_id;
+  a.types = ctx->d_types; a.n_types = ctx->n_types;
+  a.rec = set->rec; a.cell_start = set->ray_start; a.cell_tri = set->ray_tri; a.n_tri = set->n_tri;
+  a.ox = g.origin[0]; a.oy = g.origin[1]; a.oz = g.origin[2]; a.cell = g.cell; a.inv_cell = 1.0f / g.cell;
+  a.nx = g.nx; a.ny = g.ny; a.nz = g.nz; a.hix = g.hi[0]; a.hiy = g.hi[1]; a.hiz = g.hi[2];
+  a.W = p.width; a.H = p.height; a.bx = (p.width + 15) / 16;
+  a.blocks_per_cam = (unsigned)(a.bx * ((p.height + 15) / 16));
+  a.inv_w = 1.0f / (float)p.width; a.inv_h = 1.0f / (float)p.height;
+  a.th = (float)tan((double)p.fov_deg * (M_PI / 360.0)); a.tha = a.th * p.aspect;
+  a.far = p.far; a.flags = p.flags; a.depth = depth_out; a.seg = seg_out;
+  const int64_t blocks = n_cam * (int64_t)a.blocks_per_cam;
+  if (blocks > 0x7fffffffLL) return DSIM_E_ARG;
+#ifdef DSIM_CAM_COUNT
+  if (!g_cam_tests && hipMalloc((void**)&g_cam_tests, sizeof(unsigned long long)) == hipSuccess)
+    (void)hipMemset(g_cam_tests, 0, sizeof(unsigned long long));
+  a.tests = g_cam_tests;
+#endif
+  const hipStream_t st_ = (hipStream_t)stream;
+  const bool lds = set->n_tri <= OBS_LDS_TRI;
+  const size_t shm = lds ? (size_t)set->n_tri * 64 : 0;
+  if (lds && seg_out) hipLaunchKernelGGL((k_depth_image<true, true>), dim3((unsigned)blocks), dim3(256), shm, st_, a);
+  else if (lds) hipLaunchKernelGGL((k_depth_image<true, false>), dim3((unsigned)blocks), dim3(256), shm, st_, a);
+  else if (seg_out) hipLaunchKernelGGL((k_depth_image<false, true>), dim3((unsigned)blocks), dim3(256), 0, st_, a);
+  else hipLaunchKernelGGL((k_depth_image<false, false>), dim3((unsigned)blocks), dim3(256), 0, st_, a);
+  return (int)hipGetLastError();
+}
+
+#ifdef DSIM_CAM_COUNT
+// the measuring build only: triangle tests counted since the last call (synchronises the device)
+int dsim_camera_tests(uint64_t* out) {
+  if (!out) return DSIM_E_ARG;
+  *out = 0;
+  if (!g_cam_tests) return DSIM_OK;
+  hipError_t e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = hipMemcpy(out, g_cam_tests, sizeof(uint64_t), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemset(g_cam_tests, 0, sizeof(uint64_t));
+  return (int)e;
+}
+#endif
+
+}  // extern "C"

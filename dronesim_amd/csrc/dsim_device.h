@@ -52,7 +52,7 @@ struct DevType {
   // with a 36-byte scratch reservation)
   double raxis64[DSIM_MAX_ACT][3], rxa64[DSIM_MAX_ACT][3];   // (double)raxis, (double)rxa — the fp32 values, widened (hexa_wrench_base)
   float coll_sphere;                          // bounding sphere of the collision shapes about the COM (drone-drone contact watch)
-  float _pad_sphere;
+  float arm;                                  // the URDF's `arm` L: the depth camera's eye height above the reported point, and its near plane
 };
 
 // The table is written once (dsim_create) and only read by kernels, which read it through the CONSTANT address space.  A

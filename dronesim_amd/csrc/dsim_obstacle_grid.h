@@ -93,15 +93,11 @@ static inline int plan(const float* tri, int64_t n_tri, float reach, dsim_obstac
   return DSIM_E_ARG;
 }
 
-static inline int build(const float* tri, int64_t n_tri, const dsim_obstacle_grid* g, int32_t* cell_start, int32_t* cell_tri) {
-  dsim_obstacle_grid p;
-  if (!g || !cell_start || !cell_tri) return DSIM_E_ARG;
-  const int rc = plan(tri, n_tri, g->reach, &p);
-  if (rc) return rc;
-  if (memcmp(&p, g, sizeof(p)) != 0) return DSIM_E_ARG;        // not this soup's plan: the arrays would have another size
+// count, prefix sum, fill for the grid `p` (cells_of decides where a triangle is listed): triangles ascend inside a cell because
+// they are visited in order
+static inline void fill_lists(const float* tri, int64_t n_tri, const dsim_obstacle_grid& p, int32_t* cell_start, int32_t* cell_tri) {
   const int64_t cells = (int64_t)p.nx * p.ny * p.nz;
   for (int64_t c = 0; c <= cells; ++c) cell_start[c] = 0;
-  // count, prefix sum, fill: triangles ascend inside a cell because they are visited in order
   for (int pass = 0; pass < 2; ++pass) {
     for (int64_t t = 0; t < n_tri; ++t) {
       const CellRange r = cells_of(tri + 9 * t, p);
@@ -120,6 +116,63 @@ static inline int build(const float* tri, int64_t n_tri, const dsim_obstacle_gri
       cell_start[0] = 0;
     }
   }
+}
+
+static inline int build(const float* tri, int64_t n_tri, const dsim_obstacle_grid* g, int32_t* cell_start, int32_t* cell_tri) {
+  dsim_obstacle_grid p;
+  if (!g || !cell_start || !cell_tri) return DSIM_E_ARG;
+  const int rc = plan(tri, n_tri, g->reach, &p);
+  if (rc) return rc;
+  if (memcmp(&p, g, sizeof(p)) != 0) return DSIM_E_ARG;        // not this soup's plan: the arrays would have another size
+  fill_lists(tri, n_tri, p, cell_start, cell_tri);
+  return DSIM_OK;
+}
+
+// ---- the ray grid (dsim_depth_image) ---------------------------------------------------------------------------------------------
+// A second grid of the same soup for ray traversal.  The watch grid lists a triangle in every cell within `reach` of it, which
+// at the size of a gate is every cell; a ray walks cells and wants each list short.  Here reach = 0: a triangle is listed in the
+// cells its own bounding box touches, grown by the same hundredth of a cell (cells_of), which covers the fp32 rounding of the
+// device's cell walk at a cell face.  The box [lo, hi] is the soup's, grown by that slack of the first candidate edge and rounded
+// outwards; the edge starts at diagonal / (2 cbrt(n_tri)) and is doubled until the caps hold.  one_cell: the whole box as ONE
+// cell that lists every triangle (the brute-force baseline a measurement compares the grid against).
+static inline int ray_plan(const float* tri, int64_t n_tri, bool one_cell, dsim_obstacle_grid* out) {
+  if (!out || !soup_ok(tri, n_tri, 1.0f)) return DSIM_E_ARG;
+  double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+  for (int64_t t = 0; t < n_tri; ++t)
+    for (int k = 0; k < 9; ++k) { lo[k % 3] = fmin(lo[k % 3], tri[9 * t + k]); hi[k % 3] = fmax(hi[k % 3], tri[9 * t + k]); }
+  const double dx = hi[0] - lo[0], dy = hi[1] - lo[1], dz = hi[2] - lo[2];
+  double cell = sqrt(dx * dx + dy * dy + dz * dz) / (2.0 * cbrt((double)n_tri));
+  if (!(cell > 0.0) || !isfinite(cell)) return DSIM_E_ARG;
+  const double pad = 1e-2 * cell;
+  for (int k = 0; k < 3; ++k) {
+    lo[k] = (double)nextafterf((float)(lo[k] - pad), -INFINITY);
+    hi[k] = (double)nextafterf((float)(hi[k] + pad), INFINITY);
+    if (!isfinite(lo[k]) || !isfinite(hi[k])) return DSIM_E_ARG;
+  }
+  if (one_cell) cell = 2.0 * fmax(fmax(hi[0] - lo[0], hi[1] - lo[1]), hi[2] - lo[2]);
+  for (int tries = 0; tries < 64; ++tries, cell *= 2.0) {
+    dsim_obstacle_grid g;
+    memset(&g, 0, sizeof(g));
+    if (!grid_at(lo, hi, cell, 0.0f, &g)) continue;
+    if (!((double)g.cell * 1e-2 > 0.0) || !isfinite(g.cell)) return DSIM_E_ARG;
+    int64_t len = 0;
+    for (int64_t t = 0; t < n_tri && len <= DSIM_OBS_MAX_LIST; ++t) len += cells_in(cells_of(tri + 9 * t, g));
+    if (len > DSIM_OBS_MAX_LIST) continue;
+    g.list_len = len;
+    *out = g;
+    return DSIM_OK;
+  }
+  return DSIM_E_ARG;
+}
+
+static inline int ray_build(const float* tri, int64_t n_tri, bool one_cell, const dsim_obstacle_grid* g, int32_t* cell_start,
+                            int32_t* cell_tri) {
+  dsim_obstacle_grid p;
+  if (!g || !cell_start || !cell_tri) return DSIM_E_ARG;
+  const int rc = ray_plan(tri, n_tri, one_cell, &p);
+  if (rc) return rc;
+  if (memcmp(&p, g, sizeof(p)) != 0) return DSIM_E_ARG;        // not this soup's ray plan
+  fill_lists(tri, n_tri, p, cell_start, cell_tri);
   return DSIM_OK;
 }
 

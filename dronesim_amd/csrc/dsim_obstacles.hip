@@ -18,6 +18,11 @@ struct dsim_obstacles {
   int* cell_tri;                 // [list_len]
   int n_tri;
   dsim_obstacle_grid grid;
+  // the ray grid (dsim_obstacles_enable_rays; dsim_camera.hip): null until enabled.  The soup is kept on the host for it.
+  int* ray_start;
+  int* ray_tri;
+  dsim_obstacle_grid ray_grid;
+  std::vector<float> tri_host;
 };
 
 struct ObsK {
@@ -167,6 +172,8 @@ int dsim_obstacles_create(dsim_ctx* ctx, const float* tri_host, const int32_t* b
   dsim_obstacles* s = new (std::nothrow) dsim_obstacles();
   if (!s) return (int)hipErrorOutOfMemory;
   s->rec = nullptr; s->cell_start = nullptr; s->cell_tri = nullptr; s->n_tri = (int)n_tri; s->grid = g;
+  s->ray_start = nullptr; s->ray_tri = nullptr;
+  try { s->tri_host.assign(tri_host, tri_host + 9 * n_tri); } catch (const std::bad_alloc&) { delete s; return (int)hipErrorOutOfMemory; }
   hipError_t e = hipSetDevice(ctx->device);           // (as dsim_dev_alloc: the set lives where the ctx's streams run)
   if (e == hipSuccess) e = hipMalloc((void**)&s->rec, rec.size() * sizeof(float));
   if (e == hipSuccess) e = hipMalloc((void**)&s->cell_start, start.size() * sizeof(int32_t));
@@ -187,6 +194,8 @@ int dsim_obstacles_destroy(dsim_ctx* ctx, dsim_obstacles* set) {
   if (set->rec && (f = hipFree(set->rec)) != hipSuccess) e = f;
   if (set->cell_start && (f = hipFree(set->cell_start)) != hipSuccess) e = f;
   if (set->cell_tri && (f = hipFree(set->cell_tri)) != hipSuccess) e = f;
+  if (set->ray_start && (f = hipFree(set->ray_start)) != hipSuccess) e = f;
+  if (set->ray_tri && (f = hipFree(set->ray_tri)) != hipSuccess) e = f;
   delete set;
   return (int)e;
 }
@@ -221,3 +230,6 @@ int dsim_obstacle_clearance(dsim_ctx* ctx, void* stream, int64_t n, dsim_view st
 }
 
 }  // extern "C"
+
+// the depth camera: the second consumer of the set (it shares the set's private record above and the LDS threshold)
+#include "dsim_camera.hip"

@@ -80,6 +80,7 @@ class CtrlAviary(PlacedFleetArrays, FleetObservation):
     _mem_handed_out = True        # ... but not to the next fused launch: the block has been handed out since the last one
     _drone_watch = False          # the drone-drone contact watch behind every step (set by __init__)
     _obst = None                  # the static-obstacle watch's device set (set by __init__)
+    _vision = None                # the depth camera of vision_attributes=True (set by __init__)
 
     @staticmethod
     def _mem_hint_wanted(mem_hint: bool) -> bool:
@@ -127,6 +128,11 @@ class CtrlAviary(PlacedFleetArrays, FleetObservation):
         obstacle_watch=None,
         obstacle_margin: float = 1.0,
         obstacle_offsets=None,
+        vision_attributes: bool = False,
+        vision_scene=None,
+        vision_drones=None,
+        vision_res=(64, 48),
+        vision_ground: bool = True,
     ):
         if gui or record or obstacles:
             raise NotImplementedError("gui/record/obstacles are rendering features outside the hot path")
@@ -149,6 +155,33 @@ class CtrlAviary(PlacedFleetArrays, FleetObservation):
         # obstacle_offsets [N, 3] (the caller's numbering): the set lies in the frame of each drone's task, p_i - offset_i.
         # Set up at the end of __init__ (_obstacle_setup), when the context and the storage order exist.
         self._obst_set, self._obst_margin, self._obst = obstacle_watch, float(obstacle_margin), None
+        # BaseAviary(vision_attributes=True) keeps self.rgb / self.dep / self.seg per drone at IMG_RES = [64, 48] and refreshes them
+        # from _getDroneImages whenever step_counter % IMG_CAPTURE_FREQ == 0 (BaseAviary.py:236-261, 453-502, 794-853).  Here:
+        # env.dep / env.seg ([n, H, W] device tensors; no rgb) of the static world `vision_scene` (default: the obstacle_watch
+        # set, whose device copy the camera then shares), captured on the env's stream behind the step the cadence names; a
+        # step_fused launch with n_steps > 1 captures once, at its end, when a capture fell due inside it.  vision_drones: the
+        # drones that carry a camera (the caller's numbering; None: all).  The set lies in the frame of obstacle_offsets.  The
+        # other drones are not drawn.  Checked here, set up at the end of __init__ (_vision_setup).
+        self._vision_args = None
+        if vision_attributes:
+            self.IMG_RES = np.array([int(vision_res[0]), int(vision_res[1])])
+            self.IMG_FRAME_PER_SEC = 24
+            self.IMG_CAPTURE_FREQ = int(freq) // self.IMG_FRAME_PER_SEC
+            if self.IMG_CAPTURE_FREQ < 1 or self.IMG_CAPTURE_FREQ % int(aggregate_phy_steps) != 0:
+                raise ValueError(f"aggregate_phy_steps = {aggregate_phy_steps} is incompatible with the image capture rate of "
+                                 f"{self.IMG_FRAME_PER_SEC} Hz at freq = {freq}: IMG_CAPTURE_FREQ = {self.IMG_CAPTURE_FREQ} physics "
+                                 "steps must be a positive multiple of it (BaseAviary.py:247-253)")
+            if not (1 <= self.IMG_RES[0] <= 1024 and 1 <= self.IMG_RES[1] <= 1024):
+                raise ValueError(f"vision_res must be (width, height) with 1 <= each <= 1024, got {vision_res!r}")
+            if vision_scene is None and obstacle_watch is None:
+                raise ValueError("vision_attributes=True needs a world to look at: vision_scene=ObstacleSet (or obstacle_watch)")
+            if vision_drones is not None:
+                vd = np.asarray(vision_drones, dtype=np.int64).ravel()
+                if vd.size < 1 or vd.min() < 0 or vd.max() >= num_drones:
+                    raise ValueError(f"vision_drones must name drones in [0, {num_drones})")
+            self._vision_args = (vision_scene, vision_drones, bool(vision_ground))
+        elif vision_scene is not None or vision_drones is not None:
+            raise ValueError("vision_scene / vision_drones without vision_attributes=True")
         # the add-on terms of the PYB_* modes (dead code in the reference fork, intended formulas); Physics.DYN: the
         # reference's own explicit model, BaseAviary._dynamics (BaseAviary.py:1767-1828; DSIM_OPT_DYN)
         self._phys_options = {Physics.PYB: 0, Physics.PYB_DW: 0, Physics.PYB_GND: nat.OPT_GROUND,
@@ -361,6 +394,7 @@ class CtrlAviary(PlacedFleetArrays, FleetObservation):
         nat.check(self.ctx.lib.dsim_reserve(self.ctx.handle, self.ctx.stream_ptr(), self.state.n_pad))
         self._housekeeping()
         self._obstacle_setup(obstacle_offsets)
+        self._vision_setup(obstacle_offsets)
 
     # ------------------------------------------------------------------ helpers
     def _soa3(self, a: np.ndarray) -> torch.Tensor:
@@ -461,6 +495,7 @@ class CtrlAviary(PlacedFleetArrays, FleetObservation):
         self._step_plan = None
         self.step_counter = 0
         self._env_steps = 0
+        self._vision_seen = 0
         if getattr(self, "_downwash", None) is not None:
             self._downwash.invalidate_prebin()
         pos, rpy = self._soa3(self.INIT_XYZS), self._soa3(self.INIT_RPYS)
@@ -707,6 +742,12 @@ class CtrlAviary(PlacedFleetArrays, FleetObservation):
                 dw.invalidate_prebin()
         if self._obst is not None:
             self.obstacle_clearance()     # (eager, not an Env.step: the watch's kernel is loaded before the capture starts)
+        if self._vision is not None:
+            if self.IMG_CAPTURE_FREQ != self.AGGR_PHY_STEPS:
+                raise NotImplementedError(f"graph capture with vision_attributes: the images are due every "
+                                          f"{self.IMG_CAPTURE_FREQ // self.AGGR_PHY_STEPS} Env.steps, and a captured sequence is captured "
+                                          "at any length; only a cadence of 1 (IMG_CAPTURE_FREQ == AGGR_PHY_STEPS) is part of the graph")
+            self._vision.capture()        # (eager: the camera's kernel is loaded before the capture starts)
         # nothing may allocate under capture: the fallback queue of hexa fleets is reserved up front
         nat.check(self.ctx.lib.dsim_reserve(self.ctx.handle, self.ctx.stream_ptr(), self.state.n_pad))
         self._graph_made = True
@@ -737,12 +778,41 @@ class CtrlAviary(PlacedFleetArrays, FleetObservation):
             self.last_clearance = self._drone_query(self._drone_watch_margin, None)
         if self._obst is not None:
             self._watch_obstacles()
+        if self._vision is not None:
+            # due when a multiple of IMG_CAPTURE_FREQ lies in (the counter before the launch, the counter now]: for a launch of
+            # one Env.step that is step_counter % IMG_CAPTURE_FREQ == 0 (BaseAviary.py:483)
+            f = self.IMG_CAPTURE_FREQ
+            due = self.step_counter // f > self._vision_seen // f
+            self._vision_seen = self.step_counter
+            if due:
+                self._vision.capture()
+
+    def _vision_setup(self, offsets) -> None:
+        """vision_attributes=True: the camera, its device set (shared with the obstacle watch when both look at the same
+        ObstacleSet) and env.dep / env.seg."""
+        if self._vision_args is None:
+            return
+        from ..camera import DepthCamera
+        scene, drones, ground = self._vision_args
+        shared = self._obst is not None and (scene is None or scene is self._obst_set)
+        self._vision = DepthCamera(self.ctx, self.state, self._obst if shared else scene, res=tuple(int(v) for v in self.IMG_RES),
+                                   ground=ground, cameras=drones, offsets=offsets, type_id=self._type_id)
+        self.dep, self.seg = self._vision.dep, self._vision.seg
+        self.dep.fill_(1.0)                # nothing seen yet (BaseAviary.py:245 starts from ones too)
+        self.seg.fill_(-1)
+
+    def drone_images(self):
+        """(dep, seg) of the CURRENT state, captured now on the env's stream into env.dep / env.seg (BaseAviary._getDroneImages
+        for every camera drone at once): float32 depth-buffer values and int32 body indices [n, H, W]."""
+        if self._vision is None:
+            raise ValueError("drone_images() needs an env made with vision_attributes=True")
+        return self._vision.capture()
 
     def _obstacle_setup(self, offsets) -> None:
         """obstacle_watch: the device set for reach = R_max + margin, the offsets in storage order and the tensors every
         per-step query writes (fixed addresses: a captured sequence holds them)."""
         if self._obst_set is None:
-            if offsets is not None:
+            if offsets is not None and self._vision_args is None:
                 raise ValueError("obstacle_offsets without obstacle_watch")
             return
         from .. import obstacles as obs
@@ -820,6 +890,8 @@ class CtrlAviary(PlacedFleetArrays, FleetObservation):
         return seen - (int(self._clr_on_demand.item()) if self._clr_on_demand is not None else 0)
 
     def close(self):
+        if self._vision is not None:
+            self._vision.close()
         if self._obst is not None:
             self._obst.close()
         self.ctx.close()

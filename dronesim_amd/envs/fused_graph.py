@@ -58,6 +58,8 @@ class FusedGraph:
                         nat.check(lib.dsim_step(h, sp, n, self._sview, self._tview, ctypes.byref(self._args)))
                         if env._obst is not None:          # the static-obstacle watch: one query behind every step, as in eager mode
                             env._watch_obstacles()
+                        if env._vision is not None:        # the depth camera at a cadence of 1: one capture behind every step
+                            env._vision.capture()
                 finally:
                     if dw is not None:
                         dw._box_refresh = refresh
@@ -85,3 +87,4 @@ class FusedGraph:
         env._fused_plan = None
         env.step_counter += env.AGGR_PHY_STEPS * self.steps
         env._env_steps += self.steps
+        env._vision_seen = env.step_counter

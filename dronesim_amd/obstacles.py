@@ -74,6 +74,12 @@ class DeviceObstacles:
     def handle(self):
         return self._h
 
+    def enable_rays(self) -> "DeviceObstacles":
+        """The set's ray grid for the depth camera (dsim_obstacles_enable_rays: host work, an upload and a synchronisation, not
+        inside a graph capture; nothing happens when the set already has it)."""
+        nat.check(self.ctx.lib.dsim_obstacles_enable_rays(self.ctx.handle, self._h))
+        return self
+
     def close(self) -> None:
         if self._h:
             self.ctx.lib.dsim_obstacles_destroy(None, self._h)
@@ -193,6 +199,18 @@ class ObstacleSet:
         start = np.zeros(g.nx * g.ny * g.nz + 1, dtype=np.int32)
         lst = np.zeros(max(int(g.list_len), 1), dtype=np.int32)
         nat.check(lib.dsim_obstacle_grid_build(tri.ctypes.data, self.n_tri, ctypes.byref(g), start.ctypes.data, lst.ctypes.data))
+        return g, start, lst[: int(g.list_len)]
+
+    def ray_grid(self):
+        """The host-side RAY grid of this set (dsim_obstacle_ray_grid_plan / _build; needs no device): a triangle is listed in
+        the cells its own bounding box touches.  (nat.ObstacleGrid, cell_start int32 [cells + 1], cell_tri int32 [list_len])."""
+        lib = nat.load()
+        tri = np.ascontiguousarray(self.triangles.reshape(-1, 9))
+        g = nat.ObstacleGrid()
+        nat.check(lib.dsim_obstacle_ray_grid_plan(tri.ctypes.data, self.n_tri, ctypes.byref(g)))
+        start = np.zeros(g.nx * g.ny * g.nz + 1, dtype=np.int32)
+        lst = np.zeros(max(int(g.list_len), 1), dtype=np.int32)
+        nat.check(lib.dsim_obstacle_ray_grid_build(tri.ctypes.data, self.n_tri, ctypes.byref(g), start.ctypes.data, lst.ctypes.data))
         return g, start, lst[: int(g.list_len)]
 
     def to_device(self, ctx, reach: float) -> DeviceObstacles:

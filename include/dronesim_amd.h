@@ -43,7 +43,9 @@ extern "C" {
                               Added since, without a new number because a caller built against 11.1 never sees them (new functions,
                               a new struct, a new enum value; nothing that existed changed size, layout or meaning): the
                               static-obstacle watch, dsim_obstacle_grid_plan / _build, dsim_obstacles_create / _destroy,
-                              dsim_obstacle_clearance, dsim_obstacle_grid, DSIM_Q_OBSTACLE_CONTACTS */
+                              dsim_obstacle_clearance, dsim_obstacle_grid, DSIM_Q_OBSTACLE_CONTACTS; the depth camera,
+                              dsim_obstacle_ray_grid_plan / _build, dsim_obstacles_enable_rays, dsim_depth_image, dsim_camera_params,
+                              DSIM_CAM_*, DSIM_SEG_GROUND */
 #define DSIM_MAX_ACT 6     /* actuators per vehicle (quad 4, morphing hexa 6) */
 #define DSIM_MAX_TYPES 8
 
@@ -726,6 +728,55 @@ int dsim_obstacles_destroy(dsim_ctx* ctx, dsim_obstacles* set);
 int dsim_obstacle_clearance(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, const dsim_obstacles* set,
                             const float* offset, const uint8_t* type_id, float margin,
                             float* clearance_out, int32_t* nearest_out, uint64_t* contacts_out);
+
+/* Depth camera: per-drone depth and segmentation images of the obstacle set.  The reference's envs keep, with
+ * vision_attributes=True, an rgb / depth / segmentation image per drone from p.getCameraImage (BaseAviary._getDroneImages,
+ * BaseAviary.py:794-853).  Depth and segmentation of the STATIC world are geometry and are reproduced here by casting one ray
+ * per pixel against the set; two deviations from Bullet's renderer: the other drones are not drawn, and there is no RGB.
+ *
+ * Camera of drone i (line by line what _getDroneImages hands to computeViewMatrix / computeProjectionMatrixFOV), in the frame
+ * p = p_i - offset_i of the drone's task, with L = dsim_type_params.arm of its type:
+ *     eye = p + (0, 0, L)     target = p + R(quat_i) (1000, 0, 0)     up = (0, 0, 1)     near = L
+ *     f = normalize(target - eye)     s = normalize(f x up)     u = s x f     th = tan(fov / 2)
+ *     d(r, c) = f + ((c + 1/2) / W 2 - 1) th aspect s + (1 - (r + 1/2) / H 2) th u        row r from the top, column c
+ * d is not normalised, so the ray parameter t of a hit IS its eye-space depth.  A pixel takes the nearest hit with
+ * near <= t <= far over both faces of every triangle; DSIM_CAM_GROUND adds the plane z = 0 of the task frame (the reference always
+ * loads plane.urdf) as an analytic ray-plane hit, also for rays that never enter the set's box, reported as body DSIM_SEG_GROUND.
+ *     depth_out[cam][r][c]  the depth-buffer value PyBullet returns, far (t - near) / (t (far - near)), 1.0 where nothing is hit;
+ *                           with DSIM_CAM_METRIC t itself in metres, +inf where nothing is hit
+ *     seg_out[cam][r][c]    the BODY index of the hit triangle, -1 for none, DSIM_SEG_GROUND for the plane; nullable
+ * A camera whose drone state (or offset) is not finite, whose cam_index entry is outside [0, n_pad), or whose basis is degenerate
+ * (|f x up|^2 < 1e-12: a vehicle pitched to the vertical, where Bullet's view matrix is NaN) has no defined image: it gets the
+ * no-hit value and -1 everywhere; nothing faults and the call returns DSIM_OK.
+ *
+ * The ray grid.  The watch grid lists a triangle in every cell within `reach` of it — at a gate's size every cell lists every
+ * triangle — so rays walk a SECOND grid of the same set: reach = 0 in dsim_obstacle_grid, a triangle listed only in the cells
+ * its bounding box touches (plus the hundredth-of-a-cell slack), box = the set's own grown by that slack, cell edge from
+ * bounding-box diagonal / (2 cbrt(n_tri)), doubled until the caps of the watch grid hold.  dsim_obstacle_ray_grid_plan / _build
+ * are its host-only half (as dsim_obstacle_grid_plan / _build); dsim_obstacles_enable_rays plans, builds and uploads it for a
+ * device set, SYNCHRONISES (not inside a capture) and returns DSIM_OK at once when the set already has it.
+ *
+ * dsim_depth_image: stream-ordered, allocates nothing, never synchronises (it may be captured); the outputs are the caller's,
+ * float32 / int32 [n_cam][height][width].  cam_index: int32 [n_cam] (device), drone indices in STORAGE order, NULL = drones
+ * 0 .. n_cam - 1 (n_cam <= n_pad then).  offset and type_id as in dsim_obstacle_clearance.  DSIM_E_ARG, nothing written: a
+ * null ctx / set / params / depth_out, a set without rays enabled, width or height outside 1 .. 1024, fov_deg outside (0, 180),
+ * aspect <= 0, far <= 0 or not finite, n_cam < 1, type_id missing with several types, any type with
+ * arm <= 0.  One lane per pixel; a wave is an 8 x 8 pixel tile of one camera. */
+enum { DSIM_CAM_METRIC = 1u << 0, DSIM_CAM_GROUND = 1u << 1 };
+#define DSIM_SEG_GROUND (-2)
+typedef struct dsim_camera_params {
+  int32_t  width, height;  /* 1 .. 1024 each (the reference: IMG_RES = [64, 48])                                  */
+  float    fov_deg;        /* vertical field of view (the reference: 60)                                          */
+  float    aspect;         /* scales the horizontal extent (the reference passes 1.0 at 64 x 48)                  */
+  float    far;            /* far plane [m] (the reference: 1000); near is the arm of the drone's type            */
+  uint32_t flags;          /* DSIM_CAM_*                                                                          */
+} dsim_camera_params;
+int dsim_obstacle_ray_grid_plan(const float* tri, int64_t n_tri, dsim_obstacle_grid* out);
+int dsim_obstacle_ray_grid_build(const float* tri, int64_t n_tri, const dsim_obstacle_grid* g, int32_t* cell_start, int32_t* cell_tri);
+int dsim_obstacles_enable_rays(dsim_ctx* ctx, dsim_obstacles* set);
+int dsim_depth_image(dsim_ctx* ctx, void* stream, dsim_view state, const dsim_obstacles* set,
+                     const dsim_camera_params* params, int64_t n_cam, const int32_t* cam_index,
+                     const float* offset, const uint8_t* type_id, float* depth_out, int32_t* seg_out);
 
 /* The rotor-noise normals the step kernels draw (diagnostics / distribution studies; no counterpart in the reference, whose
  * draws come from numpy's global generator): for drones [0, n) and the physics sub-steps [0, substeps) of Env.step number
