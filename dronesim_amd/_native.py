@@ -24,6 +24,7 @@ EXPORTS = (
     "dsim_clearance", "dsim_clearance_workspace", "dsim_abi_minor",
     "dsim_obstacle_grid_plan", "dsim_obstacle_grid_build", "dsim_obstacles_create", "dsim_obstacles_destroy", "dsim_obstacle_clearance",
     "dsim_obstacle_ray_grid_plan", "dsim_obstacle_ray_grid_build", "dsim_obstacles_enable_rays", "dsim_depth_image",
+    "dsim_depth_image_drones", "dsim_depth_image_drones_workspace",
 )
 
 ABI_VERSION = 11
@@ -75,6 +76,22 @@ class CameraParams(ctypes.Structure):
         ("aspect", ctypes.c_float),
         ("far", ctypes.c_float),
         ("flags", ctypes.c_uint32),
+    ]
+
+
+def seg_drone(k: int) -> int:
+    """DSIM_SEG_DRONE(k): drone k in a segmentation image (its own inverse)."""
+    return -3 - k
+
+
+class CameraDrones(ctypes.Structure):
+    """dsim_camera_drones (dsim_depth_image_drones)."""
+    _fields_ = [
+        ("grid", ctypes.c_void_p),
+        ("radius_all", ctypes.c_void_p),
+        ("label", ctypes.c_void_p),
+        ("range", ctypes.c_float),
+        ("outside_out", ctypes.c_void_p),
     ]
 
 
@@ -252,6 +269,9 @@ def load(path: str = None) -> ctypes.CDLL:
     lib.dsim_obstacle_ray_grid_build.argtypes = [vp, i64, ctypes.POINTER(ObstacleGrid), vp, vp]
     lib.dsim_obstacles_enable_rays.argtypes = [vp, vp]
     lib.dsim_depth_image.argtypes = [vp, vp, View, vp, ctypes.POINTER(CameraParams), i64, vp, vp, vp, vp, vp]
+    lib.dsim_depth_image_drones_workspace.restype = ctypes.c_int64
+    lib.dsim_depth_image_drones_workspace.argtypes = [i64, i32, i32]
+    lib.dsim_depth_image_drones.argtypes = [vp, vp, View, vp, ctypes.POINTER(CameraParams), i64, vp, vp, vp, ctypes.POINTER(CameraDrones), vp, vp]
     if lib.dsim_abi_version() != ABI_VERSION or lib.dsim_abi_minor() != ABI_MINOR:
         raise ImportError(f"libdronesim_amd.so ABI {lib.dsim_abi_version()}.{lib.dsim_abi_minor()} != binding {ABI_VERSION}.{ABI_MINOR}")
     _lib = lib

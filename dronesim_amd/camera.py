@@ -4,6 +4,10 @@ The reference's envs keep, with ``vision_attributes=True``, an image triple per 
 (BaseAviary._getDroneImages, BaseAviary.py:794-853).  Depth and segmentation of the static world are geometry: one ray per pixel
 against the set's triangles gives them exactly.  Two deviations from Bullet's renderer: the other drones are not drawn, and there
 is no RGB (shading is not reproducible).  The camera model is in include/dronesim_amd.h.
+
+``drones=True`` (dsim_depth_image_drones) draws the other drones as well, with two deviations of its own: a drone is drawn as its
+bounding sphere (DroneType.collision_sphere about its stored position), not as its mesh, and the camera's own drone is never
+drawn (its eye sits ``arm`` above its own centre, usually inside its own sphere).
 """
 from __future__ import annotations
 
@@ -29,10 +33,17 @@ class DepthCamera:
     ``type_id``: uint8 device tensor [n_pad] in storage order, required with several types.  ``obstacle_set``: an
     :class:`ObstacleSet` (a device set is made for it) or a :class:`DeviceObstacles` to share.  The camera owns its outputs:
     ``dep`` float32 [n_cam, H, W] (row 0 at the top, as PyBullet returns it; the depth-buffer value, or metres with
-    ``metric=True``) and ``seg`` int32 (body index, -1 nothing, -2 the ground plane)."""
+    ``metric=True``) and ``seg`` int32 (body index, -1 nothing, -2 the ground plane).
+
+    ``drones=True``: the other drones of the fleet are drawn as their bounding spheres, up to ``drone_range`` metres of
+    eye-space depth (None: ``far``); ``seg`` reports drone k of the CALLER's numbering as -3 - k (:meth:`seg_drone` maps back).
+    The fleet is binned per capture on an xy grid over its bounding box, re-measured every 256 captures like the contact
+    watch's (one host sync; never under stream capture, where the box of the last eager capture stands), or over ``drone_box`` =
+    (xmin, ymin, xmax, ymax); a drone outside the box is still drawn exactly, and :meth:`drones_outside` counts such drones.
+    ``obstacle_set`` may then be None: a world of drones and, with ``ground``, the plane."""
 
     def __init__(self, ctx, state, obstacle_set, res=(64, 48), fov=60.0, aspect=1.0, far=1000.0, ground=False, metric=False,
-                 cameras=None, offsets=None, type_id=None):
+                 cameras=None, offsets=None, type_id=None, drones=False, drone_range=None, drone_box=None):
         w, h = (int(v) for v in res)
         if not (1 <= w <= 1024 and 1 <= h <= 1024):
             raise ValueError(f"res must be (width, height) with 1 <= each <= 1024, got {res!r}")
@@ -46,13 +57,23 @@ class DepthCamera:
             raise ValueError("every drone type needs arm > 0: it is the camera's height above the drone and its near plane")
         if len(ctx.types) > 1 and type_id is None:
             raise ValueError("type_id is required with several drone types")
+        if not drones and (drone_range is not None or drone_box is not None):
+            raise ValueError("drone_range / drone_box without drones=True")
+        if drone_range is not None and not float(drone_range) > 0.0:
+            raise ValueError("drone_range must be positive")
+        if drone_box is not None:
+            drone_box = tuple(float(v) for v in drone_box)
+            if len(drone_box) != 4 or not all(np.isfinite(drone_box)) or not (drone_box[0] <= drone_box[2] and drone_box[1] <= drone_box[3]):
+                raise ValueError("drone_box must be (xmin, ymin, xmax, ymax)")
+        if obstacle_set is None and not drones:
+            raise TypeError("obstacle_set takes an ObstacleSet or a DeviceObstacles (None only with drones=True)")
         self.ctx, self.state = ctx, state
         self._owns_set = isinstance(obstacle_set, ObstacleSet)
         if self._owns_set:
             obstacle_set = obstacle_set.to_device(ctx, camera_reach(ctx.types))
-        if not isinstance(obstacle_set, DeviceObstacles):
+        if obstacle_set is not None and not isinstance(obstacle_set, DeviceObstacles):
             raise TypeError("obstacle_set takes an ObstacleSet or a DeviceObstacles")
-        self.set = obstacle_set.enable_rays()
+        self.set = obstacle_set.enable_rays() if obstacle_set is not None else None
         order = getattr(state, "order", None) or getattr(ctx, "order", None)
         n, dev = state.n, ctx.device
         self._index = None
@@ -82,16 +103,69 @@ class DepthCamera:
                                        (nat.CAM_GROUND if ground else 0) | (nat.CAM_METRIC if metric else 0))
         self.dep = torch.empty((n_cam, h, w), dtype=torch.float32, device=dev)
         self.seg = torch.empty((n_cam, h, w), dtype=torch.int32, device=dev)
+        self.drones = bool(drones)
+        if self.drones:
+            from .downwash import Downwash
+            self._grid = Downwash(ctx, state, type_id, None)     # the helper the contact watch bins with
+            self._drone_box = drone_box
+            # storage slot -> the caller's number (a type-major fleet): what seg names a drone by
+            self._label = torch.from_numpy(order.drone_np.astype(np.int32)).to(dev) if order is not None else None
+            self._outside = torch.zeros((1,), dtype=torch.int64, device=dev)
+            self._dr = nat.CameraDrones()
+            self._dr.radius_all = None
+            self._dr.label = self._label.data_ptr() if self._label is not None else None
+            self._dr.range = float(far if drone_range is None else drone_range)
+            self._dr.outside_out = self._outside.data_ptr()
 
     def capture(self, seg: bool = True):
-        """Enqueues one dsim_depth_image on the current stream (it may be captured into a graph) and returns (dep, seg): the
-        camera's own tensors, overwritten by the next capture.  ``seg=False`` leaves the segmentation image unwritten."""
+        """Enqueues one dsim_depth_image (``drones=True``: dsim_depth_image_drones) on the current stream (it may be captured into
+        a graph) and returns (dep, seg): the camera's own tensors, overwritten by the next capture.  ``seg=False`` leaves the
+        segmentation image unwritten."""
+        common = (self._index.data_ptr() if self._index is not None else None, self._off.data_ptr() if self._off is not None else None,
+                  self._type_id.data_ptr() if self._type_id is not None else None)
+        if self.drones:
+            self._grid_args = self._grid.sphere_grid(self._drone_box)          # (kept: the struct outlives the call)
+            self._dr.grid = ctypes.addressof(self._grid_args)
+            nat.check(self.ctx.lib.dsim_depth_image_drones(
+                self.ctx.handle, self.ctx.stream_ptr(), self.state.view(), self.set.handle if self.set is not None else None,
+                ctypes.byref(self.params), self.n_cam, *common, ctypes.byref(self._dr), self.dep.data_ptr(),
+                self.seg.data_ptr() if seg else None))
+            return self.dep, (self.seg if seg else None)
         nat.check(self.ctx.lib.dsim_depth_image(
             self.ctx.handle, self.ctx.stream_ptr(), self.state.view(), self.set.handle, ctypes.byref(self.params), self.n_cam,
-            self._index.data_ptr() if self._index is not None else None, self._off.data_ptr() if self._off is not None else None,
-            self._type_id.data_ptr() if self._type_id is not None else None, self.dep.data_ptr(),
-            self.seg.data_ptr() if seg else None))
+            *common, self.dep.data_ptr(), self.seg.data_ptr() if seg else None))
         return self.dep, (self.seg if seg else None)
+
+    @staticmethod
+    def seg_drone(seg):
+        """The drone number where a segmentation image shows a drone (seg <= -3: DSIM_SEG_DRONE), -1 elsewhere; a tensor or an
+        array of seg's kind."""
+        if isinstance(seg, torch.Tensor):
+            return torch.where(seg <= -3, -3 - seg, torch.full_like(seg, -1))
+        seg = np.asarray(seg)
+        return np.where(seg <= -3, -3 - seg, -1)
+
+    def refresh_drone_box(self) -> None:
+        """Has the next eager capture re-measure the box of the drones' grid (no-op with ``drone_box``): for a caller that is about
+        to capture a graph, whose captures keep the box and the workspace of the last eager one."""
+        if not self.drones:
+            raise ValueError("refresh_drone_box() needs a camera made with drones=True")
+        self._grid._box = None
+
+    def graph_keepalive(self):
+        """What a captured capture() holds the addresses of, for the owner of the graph to keep alive: an eager capture that later
+        re-measures the box and outgrows the drones' workspace makes a new one, and the old must outlive the graph."""
+        keep = [self.dep, self.seg, self._index, self._off, self._type_id]
+        if self.drones:
+            keep += [self._grid._ws, self._label, self._outside]
+        return tuple(keep)
+
+    def drones_outside(self) -> int:
+        """Drones x captures so far that were binned outside the grid's box (synchronises the stream): drawn all the same, but
+        tested by every ray — a count that grows says the box (``drone_box``, or the one a graph was captured with) is stale."""
+        if not self.drones:
+            raise ValueError("drones_outside() needs a camera made with drones=True")
+        return int(self._outside.item())
 
     def close(self) -> None:
         if self._owns_set:

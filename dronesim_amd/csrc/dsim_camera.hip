@@ -1,4 +1,5 @@
-// Depth camera (dsim_depth_image): per-drone depth and segmentation images of the static obstacle set, one ray per pixel against
+// Depth camera (dsim_depth_image, dsim_depth_image_drones): per-drone depth and segmentation images of the static obstacle set —
+// and, with the second entry point, of the other drones as their bounding spheres — one ray per pixel against
 // the set's RAY grid (dsim_obstacle_grid.h: ray_plan; include/dronesim_amd.h has the camera model).  Compiled as part of
 // dsim_obstacles.hip, which includes this file: it reads the set's private record (struct dsim_obstacles) and shares OBS_LDS_TRI.
 #pragma once
@@ -6,6 +7,14 @@
 #include <stdlib.h>
 
 #define CAM_TILE 8                 // a wave is an 8 x 8 pixel tile; a workgroup the 2 x 2 tiles of a 16 x 16 pixel block
+
+// The other drones as their bounding spheres (dsim_depth_image_drones): the fleet binned on the contact watch's xy grid
+// (dsim_kernels.h: SphereGrid), the caller's label table and the range beyond which no drone is drawn.
+struct CamDr {
+  SphereGrid g;
+  const int* label;                // [m] k of DSIM_SEG_DRONE per world index, or null: the world index
+  float range;
+};
 
 struct CamK {
   KView st;
@@ -31,14 +40,41 @@ struct CamK {
 #ifdef DSIM_CAM_COUNT
   unsigned long long* tests;              // triangle tests, summed over every ray (a measuring build: tools/bench_camera.py)
 #endif
+  CamDr dr;                               // DRONES instances only (at the end: the other instances' arguments lie where they lay)
 };
+
+// One sphere (x, y, z, R) against the ray w + t d, cancellation-free: m = c - w, tc = m.d / d.d the parameter of the ray's closest
+// point, rho^2 = |m - tc d|^2, roots tc -+ sqrt((R^2 - rho^2) / d.d).  (b^2 - a c loses a 5 cm sphere at 50 m in float32: both
+// terms are ~2500 and their difference ~0.0025.)  The first root unless it lies in front of the near plane: both faces are seen,
+// as with triangles.  The world index is read only by a lane that hits: the camera's own drone is never drawn.
+__device__ __forceinline__ void cam_sphere(const float4 p, const int* __restrict__ idx, int k, int own, float wx, float wy, float wz,
+                                           float dx, float dy, float dz, float inv_a, float near, float tmax, float& best, int& body) {
+  const float mx = p.x - wx, my = p.y - wy, mz = p.z - wz;
+  const float tc = (mx * dx + my * dy + mz * dz) * inv_a;
+  const float qx = mx - tc * dx, qy = my - tc * dy, qz = mz - tc * dz;
+  const float disc = p.w * p.w - (qx * qx + qy * qy + qz * qz);
+  const float h = DSIM_SQRT(fmaxf(disc, 0.0f) * inv_a);
+  const float t0 = tc - h, t1 = tc + h;
+  const float t = t0 >= near ? t0 : t1;
+  if (p.w > 0.0f && disc >= 0.0f && t >= near && t <= tmax && t < best) {       // (a NaN anywhere fails a comparison)
+    const int j = idx[k];
+    if (j != own) { best = t; body = DSIM_SEG_DRONE(j); }
+  }
+}
 
 // One lane per pixel.  The pose and the basis are the same for the whole workgroup: the drone's index comes from blockIdx, its
 // position and quaternion are read through the view with that uniform index, and f, s, u and the eye stay in scalar registers.
 // A lane slab-clips its ray against the grid's box, walks the cells by 3-D DDA (Amanatides & Woo, three named scalars per
 // quantity and selects: an array indexed by the stepping axis would live in scratch), tests the list of every cell with
 // Moller-Trumbore from the records (a, ab, ac; body in r3.w) and stops as soon as its best t is not beyond the cell's exit.
-template <bool LDS, bool SEG>
+// DRONES: behind the triangle walk the same lane walks the drone grid's xy cells by 2-D DDA from the eye in the WORLD frame
+// (p_i + (0, 0, L): the triangles and the plane keep the task frame p_i - offset_i; d is the same, so both t are eye-space depth
+// and share `best`).  Cells are 2 R_max or more: a sphere whose centre lies in a cell reaches into adjacent cells only, so the
+// spheres of the 3 x 3 block around the ray's cell are all that can be hit inside it — the whole block at the first cell, the
+// three newly adjacent cells after every step — and the walk stops as soon as best is not beyond the cell's exit.  The box the
+// ray is clipped to is the grid's grown by one ring of (empty) cells: a sphere of a border cell reaches outside the grid's box.
+// Then the outside list.  TRIS = false: no obstacle set (drones and, optionally, the plane).
+template <bool LDS, bool SEG, bool DRONES = false, bool TRIS = true>
 __global__ __launch_bounds__(256) void k_depth_image(CamK a) {
   extern __shared__ float4 s_cam_rec[];
   const unsigned cam = blockIdx.x / a.blocks_per_cam, blk = blockIdx.x - cam * a.blocks_per_cam;
@@ -54,12 +90,14 @@ __global__ __launch_bounds__(256) void k_depth_image(CamK a) {
   // ---- the camera (uniform) -------------------------------------------------------------------------------------------------
   const long long i = a.cam_index ? (long long)a.cam_index[cam] : (long long)cam;
   bool defined = i >= 0 && i < a.n_pad;
+  float wx = 0.0f, wy = 0.0f, wz = 0.0f;                        // DRONES: the eye in the world frame
   float ex = 0.0f, ey = 0.0f, ez = 0.0f, fx = 1.0f, fy = 0.0f, fz = 0.0f, sx = 0.0f, sy = 0.0f, near = 1.0f;
   if (defined) {
     const long long o = kv_off(a.st, i);
     const float* p = a.st.base + o;
     const long long fs = a.st.field_stride;
     float px = p[0], py = p[fs], pz = p[2 * fs];
+    const float rx = px, ry = py, rz = pz;                     // the stored position: the world frame
     Q4 q;
     q.x = p[3 * fs]; q.y = p[4 * fs]; q.z = p[5 * fs]; q.w = p[6 * fs];
     if (a.offset) { px -= a.offset[i]; py -= a.offset[a.n_pad + i]; pz -= a.offset[2 * a.n_pad + i]; }
@@ -75,6 +113,7 @@ __global__ __launch_bounds__(256) void k_depth_image(CamK a) {
     const float si = 1.0f / sqrtf(ss);
     sx = fy * si; sy = -fx * si;
     ex = px; ey = py; ez = pz + near;
+    if (DRONES) { wx = rx; wy = ry; wz = rz + near; }
     // (a NaN anywhere fails a comparison here: |x| <= FLT_MAX holds for finite x only)
     defined = fabsf(ex) <= 3.0e38f && fabsf(ey) <= 3.0e38f && fabsf(ez) <= 3.0e38f && fabsf(fx) <= 2.0f && fabsf(fy) <= 2.0f &&
               fabsf(fz) <= 2.0f && ss >= 1e-12f && fabsf(sx) <= 2.0f && fabsf(sy) <= 2.0f && near > 0.0f;
@@ -115,7 +154,7 @@ __global__ __launch_bounds__(256) void k_depth_image(CamK a) {
 #ifdef DSIM_CAM_COUNT
   unsigned n_tests = 0u;
 #endif
-  if (live && t_in <= t_out && inside_x && inside_y && inside_z) {
+  if (TRIS && live && t_in <= t_out && inside_x && inside_y && inside_z) {
     // the cell of the entry point, clamped; per axis the direction of travel, t at the next face and t per cell
     const float qx = ex + t_in * dx, qy = ey + t_in * dy, qz = ez + t_in * dz;
     int cx = min(max((int)floorf((qx - a.ox) * a.inv_cell), 0), a.nx - 1);
@@ -163,10 +202,69 @@ __global__ __launch_bounds__(256) void k_depth_image(CamK a) {
       if (cx < 0 || cx >= a.nx || cy < 0 || cy >= a.ny || cz < 0 || cz >= a.nz) break;
     }
   }
+  if (DRONES) {
+    const SphereGrid& g = a.dr.g;
+    const float tmax = fminf(a.far, a.dr.range);
+    const float inv_a = 1.0f / (dx * dx + dy * dy + dz * dz);
+    const long long i_w = i + g.local_offset;
+    const int own = i_w < 0x7fffffffLL ? (int)i_w : -1;
+    const float gx0 = g.xmin - g.cell, gx1 = g.xmin + (float)(g.nx + 1) * g.cell;
+    const float gy0 = g.ymin - g.cell, gy1 = g.ymin + (float)(g.ny + 1) * g.cell;
+    const float sx0 = (gx0 - wx) * ix_, sx1 = (gx1 - wx) * ix_;
+    const float sy0 = (gy0 - wy) * iy_, sy1 = (gy1 - wy) * iy_;
+    const float s_in = fmaxf(fmaxf(fminf(sx0, sx1), fminf(sy0, sy1)), near);
+    const float s_out = fminf(fminf(fmaxf(sx0, sx1), fmaxf(sy0, sy1)), fminf(tmax, best));   // (starts from the triangle hit)
+    const bool in_x = dx != 0.0f || (wx >= gx0 && wx <= gx1);
+    const bool in_y = dy != 0.0f || (wy >= gy0 && wy <= gy1);
+    if (live && s_in <= s_out && in_x && in_y) {
+      // cell indices -1 .. nx (ny): the ring included; the blocks below are clamped to the cells that exist
+      const float qx = wx + s_in * dx, qy = wy + s_in * dy;
+      int cx = min(max((int)floorf((qx - gx0) * g.inv_cell), 0), g.nx + 1) - 1;
+      int cy = min(max((int)floorf((qy - gy0) * g.inv_cell), 0), g.ny + 1) - 1;
+      const int stx = dx > 0.0f ? 1 : -1, sty = dy > 0.0f ? 1 : -1;
+      const float dtx = dx != 0.0f ? g.cell * fabsf(ix_) : INFINITY;
+      const float dty = dy != 0.0f ? g.cell * fabsf(iy_) : INFINITY;
+      float tmx = dx != 0.0f ? (gx0 + (float)(cx + 1 + (dx > 0.0f ? 1 : 0)) * g.cell - wx) * ix_ : INFINITY;
+      float tmy = dy != 0.0f ? (gy0 + (float)(cy + 1 + (dy > 0.0f ? 1 : 0)) * g.cell - wy) * iy_ : INFINITY;
+      int bx0 = cx - 1, bx1 = cx + 1, by0 = cy - 1, by1 = cy + 1;           // the block to test: 3 x 3 at the first cell
+      const int max_cells = g.nx + g.ny + 4;
+      for (int it = 0; it < max_cells; ++it) {
+        const int xlo = max(bx0, 0), xhi = min(bx1, g.nx - 1), yhi = min(by1, g.ny - 1);
+        if (xlo <= xhi) {
+          for (int yy = max(by0, 0); yy <= yhi; ++yy) {                      // a row of the block is one run of sorted[]
+            const int end = g.cell_start[yy * g.nx + xhi + 1];
+            for (int k = g.cell_start[yy * g.nx + xlo]; k < end; ++k) {
+              cam_sphere(g.sorted[k], g.sidx, k, own, wx, wy, wz, dx, dy, dz, inv_a, near, tmax, best, body);
+#ifdef DSIM_CAM_COUNT
+              ++n_tests;
+#endif
+            }
+          }
+        }
+        const float t_exit = fminf(tmx, tmy);
+        if (best <= t_exit || t_exit >= s_out) break;          // nothing nearer can lie in a later cell / the ray leaves the box (dx = dy = 0: at once)
+        const bool gx = tmx <= tmy;
+        cx += gx ? stx : 0; cy += gx ? 0 : sty;
+        tmx += gx ? dtx : 0.0f; tmy += gx ? 0.0f : dty;
+        if (cx < -1 || cx > g.nx || cy < -1 || cy > g.ny) break;
+        bx0 = gx ? cx + stx : cx - 1; bx1 = gx ? cx + stx : cx + 1;          // the newly adjacent column or row
+        by0 = gx ? cy - 1 : cy + sty; by1 = gx ? cy + 1 : cy + sty;
+      }
+    }
+    if (live) {                                                // drones outside the grid's box: every ray, the list is short
+      const int n_out = *g.outside_n;
+      for (int k = 0; k < n_out; ++k)
+        cam_sphere(g.outside[k], g.outside_idx, k, own, wx, wy, wz, dx, dy, dz, inv_a, near, tmax, best, body);
+    }
+  }
   if (live) {
     const bool got = best < INFINITY;
     a.depth[out] = metric ? best : (got ? a.far * (best - near) * DSIM_RCP(best * (a.far - near)) : 1.0f);
-    if (SEG) a.seg[out] = got ? body : -1;
+    if (SEG) {
+      int sg = got ? body : -1;
+      if (DRONES && sg <= DSIM_SEG_DRONE(0) && a.dr.label) sg = DSIM_SEG_DRONE(a.dr.label[DSIM_SEG_DRONE(sg)]);   // (its own inverse)
+      a.seg[out] = sg;
+    }
   }
 #ifdef DSIM_CAM_COUNT
   if (a.tests && n_tests) atomicAdd(a.tests, (unsigned long long)n_tests);
@@ -176,6 +274,46 @@ __global__ __launch_bounds__(256) void k_depth_image(CamK a) {
 #ifdef DSIM_CAM_COUNT
 static unsigned long long* g_cam_tests = nullptr;              // device counter of the measuring build
 #endif
+
+// the arguments both entry points share, checked and laid out for the kernel; set = null (dsim_depth_image_drones): no triangles
+static int cam_fill(dsim_ctx* ctx, const dsim_view& state, const dsim_obstacles* set, const dsim_camera_params* params, int64_t n_cam,
+                    const int32_t* cam_index, const float* offset, const uint8_t* type_id, float* depth_out, int32_t* seg_out,
+                    CamK* out, int64_t* blocks_out) {
+  if (!ctx || !params || !depth_out || (set && !set->ray_start) || n_cam < 1) return DSIM_E_ARG;
+  const dsim_camera_params& p = *params;
+  if (p.width < 1 || p.width > 1024 || p.height < 1 || p.height > 1024) return DSIM_E_ARG;
+  if (!(p.far > 0.0f) || !isfinite(p.far) || !(p.fov_deg > 0.0f) || !(p.fov_deg < 180.0f) || !(p.aspect > 0.0f) || !isfinite(p.aspect))
+    return DSIM_E_ARG;
+  if (ctx->n_types > 1 && !type_id) return DSIM_E_ARG;
+  for (int t = 0; t < ctx->n_types; ++t) if (!((float)ctx->h_types[t].arm > 0.0f)) return DSIM_E_ARG;
+  if (!cam_index && n_cam > state.n_pad) return DSIM_E_ARG;
+  CamK& a = *out;
+  memset(&a, 0, sizeof(a));
+  const int rc = make_kview(state, 7, &a.st);
+  if (rc) return rc;
+  a.n_pad = state.n_pad; a.cam_index = cam_index; a.offset = offset; a.type_id = type_id;
+  a.types = ctx->d_types; a.n_types = ctx->n_types;
+  if (set) {
+    const dsim_obstacle_grid& g = set->ray_grid;
+    a.rec = set->rec; a.cell_start = set->ray_start; a.cell_tri = set->ray_tri; a.n_tri = set->n_tri;
+    a.ox = g.origin[0]; a.oy = g.origin[1]; a.oz = g.origin[2]; a.cell = g.cell; a.inv_cell = 1.0f / g.cell;
+    a.nx = g.nx; a.ny = g.ny; a.nz = g.nz; a.hix = g.hi[0]; a.hiy = g.hi[1]; a.hiz = g.hi[2];
+  }
+  a.W = p.width; a.H = p.height; a.bx = (p.width + 15) / 16;
+  a.blocks_per_cam = (unsigned)(a.bx * ((p.height + 15) / 16));
+  a.inv_w = 1.0f / (float)p.width; a.inv_h = 1.0f / (float)p.height;
+  a.th = (float)tan((double)p.fov_deg * (M_PI / 360.0)); a.tha = a.th * p.aspect;
+  a.far = p.far; a.flags = p.flags; a.depth = depth_out; a.seg = seg_out;
+  const int64_t blocks = n_cam * (int64_t)a.blocks_per_cam;
+  if (blocks > 0x7fffffffLL) return DSIM_E_ARG;
+#ifdef DSIM_CAM_COUNT
+  if (!g_cam_tests && hipMalloc((void**)&g_cam_tests, sizeof(unsigned long long)) == hipSuccess)
+    (void)hipMemset(g_cam_tests, 0, sizeof(unsigned long long));
+  a.tests = g_cam_tests;
+#endif
+  *blocks_out = blocks;
+  return DSIM_OK;
+}
 
 extern "C" {
 
@@ -224,35 +362,11 @@ int dsim_obstacles_enable_rays(dsim_ctx* ctx, dsim_obstacles* set) {
 int dsim_depth_image(dsim_ctx* ctx, void* stream, dsim_view state, const dsim_obstacles* set, const dsim_camera_params* params,
                      int64_t n_cam, const int32_t* cam_index, const float* offset, const uint8_t* type_id, float* depth_out,
                      int32_t* seg_out) {
-  if (!ctx || !set || !params || !depth_out || !set->ray_start || n_cam < 1) return DSIM_E_ARG;
-  const dsim_camera_params& p = *params;
-  if (p.width < 1 || p.width > 1024 || p.height < 1 || p.height > 1024) return DSIM_E_ARG;
-  if (!(p.far > 0.0f) || !isfinite(p.far) || !(p.fov_deg > 0.0f) || !(p.fov_deg < 180.0f) || !(p.aspect > 0.0f) || !isfinite(p.aspect))
-    return DSIM_E_ARG;
-  if (ctx->n_types > 1 && !type_id) return DSIM_E_ARG;
-  for (int t = 0; t < ctx->n_types; ++t) if (!((float)ctx->h_types[t].arm > 0.0f)) return DSIM_E_ARG;
-  if (!cam_index && n_cam > state.n_pad) return DSIM_E_ARG;
+  if (!set) return DSIM_E_ARG;
   CamK a;
-  const int rc = make_kview(state, 7, &a.st);
+  int64_t blocks;
+  const int rc = cam_fill(ctx, state, set, params, n_cam, cam_index, offset, type_id, depth_out, seg_out, &a, &blocks);
   if (rc) return rc;
-  const dsim_obstacle_grid& g = set->ray_grid;
-  a.n_pad = state.n_pad; a.cam_index = cam_index; a.offset = offset; a.type_id = type_id;
-  a.types = ctx->d_types; a.n_types = ctx->n_types;
-  a.rec = set->rec; a.cell_start = set->ray_start; a.cell_tri = set->ray_tri; a.n_tri = set->n_tri;
-  a.ox = g.origin[0]; a.oy = g.origin[1]; a.oz = g.origin[2]; a.cell = g.cell; a.inv_cell = 1.0f / g.cell;
-  a.nx = g.nx; a.ny = g.ny; a.nz = g.nz; a.hix = g.hi[0]; a.hiy = g.hi[1]; a.hiz = g.hi[2];
-  a.W = p.width; a.H = p.height; a.bx = (p.width + 15) / 16;
-  a.blocks_per_cam = (unsigned)(a.bx * ((p.height + 15) / 16));
-  a.inv_w = 1.0f / (float)p.width; a.inv_h = 1.0f / (float)p.height;
-  a.th = (float)tan((double)p.fov_deg * (M_PI / 360.0)); a.tha = a.th * p.aspect;
-  a.far = p.far; a.flags = p.flags; a.depth = depth_out; a.seg = seg_out;
-  const int64_t blocks = n_cam * (int64_t)a.blocks_per_cam;
-  if (blocks > 0x7fffffffLL) return DSIM_E_ARG;
-#ifdef DSIM_CAM_COUNT
-  if (!g_cam_tests && hipMalloc((void**)&g_cam_tests, sizeof(unsigned long long)) == hipSuccess)
-    (void)hipMemset(g_cam_tests, 0, sizeof(unsigned long long));
-  a.tests = g_cam_tests;
-#endif
   const hipStream_t st_ = (hipStream_t)stream;
   const bool lds = set->n_tri <= OBS_LDS_TRI;
   const size_t shm = lds ? (size_t)set->n_tri * 64 : 0;
@@ -260,6 +374,38 @@ int dsim_depth_image(dsim_ctx* ctx, void* stream, dsim_view state, const dsim_ob
   else if (lds) hipLaunchKernelGGL((k_depth_image<true, false>), dim3((unsigned)blocks), dim3(256), shm, st_, a);
   else if (seg_out) hipLaunchKernelGGL((k_depth_image<false, true>), dim3((unsigned)blocks), dim3(256), 0, st_, a);
   else hipLaunchKernelGGL((k_depth_image<false, false>), dim3((unsigned)blocks), dim3(256), 0, st_, a);
+  return (int)hipGetLastError();
+}
+
+int64_t dsim_depth_image_drones_workspace(int64_t m, int32_t nx, int32_t ny) {
+  return dsim_sphere_grid_workspace(m, nx, ny);
+}
+
+int dsim_depth_image_drones(dsim_ctx* ctx, void* stream, dsim_view state, const dsim_obstacles* set, const dsim_camera_params* params,
+                            int64_t n_cam, const int32_t* cam_index, const float* offset, const uint8_t* type_id,
+                            const dsim_camera_drones* drones, float* depth_out, int32_t* seg_out) {
+  if (!drones || !drones->grid || !(drones->range > 0.0f)) return DSIM_E_ARG;
+  CamK a;
+  int64_t blocks;
+  int rc = cam_fill(ctx, state, set, params, n_cam, cam_index, offset, type_id, depth_out, seg_out, &a, &blocks);
+  if (rc) return rc;
+  const dsim_downwash_args* g = drones->grid;
+  if (g->halo) return DSIM_E_UNSUPPORTED;
+  // the drones of the state block among the world's: all of them (pos_all NULL), or those from local_offset on
+  const int64_t n = g->pos_all ? (g->m - g->local_offset < state.n_pad ? g->m - g->local_offset : state.n_pad) : g->m;
+  const hipStream_t st_ = (hipStream_t)stream;
+  rc = dsim_sphere_grid_build(ctx, st_, n, state, g, drones->radius_all, (unsigned long long*)drones->outside_out, &a.dr.g);
+  if (rc) return rc;
+  a.dr.label = drones->label; a.dr.range = drones->range;
+  const bool tris = set != nullptr, lds = tris && set->n_tri <= OBS_LDS_TRI;
+  const size_t shm = lds ? (size_t)set->n_tri * 64 : 0;
+  const dim3 gr((unsigned)blocks), tb(256);
+  if (lds && seg_out) hipLaunchKernelGGL((k_depth_image<true, true, true, true>), gr, tb, shm, st_, a);
+  else if (lds) hipLaunchKernelGGL((k_depth_image<true, false, true, true>), gr, tb, shm, st_, a);
+  else if (tris && seg_out) hipLaunchKernelGGL((k_depth_image<false, true, true, true>), gr, tb, 0, st_, a);
+  else if (tris) hipLaunchKernelGGL((k_depth_image<false, false, true, true>), gr, tb, 0, st_, a);
+  else if (seg_out) hipLaunchKernelGGL((k_depth_image<false, true, true, false>), gr, tb, 0, st_, a);
+  else hipLaunchKernelGGL((k_depth_image<false, false, true, false>), gr, tb, 0, st_, a);
   return (int)hipGetLastError();
 }
 

@@ -1158,14 +1158,37 @@ struct ClrK {
   int* nearest;                // [n_pad] or null
   unsigned long long* counters;   // the ctx's (DSIM_Q_DRONE_CONTACTS: DSIM_DRONE_SHARDS shards behind the ground watch's)
   unsigned long long* pairs_out;  // nullable device counter
+  // OUTSIDE (the camera's binning, dsim_sphere_grid_build): the drones outside the grid's box, listed for the rays
+  float4* outside;             // [m]
+  int* outside_idx;            // [m]
+  int* outside_n;              // the list's length, zeroed on the stream in front of the scatter
+  unsigned long long* outside_out;   // nullable device counter
 };
+// OUTSIDE: the contact watch clamps a drone outside the box into a border cell, which keeps every close pair in adjacent cells; a
+// ray needs a sphere where it IS.  Such a drone keeps its clamped slot (the counts stand) with R = -1, which no query draws, and
+// goes on the outside list with its radius; a position that is not finite gets R = -1 and goes on no list.
+template <bool OUTSIDE>
 __global__ __launch_bounds__(256) void k_clr_scatter(DwK a, ClrK c) {
   const long long j = (long long)blockIdx.x * 256 + threadIdx.x;
   if (j >= a.m) return;
   const float x = dw_pos(a, j, 0), y = dw_pos(a, j, 1), z = dw_pos(a, j, 2);
-  const float r = c.radius_all ? c.radius_all[j] : a.types[a.type_id ? min((int)a.type_id[j], a.n_types - 1) : 0].coll_sphere;
+  float r = c.radius_all ? c.radius_all[j] : a.types[a.type_id ? min((int)a.type_id[j], a.n_types - 1) : 0].coll_sphere;
   int cx, cy;
   const int slot = atomicAdd(&a.cursor[dw_cell(a, x, y, cx, cy)], 1);
+  if (OUTSIDE) {
+    const float fx = floorf((x - a.xmin) * a.inv_cell), fy = floorf((y - a.ymin) * a.inv_cell);       // (as dw_cell, unclamped)
+    const bool inside = fx >= 0.0f && fx < (float)a.nx && fy >= 0.0f && fy < (float)a.ny;
+    const bool finite = fabsf(x) <= 3.0e38f && fabsf(y) <= 3.0e38f && fabsf(z) <= 3.0e38f;
+    if (finite && !inside) {
+      if (r > 0.0f) {
+        const int k = atomicAdd(c.outside_n, 1);
+        c.outside[k] = make_float4(x, y, z, r);
+        c.outside_idx[k] = (int)j;
+      }
+      if (c.outside_out) atomicAdd(c.outside_out, 1ULL);
+    }
+    r = finite && inside ? r : -1.0f;
+  }
   a.sorted[slot] = make_float4(x, y, z, r);
   c.sidx[slot] = (int)j;
 }
@@ -1662,9 +1685,59 @@ int dsim_clearance(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, cons
   if (rc) return rc;
   WsWalk w = sort_ws(g->workspace, GridGeo(*g).ncells(), g->m).end;
   ClrK c = {radius_all, w.take<int>(g->m), margin, clearance_out, nearest_out, ctx->d_counters, (unsigned long long*)pairs_out};
-  hipLaunchKernelGGL(k_clr_scatter, dim3(grid_for(a.m)), dim3(256), 0, st_, a, c);
+  hipLaunchKernelGGL(k_clr_scatter<false>, dim3(grid_for(a.m)), dim3(256), 0, st_, a, c);
   hipLaunchKernelGGL(k_clearance_query, dim3(grid_for(a.m)), dim3(256), 0, st_, a, c);
   return (int)hipGetLastError();
 }
 
 }  // extern "C"
+
+// ---- the fleet as spheres for rays (dsim_kernels.h: SphereGrid; the caller is dsim_depth_image_drones in dsim_camera.hip) ----
+// the contact watch's workspace + the outside list (16-byte aligned float4 [m] | int [m] | its length, 4 ints)
+static void sphere_ws(const int32_t* ws, int64_t ncells, int64_t m, ClrK* c, WsWalk* end) {
+  WsWalk w = sort_ws(ws, ncells, m).end;
+  c->sidx = w.take<int>(m);
+  c->outside = w.take<float4>(m, true); c->outside_idx = w.take<int>(m); c->outside_n = w.take<int>(4);
+  *end = w;
+}
+int64_t dsim_sphere_grid_workspace(int64_t m, int32_t nx, int32_t ny) {
+  const int64_t base = dsim_clearance_workspace(m, nx, ny);
+  if (base < 0) return -1;
+  ClrK c;
+  WsWalk w;
+  sphere_ws(nullptr, (int64_t)nx * ny, m, &c, &w);
+  return w.len > base ? w.len : base;
+}
+int dsim_sphere_grid_build(dsim_ctx* ctx, hipStream_t st_, int64_t n, const dsim_view& state, const dsim_downwash_args* g,
+                           const float* radius_all, unsigned long long* outside_out, SphereGrid* out) {
+  if (!ctx || !g || !out) return DSIM_E_ARG;
+  if (g->halo) return DSIM_E_UNSUPPORTED;
+  if ((g->pos_all != nullptr) != (radius_all != nullptr)) return DSIM_E_ARG;     // the world's radii travel with its positions
+  if (ctx->n_types > 1 && !g->type_id && !radius_all) return DSIM_E_ARG;
+  float r_max = 0.0f;
+  for (int t = 0; t < ctx->n_types; ++t) r_max = fmaxf(r_max, (float)ctx->h_types[t].collision_sphere);
+  if (g->nx < 1 || g->ny < 1 || g->m < 1 || !(g->cell > 0.0f) || !isfinite(g->cell) || !isfinite(g->xmin) || !isfinite(g->ymin) ||
+      g->workspace_len < dsim_sphere_grid_workspace(g->m, g->nx, g->ny))
+    return DSIM_E_ARG;
+  // A capture of this call is replayed: it may assume nothing about which count buffer the last call left zeroed.  Without the
+  // context's record of the workspace grid_build clears both count buffers on the stream, every call; and the record is dropped
+  // again behind it, so that the next dsim_downwash / dsim_clearance of this context starts from scratch as well.
+  (void)dsim_downwash_reset(ctx);
+  DwK a;
+  int rc = grid_build(DwCall{ctx, st_, n, state, g, GridGeo(*g)}, 2.0f * r_max, &a, nullptr, nullptr, false);
+  (void)dsim_downwash_reset(ctx);
+  if (rc) return rc;
+  ClrK c;
+  memset(&c, 0, sizeof(c));
+  WsWalk w;
+  sphere_ws(g->workspace, GridGeo(*g).ncells(), g->m, &c, &w);
+  c.radius_all = radius_all; c.outside_out = outside_out;
+  hipError_t e = hipMemsetAsync(c.outside_n, 0, 4 * sizeof(int), st_);
+  if (e != hipSuccess) return (int)e;
+  hipLaunchKernelGGL(k_clr_scatter<true>, dim3(grid_for(a.m)), dim3(256), 0, st_, a, c);
+  out->sorted = a.sorted; out->sidx = c.sidx; out->cell_start = a.count;
+  out->outside = c.outside; out->outside_idx = c.outside_idx; out->outside_n = c.outside_n;
+  out->xmin = g->xmin; out->ymin = g->ymin; out->cell = g->cell; out->inv_cell = a.inv_cell; out->nx = g->nx; out->ny = g->ny;
+  out->local_offset = g->local_offset;
+  return (int)hipGetLastError();
+}

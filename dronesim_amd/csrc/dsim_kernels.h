@@ -766,6 +766,29 @@ static inline CallRuns call_runs(const dsim_step_args* args, long long n_pad, in
 }
 
 static inline unsigned grid_for(long long n) { return (unsigned)((n + 255) / 256); }
+
+// The fleet binned as spheres for rays (dsim_depth_image_drones): the count / scan / scatter pass of the contact watch
+// (dsim_downwash.hip: grid_build + k_clr_scatter), shared with the camera in dsim_camera.hip through these two functions.
+// sorted[s] = (x, y, z, R) in cell order with the world index in sidx[s]; cell_start is the exclusive prefix over the nx * ny cells
+// (cell_start[nx ny] = m).  A drone outside the grid's box, or whose position is not finite, sits in its clamped cell with R = -1
+// (not drawn from there); the finite ones with R > 0 are also on the outside list, which every ray tests.
+struct SphereGrid {
+  const float4* sorted;
+  const int* sidx;
+  const int* cell_start;
+  const float4* outside;       // [*outside_n] (x, y, z, R)
+  const int* outside_idx;      // their world indices
+  const int* outside_n;
+  float xmin, ymin, cell, inv_cell;
+  int nx, ny;
+  long long local_offset;      // world index of drone 0 of the state block
+};
+int64_t dsim_sphere_grid_workspace(int64_t m, int32_t nx, int32_t ny);
+// Enqueues the binning on `stream` (it may be captured: nothing is allocated, and the call assumes nothing about what the last one
+// left in the workspace).  outside_out: nullable device counter, += finite drones binned outside the box.  Validation as
+// dsim_clearance (DSIM_E_ARG / DSIM_E_UNSUPPORTED for a halo plan), before anything is enqueued.
+int dsim_sphere_grid_build(dsim_ctx* ctx, hipStream_t stream, int64_t n, const dsim_view& state, const dsim_downwash_args* g,
+                           const float* radius_all, unsigned long long* outside_out, SphereGrid* out);
 // Which lattice a launch's rotor noise is drawn on (include/dronesim_amd.h: DSIM_OPT_NOISE_FINE / _COARSE): resolved ONCE per
 // entry point into the FINE bit of StepK.options — the kernels test that bit, the launchers route on it.
 static inline uint32_t resolve_noise_lattice(uint32_t options, int substeps) {

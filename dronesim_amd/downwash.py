@@ -722,3 +722,39 @@ class Downwash:
                                      rad.data_ptr() if rad is not None else None, margin, clr.data_ptr(), near.data_ptr(),
                                      pairs_out.data_ptr() if pairs_out is not None else None))
         return clr[: st.n], near[: st.n]
+
+    def sphere_grid(self, box=None) -> nat.DownwashArgs:
+        """The grid argument of dsim_depth_image_drones (DepthCamera(drones=True)): the fleet's xy grid with cells of 2 R_max or
+        more, chosen as clearance() chooses its own (clearance_grid: at most CLEARANCE_CELLS_PER_DRONE cells per drone) over the
+        fleet's bounding box, re-measured every ``box_refresh`` calls (one host sync), or over ``box`` = (xmin, ymin, xmax, ymax).
+        A drone outside the box is still drawn exactly (the library lists it for every ray); the box only decides how short that
+        list is.  Under stream capture nothing is measured or allocated: the box and the workspace are those of the last eager
+        call, which has to exist."""
+        st, lib = self.state, self.ctx.lib
+        if self.dist is not None and self.dist.is_initialized() and self.dist.get_world_size() > 1:
+            raise NotImplementedError("the drones in the camera's images on a sharded fleet: the radii of the other ranks' drones "
+                                      "would have to travel with their positions")
+        key = ("rays", None if box is None else tuple(float(v) for v in box))
+        capturing = self.ctx.device.type == "cuda" and torch.cuda.is_current_stream_capturing()
+        stale = self._box is None or getattr(self, "_clr_key", None) != key or (box is None and self._box_age >= self._box_refresh)
+        if stale and capturing:
+            if self._box is None or getattr(self, "_clr_key", None) != key:
+                raise RuntimeError("sphere_grid under stream capture needs the box of an eager call before it")
+            stale = False
+        if stale:
+            if box is not None:
+                lo, hi = key[1][:2], key[1][2:]
+            else:
+                src = torch.nan_to_num(st.raw_fields(0, 2), nan=0.0, posinf=0.0, neginf=0.0)      # (a lost drone does not stretch the box)
+                lo, hi = src.min(dim=1).values.cpu(), src.max(dim=1).values.cpu()
+            r_max = max(float(t.collision_sphere) for t in self.ctx.types)
+            # margin: what makes the cell 0.25 m at least (a fleet of points still gets a grid)
+            self.cell, *grid = clearance_grid(lo, hi, r_max, max(0.25 - 2.0 * r_max, 0.0), st.n)
+            self._box, self._box_age, self._clr_key = tuple(grid), 0, key
+        elif self._box_age >= self._box_refresh:
+            self._box_age = 0                      # a pinned or captured box stands (_grid_box would measure one of its own)
+        self._auto_cell = False
+        self._prebin_version = None
+        a = self._grid_args(None, 0)
+        self._workspace(a, lib.dsim_depth_image_drones_workspace(a.m, a.nx, a.ny))
+        return a

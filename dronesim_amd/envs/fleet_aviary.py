@@ -133,6 +133,8 @@ class CtrlAviary(PlacedFleetArrays, FleetObservation):
         vision_drones=None,
         vision_res=(64, 48),
         vision_ground: bool = True,
+        vision_see_drones: bool = False,
+        vision_drone_range: Optional[float] = None,
     ):
         if gui or record or obstacles:
             raise NotImplementedError("gui/record/obstacles are rendering features outside the hot path")
@@ -161,7 +163,20 @@ class CtrlAviary(PlacedFleetArrays, FleetObservation):
         # set, whose device copy the camera then shares), captured on the env's stream behind the step the cadence names; a
         # step_fused launch with n_steps > 1 captures once, at its end, when a capture fell due inside it.  vision_drones: the
         # drones that carry a camera (the caller's numbering; None: all).  The set lies in the frame of obstacle_offsets.  The
-        # other drones are not drawn.  Checked here, set up at the end of __init__ (_vision_setup).
+        # other drones are not drawn unless vision_see_drones=True (vision_drones already says who carries a camera): then every
+        # other drone appears in dep and seg as its bounding sphere, up to vision_drone_range metres (None: the far plane), seg
+        # naming drone k of the caller's numbering as -3 - k (DepthCamera.seg_drone); the camera's own drone is never drawn, and
+        # vision_scene becomes optional (a world of drones and the plane).  Checked here, set up at the end of __init__
+        # (_vision_setup).
+        if vision_see_drones and dist is not None and dist.is_initialized() and dist.get_world_size() > 1:
+            raise NotImplementedError("vision_see_drones on a sharded fleet: the radii of the other ranks' drones would have to "
+                                      "travel with their positions (dsim_depth_image_drones takes pos_all / radius_all)")
+        if (vision_see_drones or vision_drone_range is not None) and not vision_attributes:
+            raise ValueError("vision_see_drones / vision_drone_range without vision_attributes=True")
+        if vision_drone_range is not None and not vision_see_drones:
+            raise ValueError("vision_drone_range without vision_see_drones=True")
+        if vision_drone_range is not None and not float(vision_drone_range) > 0.0:
+            raise ValueError("vision_drone_range must be positive")
         self._vision_args = None
         if vision_attributes:
             self.IMG_RES = np.array([int(vision_res[0]), int(vision_res[1])])
@@ -173,13 +188,13 @@ class CtrlAviary(PlacedFleetArrays, FleetObservation):
                                  "steps must be a positive multiple of it (BaseAviary.py:247-253)")
             if not (1 <= self.IMG_RES[0] <= 1024 and 1 <= self.IMG_RES[1] <= 1024):
                 raise ValueError(f"vision_res must be (width, height) with 1 <= each <= 1024, got {vision_res!r}")
-            if vision_scene is None and obstacle_watch is None:
+            if vision_scene is None and obstacle_watch is None and not vision_see_drones:
                 raise ValueError("vision_attributes=True needs a world to look at: vision_scene=ObstacleSet (or obstacle_watch)")
             if vision_drones is not None:
                 vd = np.asarray(vision_drones, dtype=np.int64).ravel()
                 if vd.size < 1 or vd.min() < 0 or vd.max() >= num_drones:
                     raise ValueError(f"vision_drones must name drones in [0, {num_drones})")
-            self._vision_args = (vision_scene, vision_drones, bool(vision_ground))
+            self._vision_args = (vision_scene, vision_drones, bool(vision_ground), bool(vision_see_drones), vision_drone_range)
         elif vision_scene is not None or vision_drones is not None:
             raise ValueError("vision_scene / vision_drones without vision_attributes=True")
         # the add-on terms of the PYB_* modes (dead code in the reference fork, intended formulas); Physics.DYN: the
@@ -747,7 +762,11 @@ class CtrlAviary(PlacedFleetArrays, FleetObservation):
                 raise NotImplementedError(f"graph capture with vision_attributes: the images are due every "
                                           f"{self.IMG_CAPTURE_FREQ // self.AGGR_PHY_STEPS} Env.steps, and a captured sequence is captured "
                                           "at any length; only a cadence of 1 (IMG_CAPTURE_FREQ == AGGR_PHY_STEPS) is part of the graph")
-            self._vision.capture()        # (eager: the camera's kernel is loaded before the capture starts)
+            # (eager: the camera's kernel is loaded before the capture starts; with vision_see_drones this capture also measures the
+            # box of the drones' grid and makes its workspace, which stand for the whole graph)
+            if self._vision.drones:
+                self._vision.refresh_drone_box()
+            self._vision_capture()
         # nothing may allocate under capture: the fallback queue of hexa fleets is reserved up front
         nat.check(self.ctx.lib.dsim_reserve(self.ctx.handle, self.ctx.stream_ptr(), self.state.n_pad))
         self._graph_made = True
@@ -785,7 +804,7 @@ class CtrlAviary(PlacedFleetArrays, FleetObservation):
             due = self.step_counter // f > self._vision_seen // f
             self._vision_seen = self.step_counter
             if due:
-                self._vision.capture()
+                self._vision_capture()
 
     def _vision_setup(self, offsets) -> None:
         """vision_attributes=True: the camera, its device set (shared with the obstacle watch when both look at the same
@@ -793,10 +812,11 @@ class CtrlAviary(PlacedFleetArrays, FleetObservation):
         if self._vision_args is None:
             return
         from ..camera import DepthCamera
-        scene, drones, ground = self._vision_args
+        scene, drones, ground, see_drones, drone_range = self._vision_args
         shared = self._obst is not None and (scene is None or scene is self._obst_set)
         self._vision = DepthCamera(self.ctx, self.state, self._obst if shared else scene, res=tuple(int(v) for v in self.IMG_RES),
-                                   ground=ground, cameras=drones, offsets=offsets, type_id=self._type_id)
+                                   ground=ground, cameras=drones, offsets=offsets, type_id=self._type_id, drones=see_drones,
+                                   drone_range=drone_range)
         self.dep, self.seg = self._vision.dep, self._vision.seg
         self.dep.fill_(1.0)                # nothing seen yet (BaseAviary.py:245 starts from ones too)
         self.seg.fill_(-1)
@@ -806,6 +826,11 @@ class CtrlAviary(PlacedFleetArrays, FleetObservation):
         for every camera drone at once): float32 depth-buffer values and int32 body indices [n, H, W]."""
         if self._vision is None:
             raise ValueError("drone_images() needs an env made with vision_attributes=True")
+        return self._vision_capture()
+
+    def _vision_capture(self):
+        if self._vision.drones and self._downwash is not None:
+            self._downwash.invalidate_prebin()            # the drones' binning drops the ctx's grid bookkeeping
         return self._vision.capture()
 
     def _obstacle_setup(self, offsets) -> None:

@@ -59,7 +59,7 @@ class FusedGraph:
                         if env._obst is not None:          # the static-obstacle watch: one query behind every step, as in eager mode
                             env._watch_obstacles()
                         if env._vision is not None:        # the depth camera at a cadence of 1: one capture behind every step
-                            env._vision.capture()
+                            env._vision_capture()
                 finally:
                     if dw is not None:
                         dw._box_refresh = refresh
@@ -68,6 +68,10 @@ class FusedGraph:
                         # the captured launches hold these addresses: an eager step that later re-measures the box and
                         # outgrows the workspace allocates a new one — this one must outlive the graph
                         self._keepalive = (dw._ws, dw.force, dw.type_id)
+                    if env._vision is not None:
+                        # the captured captures hold the camera's addresses, among them the workspace of the drones' grid: an eager
+                        # capture that later re-measures the box and outgrows it allocates a new one — this one must outlive the graph
+                        self._keepalive_vision = env._vision.graph_keepalive()
                 nat.check(lib.dsim_counter_add(h, sp, self._counter.data_ptr(), steps))
         torch.cuda.current_stream(dev).wait_stream(side)
         self._counter_host = 0

@@ -26,6 +26,7 @@ def main(argv=None):
     ap.add_argument("--duration_sec", type=float, default=3.0)
     ap.add_argument("--gate_urdf", default=os.path.join(ROOT, "tests", "golden", "gate_50_curved.urdf"))
     ap.add_argument("--out", default="depth.npy")
+    ap.add_argument("--see-drones", action="store_true", help="draw the other drones too, as their bounding spheres (vision_see_drones)")
     A = ap.parse_args(argv)
     g = np.load(os.path.join(ROOT, "tests", "golden", "traj_track_waypoints.npz"))
     n, AGGR, FREQ = A.num_drones, 2, 240                                   # fly_INDI_TrajectoryTrack.py:108,162-164
@@ -33,23 +34,25 @@ def main(argv=None):
     off = np.stack([np.arange(n) % side, np.arange(n) // side, np.zeros(n)], 1).astype(np.float64)
     gate = ObstacleSet.from_urdf(A.gate_urdf, g["gates"][1], (0, 0, 0))    # :216-221: every replica sees its own gate
     env = CtrlAviary(["robobee"], n, initial_xyzs=g["gates"][0][None, :] + off, aggregate_phy_steps=AGGR, freq=FREQ,
-                     dict_io=False, obstacle_watch=gate, obstacle_offsets=off, vision_attributes=True)
+                     dict_io=False, obstacle_watch=gate, obstacle_offsets=off, vision_attributes=True,
+                     vision_see_drones=A.see_drones, vision_drone_range=20.0 if A.see_drones else None)
     n_wp = g["target_pos"].shape[0]
     tgt = WaypointTargets(env.ctx, n, g["target_pos"], g["target_vel"], g["target_acc"], g["target_yaw"],
                           wp_counters=(np.arange(n) * n_wp // 6) % n_wp, offsets=off)
-    best, frame, frames = -1, None, 0
+    best, frame, frames, drone_px = -1, None, 0, 0
     for k in range(int(A.duration_sec * FREQ / AGGR)):
         env.step_fused(tgt, control_timestep=AGGR / FREQ, action=np.full((n, 4), 0.4, dtype=np.float32) if k == 0 else None)
         if env.step_counter % env.IMG_CAPTURE_FREQ == 0:                   # env.dep / env.seg were refreshed behind this step
             frames += 1
             seen = (env.seg == 0).flatten(1).sum(1)                        # pixels of the gate, per drone
+            drone_px = max(drone_px, int((env.seg <= -3).sum()))            # (--see-drones: the neighbours on the lattice of replicas)
             i = int(seen.argmax())
             if int(seen[i]) > best:
                 best, frame = int(seen[i]), env.dep[i].clone()
     torch.cuda.synchronize()
     np.save(A.out, frame.cpu().numpy())
     print(f"{frames} captures of {n} x {env.IMG_RES[0]} x {env.IMG_RES[1]} pixels; saved the frame with {best} gate pixels to {A.out}; "
-          f"obstacle contacts {env.obstacle_contacts()}")
+          f"obstacle contacts {env.obstacle_contacts()}" + (f"; up to {drone_px} pixels per capture show another drone" if A.see_drones else ""))
     env.close()
 
 

@@ -45,7 +45,8 @@ extern "C" {
                               static-obstacle watch, dsim_obstacle_grid_plan / _build, dsim_obstacles_create / _destroy,
                               dsim_obstacle_clearance, dsim_obstacle_grid, DSIM_Q_OBSTACLE_CONTACTS; the depth camera,
                               dsim_obstacle_ray_grid_plan / _build, dsim_obstacles_enable_rays, dsim_depth_image, dsim_camera_params,
-                              DSIM_CAM_*, DSIM_SEG_GROUND */
+                              DSIM_CAM_*, DSIM_SEG_GROUND; the other drones in the camera's images, dsim_depth_image_drones,
+                              dsim_depth_image_drones_workspace, dsim_camera_drones, DSIM_SEG_DRONE */
 #define DSIM_MAX_ACT 6     /* actuators per vehicle (quad 4, morphing hexa 6) */
 #define DSIM_MAX_TYPES 8
 
@@ -732,7 +733,8 @@ int dsim_obstacle_clearance(dsim_ctx* ctx, void* stream, int64_t n, dsim_view st
 /* Depth camera: per-drone depth and segmentation images of the obstacle set.  The reference's envs keep, with
  * vision_attributes=True, an rgb / depth / segmentation image per drone from p.getCameraImage (BaseAviary._getDroneImages,
  * BaseAviary.py:794-853).  Depth and segmentation of the STATIC world are geometry and are reproduced here by casting one ray
- * per pixel against the set; two deviations from Bullet's renderer: the other drones are not drawn, and there is no RGB.
+ * per pixel against the set; two deviations from Bullet's renderer: the other drones are not drawn (dsim_depth_image_drones below
+ * draws them, as spheres), and there is no RGB.
  *
  * Camera of drone i (line by line what _getDroneImages hands to computeViewMatrix / computeProjectionMatrixFOV), in the frame
  * p = p_i - offset_i of the drone's task, with L = dsim_type_params.arm of its type:
@@ -777,6 +779,47 @@ int dsim_obstacles_enable_rays(dsim_ctx* ctx, dsim_obstacles* set);
 int dsim_depth_image(dsim_ctx* ctx, void* stream, dsim_view state, const dsim_obstacles* set,
                      const dsim_camera_params* params, int64_t n_cam, const int32_t* cam_index,
                      const float* offset, const uint8_t* type_id, float* depth_out, int32_t* seg_out);
+
+/* The other drones in the images.  The reference renders the whole Bullet world, so every other vehicle appears in dep and seg;
+ * dsim_depth_image_drones is dsim_depth_image with the drones of the world drawn as well — two deviations from Bullet's renderer:
+ * a drone is drawn as its BOUNDING SPHERE, not as its mesh, and the camera's OWN drone is never drawn (its eye sits L above its
+ * own centre, usually inside its own sphere).
+ *
+ * Every other drone j of the world with R_j = dsim_type_params.collision_sphere > 0 (or radius_all[j] > 0) is the sphere of
+ * radius R_j about its STORED position p_j.  The sphere ray starts at the eye in the world frame, e_w = p_i + (0, 0, L); the
+ * triangles and the plane keep the task-frame eye e_w - offset_i; the direction d is the same unnormalised pixel ray, so t is
+ * eye-space depth in both and the two are compared directly.  A sphere is hit at the smallest root t of |e_w + t d - p_j| = R_j
+ * with near <= t <= min(far, range); a first root below near gives way to the second (both faces are seen, as with triangles).
+ * The pixel takes the nearest of the triangle, plane and sphere hits.  R = 0: not drawn.  A drone whose position is not finite is
+ * not drawn and faults nothing.  seg_out reports a drone hit as DSIM_SEG_DRONE(k) = -3 - k, k the drone's world index or, with a
+ * label table (int32 [m], device), label[world index]; -1 and DSIM_SEG_GROUND keep their meaning, body indices stay >= 0.
+ *
+ * The drones are binned per call, on the stream, on the xy grid of `grid` exactly as dsim_clearance bins them (pos_all NULL: the
+ * world is this fleet, read from the state block; pos_all with radius_all: the gathered world, this block at local_offset; a
+ * halo plan: DSIM_E_UNSUPPORTED), cell >= 2 R_max (R_max over the type table; with radius_all the caller keeps cell >= 2 max
+ * radius_all).  A ray walks the xy cells and tests the spheres of the cells adjacent to its own, which is exact for such cells.
+ * The box [xmin, xmin + nx cell] x [ymin, ymin + ny cell] need not hold every drone: one outside it is still drawn exactly, from
+ * a list every ray tests — expected to be empty or short — and counted into *outside_out (nullable device counter, += per call),
+ * so that the host can see the list grow and re-measure its box.  set may be NULL: a world of drones and, with DSIM_CAM_GROUND,
+ * the plane.  Stream-ordered, allocates nothing, may be captured (a replay assumes nothing about earlier calls): grid->workspace
+ * holds dsim_depth_image_drones_workspace(m, nx, ny) int32 entries and is the call's until it has run.  The call drops the
+ * context's record of the downwash grid (as dsim_downwash_reset): a dsim_step that binned ahead for the next dsim_downwash is not
+ * vouched for, that query bins the fleet itself.  DSIM_E_ARG, nothing enqueued: what dsim_depth_image refuses (a NULL set
+ * excepted), a null drones / grid / workspace, range <= 0 or NaN, cell <= 0 or < 2 R_max, nx or ny < 1, m < 1 (pos_all NULL:
+ * m is the fleet's size, m > n_pad is refused), a workspace too short, radius_all without pos_all or the reverse. */
+#define DSIM_SEG_DRONE(k) (-3 - (k))
+typedef struct dsim_camera_drones {
+  const dsim_downwash_args* grid;   /* xy grid as for dsim_clearance (pos_all NULL: this fleet; halo plan: DSIM_E_UNSUPPORTED) */
+  const float*   radius_all;        /* with grid->pos_all, as dsim_clearance */
+  const int32_t* label;             /* nullable [m]: k of DSIM_SEG_DRONE per world index */
+  float          range;             /* > 0: drones are drawn for t <= min(far, range) */
+  uint64_t*      outside_out;       /* nullable device counter: += drones binned outside the box */
+} dsim_camera_drones;
+int64_t dsim_depth_image_drones_workspace(int64_t m, int32_t nx, int32_t ny);
+int dsim_depth_image_drones(dsim_ctx* ctx, void* stream, dsim_view state, const dsim_obstacles* set,
+                            const dsim_camera_params* params, int64_t n_cam, const int32_t* cam_index,
+                            const float* offset, const uint8_t* type_id, const dsim_camera_drones* drones,
+                            float* depth_out, int32_t* seg_out);
 
 /* The rotor-noise normals the step kernels draw (diagnostics / distribution studies; no counterpart in the reference, whose
  * draws come from numpy's global generator): for drones [0, n) and the physics sub-steps [0, substeps) of Env.step number
