@@ -25,6 +25,7 @@ EXPORTS = (
     "dsim_obstacle_grid_plan", "dsim_obstacle_grid_build", "dsim_obstacles_create", "dsim_obstacles_destroy", "dsim_obstacle_clearance",
     "dsim_obstacle_ray_grid_plan", "dsim_obstacle_ray_grid_build", "dsim_obstacles_enable_rays", "dsim_depth_image",
     "dsim_depth_image_drones", "dsim_depth_image_drones_workspace",
+    "dsim_trajgen", "dsim_trajgen_workspace", "dsim_traj_sample_bank",
 )
 
 ABI_VERSION = 11
@@ -92,6 +93,42 @@ class CameraDrones(ctypes.Structure):
         ("label", ctypes.c_void_p),
         ("range", ctypes.c_float),
         ("outside_out", ctypes.c_void_p),
+    ]
+
+
+TRAJGEN_GIVEN, TRAJGEN_TMIN, TRAJGEN_OPTIMIZE = 0, 1, 2     # dsim_trajgen_args.mode
+TRAJGEN_LMAX = 9                                              # DSIM_TRAJGEN_LMAX: waypoints per course
+TRAJGEN_BAD_COUNT, TRAJGEN_BAD_WAYPOINT, TRAJGEN_BAD_SEGMENT, TRAJGEN_BAD_TIME = 1, 2, 3, 4    # status of a course
+
+
+class TrajBank(ctypes.Structure):
+    """dsim_traj_bank: K courses, course-minor (dsim_trajgen, dsim_traj_sample_bank)."""
+    _fields_ = [
+        ("K", ctypes.c_int64),
+        ("K_pad", ctypes.c_int64),
+        ("L_max", ctypes.c_int32),
+        ("_pad", ctypes.c_int32),
+        ("coeffs", ctypes.c_void_p),
+        ("ts", ctypes.c_void_p),
+        ("n_seg", ctypes.c_void_p),
+    ]
+
+
+class TrajGenArgs(ctypes.Structure):
+    """dsim_trajgen_args."""
+    _fields_ = [
+        ("wp", ctypes.c_void_p),
+        ("n_wp", ctypes.c_void_p),
+        ("max_vel", ctypes.c_double),
+        ("gamma", ctypes.c_double),
+        ("mode", ctypes.c_int32),
+        ("max_evals", ctypes.c_int32),
+        ("cost", ctypes.c_void_p),
+        ("evals", ctypes.c_void_p),
+        ("status", ctypes.c_void_p),
+        ("seg_times", ctypes.c_void_p),
+        ("workspace", ctypes.c_void_p),
+        ("workspace_len", ctypes.c_int64),
     ]
 
 
@@ -272,6 +309,10 @@ def load(path: str = None) -> ctypes.CDLL:
     lib.dsim_depth_image_drones_workspace.restype = ctypes.c_int64
     lib.dsim_depth_image_drones_workspace.argtypes = [i64, i32, i32]
     lib.dsim_depth_image_drones.argtypes = [vp, vp, View, vp, ctypes.POINTER(CameraParams), i64, vp, vp, vp, ctypes.POINTER(CameraDrones), vp, vp]
+    lib.dsim_trajgen_workspace.restype = ctypes.c_int64
+    lib.dsim_trajgen_workspace.argtypes = [i64, i32]
+    lib.dsim_trajgen.argtypes = [vp, vp, ctypes.POINTER(TrajBank), ctypes.POINTER(TrajGenArgs)]
+    lib.dsim_traj_sample_bank.argtypes = [vp, vp, i64, ctypes.POINTER(TrajBank), vp, vp, ctypes.c_double, vp, vp, View]
     if lib.dsim_abi_version() != ABI_VERSION or lib.dsim_abi_minor() != ABI_MINOR:
         raise ImportError(f"libdronesim_amd.so ABI {lib.dsim_abi_version()}.{lib.dsim_abi_minor()} != binding {ABI_VERSION}.{ABI_MINOR}")
     _lib = lib

@@ -710,3 +710,6 @@ int dsim_traj_sample(dsim_ctx* ctx, void* stream, int64_t n, const double* coeff
 }
 
 }  // extern "C"
+
+// the trajectory bank (dsim_trajgen, dsim_traj_sample_bank): part of this translation unit
+#include "dsim_traj.hip"

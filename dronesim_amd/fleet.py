@@ -578,3 +578,132 @@ class TrajectoryTargets(Targets):
             self.ctx.handle, self.ctx.stream_ptr(), self.n, self.coeffs.data_ptr(), self.TS.data_ptr(), self.n_seg,
             self.t.data_ptr(), float(dt_advance), self.yaw_state.data_ptr(),
             self.offsets.data_ptr() if self.offsets is not None else None, self.view()))
+
+
+class TrajectoryBank:
+    """K min-snap courses made ON THE DEVICE in one launch (dsim_trajgen): what the reference's
+    ``trajGenerator(waypoints, max_vel, gamma)`` (dronesim/utils/trajGen.py:13-106) computes per call on the host.
+
+    ``waypoints``: [K, L, 3], or a list of K arrays [L_k, 3] (2 <= L_k <= 9).  ``times``: "optimize" (the reference's
+    behaviour: segment times minimise snap cost + gamma * duration subject to T >= Tmin, by the library's bounded pattern search,
+    at most ``max_evals`` evaluations per course), "tmin" (T = Tmin = distance / max_vel), or the cumulative times themselves,
+    [K, L] or a list of [L_k] like ``trajGenerator.TS``.  ``L_max``: the bank's room in waypoints per course (default: the longest
+    course).  A course that cannot be made (a non-finite waypoint, two equal consecutive waypoints, fewer than 2 or more than
+    L_max waypoints) has ``status != 0`` and NaN coefficients; the others are not affected."""
+
+    def __init__(self, ctx: Context, waypoints, max_vel: float = 5, gamma: float = 100, times="optimize", max_evals: int = 2000,
+                 L_max: Optional[int] = None):
+        self.ctx = ctx
+        dev = ctx.device
+        wps = [np.asarray(w, dtype=np.float64).reshape(-1, 3) for w in waypoints]
+        self.K = len(wps)
+        self.K_pad = pad_to(self.K, 64)
+        self.L_max = int(L_max) if L_max is not None else max([2] + [w.shape[0] for w in wps])
+        Lm = self.L_max
+        wp = np.zeros((Lm, 3, self.K_pad))
+        n_wp = np.zeros(self.K_pad, dtype=np.int32)
+        for k, w in enumerate(wps):
+            n_wp[k] = w.shape[0]
+            m = min(w.shape[0], Lm)
+            wp[:m, :, k] = w[:m]
+        ts = np.full((Lm, self.K_pad), np.nan)
+        if isinstance(times, str):
+            mode = {"optimize": nat.TRAJGEN_OPTIMIZE, "tmin": nat.TRAJGEN_TMIN}[times]
+        else:
+            mode = nat.TRAJGEN_GIVEN
+            for k, t in enumerate(times):
+                t = np.asarray(t, dtype=np.float64).ravel()
+                m = min(t.size, Lm)
+                ts[:m, k] = t[:m]
+        self.mode = mode
+        f64 = dict(dtype=torch.float64, device=dev)
+        self.wp = torch.from_numpy(wp).to(dev)
+        self.n_wp = torch.from_numpy(n_wp).to(dev)
+        self.coeffs = torch.full(((Lm - 1) * 30, self.K_pad), float("nan"), **f64)   # [((seg*10 + j)*3 + d), k]; the padding courses stay NaN
+        self.ts = torch.from_numpy(ts).to(dev)                                    # [seg, k]
+        self.seg_times = torch.full((Lm - 1, self.K_pad), float("nan"), **f64)    # [seg, k]: T itself
+        self._n_seg = torch.zeros((self.K_pad,), dtype=torch.int32, device=dev)
+        self._cost = torch.full((self.K_pad,), float("nan"), **f64)
+        self._evals = torch.zeros((self.K_pad,), dtype=torch.int32, device=dev)
+        self._status = torch.zeros((self.K_pad,), dtype=torch.int32, device=dev)
+        need = int(ctx.lib.dsim_trajgen_workspace(self.K_pad, Lm)) if 2 <= Lm <= nat.TRAJGEN_LMAX else 0
+        ws = torch.empty((max(need, 1),), **f64)
+        self.c = nat.TrajBank(K=self.K, K_pad=self.K_pad, L_max=Lm, coeffs=self.coeffs.data_ptr(), ts=self.ts.data_ptr(),
+                              n_seg=self._n_seg.data_ptr())
+        args = nat.TrajGenArgs(wp=self.wp.data_ptr(), n_wp=self.n_wp.data_ptr(), max_vel=float(max_vel), gamma=float(gamma), mode=mode,
+                               max_evals=int(max_evals), cost=self._cost.data_ptr(), evals=self._evals.data_ptr(),
+                               status=self._status.data_ptr(), seg_times=self.seg_times.data_ptr(), workspace=ws.data_ptr(), workspace_len=need)
+        nat.check(ctx.lib.dsim_trajgen(ctx.handle, ctx.stream_ptr(), ctypes.byref(self.c), ctypes.byref(args)))
+        ws.record_stream(torch.cuda.current_stream(dev))                          # (the launch may still be using it when this returns)
+
+    @property
+    def n_seg(self) -> np.ndarray:
+        return self._n_seg[: self.K].cpu().numpy()
+
+    @property
+    def cost(self) -> np.ndarray:
+        """trace(P^T Q P) per course (``trajGenerator.cost``: without the gamma term)."""
+        return self._cost[: self.K].cpu().numpy()
+
+    @property
+    def evals(self) -> np.ndarray:
+        return self._evals[: self.K].cpu().numpy()
+
+    @property
+    def status(self) -> np.ndarray:
+        return self._status[: self.K].cpu().numpy()
+
+    def coeffs_of(self, k: int) -> np.ndarray:
+        """[n_seg*10, 3], as ``trajGenerator.coeffs``."""
+        ns = int(self._n_seg[k])
+        return self.coeffs[: ns * 30, k].cpu().numpy().reshape(ns * 10, 3)
+
+    def T_of(self, k: int) -> np.ndarray:
+        """[n_seg]: the segment times themselves (``np.diff(TS_of(k))`` loses their last bits)."""
+        return self.seg_times[: int(self._n_seg[k]), k].cpu().numpy()
+
+    def TS_of(self, k: int) -> np.ndarray:
+        """[n_seg+1], as ``trajGenerator.TS``."""
+        return self.ts[: int(self._n_seg[k]) + 1, k].cpu().numpy()
+
+
+class BankTrajectoryTargets(Targets):
+    """:class:`TrajectoryTargets` with a course per drone: drone d (the caller's numbering) flies course ``traj_id[d]`` of a
+    :class:`TrajectoryBank` (``None``: course d, which needs ``bank.K == n``), from its own time ``t0[d]`` and with its own
+    position ``offsets[d]`` (dsim_traj_sample_bank).  Call :meth:`sample` once per control step, then pass the object as
+    ``targets``."""
+
+    def __init__(self, ctx: Context, n: int, bank: TrajectoryBank, traj_id=None, t0=None, offsets=None, layout: str = "soa",
+                 pad: int = 256):
+        super().__init__(ctx, n, layout, pad=pad)
+        self._const, self._period, self._hint_ok = {}, {}, False      # every field is written on the device (dsim_traj_sample_bank)
+        self.ctx, self.bank = ctx, bank
+        dev = ctx.device
+        if traj_id is None:
+            if bank.K != n:
+                raise ValueError(f"traj_id=None needs one course per drone: the bank holds {bank.K}, the fleet {n}")
+            traj_id = None if self.order is None else np.arange(n, dtype=np.int32)     # (stored type-major: slot s flies course drone[s])
+        self.traj_id = None
+        if traj_id is not None:
+            ids = np.zeros(self.n_pad, dtype=np.int32)
+            tid = np.asarray(traj_id, dtype=np.int32)                  # (per-drone arrays: storage order)
+            ids[:n] = tid if self.order is None else self.order.to_storage_np(tid)
+            self.traj_id = torch.from_numpy(ids).to(dev)
+        self.t = torch.zeros((self.n_pad,), dtype=torch.float64, device=dev)
+        if t0 is not None:
+            t0 = np.asarray(t0, dtype=np.float64)
+            self.t[:n] = torch.from_numpy(t0 if self.order is None else self.order.to_storage_np(t0)).to(dev)
+        self.yaw_state = torch.zeros((3, self.n_pad), dtype=torch.float64, device=dev)
+        self.offsets = None
+        if offsets is not None:
+            o = np.zeros((3, self.n_pad), dtype=np.float32)
+            off = np.asarray(offsets, dtype=np.float32)
+            o[:, :n] = (off if self.order is None else self.order.to_storage_np(off)).T
+            self.offsets = torch.from_numpy(o).to(dev)
+
+    def sample(self, dt_advance: float) -> None:
+        """targets <- get_des_state(t) of each drone's own course; t += dt_advance."""
+        nat.check(self.ctx.lib.dsim_traj_sample_bank(
+            self.ctx.handle, self.ctx.stream_ptr(), self.n, ctypes.byref(self.bank.c),
+            self.traj_id.data_ptr() if self.traj_id is not None else None, self.t.data_ptr(), float(dt_advance),
+            self.yaw_state.data_ptr(), self.offsets.data_ptr() if self.offsets is not None else None, self.view()))

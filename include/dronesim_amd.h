@@ -46,7 +46,9 @@ extern "C" {
                               dsim_obstacle_clearance, dsim_obstacle_grid, DSIM_Q_OBSTACLE_CONTACTS; the depth camera,
                               dsim_obstacle_ray_grid_plan / _build, dsim_obstacles_enable_rays, dsim_depth_image, dsim_camera_params,
                               DSIM_CAM_*, DSIM_SEG_GROUND; the other drones in the camera's images, dsim_depth_image_drones,
-                              dsim_depth_image_drones_workspace, dsim_camera_drones, DSIM_SEG_DRONE */
+                              dsim_depth_image_drones_workspace, dsim_camera_drones, DSIM_SEG_DRONE; the trajectory bank,
+                              dsim_trajgen, dsim_trajgen_workspace, dsim_traj_sample_bank, dsim_traj_bank, dsim_trajgen_args,
+                              DSIM_TRAJGEN_* */
 #define DSIM_MAX_ACT 6     /* actuators per vehicle (quad 4, morphing hexa 6) */
 #define DSIM_MAX_TYPES 8
 
@@ -490,6 +492,84 @@ int dsim_observe(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, const 
 int dsim_traj_sample(dsim_ctx* ctx, void* stream, int64_t n, const double* coeffs, const double* ts,
                      int32_t n_seg, double* t, double dt_advance, double* yaw_state, const float* offset,
                      dsim_view targets_out);
+
+/* ---- trajectory bank: a course per drone --------------------------------------------------------------------------
+ * K min-snap courses side by side in caller-owned device memory, all fp64, course-minor ("K_pad apart") so that lanes
+ * with neighbouring courses read neighbouring words:
+ *     coeffs[((seg * 10 + j) * 3 + d) * K_pad + k]    seg < L_max - 1, j < 10 ascending powers, d < 3
+ *     ts[seg * K_pad + k]                             seg < L_max: the reference's TS, cumulative, ts[0] = 0
+ *     n_seg[k]                                        int32, 1 .. L_max - 1; 0 marks a course that could not be made
+ * K_pad: a multiple of 64, >= K.  2 <= L_max <= DSIM_TRAJGEN_LMAX (n_seg <= 8).  Entries of segments past a course's own
+ * n_seg hold NaN.  Bytes: 240 (L_max - 1) + 8 L_max + 4 per course, 2 236 at L_max = 9.                                 */
+#define DSIM_TRAJGEN_LMAX 9
+typedef struct dsim_traj_bank {
+  int64_t  K, K_pad;
+  int32_t  L_max;
+  int32_t  _pad;
+  double*  coeffs;
+  double*  ts;
+  int32_t* n_seg;
+} dsim_traj_bank;
+
+/* trajGenerator.__init__ (dronesim/utils/trajGen.py:13-106, trajutils.py:13-36) for K courses in one launch: one lane per
+ * course.  Course k: n_wp[k] waypoints wp[(l * 3 + d) * K_pad + k] (2 <= n_wp[k] <= L_max), one max_vel and gamma for all.
+ *   Tmin_i = |wp[i+1] - wp[i]| / max_vel (trajGen.py:33-34); segment times T by mode:
+ *     DSIM_TRAJGEN_GIVEN     bank->ts holds the cumulative times on entry and is left as it is;
+ *     DSIM_TRAJGEN_TMIN      T = Tmin;
+ *     DSIM_TRAJGEN_OPTIMIZE  minimises J(T) = trace(P^T Q P) + gamma sum(T) subject to T >= Tmin (trajGen.py:27-40).
+ *   coeffs = MinimizeSnap(T) (trajGen.py:45-106): order 10, positions at both ends of every segment, derivatives 1-4
+ *   continuous, at rest at both ends, the 4 (L - 2) interior derivatives free and chosen to minimise the cost; L = 2 has none.
+ * The reference inverts the dense 10 n_seg-square constraint matrix.  Here a segment's cost is the quadratic form of its
+ * scaled end values in ONE constant 10 x 10 matrix (a table, exact rationals rounded once) over T^7, and the interior
+ * derivatives solve a symmetric positive definite block-tridiagonal system of 4 x 4 blocks: one sweep along the course in
+ * registers gives J (that is an evaluation of the search: a few hundred flops per segment), a second sweep back gives the
+ * coefficients.  Each segment is solved for p(t) - wp[seg], which costs the same.
+ * The reference searches T with scipy's COBYLA; this search is a greedy multiplicative pattern search, deterministic and
+ * derivative-free: from x = Tmin and step = 0.5, sweep i and try y_i = max(Tmin_i, x_i (1 + step)), then
+ * max(Tmin_i, x_i / (1 + step)) (a y_i equal to x_i is skipped); J(y) < J(x) is accepted at once and the sweep moves to
+ * i + 1; a sweep that accepted nothing halves step; it ends at step <= 1e-4 or after max_evals evaluations of J (>= 1; the
+ * first is J(Tmin), so max_evals = 1 returns Tmin).  It reaches the reference's J to parts in 1e9 on the fixture courses
+ * (tests/README_trajgen.md); T itself agrees to about 1e-3, the minimum is flat.
+ * Out: bank->coeffs, ->ts (not in GIVEN), ->n_seg; cost[k] = trace(P^T Q P) without the gamma term (trajGenerator.cost);
+ * evals[k] = evaluations of J the search spent (0 in GIVEN / TMIN); status[k] = 0, or DSIM_TRAJGEN_BAD_* for a course that
+ * cannot be made — n_wp[k] out of [2, L_max], a non-finite waypoint, a zero-length segment (the reference's matrix is singular
+ * there), in GIVEN a time step that is not positive and finite — whose coeffs, ts and cost are NaN and n_seg 0.  The other
+ * courses of the launch are not affected.  cost, evals, status: [K_pad].  seg_times (nullable) receives the segment times
+ * the coefficients were made for, NaN past n_seg and for such a course: T >= Tmin holds for them exactly.
+ * workspace: dsim_trajgen_workspace(K_pad, L_max) fp64 entries (22 (L_max - 2) K_pad: what the sweep back needs of the
+ * sweep along), the call's until it has run; may be NULL at L_max = 2.  Stream-ordered, allocates and synchronises nothing.
+ * DSIM_E_ARG, nothing enqueued: a null pointer, K < 1, K_pad < K or no multiple of 64, L_max outside [2, DSIM_TRAJGEN_LMAX],
+ * max_vel / gamma not finite or max_vel <= 0, an unknown mode, max_evals < 1, a workspace too small.                    */
+enum { DSIM_TRAJGEN_GIVEN = 0, DSIM_TRAJGEN_TMIN = 1, DSIM_TRAJGEN_OPTIMIZE = 2 };
+enum { DSIM_TRAJGEN_BAD_COUNT = 1, DSIM_TRAJGEN_BAD_WAYPOINT = 2, DSIM_TRAJGEN_BAD_SEGMENT = 3, DSIM_TRAJGEN_BAD_TIME = 4 };
+typedef struct dsim_trajgen_args {
+  const double*  wp;
+  const int32_t* n_wp;
+  double   max_vel, gamma;
+  int32_t  mode;
+  int32_t  max_evals;       /* the search's cap on evaluations of J (2000 is ample: the fixture courses take 14 .. 539) */
+  double*  cost;
+  int32_t* evals;
+  int32_t* status;
+  double*  seg_times;       /* nullable [L_max - 1][K_pad]: T itself, seg_times[seg * K_pad + k] (differences of ts lose its last bits) */
+  double*  workspace;
+  int64_t  workspace_len;
+} dsim_trajgen_args;
+int64_t dsim_trajgen_workspace(int64_t K_pad, int32_t L_max);
+int dsim_trajgen(dsim_ctx* ctx, void* stream, const dsim_traj_bank* bank, const dsim_trajgen_args* args);
+
+/* dsim_traj_sample with a course per drone: drone i samples course traj_id[i] of the bank (traj_id: device int32 [n_pad];
+ * NULL = the identity, which needs bank->K >= n).  Everything else — t, dt_advance, yaw_state, offset, the clamp past the
+ * end, the segment search, fp64 polynomials, the stateful yaw rule and its NaN at zero horizontal velocity — is
+ * dsim_traj_sample's, statement by statement: with one course the two calls write the same bits.
+ * A drone whose traj_id is outside [0, K), or whose course has n_seg outside [1, L_max - 1], gets NaN in all ten target
+ * fields and in its yaw_state; a course with NaN ts gives NaN targets through the arithmetic.  Nothing is read out of bounds.
+ * Bytes: a drone reads the 30 fp64 coefficients of its segment per sample, 240 B, besides its 8 B of t, 24 B of
+ * yaw_state and up to 8 L_max of ts — more than the 168 B per drone of the fused step itself.  With K = n that comes from HBM,
+ * uncoalesced only in that neighbouring drones may sit in different segments; with courses shared among drones it is served
+ * from L2. */
+int dsim_traj_sample_bank(dsim_ctx* ctx, void* stream, int64_t n, const dsim_traj_bank* bank, const int32_t* traj_id,
+                          double* t, double dt_advance, double* yaw_state, const float* offset, dsim_view targets_out);
 
 /* The same rows as dsim_observe, written field-major: SoA [obs_width][n_pad] (coalesced), the slab a
  * device-side Logger appends per step (dronesim/utils/Logger.py:117-139 stores exactly this vector). */
