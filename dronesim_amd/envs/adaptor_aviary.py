@@ -38,18 +38,14 @@ class _AdaptorAviary(CtrlAviary):
             nat.check(self.ctx.lib.dsim_step_adaptor(self.ctx.handle, self.ctx.stream_ptr(), self.NUM_DRONES, plan.state_view,
                                                      action.data_ptr(), self._MODE, plan.echo_ptr, plan.args_ref))
             self._use_last_action = True
-            self.step_counter += self.AGGR_PHY_STEPS
-            self._env_steps += 1
-            self._watch_after_step()
+            self._stepped()
             return plan.out, self._computeReward(), self._computeDone(), plan.info
         args = self.step_args(self.AGGR_PHY_STEPS * self.TIMESTEP)
         # A homogeneous fleet in whole tiles steps in ONE launch that takes the action as the caller holds it ([N, 4] rows
         # on the device: no transpose) and writes Env.step's observation rows itself (k_adaptor_fast).
         one_launch = (not self.dict_io and self.order is None and len(self.types) == 1 and self.state.n_pad % 256 == 0
                       and not self.ground_plane and self._type_id is None)
-        rows_in = (one_launch and isinstance(action, torch.Tensor) and action.dtype == torch.float32 and action.is_contiguous()
-                   and action.device == self.ctx.device and tuple(action.shape) == (self.NUM_DRONES, 4)
-                   and action.data_ptr() % 16 == 0)
+        rows_in = one_launch and self._is_action_rows(action)
         if rows_in:
             args.options |= nat.OPT_ACTION_ROWS
             act_ptr = action.data_ptr()
@@ -64,9 +60,7 @@ class _AdaptorAviary(CtrlAviary):
                                                  self.state.view(), act_ptr, self._MODE,
                                                  self._last_action.data_ptr(), ctypes.byref(args)))
         self._use_last_action = True
-        self.step_counter += self.AGGR_PHY_STEPS
-        self._env_steps += 1
-        self._watch_after_step()
+        self._stepped()
         out = self._computeObs(obs)
         self._step_plan = None
         if rows_in and out is obs:

@@ -56,10 +56,7 @@ class FusedGraph:
                             self._args.ext_force = dw.compute().data_ptr()
                             self._args.bin_next = dw.bin_next_ptr() if i + 1 < steps else None
                         nat.check(lib.dsim_step(h, sp, n, self._sview, self._tview, ctypes.byref(self._args)))
-                        if env._obst is not None:          # the static-obstacle watch: one query behind every step, as in eager mode
-                            env._watch_obstacles()
-                        if env._vision is not None:        # the depth camera at a cadence of 1: one capture behind every step
-                            env._vision_capture()
+                        env._captured_step()               # the obstacle watch's query and the camera's capture, as in eager mode
                 finally:
                     if dw is not None:
                         dw._box_refresh = refresh
@@ -68,10 +65,7 @@ class FusedGraph:
                         # the captured launches hold these addresses: an eager step that later re-measures the box and
                         # outgrows the workspace allocates a new one — this one must outlive the graph
                         self._keepalive = (dw._ws, dw.force, dw.type_id)
-                    if env._vision is not None:
-                        # the captured captures hold the camera's addresses, among them the workspace of the drones' grid: an eager
-                        # capture that later re-measures the box and outgrows it allocates a new one — this one must outlive the graph
-                        self._keepalive_vision = env._vision.graph_keepalive()
+                    self._keepalive_vision = env._capture_keepalive()
                 nat.check(lib.dsim_counter_add(h, sp, self._counter.data_ptr(), steps))
         torch.cuda.current_stream(dev).wait_stream(side)
         self._counter_host = 0
@@ -91,4 +85,4 @@ class FusedGraph:
         env._fused_plan = None
         env.step_counter += env.AGGR_PHY_STEPS * self.steps
         env._env_steps += self.steps
-        env._vision_seen = env.step_counter
+        env._replayed()

@@ -1,7 +1,8 @@
 """The observation side of the fleet env: the 20/22-wide state vectors of ``_getDroneStateVector`` (BaseAviary.py:764-790),
 ``_computeObs`` in the reference's dict form for small fleets and as device tensors for large ones (CtrlAviary.py:225-232),
 and the neighbour lists that stand in for the reference's dense adjacency rows (BaseAviary.py:901-921).  A mix-in of
-``CtrlAviary``: it uses the env's attributes as they are."""
+``CtrlAviary``: it uses the env's attributes as they are.  (The contact watches are no observation: drone_clearance() lives in
+watches.py.)"""
 from __future__ import annotations
 
 from typing import NamedTuple, Optional
@@ -68,34 +69,11 @@ class FleetObservation:
             self._downwash.invalidate_prebin()            # the adjacency pass re-uses the ctx's grid bookkeeping
         k = self.neighbors_k if max_k is None else int(max_k)
         cnt, lst = self._adjacency.adjacency(float(self.NEIGHBOURHOOD_RADIUS), max_k=k)
-        if self.order is not None:              # per-slot results of slot indices -> per-drone results of drone indices
+        if self.order is not None:
             cnt = self.order.to_caller(cnt, 0)
             if lst is not None:
-                lst = self.order.to_caller(lst, 1).long()
-                lst = torch.where(lst >= 0, self.order.drone[lst.clamp(min=0)], lst).to(torch.int32)
+                lst = self.order.indices_to_caller(lst, 1)
         return cnt, lst
-
-    def drone_clearance(self, margin: float = 1.0):
-        """Per-drone clearance of the CURRENT state between the vehicles' bounding spheres (dsim_clearance; no counterpart in
-        the reference, whose Bullet world makes the vehicles collide instead): (clearance [N] float32, nearest [N] int32) in
-        the caller's numbering — clearance[i] = min(margin, min_j |p_i - p_j| - R_i - R_j), nearest[i] = the drone that
-        attains it, -1 when none is closer than ``margin``.  Negative clearance: the two spheres overlap."""
-        if self._clr_on_demand is None:
-            self._clr_on_demand = torch.zeros((1,), dtype=torch.int64, device=self.ctx.device)
-        return self._drone_query(float(margin), self._clr_on_demand)
-
-    def _drone_query(self, margin: float, pairs_out):
-        from ..downwash import Downwash
-        if self._clearance is None:
-            self._clearance = Downwash(self.ctx, self.state, self._type_id, None)
-        if self._downwash is not None:
-            self._downwash.invalidate_prebin()            # the clearance pass re-uses the ctx's grid bookkeeping
-        clr, near = self._clearance.clearance(margin, pairs_out=pairs_out)
-        if self.order is not None:              # per-slot results of slot indices -> per-drone results of drone indices
-            clr = self.order.to_caller(clr, 0)
-            near = self.order.to_caller(near, 0).long()
-            near = torch.where(near >= 0, self.order.drone[near.clamp(min=0)], near).to(torch.int32)
-        return clr, near
 
     def _getAdjacencyMatrix(self, pos: np.ndarray) -> np.ndarray:
         """BaseAviary.py:901-921 — O(N^2), only produced in dict mode (small fleets)."""

@@ -1,0 +1,284 @@
+"""The services that follow every step of the fleet env on its stream: the drone-drone contact watch (``drone_watch``), the
+static-obstacle watch (``obstacle_watch``) and the depth camera (``vision_attributes``).  Their keywords, set-up, state and public
+calls, the one epilogue of a launch (``_stepped``) and the four hooks a captured sequence goes through (``_capture_prepare``,
+``_captured_step``, ``_capture_keepalive``, ``_replayed``).  A mix-in of ``CtrlAviary``: it uses the env's attributes as they are."""
+from __future__ import annotations
+
+from typing import Optional
+
+import numpy as np
+import torch
+
+from .. import _native as nat
+
+
+class StepWatches:
+    # (class-level "nothing on": an env made without __init__ steps with no service behind it)
+    _drone_watch = False          # the drone-drone contact watch behind every step (set by _watch_options)
+    _obst = None                  # the static-obstacle watch's device set (set by _watch_setup)
+    _vision = None                # the depth camera of vision_attributes=True (set by _watch_setup)
+
+    # ------------------------------------------------------------------ construction
+    def _watch_options(self, *, num_drones, freq, aggregate_phy_steps, dist, drone_watch, drone_watch_margin, obstacle_watch,
+                       obstacle_margin, vision_attributes, vision_scene, vision_drones, vision_res, vision_ground,
+                       vision_see_drones, vision_drone_range) -> None:
+        """The services' keywords of ``CtrlAviary.__init__``: checked and stashed (the set-up follows in _watch_setup, when the
+        context and the storage order exist)."""
+        # The reference's Bullet world lets the vehicles' collision shapes act on each other; here every drone is integrated
+        # alone.  drone_watch=True: every step / step_fused / adaptor step is followed, on the env's stream, by one
+        # dsim_clearance on the state it left (once per Env.step, like the ground watch): drone_contacts() reports how many
+        # pairs of bounding spheres overlapped so far, last_clearance holds (clearance, nearest) of the last step
+        # (drone_clearance()).  Off by default: nothing is launched.
+        if drone_watch and dist is not None and dist.is_initialized() and dist.get_world_size() > 1:
+            raise NotImplementedError("drone_watch on a sharded fleet: the radii of the other ranks' drones would have to travel "
+                                      "with their positions (Downwash.clearance takes world_pos / world_radius)")
+        self._drone_watch, self._drone_watch_margin = bool(drone_watch), float(drone_watch_margin)
+        self.last_clearance = None
+        self._clearance = None    # grid for drone_clearance(), built on first use
+        self._clr_on_demand = None    # int64 [1]: pairs the on-demand queries counted (not Env.steps: drone_contacts() leaves them out)
+        # The reference's Bullet world also holds static bodies (p.loadURDF of a gate); here they act on nothing.
+        # obstacle_watch=ObstacleSet: every step / step_fused / adaptor step is followed, on the env's stream, by one
+        # dsim_obstacle_clearance on the state it left (once per LAUNCH: a step_fused with n_steps > 1 is sampled once, at its end);
+        # obstacle_contacts() reports the drone x Env.step count, last_obstacle_clearance the tensors of the last step.
+        # obstacle_offsets [N, 3] (the caller's numbering): the set lies in the frame of each drone's task, p_i - offset_i.
+        # Set up at the end of __init__ (_obstacle_setup), when the context and the storage order exist.
+        self._obst_set, self._obst_margin, self._obst = obstacle_watch, float(obstacle_margin), None
+        # BaseAviary(vision_attributes=True) keeps self.rgb / self.dep / self.seg per drone at IMG_RES = [64, 48] and refreshes them
+        # from _getDroneImages whenever step_counter % IMG_CAPTURE_FREQ == 0 (BaseAviary.py:236-261, 453-502, 794-853).  Here:
+        # env.dep / env.seg ([n, H, W] device tensors; no rgb) of the static world `vision_scene` (default: the obstacle_watch
+        # set, whose device copy the camera then shares), captured on the env's stream behind the step the cadence names; a
+        # step_fused launch with n_steps > 1 captures once, at its end, when a capture fell due inside it.  vision_drones: the
+        # drones that carry a camera (the caller's numbering; None: all).  The set lies in the frame of obstacle_offsets.  The
+        # other drones are not drawn unless vision_see_drones=True (vision_drones already says who carries a camera): then every
+        # other drone appears in dep and seg as its bounding sphere, up to vision_drone_range metres (None: the far plane), seg
+        # naming drone k of the caller's numbering as -3 - k (DepthCamera.seg_drone); the camera's own drone is never drawn, and
+        # vision_scene becomes optional (a world of drones and the plane).  Checked here, set up at the end of __init__
+        # (_vision_setup).
+        if vision_see_drones and dist is not None and dist.is_initialized() and dist.get_world_size() > 1:
+            raise NotImplementedError("vision_see_drones on a sharded fleet: the radii of the other ranks' drones would have to "
+                                      "travel with their positions (dsim_depth_image_drones takes pos_all / radius_all)")
+        if (vision_see_drones or vision_drone_range is not None) and not vision_attributes:
+            raise ValueError("vision_see_drones / vision_drone_range without vision_attributes=True")
+        if vision_drone_range is not None and not vision_see_drones:
+            raise ValueError("vision_drone_range without vision_see_drones=True")
+        if vision_drone_range is not None and not float(vision_drone_range) > 0.0:
+            raise ValueError("vision_drone_range must be positive")
+        self._vision_args = None
+        if vision_attributes:
+            self.IMG_RES = np.array([int(vision_res[0]), int(vision_res[1])])
+            self.IMG_FRAME_PER_SEC = 24
+            self.IMG_CAPTURE_FREQ = int(freq) // self.IMG_FRAME_PER_SEC
+            if self.IMG_CAPTURE_FREQ < 1 or self.IMG_CAPTURE_FREQ % int(aggregate_phy_steps) != 0:
+                raise ValueError(f"aggregate_phy_steps = {aggregate_phy_steps} is incompatible with the image capture rate of "
+                                 f"{self.IMG_FRAME_PER_SEC} Hz at freq = {freq}: IMG_CAPTURE_FREQ = {self.IMG_CAPTURE_FREQ} physics "
+                                 "steps must be a positive multiple of it (BaseAviary.py:247-253)")
+            if not (1 <= self.IMG_RES[0] <= 1024 and 1 <= self.IMG_RES[1] <= 1024):
+                raise ValueError(f"vision_res must be (width, height) with 1 <= each <= 1024, got {vision_res!r}")
+            if vision_scene is None and obstacle_watch is None and not vision_see_drones:
+                raise ValueError("vision_attributes=True needs a world to look at: vision_scene=ObstacleSet (or obstacle_watch)")
+            if vision_drones is not None:
+                vd = np.asarray(vision_drones, dtype=np.int64).ravel()
+                if vd.size < 1 or vd.min() < 0 or vd.max() >= num_drones:
+                    raise ValueError(f"vision_drones must name drones in [0, {num_drones})")
+            self._vision_args = (vision_scene, vision_drones, bool(vision_ground), bool(vision_see_drones), vision_drone_range)
+        elif vision_scene is not None or vision_drones is not None:
+            raise ValueError("vision_scene / vision_drones without vision_attributes=True")
+
+    def _watch_setup(self, offsets) -> None:
+        """At the end of __init__: the obstacle set first, because the camera shares its device set."""
+        self._obstacle_setup(offsets)
+        self._vision_setup(offsets)
+
+    def _obstacle_setup(self, offsets) -> None:
+        """obstacle_watch: the device set for reach = R_max + margin, the offsets in storage order and the tensors every
+        per-step query writes (fixed addresses: a captured sequence holds them)."""
+        if self._obst_set is None:
+            if offsets is not None and self._vision_args is None:
+                raise ValueError("obstacle_offsets without obstacle_watch")
+            return
+        from .. import obstacles as obs
+        if not isinstance(self._obst_set, obs.ObstacleSet):
+            raise TypeError("obstacle_watch takes an ObstacleSet")
+        if not self._obst_margin > 0.0:
+            raise ValueError("obstacle_margin must be positive")
+        dev, n_pad = self.ctx.device, self.state.n_pad
+        self._obst_off = None
+        if offsets is not None:
+            offsets = np.asarray(offsets, dtype=np.float64)
+            if offsets.shape != (self.NUM_DRONES, 3):
+                raise ValueError(f"obstacle_offsets must be [{self.NUM_DRONES}, 3]")
+            self._obst_off = self._soa3(offsets)
+        self._obst = self._obst_set.to_device(self.ctx, obs.watch_reach(self.ctx.types, self._obst_margin))
+        self._obst_clr = torch.empty((n_pad,), dtype=torch.float32, device=dev)
+        self._obst_near = torch.empty((n_pad,), dtype=torch.int32, device=dev)
+        self._obst_on_demand = torch.zeros((1,), dtype=torch.int64, device=dev)    # what on-demand queries counted
+        self._obst_sampled = False
+
+    def _vision_setup(self, offsets) -> None:
+        """vision_attributes=True: the camera, its device set (shared with the obstacle watch when both look at the same
+        ObstacleSet) and env.dep / env.seg."""
+        if self._vision_args is None:
+            return
+        from ..camera import DepthCamera
+        scene, drones, ground, see_drones, drone_range = self._vision_args
+        shared = self._obst is not None and (scene is None or scene is self._obst_set)
+        self._vision = DepthCamera(self.ctx, self.state, self._obst if shared else scene, res=tuple(int(v) for v in self.IMG_RES),
+                                   ground=ground, cameras=drones, offsets=offsets, type_id=self._type_id, drones=see_drones,
+                                   drone_range=drone_range)
+        self.dep, self.seg = self._vision.dep, self._vision.seg
+        self.dep.fill_(1.0)                # nothing seen yet (BaseAviary.py:245 starts from ones too)
+        self.seg.fill_(-1)
+
+    def _watch_reset(self) -> None:
+        """_housekeeping: the step counter is back at zero, and so is the last one the camera's cadence saw."""
+        self._vision_seen = 0
+
+    def _watch_close(self) -> None:
+        if self._vision is not None:
+            self._vision.close()
+        if self._obst is not None:
+            self._obst.close()
+
+    # ------------------------------------------------------------------ behind a step
+    def _stepped(self, n_steps: int = 1) -> None:
+        """The epilogue of every launch of ``n_steps`` Env.steps (step, step_fused and the adaptor envs' step, fresh or from a
+        prepared plan): the counters move on, then the watches run on the state the launch just left and on the env's stream:
+        one dsim_clearance with drone_watch=True, one dsim_obstacle_clearance with obstacle_watch, the camera when it is due."""
+        self.step_counter += self.AGGR_PHY_STEPS * n_steps
+        self._env_steps += n_steps
+        if self._drone_watch:
+            self.last_clearance = self._drone_query(self._drone_watch_margin, None)
+        if self._obst is not None:
+            self._watch_obstacles()
+        if self._vision is not None:
+            # due when a multiple of IMG_CAPTURE_FREQ lies in (the counter before the launch, the counter now]: for a launch of
+            # one Env.step that is step_counter % IMG_CAPTURE_FREQ == 0 (BaseAviary.py:483)
+            f = self.IMG_CAPTURE_FREQ
+            due = self.step_counter // f > self._vision_seen // f
+            self._vision_seen = self.step_counter
+            if due:
+                self._vision_capture()
+
+    def _drone_query(self, margin: float, pairs_out):
+        from ..downwash import Downwash
+        if self._clearance is None:
+            self._clearance = Downwash(self.ctx, self.state, self._type_id, None)
+        if self._downwash is not None:
+            self._downwash.invalidate_prebin()            # the clearance pass re-uses the ctx's grid bookkeeping
+        clr, near = self._clearance.clearance(margin, pairs_out=pairs_out)
+        if self.order is not None:
+            clr, near = self.order.to_caller(clr, 0), self.order.indices_to_caller(near, 0)
+        return clr, near
+
+    def _watch_obstacles(self) -> None:
+        """One dsim_obstacle_clearance on the state the step just left, on the env's stream (also under capture)."""
+        from .. import obstacles as obs
+        obs.query(self.ctx, self.state, self._obst, self._obst_margin, self._obst_clr, self._obst_near, self._obst_off,
+                  self._type_id)
+        self._obst_sampled = True
+
+    def _vision_capture(self):
+        if self._vision.drones and self._downwash is not None:
+            self._downwash.invalidate_prebin()            # the drones' binning drops the ctx's grid bookkeeping
+        return self._vision.capture()
+
+    # ------------------------------------------------------------------ a captured sequence (capture_fused / FusedGraph)
+    def _capture_prepare(self) -> None:
+        """Before the capture: what cannot be part of a graph is refused, and each service's kernel runs once eagerly."""
+        if self._drone_watch:
+            raise NotImplementedError("graph capture with drone_watch: the watch re-measures its grid's box on the host from "
+                                      "time to time, which a captured sequence cannot")
+        if self._obst is not None:
+            self.obstacle_clearance()     # (eager, not an Env.step: the watch's kernel is loaded before the capture starts)
+        if self._vision is not None:
+            if self.IMG_CAPTURE_FREQ != self.AGGR_PHY_STEPS:
+                raise NotImplementedError(f"graph capture with vision_attributes: the images are due every "
+                                          f"{self.IMG_CAPTURE_FREQ // self.AGGR_PHY_STEPS} Env.steps, and a captured sequence is captured "
+                                          "at any length; only a cadence of 1 (IMG_CAPTURE_FREQ == AGGR_PHY_STEPS) is part of the graph")
+            # (eager: the camera's kernel is loaded before the capture starts; with vision_see_drones this capture also measures the
+            # box of the drones' grid and makes its workspace, which stand for the whole graph)
+            if self._vision.drones:
+                self._vision.refresh_drone_box()
+            self._vision_capture()
+
+    def _captured_step(self) -> None:
+        """Behind every captured step, as in eager mode: the obstacle watch's query, then the camera at its cadence of 1."""
+        if self._obst is not None:
+            self._watch_obstacles()
+        if self._vision is not None:
+            self._vision_capture()
+
+    def _capture_keepalive(self):
+        """After the capture: what the graph must keep alive.  The captured captures hold the camera's addresses, among them the
+        workspace of the drones' grid: an eager capture that later re-measures the box and outgrows it allocates a new one."""
+        return self._vision.graph_keepalive() if self._vision is not None else ()
+
+    def _replayed(self) -> None:
+        """After a replay (the env's counters moved on already): the camera saw every step of it."""
+        self._vision_seen = self.step_counter
+
+    # ------------------------------------------------------------------ public surface
+    def drone_clearance(self, margin: float = 1.0):
+        """Per-drone clearance of the CURRENT state between the vehicles' bounding spheres (dsim_clearance; no counterpart in
+        the reference, whose Bullet world makes the vehicles collide instead): (clearance [N] float32, nearest [N] int32) in
+        the caller's numbering — clearance[i] = min(margin, min_j |p_i - p_j| - R_i - R_j), nearest[i] = the drone that
+        attains it, -1 when none is closer than ``margin``.  Negative clearance: the two spheres overlap."""
+        if self._clr_on_demand is None:
+            self._clr_on_demand = torch.zeros((1,), dtype=torch.int64, device=self.ctx.device)
+        return self._drone_query(float(margin), self._clr_on_demand)
+
+    def drone_contacts(self) -> int:
+        """Pairs of drones x Env.steps so far whose bounding spheres (DroneType.collision_sphere) overlapped behind a step
+        of a ``drone_watch=True`` env (cumulative over this env's context; synchronises the stream).  The reference's
+        Bullet world lets the vehicles' collision shapes act on each other; here contact between drones is not modelled,
+        and a non-zero count means part of the flight lies outside the domain in which trajectories are comparable with
+        the reference.  One-sided: 0 certifies that no two vehicles touched; overlapping spheres need not be touching
+        shapes.  On-demand drone_clearance() calls are not Env.steps and are left out."""
+        seen = self.ctx.query(nat.QUERY_DRONE_CONTACTS)
+        return seen - (int(self._clr_on_demand.item()) if self._clr_on_demand is not None else 0)
+
+    @property
+    def last_obstacle_clearance(self):
+        """(clearance [N] float32, nearest body [N] int32) behind the last step of an ``obstacle_watch`` env, in the
+        caller's numbering; None before the first step."""
+        if self._obst is None or not self._obst_sampled:
+            return None
+        return self._obst_to_caller(self._obst_clr, self._obst_near)
+
+    def _obst_to_caller(self, clr, near):
+        clr, near = clr[: self.NUM_DRONES], near[: self.NUM_DRONES]
+        if self.order is not None:
+            clr, near = self.order.to_caller(clr, 0), self.order.to_caller(near, 0)
+        return clr, near
+
+    def obstacle_contacts(self) -> int:
+        """Drones x sampled Env.steps so far whose bounding sphere (DroneType.collision_sphere) overlapped a triangle of the
+        ``obstacle_watch`` set (cumulative over this env's context; synchronises the stream).  The reference's Bullet world
+        makes a vehicle collide with the static bodies loaded into it; here they act on nothing, and a non-zero count means
+        part of the flight lies outside the domain in which trajectories are comparable with the reference.  One-sided:
+        0 certifies that no bounding sphere touched a triangle at the sampled states; an overlapping sphere need not be a
+        touching shape.  A step_fused launch with n_steps > 1 is sampled once, at its end.  On-demand
+        obstacle_clearance() calls are not Env.steps and are left out."""
+        seen = self.ctx.query(nat.QUERY_OBSTACLE_CONTACTS)
+        return seen - (int(self._obst_on_demand.item()) if self._obst is not None else 0)
+
+    def obstacle_clearance(self, margin: Optional[float] = None):
+        """Per-drone clearance of the CURRENT state to the ``obstacle_watch`` set (dsim_obstacle_clearance): (clearance [N]
+        float32, nearest [N] int32) in the caller's numbering — clearance[i] = min(margin, min_t dist(p_i - offset_i,
+        triangle t) - R_i), nearest[i] = the body of the triangle that attains it, -1 when none is closer than ``margin``
+        (default: the env's obstacle_margin, which is also the largest the device set serves).  Not counted as an Env.step."""
+        if self._obst is None:
+            raise ValueError("obstacle_clearance() needs an env made with obstacle_watch=ObstacleSet")
+        from .. import obstacles as obs
+        margin = self._obst_margin if margin is None else float(margin)
+        clr = torch.empty((self.state.n_pad,), dtype=torch.float32, device=self.ctx.device)
+        near = torch.empty((self.state.n_pad,), dtype=torch.int32, device=self.ctx.device)
+        obs.query(self.ctx, self.state, self._obst, margin, clr, near, self._obst_off, self._type_id, self._obst_on_demand)
+        return self._obst_to_caller(clr, near)
+
+    def drone_images(self):
+        """(dep, seg) of the CURRENT state, captured now on the env's stream into env.dep / env.seg (BaseAviary._getDroneImages
+        for every camera drone at once): float32 depth-buffer values and int32 body indices [n, H, W]."""
+        if self._vision is None:
+            raise ValueError("drone_images() needs an env made with vision_attributes=True")
+        return self._vision_capture()

@@ -136,6 +136,11 @@ class StorageOrder:
     def to_caller(self, values: torch.Tensor, dim: int = -1) -> torch.Tensor:
         return values.index_select(dim, self.slot.to(values.device))
 
+    def indices_to_caller(self, slots: torch.Tensor, dim: int = -1) -> torch.Tensor:
+        """Per-slot results that hold slot indices (negative: none) -> per-drone results that hold drone indices, int32."""
+        x = self.to_caller(slots, dim).long()
+        return torch.where(x >= 0, self.drone[x.clamp(min=0)], x).to(torch.int32)
+
     def to_storage_np(self, a: np.ndarray, axis: int = 0) -> np.ndarray:
         return np.take(a, self.drone_np, axis=axis)
 

@@ -31,6 +31,14 @@ def test_storage_order_is_a_stable_sort_by_type_and_its_maps_invert_each_other()
         rows = torch.arange(n * 5, dtype=torch.float32).reshape(n, 5)
         np.testing.assert_array_equal(o.to_caller(o.to_storage(rows, 0), 0).numpy(), rows.numpy())
         np.testing.assert_array_equal(o.to_storage_np(np.arange(n)), o.drone_np)
+        # per-slot results that hold slot indices (-1: none) -> per-drone results that hold drone indices, along any dim
+        near = np.where(np.arange(n) % 3 == 0, -1, np.random.default_rng(n).integers(0, n, n)).astype(np.int32)
+        per_drone = near[o.slot_np]
+        want = np.where(per_drone >= 0, o.drone_np[per_drone.clip(min=0)], -1)
+        got = o.indices_to_caller(torch.from_numpy(near), 0)
+        assert got.dtype == torch.int32
+        np.testing.assert_array_equal(got.numpy(), want)
+        np.testing.assert_array_equal(o.indices_to_caller(torch.from_numpy(np.stack([near, near])), 1).numpy(), np.stack([want, want]))
         # the noise key of a slot is the caller's index of the drone stored there; padding slots map to themselves
         did = o.drone_id(n + 37).numpy()
         np.testing.assert_array_equal(did[:n], o.drone_np)
