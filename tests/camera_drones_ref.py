@@ -313,3 +313,95 @@ def lattice_reference(rng, res=(64, 48)):
 # test_restated_sphere_error_is_what_is_recorded; the GPU tests grant the kernel 4 x this on pixels where a sphere wins
 SPHERE_RESTATED_WORST = 3.14e-7
 SPHERE_TOL = 4.0 * SPHERE_RESTATED_WORST
+
+
+# ---- the axis fleet: the edge table's rays against spheres (tests/test_gpu_camera_edges.py) ------------------------------------------
+AXIS_N = 128
+AXIS_CAMERA = 6                  # a tello (even numbers are tellos, odd ones up to 63 hexas: stored type-major)
+AXIS_EYE = (0.0, 0.0, 1.0)       # the camera drone's position
+AXIS_RANGE = 25.0                # cuts the 41 m group
+AXIS_RES = ((17, 17), (1, 33))
+# per viewing direction: depth -> the rows of the 1 x 33 image whose pixel-centre rays the drones there are laid on (row 16 is the
+# level ray, which is row 8 of 17 x 17 as well); the first of a depth lies exactly on the ray's line in xy, the second 0.125 m
+# beside it, a third on the line again
+_AXIS_ROWS = {"+": {7.0: (20, 11), 19.0: (18, 13), 41.0: (16, 15, 17)}, "-": {7.0: (20, 11), 19.0: (16, 13)}}
+_AXIS_SIDE = {7.0: (9, 6), 19.0: (7, 10), 41.0: (9, 11)}       # 17 x 17: (row, column) of one more drone per depth, off the zero column
+
+
+def axis_fleet():
+    """The edge table's four axis cameras (camera_ref.EDGE_QUATS, carried in turn by drone AXIS_CAMERA, a tello at AXIS_EYE) in
+    front of 32 hexa_6DOF_simple (R = 0.202 m) laid sparsely on and beside the lines x = 0 and y = 0 through the camera, about 7, 19
+    and 41 m away (41 m along +x and +y only), at the heights where pixel-centre rays of the zero column pass; 95 more tellos
+    scattered above.  Returns (stored [128, 7] float32 with the camera looking along +x, models [128], radius [128], info): info
+    names, per direction, the hexas by depth."""
+    L = cr.ARM["tello"]
+    st = np.zeros((AXIS_N, 7), dtype=np.float32)
+    st[:, 6] = 1.0
+    models = ["hexa_6DOF_simple" if (i % 2 == 1 and i < 64) else "tello" for i in range(AXIS_N)]
+    hexas = iter(range(1, 64, 2))
+    st[AXIS_CAMERA, :3] = AXIS_EYE
+    info = {}
+    for name, q, zero in cr.EDGE_QUATS:
+        eye, d33 = cr.camera_rays(AXIS_EYE, np.array(q, np.float32), L, 1, 33)
+        _, d17 = cr.camera_rays(AXIS_EYE, np.array(q, np.float32), L, 17, 17)
+        side = np.zeros(3)
+        side[zero] = 0.125
+        by_depth = {}
+        for D, rows in _AXIS_ROWS[name[0]].items():
+            pts = [eye + D * d33[r, 0] + (side if k == 1 else 0.0) for k, r in enumerate(rows)]
+            if name[0] == "+" or D < 41.0:
+                pts.append(eye + D * d17[_AXIS_SIDE[D]])
+            ids = []
+            for p in pts:
+                j = next(hexas)
+                st[j, :3] = p
+                ids.append(j)
+            assert st[ids[0], zero] == 0.0                     # exactly on the ray's line in xy
+            by_depth[D] = ids
+        info[name] = by_depth
+    assert next(hexas, None) is None
+    rest = [i for i in range(AXIS_N) if models[i] == "tello" and i != AXIS_CAMERA]
+    p = np.random.default_rng(23).uniform([-15.0, -15.0, 3.0], [35.0, 35.0, 30.0], (len(rest), 3))
+    st[rest, :3] = (np.round(p * 1024.0) / 1024.0).astype(np.float32)
+    return st, models, type_radii(models), info
+
+
+def axis_grid(box=None):
+    """(cell, xmin, ymin, nx, ny) of the axis fleet's sphere grid as Downwash.sphere_grid chooses it: over the fleet's bounding box,
+    or over a pinned box."""
+    from dronesim_amd.downwash import clearance_grid
+    from dronesim_amd.params import builtin_type
+    st = axis_fleet()[0]
+    r_max = max(float(builtin_type(m).collision_sphere) for m in ("tello", "hexa_6DOF_simple"))
+    lo, hi = ((float(st[:, 0].min()), float(st[:, 1].min())), (float(st[:, 0].max()), float(st[:, 1].max()))) if box is None else (box[:2], box[2:])
+    return clearance_grid(lo, hi, r_max, max(0.25 - 2.0 * r_max, 0.0), AXIS_N)
+
+
+def axis_pinned_box():
+    """A drone_box for the axis fleet, (xmin, ymin, xmax, ymax), laid so that (with the grid's one-cell margin and the cell size
+    clearance_grid gives it) the grid's high x border lies 0.1 m beyond the 41 m drones of the +x line, whose spheres (R = 0.2 m)
+    then reach out of the outermost cell into the ring the walk's box is grown by; a cell border lies along y = 0, the line of the
+    cameras along x, to float32 rounding; and every drone of the lines along y lies outside, on the outside list."""
+    cell = axis_grid((-19.5, -1.0, 41.0, 1.0))[0]
+    nx = int(np.ceil((41.1 + 19.5 + cell) / cell)) + 1
+    lo_x = 41.1 - nx * cell + cell
+    box = (lo_x, -2.0 * cell, lo_x + (nx - 2.5) * cell, 1.5 * cell)
+    got = axis_grid(box)
+    assert got[0] == cell and got[3] == nx and got[4] == 6 and abs(got[1] + nx * cell - 41.1) < 1e-9 and abs(got[2] + 3.0 * cell) < 1e-12, got
+    return box
+
+
+def axis_reference(quat, res, rng=None, subdiv=None):
+    """reference_image of the axis camera with the quaternion `quat`."""
+    st, _, rad, _ = axis_fleet()
+    sc = cr.scene(subdiv) if subdiv is not None else None
+    tri, body = (sc.triangles, sc.body) if sc is not None else (None, None)
+    return reference_image(tri, body, st[:, :3], rad, AXIS_CAMERA, np.array(quat, np.float32), cr.ARM["tello"], res[0], res[1], far=FAR, rng=rng)
+
+
+def edge_fleet_reference(sc, pose, res, ground=False):
+    """reference_image of one pose of camera_ref.edge_fleet(sc) with the fleet's other 69 drones drawn (the edge table's cameras
+    sit around the set, the rest hover on a line 20 m off)."""
+    st = cr.edge_fleet(sc)[0]
+    rad = type_radii([cr.FLEET_MODELS[i % 2] for i in range(cr.FLEET_N)])
+    return reference_image(sc.triangles, sc.body, st[:, :3], rad, pose["drone"], pose["quat"], pose["L"], res[0], res[1], far=FAR, ground=ground)

@@ -323,3 +323,82 @@ def camera_poses():
     pos = (np.round(pos * 1024.0) / 1024.0).astype(np.float32)       # multiples of 2^-10 m: p + offset is exact in float32
     rpy = [(0.0, 0.0, 0.4), (0.0, 0.0, 0.05), (0.0, 0.0, 3.0), (0.0, 0.0, 0.0), (0.3, 0.3, -0.15)]
     return pos, np.array([quat_from_rpy(*e) for e in rpy], dtype=np.float32)
+
+
+# ---- the edge table: axis-parallel rays, eyes on cell faces (tests/test_gpu_camera_edges.py) ---------------------------------------
+# raw quaternions (the kernel normalises by 2 / q.q): for (0, 0, +-1, 1) q.q = 2 and r0 = 1 - 1 * 1 = 0 exactly.  On the centre
+# column of an odd-width image ca = 0, so the component d.s of its rays — dy for the cameras along x, dx for those along y — is
+# exactly zero in float32 (EDGE_QUATS' third entry names it); the yaw pi / 4 camera has no such column
+EDGE_QUATS = (("+x", (0.0, 0.0, 0.0, 1.0), 1), ("-x", (0.0, 0.0, 1.0, 0.0), 1), ("+y", (0.0, 0.0, 1.0, 1.0), 0), ("-y", (0.0, 0.0, -1.0, 1.0), 0))
+EDGE_DIAG = ("diag", tuple(float(v) for v in quat_from_rpy(0.0, 0.0, np.pi / 4).astype(np.float32)), None)
+EDGE_EYES = ("corner", "lo_x", "hi_y", "off_y", "off_corner")
+# every eye with the four axis cameras; yaw pi / 4 from the first two only: from hi_y and off_y it sees nothing, and from
+# off_corner it grazes the gate's plane (17 to 19 of 289 pixels ambiguous, 33 of 33 at 1 x 33: over the 1 % cap, so left out)
+EDGE_RES = ((17, 17), (1, 33), (33, 1), (1, 1), (5, 7))
+EDGE_EYE_Z = 0.9635
+# the fleet's drones that carry the 22 edge poses, in the table's order: both parities, so both arms (0.0635 / 1.0635) among the
+# axis cameras; the two yaw pi / 4 cameras have the short arm (with the long one, whose near plane is 1.06 m away, the camera at the
+# corner has 3 of 289 pixels ambiguous and the one on the low x face 1 of 33 at 33 x 1: over the cap)
+EDGE_CAMERAS = (3, 8, 21, 30, 45, 52, 9, 14, 61, 2, 17, 26, 35, 44, 53, 66, 11, 20, 29, 38, 56, 58)
+
+
+def edge_eyes(sc):
+    """{name: eye [3] float32} from the set's own ray grid.  corner: x, y and z on interior cell planes, each formed as the kernel
+    forms a face, fl(origin[k] + fl(j) cell); lo_x: on the box's low x face, y on a cell plane; hi_y: on its high y face; off_y:
+    0.5 m beyond the high y face (a camera along x has dy = 0 with the eye outside that slab); off_corner: one cell out in x and y."""
+    f32 = np.float32
+    g = sc.ray_grid()[0]
+    o, hi, cell = np.array(list(g.origin), f32), np.array(list(g.hi), f32), f32(g.cell)
+    face = lambda k, j: f32(o[k] + f32(j) * cell)
+    jx, jy, jz = g.nx // 2, g.ny // 3, g.nz // 2
+    assert 0 < jx < g.nx and 0 < jy < g.ny and 0 < jz < g.nz
+    z = f32(EDGE_EYE_Z)
+    return {"corner": np.array([face(0, jx), face(1, jy), face(2, jz)], f32),
+            "lo_x": np.array([o[0], face(1, jy), z], f32),
+            "hi_y": np.array([f32(2.5), hi[1], z], f32),
+            "off_y": np.array([f32(0.25), f32(hi[1] + f32(0.5)), z], f32),
+            "off_corner": np.array([f32(o[0] - cell), f32(o[1] - cell), z], f32)}
+
+
+def _below(ez, L):
+    """pz with fl(pz + L) == ez: the stored height whose eye is exactly ez (searched among the neighbours of fl(ez - L))."""
+    f32 = np.float32
+    pz = f32(f32(ez) - f32(L))
+    for cand in (pz, np.nextafter(pz, f32(np.inf)), np.nextafter(pz, f32(-np.inf))):
+        if f32(cand + f32(L)) == f32(ez):
+            return f32(cand)
+    raise AssertionError((ez, L))
+
+
+def edge_poses(sc):
+    """The edge table of a set: a list of dicts eye (name), cam (name), drone (of the 70), L, pos [3] and quat [4] float32, zero
+    (the component of d that is exactly 0 on the centre column of an odd-width image: 0, 1 or None), eye_xyz [3] float32."""
+    eyes = edge_eyes(sc)
+    combos = [(e, q) for e in EDGE_EYES for q in EDGE_QUATS] + [(e, EDGE_DIAG) for e in ("corner", "lo_x")]
+    assert len(combos) == len(EDGE_CAMERAS)
+    out = []
+    for (e, (qn, q, zero)), d in zip(combos, EDGE_CAMERAS):
+        L = ARM[FLEET_MODELS[d % 2]]
+        eye = eyes[e]
+        pos = np.array([eye[0], eye[1], _below(eye[2], L)], np.float32)
+        out.append(dict(eye=e, cam=qn, drone=d, L=L, pos=pos, quat=np.array(q, np.float32), zero=zero, eye_xyz=eye))
+    return out
+
+
+def edge_fleet(sc):
+    """(stored [70, 7] float32 in the caller's numbering, the table): fleet_state(False) with the table's poses on EDGE_CAMERAS."""
+    st = fleet_state(False)[0]
+    table = edge_poses(sc)
+    for p in table:
+        st[p["drone"], :3], st[p["drone"], 3:] = p["pos"], p["quat"]
+    return st, table
+
+
+# the edge pose whose 1 x 1024 and 1024 x 1 images (the documented maxima) are compared as well: the corner eye looking along -x
+EDGE_STRIP = ("corner", "-x")
+EDGE_STRIP_RES = ((1, 1024), (1024, 1))
+# the float32 restatement's worst t_error against cast() over the edge table (both sets, the five resolutions, and the two strips
+# of EDGE_STRIP): measured by tests/test_camera_cpu.py::test_edge_restated_error_is_what_is_recorded; on the edge images the
+# kernel is granted 4 x max(RESTATED_WORST, EDGE_RESTATED_WORST)
+EDGE_RESTATED_WORST = 3.32e-7
+EDGE_KERNEL_TOL = 4.0 * max(RESTATED_WORST, EDGE_RESTATED_WORST)

@@ -116,6 +116,152 @@ def test_the_walk_finds_what_brute_force_finds():
     assert hits > 400
 
 
+# ---- the edge table: what tests/test_gpu_camera_edges.py takes for granted ------------------------------------------------------------
+_EDGE_REF = {}
+
+
+def edge_refs(sd):
+    """{(pose number, res): (without ground, with ground)} of a set's edge table over EDGE_RES, plus the two strips of EDGE_STRIP;
+    computed once."""
+    if sd not in _EDGE_REF:
+        sc = cr.scene(sd)
+        out = {}
+        for k, p in enumerate(cr.edge_poses(sc)):
+            for res in cr.EDGE_RES + (cr.EDGE_STRIP_RES if (p["eye"], p["cam"]) == cr.EDGE_STRIP else ()):
+                out[k, res] = cr.reference_image(sc.triangles, sc.body, p["pos"], p["quat"], p["L"], res[0], res[1], ground="both")
+        _EDGE_REF[sd] = (sc, cr.edge_poses(sc), out)
+    return _EDGE_REF[sd]
+
+
+def test_edge_table_is_the_table():
+    """22 poses: the five eyes x the four axis cameras, yaw pi / 4 from the corner and the low x face; both arms among them, on
+    distinct drones of the fleet that carry none of the five old poses; the fleet holds them as given."""
+    for sd in (0, 2):
+        sc = cr.scene(sd)
+        st, table = cr.edge_fleet(sc)
+        assert [(p["eye"], p["cam"]) for p in table] == [(e, q[0]) for e in cr.EDGE_EYES for q in cr.EDGE_QUATS] + [("corner", "diag"), ("lo_x", "diag")]
+        drones = [p["drone"] for p in table]
+        assert len(set(drones)) == 22 and not set(drones) & set(cr.CAMERAS) and max(drones) < cr.FLEET_N
+        assert {p["L"] for p in table if p["zero"] is not None} == {0.0635, 1.0635}
+        for e in cr.EDGE_EYES:
+            assert len({p["L"] for p in table if p["eye"] == e and p["zero"] is not None}) == 2
+        for p in table:
+            assert np.array_equal(st[p["drone"], :3], p["pos"]) and np.array_equal(st[p["drone"], 3:], p["quat"])
+            assert p["L"] == cr.ARM[cr.FLEET_MODELS[p["drone"] % 2]]
+
+
+def test_edge_eyes_lie_exactly_where_they_claim():
+    """In float32, as the kernel forms them: the corner eye's x, y and z = fl(pz + L) equal interior faces fl(origin + fl(j) cell) of
+    the set's ray grid; lo_x has ex == origin[0], hi_y has ey == hi[1]; off_y lies 0.5 m beyond hi[1] and off_corner a cell outside in
+    x and y; every other coordinate is strictly inside the box."""
+    f32 = np.float32
+    for sd, dims in ((0, (7, 6, 4)), (2, (17, 14, 10))):
+        sc = cr.scene(sd)
+        g = sc.ray_grid()[0]
+        assert (g.nx, g.ny, g.nz) == dims                      # (what the poses were looked at with; they follow the grid if it changes)
+        o, hi, cell = np.array(list(g.origin), f32), np.array(list(g.hi), f32), f32(g.cell)
+        faces = [np.array([f32(o[k] + f32(j) * cell) for j in range(1, n)], f32) for k, n in enumerate(dims)]
+        for p in cr.edge_poses(sc):
+            e = np.array([p["pos"][0], p["pos"][1], f32(p["pos"][2] + f32(p["L"]))], f32)      # the kernel's eye
+            assert e.dtype == np.float32 and np.array_equal(e, p["eye_xyz"])
+            inside = (e > o) & (e < hi)
+            if p["eye"] == "corner":
+                assert all(e[k] in faces[k] for k in range(3)) and inside.all()
+            elif p["eye"] == "lo_x":
+                assert e[0] == o[0] and e[1] in faces[1] and inside[1:].all()
+            elif p["eye"] == "hi_y":
+                assert e[1] == hi[1] and inside[0] and inside[2]
+            elif p["eye"] == "off_y":
+                assert e[1] == f32(hi[1] + f32(0.5)) and e[1] > hi[1] and inside[2]         # (in front of the box in x as well)
+            else:
+                assert e[0] == f32(o[0] - cell) and e[1] == f32(o[1] - cell) and e[0] < o[0] and e[1] < o[1] and inside[2]
+
+
+def test_edge_zero_components_are_exactly_zero():
+    """The float32 restatement of the rays (camera_drones_ref.rays32, operation by operation): on the centre column of the
+    odd-width images the claimed component of d is == 0.0 for every axis pose, at every height; no other column has a zero there,
+    and the yaw pi / 4 cameras have none at all."""
+    from tests import camera_drones_ref as dr
+    for p in cr.edge_poses(cr.scene(0)):
+        for W, H in cr.EDGE_RES + cr.EDGE_STRIP_RES:
+            _, d = dr.rays32(p["pos"], p["quat"], p["L"], W, H)
+            if p["zero"] is None:
+                assert (d[..., :2] != 0.0).all()
+                continue
+            z = d[..., p["zero"]] == 0.0
+            want = np.zeros((H, W), bool)
+            if W % 2:
+                want[:, W // 2] = True
+            assert np.array_equal(z, want), (p["eye"], p["cam"], W, H)
+            assert (d[..., 1 - p["zero"]] != 0.0).all()
+
+
+def test_edge_masks_stay_under_the_cap():
+    """Every image the GPU test compares: the ambiguity mask is at most 1 % of it, which for an image of fewer than 100 pixels
+    means no ambiguous pixel at all."""
+    for sd in (0, 2):
+        _, table, refs = edge_refs(sd)
+        for (k, res), pair in refs.items():
+            for ref in pair:
+                assert ref["ambiguous"].sum() <= res[0] * res[1] // 100, (sd, table[k]["eye"], table[k]["cam"], res, int(ref["ambiguous"].sum()))
+
+
+def test_edge_table_is_not_vacuous():
+    """Summed over the table (17 x 17 and 1 x 33, both sets): at least 20 triangle hits in zero-component columns, some of them
+    from the eye on the cell-plane corner; from off_y the cameras along x (dy = 0, the eye outside the y slab) hit no triangle in
+    that column while the plane still answers there."""
+    zero_hits = corner_hits = 0
+    for sd in (0, 2):
+        _, table, refs = edge_refs(sd)
+        for k, p in enumerate(table):
+            if p["zero"] is None:
+                continue
+            for res in ((17, 17), (1, 33)):
+                bare, gnd = refs[k, res]
+                col = bare["seg"][:, res[0] // 2]
+                zero_hits += int((col >= 0).sum())
+                corner_hits += int((col >= 0).sum()) if p["eye"] == "corner" else 0
+                if p["eye"] == "off_y" and p["zero"] == 1:
+                    gcol = gnd["seg"][:, res[0] // 2]
+                    assert not (col >= 0).any() and np.isinf(bare["t"][:, res[0] // 2]).all()
+                    assert (gcol[np.isfinite(gnd["t"][:, res[0] // 2])] == cr.SEG_GROUND).all() and (gcol == cr.SEG_GROUND).sum() >= res[1] // 2 - 1
+    print(f"triangle hits in zero-component columns: {zero_hits}, from the cell-plane corner: {corner_hits}")
+    assert zero_hits >= 20 and corner_hits >= 1
+
+
+def test_edge_walk_finds_what_brute_force_finds():
+    """The kernel's route restated in float32 (slab clip with its NaN rule, the inside tests, the clamped entry cell, the selects
+    for a zero component, the tie rule, the lists with their slack at a face) over the edge table at 17 x 17 and 1 x 33: outside the
+    mask it hits what the fp64 caster hits, at the same depth to the recorded float32 error, and it is pixel for pixel the float32
+    brute force over all triangles — no triangle is lost at a face or along a cell plane."""
+    for sd in (0, 2):
+        sc, table, refs = edge_refs(sd)
+        for k, p in enumerate(table):
+            for res in ((17, 17), (1, 33)):
+                ref = refs[k, res][0]
+                t = cr.walked_image(sc, p["pos"], p["quat"], p["L"], *res)[0]
+                assert not ((np.isfinite(t) != np.isfinite(ref["t"])) & ~ref["ambiguous"]).any(), (sd, p["eye"], p["cam"], res)
+                assert cr.t_error(t, ref) <= cr.EDGE_RESTATED_WORST
+                assert np.array_equal(t, cr.restated_image(sc.triangles, p["pos"], p["quat"], p["L"], *res)), (sd, p["eye"], p["cam"], res)
+
+
+def test_edge_restated_error_is_what_is_recorded():
+    """test_restated_error_is_what_is_recorded over the edge table: every image the GPU test compares (both sets, the five
+    resolutions, the two strips).  The record is not above the worst by more than 2 %, and the bar the edge images get is 4 x the
+    larger of the two records."""
+    worst = 0.0
+    for sd in (0, 2):
+        sc, table, refs = edge_refs(sd)
+        for (k, res), (ref, _) in refs.items():
+            p = table[k]
+            t32 = cr.restated_image(sc.triangles, p["pos"], p["quat"], p["L"], *res)
+            assert not ((np.isfinite(t32) != np.isfinite(ref["t"])) & ~ref["ambiguous"]).any()
+            worst = max(worst, cr.t_error(t32, ref))
+    print(f"edge restated worst {worst:.3e}")
+    assert worst <= cr.EDGE_RESTATED_WORST <= 1.02 * worst, worst
+    assert cr.EDGE_KERNEL_TOL == 4.0 * max(cr.RESTATED_WORST, cr.EDGE_RESTATED_WORST)
+
+
 # ---- the ray grid -------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("what", ["scene", "soup"])
 def test_ray_grid_lists_every_triangle_where_its_box_lies(nat, what):

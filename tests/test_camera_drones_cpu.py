@@ -185,6 +185,121 @@ def test_the_scenes_are_what_the_gpu_tests_need():
     assert all(not (r["t"][r["is_drone"]] > 20.0).any() for r in dr.lattice_reference(20.0))
 
 
+# ---- the axis fleet: what tests/test_gpu_camera_edges.py takes for granted ----------------------------------------------------------
+def test_axis_fleet_is_laid_out_as_described():
+    """32 hexas on odd numbers (type-major storage differs from the caller's order), the camera a tello; per depth the first drone
+    exactly on the ray's line in xy and the others within a sphere's radius of it or a pixel column off; the chosen grid has cells
+    of 2 R_max or more, a few metres; the pinned box's grid has a border 0.1 m beyond the 41 m drones of the +x line, which lie in
+    its outermost cell, a border along y = 0 to float32 rounding, and leaves the lines along y outside."""
+    st, models, rad, info = dr.axis_fleet()
+    assert models[dr.AXIS_CAMERA] == "tello" and sum(m == "hexa_6DOF_simple" for m in models) == 32 and len(models) == dr.AXIS_N
+    assert np.array_equal(st[dr.AXIS_CAMERA, :3], np.array(dr.AXIS_EYE, np.float32))
+    R = float(rad[1])
+    assert abs(R - 0.2020269) < 1e-6 and (rad[[i for i, m in enumerate(models) if m == "tello"]] < 0.06).all()
+    on_line = 0
+    for name, _, zero in cr.EDGE_QUATS:
+        axis, sign = 1 - zero, (1.0 if name[0] == "+" else -1.0)
+        assert set(info[name]) == ({7.0, 19.0, 41.0} if sign > 0 else {7.0, 19.0})
+        for D, ids in info[name].items():
+            assert abs(sign * st[ids, axis] - D).max() < 0.01          # the depth along the view
+            on_line += int((st[ids, zero] == 0.0).sum())
+            assert st[ids[0], zero] == 0.0 and abs(st[ids[1], zero]) == 0.125 < R
+    assert on_line == 12                                       # one per depth and direction, two in the 41 m groups
+    cell, xmin, ymin, nx, ny = dr.axis_grid()
+    assert 2.0 * R <= cell < 4.1 and nx * ny <= 4 * dr.AXIS_N                    # 41 m is more than 10 cells
+    box = dr.axis_pinned_box()
+    pc, px, py, pnx, pny = dr.axis_grid(box)
+    f32 = np.float32
+    in_cell = lambda j: (int(np.floor((st[j, 0] - f32(px)) * (f32(1.0) / f32(pc)))), int(np.floor((st[j, 1] - f32(py)) * (f32(1.0) / f32(pc)))))
+    for j in (info["+x"][41.0][0], info["+x"][41.0][2]):
+        cx, cy = in_cell(j)
+        assert cx == pnx - 1 and 0 <= cy < pny                 # the outermost cell ...
+        assert 0.0 < float(f32(px) + f32(pnx) * f32(pc)) - float(st[j, 0]) < R     # ... and the sphere reaches out of it
+    border = f32(f32(f32(py) - f32(pc)) + f32(4.0) * f32(pc))                     # the walk's face: gy0 + 4 cell
+    assert abs(float(border)) < 1e-6
+    for name in ("+y", "-y"):
+        for ids in info[name].values():
+            assert all(not 0 <= in_cell(j)[1] < pny for j in ids)
+
+
+_AXIS_REF = {}
+
+
+def axis_ref(name, q, res, rng, sd):
+    key = (name, res, rng, sd)
+    if key not in _AXIS_REF:
+        _AXIS_REF[key] = dr.axis_reference(q, res, rng, sd)
+    return _AXIS_REF[key]
+
+
+def test_axis_fleet_masks_and_what_is_in_view():
+    """Every image the GPU test compares (the four axis cameras x 17 x 17 and 1 x 33 x range none / 25 m x no set / scene(0)): the
+    union mask is at most 1 % (none at all below 100 pixels).  In the zero-component columns at least 3 drone pixels lie further
+    than 10 cells of the chosen sphere grid from the eye with no range, and none beyond the range with it; the 41 m drones of the
+    +x line (the pinned grid's outermost cell) and drones of the lines along y (outside the pinned box) win pixels; scene(0)
+    stands in front of part of the +x row."""
+    st, _, _, info = dr.axis_fleet()
+    cell = dr.axis_grid()[0]
+    far_px = 0
+    winners = set()
+    for name, q, zero in cr.EDGE_QUATS:
+        for res in dr.AXIS_RES:
+            for rng in (None, dr.AXIS_RANGE):
+                for sd in (None, 0):
+                    ref = axis_ref(name, q, res, rng, sd)
+                    assert ref["ambiguous"].sum() <= res[0] * res[1] // 100, (name, res, rng, sd)
+                    col = ref["is_drone"][:, res[0] // 2]
+                    ids = dr.seg_drone(ref["seg"][:, res[0] // 2][col])
+                    dist = np.linalg.norm(st[ids, :2] - st[dr.AXIS_CAMERA, :2], axis=1)
+                    if rng is None:
+                        far_px += int((dist > 10.0 * cell).sum()) if sd is None else 0
+                        winners |= set(ids.tolist())
+                    else:
+                        assert not (ref["t"][ref["is_drone"]] > rng).any() and not (dist > rng + 1.0).any()
+    print(f"drone pixels of zero columns beyond 10 cells ({10 * cell:.1f} m): {far_px}")
+    assert far_px >= 3
+    assert info["+x"][41.0][0] in winners and winners & set(info["+y"][41.0]) and winners & set(info["-y"][19.0])
+    bare, front = axis_ref("+x", cr.EDGE_QUATS[0][1], (17, 17), None, None), axis_ref("+x", cr.EDGE_QUATS[0][1], (17, 17), None, 0)
+    assert (front["seg"] >= 0).sum() >= 20 and (bare["is_drone"] & (front["seg"] >= 0)).any() and front["is_drone"].any()
+
+
+def test_axis_walk_finds_what_brute_force_finds():
+    """walked_spheres (the 2-D walk in float32 with the kernel's selects: inf steps for a zero component, the in_x / in_y tests, the
+    tie rule along a cell border, the ring, the outside list) on the chosen grid and on the pinned one: outside the mask it hits
+    what the fp64 caster hits, within the recorded float32 error, and is pixel for pixel the float32 brute force over all
+    spheres."""
+    st, _, rad, _ = dr.axis_fleet()
+    grids = (dr.axis_grid(), dr.axis_grid(dr.axis_pinned_box()))
+    worst, longest = 0.0, 0.0
+    for name, q, zero in cr.EDGE_QUATS:
+        qa = np.array(q, np.float32)
+        for res in dr.AXIS_RES:
+            for rng in (None, dr.AXIS_RANGE):
+                ref = axis_ref(name, q, res, rng, None)
+                t32 = dr.restated_spheres(st[:, :3], rad, dr.AXIS_CAMERA, qa, cr.ARM["tello"], *res, rng=rng)
+                worst = max(worst, sphere_error(t32, ref))
+                for grid in grids:
+                    t, steps, _ = dr.walked_spheres(st[:, :3], rad, dr.AXIS_CAMERA, qa, cr.ARM["tello"], *res, grid, rng=rng)
+                    assert np.array_equal(t, t32), (name, res, rng, grid)
+                    longest = max(longest, steps)
+    print(f"restated sphere worst on the axis fleet {worst:.4e}; longest mean walk {longest:.1f} cells")
+    assert worst <= dr.SPHERE_RESTATED_WORST                   # the record covers this fleet: SPHERE_TOL stands
+    assert longest > 30
+
+
+def test_edge_strips_with_the_fleet_drawn_stay_under_the_cap():
+    """The 1 x 1024 and 1024 x 1 images of camera_ref.EDGE_STRIP through dsim_depth_image_drones (scene(0), the edge fleet's other
+    drones drawn): the union mask is at most 1 %, and drones are in view."""
+    sc = cr.scene(0)
+    pose = next(p for p in cr.edge_poses(sc) if (p["eye"], p["cam"]) == cr.EDGE_STRIP)
+    seen = 0
+    for res in cr.EDGE_STRIP_RES:
+        ref = dr.edge_fleet_reference(sc, pose, res)
+        assert ref["ambiguous"].sum() <= res[0] * res[1] // 100, (res, int(ref["ambiguous"].sum()))
+        seen += int(ref["is_drone"].sum())
+    assert seen > 0
+
+
 # ---- the library's host side (nothing here reaches a device) -----------------------------------------------------------------------
 def test_header_declares_and_library_exports_the_call(nat):
     hdr = open(os.path.join(ROOT, "include", "dronesim_amd.h")).read()

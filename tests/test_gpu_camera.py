@@ -13,6 +13,7 @@ import pytest
 
 import __graft_entry__ as graft
 from tests import camera_ref as cr
+from tests.camera_check import check_image
 
 pytestmark = pytest.mark.gpu
 FAR = 1000.0
@@ -51,33 +52,6 @@ def make_env(torch, with_offsets, models=None, **kw):
     assert (env.order is not None) == mixed                   # the mixed fleet is stored type-major: not the caller's order
     env.state.set_fields(0, torch.from_numpy(np.ascontiguousarray(st.T)))
     return env, off
-
-
-def check_image(k, dep, seg, ref, L, metric):
-    """One camera's image against its reference; returns the worst t error over KERNEL_TOL (<= 1 passes)."""
-    amb = ref["ambiguous"]
-    assert amb.mean() <= 0.01, (k, amb.mean())               # a condition: a mask that grows cannot hide a failure
-    ok = ~amb
-    dep = dep.astype(np.float64)
-    t = dep if metric else cr.depth_buffer_to_t(dep, float(np.float32(L)), FAR)
-    hit_ref = np.isfinite(ref["t"])
-    assert np.array_equal(np.isfinite(t)[ok], hit_ref[ok]), (k, int((np.isfinite(t) != hit_ref)[ok].sum()))
-    if not metric:
-        assert (dep[ok & ~hit_ref] == 1.0).all()
-    if seg is not None:
-        assert np.array_equal(seg[ok], ref["seg"][ok]), (k, int((seg != ref["seg"])[ok].sum()))
-    m = ok & hit_ref
-    if not m.any():
-        return 0.0
-    tr, nd = ref["t"][m], np.maximum(ref["ndot"][m], 0.05)
-    bound = cr.KERNEL_TOL * tr / nd
-    if not metric:
-        near = float(np.float32(L))
-        bound = bound + 3.0 * 2.0 ** -24 * tr * tr * (FAR - near) / (FAR * near)
-    ratio = np.abs(t[m] - tr) / bound
-    print(f"  camera {k}: {int(m.sum())} hits, ambiguous {100 * amb.mean():.3f} %, worst |dt| / bound {ratio.max():.3f}")
-    assert ratio.max() <= 1.0, (k, float(ratio.max()))
-    return float(ratio.max())
 
 
 # between them the cases launch the four instances <LDS, SEG>: (108 triangles | 1548) x (seg_out | NULL)

@@ -13,6 +13,7 @@ import pytest
 import __graft_entry__ as graft
 from tests import camera_drones_ref as dr
 from tests import camera_ref as cr
+from tests.camera_check import check_image
 
 pytestmark = pytest.mark.gpu
 FAR = dr.FAR
@@ -49,32 +50,6 @@ def make_env(torch, with_offsets, stored=None, models=None, **kw):
                      ground_plane=False, **kw)
     env.state.set_fields(0, torch.from_numpy(np.ascontiguousarray(st.T)))
     return env, off
-
-
-def check_image(k, dep, seg, ref, L, metric):
-    amb = ref["ambiguous"]
-    assert amb.mean() <= 0.01, (k, amb.mean())               # a condition: a mask that grows cannot hide a failure
-    ok = ~amb
-    dep = dep.astype(np.float64)
-    t = dep if metric else cr.depth_buffer_to_t(dep, float(np.float32(L)), FAR)
-    hit_ref = np.isfinite(ref["t"])
-    assert np.array_equal(np.isfinite(t)[ok], hit_ref[ok]), (k, int((np.isfinite(t) != hit_ref)[ok].sum()))
-    if not metric:
-        assert (dep[ok & ~hit_ref] == 1.0).all()
-    if seg is not None:
-        assert np.array_equal(seg[ok], ref["seg"][ok]), (k, int((seg != ref["seg"])[ok].sum()))
-    m = ok & hit_ref
-    if not m.any():
-        return
-    tr, nd = ref["t"][m], np.maximum(ref["ndot"][m], 0.05)
-    bound = np.where(ref["is_drone"][m], dr.SPHERE_TOL, cr.KERNEL_TOL) * tr / nd
-    if not metric:
-        near = float(np.float32(L))
-        bound = bound + 3.0 * 2.0 ** -24 * tr * tr * (FAR - near) / (FAR * near)
-    ratio = np.abs(t[m] - tr) / bound
-    print(f"  camera {k}: {int(m.sum())} hits ({int(ref['is_drone'][m].sum())} on drones), ambiguous {100 * amb.mean():.3f} %, "
-          f"worst |dt| / bound {ratio.max():.3f}")
-    assert ratio.max() <= 1.0, (k, float(ratio.max()))
 
 
 # between them the cases launch the six instances <LDS, SEG, DRONES, TRIS>: (108 triangles | 1548 | no set) x (seg_out | NULL)
