@@ -26,6 +26,7 @@ EXPORTS = (
     "dsim_obstacle_ray_grid_plan", "dsim_obstacle_ray_grid_build", "dsim_obstacles_enable_rays", "dsim_depth_image",
     "dsim_depth_image_drones", "dsim_depth_image_drones_workspace",
     "dsim_trajgen", "dsim_trajgen_workspace", "dsim_traj_sample_bank",
+    "dsim_obstacle_sweep",
 )
 
 ABI_VERSION = 11
@@ -144,6 +145,25 @@ class ObstacleGrid(ctypes.Structure):
         ("list_len", ctypes.c_int64),
         ("lo", ctypes.c_float * 3),
         ("hi", ctypes.c_float * 3),
+    ]
+
+
+SWEEP_KEEP_PREV, SWEEP_PRIME = 1, 2     # dsim_sweep_args.flags
+
+
+class SweepArgs(ctypes.Structure):
+    """dsim_sweep_args (dsim_obstacle_sweep)."""
+    _fields_ = [
+        ("offset", ctypes.c_void_p),
+        ("type_id", ctypes.c_void_p),
+        ("margin", ctypes.c_float),
+        ("sag", ctypes.c_float),
+        ("prev", ctypes.c_void_p),
+        ("flags", ctypes.c_int32),
+        ("clearance_out", ctypes.c_void_p),
+        ("nearest_out", ctypes.c_void_p),
+        ("contacts_out", ctypes.c_void_p),
+        ("unswept_out", ctypes.c_void_p),
     ]
 
 
@@ -302,6 +322,7 @@ def load(path: str = None) -> ctypes.CDLL:
     lib.dsim_obstacles_create.argtypes = [vp, vp, vp, i64, ctypes.c_float, ctypes.POINTER(vp)]
     lib.dsim_obstacles_destroy.argtypes = [vp, vp]
     lib.dsim_obstacle_clearance.argtypes = [vp, vp, i64, View, vp, vp, vp, ctypes.c_float, vp, vp, vp]
+    lib.dsim_obstacle_sweep.argtypes = [vp, vp, i64, View, vp, ctypes.POINTER(SweepArgs)]
     lib.dsim_obstacle_ray_grid_plan.argtypes = [vp, i64, ctypes.POINTER(ObstacleGrid)]
     lib.dsim_obstacle_ray_grid_build.argtypes = [vp, i64, ctypes.POINTER(ObstacleGrid), vp, vp]
     lib.dsim_obstacles_enable_rays.argtypes = [vp, vp]

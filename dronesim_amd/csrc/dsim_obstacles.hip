@@ -143,6 +143,24 @@ __global__ __launch_bounds__(256) void k_obstacle_clearance(ObsK a) {
   }
 }
 
+// what both queries of the set hand their kernels: the fleet, the set's records and grid, the outputs and the counters
+static int obs_kargs(dsim_ctx* ctx, int64_t n, const dsim_view& state, const dsim_obstacles* set, const float* offset,
+                     const uint8_t* type_id, float margin, float* clearance_out, int32_t* nearest_out, uint64_t* contacts_out, ObsK* k) {
+  ObsK& a = *k;
+  const int rc = make_kview(state, 3, &a.st);
+  if (rc) return rc;
+  const dsim_obstacle_grid& g = set->grid;
+  a.n = n; a.n_pad = state.n_pad; a.tiles = (n + 255) / 256;
+  a.offset = offset; a.type_id = type_id; a.types = ctx->d_types; a.n_types = ctx->n_types;
+  a.rec = set->rec; a.cell_start = set->cell_start; a.cell_tri = set->cell_tri; a.n_tri = set->n_tri;
+  a.ox = g.origin[0]; a.oy = g.origin[1]; a.oz = g.origin[2]; a.inv_cell = 1.0f / g.cell;
+  a.nx = g.nx; a.ny = g.ny; a.nz = g.nz;
+  a.lox = g.lo[0]; a.loy = g.lo[1]; a.loz = g.lo[2]; a.hix = g.hi[0]; a.hiy = g.hi[1]; a.hiz = g.hi[2];
+  a.margin = margin; a.clearance = clearance_out; a.nearest = nearest_out;
+  a.counters = ctx->d_counters; a.contacts_out = (unsigned long long*)contacts_out;
+  return DSIM_OK;
+}
+
 extern "C" {
 
 int dsim_obstacle_grid_plan(const float* tri, int64_t n_tri, float reach, dsim_obstacle_grid* out) {
@@ -209,17 +227,8 @@ int dsim_obstacle_clearance(dsim_ctx* ctx, void* stream, int64_t n, dsim_view st
   for (int t = 0; t < ctx->n_types; ++t) r_max = fmaxf(r_max, (float)ctx->h_types[t].collision_sphere);
   if ((double)r_max + (double)margin > (double)set->grid.reach) return DSIM_E_ARG;
   ObsK a;
-  const int rc = make_kview(state, 3, &a.st);
+  const int rc = obs_kargs(ctx, n, state, set, offset, type_id, margin, clearance_out, nearest_out, contacts_out, &a);
   if (rc) return rc;
-  const dsim_obstacle_grid& g = set->grid;
-  a.n = n; a.n_pad = state.n_pad; a.tiles = (n + 255) / 256;
-  a.offset = offset; a.type_id = type_id; a.types = ctx->d_types; a.n_types = ctx->n_types;
-  a.rec = set->rec; a.cell_start = set->cell_start; a.cell_tri = set->cell_tri; a.n_tri = set->n_tri;
-  a.ox = g.origin[0]; a.oy = g.origin[1]; a.oz = g.origin[2]; a.inv_cell = 1.0f / g.cell;
-  a.nx = g.nx; a.ny = g.ny; a.nz = g.nz;
-  a.lox = g.lo[0]; a.loy = g.lo[1]; a.loz = g.lo[2]; a.hix = g.hi[0]; a.hiy = g.hi[1]; a.hiz = g.hi[2];
-  a.margin = margin; a.clearance = clearance_out; a.nearest = nearest_out;
-  a.counters = ctx->d_counters; a.contacts_out = (unsigned long long*)contacts_out;
   const unsigned blocks = (unsigned)(a.tiles < OBS_MAX_BLOCKS ? a.tiles : OBS_MAX_BLOCKS);
   const hipStream_t st_ = (hipStream_t)stream;
   if (set->n_tri <= OBS_LDS_TRI)
@@ -233,3 +242,6 @@ int dsim_obstacle_clearance(dsim_ctx* ctx, void* stream, int64_t n, dsim_view st
 
 // the depth camera: the second consumer of the set (it shares the set's private record above and the LDS threshold)
 #include "dsim_camera.hip"
+
+// the swept watch: the chord between two samples against the same set (it shares the record, tri_dist2 and the LDS threshold)
+#include "dsim_sweep.hip"

@@ -130,6 +130,9 @@ class CtrlAviary(PlacedFleetArrays, FleetObservation, StepWatches):
         obstacle_watch=None,
         obstacle_margin: float = 1.0,
         obstacle_offsets=None,
+        obstacle_sweep: bool = False,
+        obstacle_sweep_sag: float = 0.0,
+        obstacle_sweep_travel: Optional[float] = None,
         vision_attributes: bool = False,
         vision_scene=None,
         vision_drones=None,
@@ -142,7 +145,8 @@ class CtrlAviary(PlacedFleetArrays, FleetObservation, StepWatches):
             raise NotImplementedError("gui/record/obstacles are rendering features outside the hot path")
         self._watch_options(num_drones=num_drones, freq=freq, aggregate_phy_steps=aggregate_phy_steps, dist=dist,
                             drone_watch=drone_watch, drone_watch_margin=drone_watch_margin, obstacle_watch=obstacle_watch,
-                            obstacle_margin=obstacle_margin, vision_attributes=vision_attributes, vision_scene=vision_scene,
+                            obstacle_margin=obstacle_margin, obstacle_sweep=obstacle_sweep, obstacle_sweep_sag=obstacle_sweep_sag,
+                            obstacle_sweep_travel=obstacle_sweep_travel, vision_attributes=vision_attributes, vision_scene=vision_scene,
                             vision_drones=vision_drones, vision_res=vision_res, vision_ground=vision_ground,
                             vision_see_drones=vision_see_drones, vision_drone_range=vision_drone_range)
         # the add-on terms of the PYB_* modes (dead code in the reference fork, intended formulas); Physics.DYN: the
@@ -470,6 +474,7 @@ class CtrlAviary(PlacedFleetArrays, FleetObservation, StepWatches):
             self.ctx.handle, self.ctx.stream_ptr(), self.NUM_DRONES, self.state.view(), pos.data_ptr(),
             rpy.data_ptr(), vel.data_ptr() if vel is not None else None, None,
             self._type_id.data_ptr() if self._type_id is not None else None))
+        self._watch_placed()
         torch.cuda.current_stream(self.ctx.device).synchronize()   # host buffers above go out of scope
 
     def step(self, action):

@@ -16,12 +16,13 @@ class StepWatches:
     # (class-level "nothing on": an env made without __init__ steps with no service behind it)
     _drone_watch = False          # the drone-drone contact watch behind every step (set by _watch_options)
     _obst = None                  # the static-obstacle watch's device set (set by _watch_setup)
+    _obst_sweep = False           # ... queried along the chord between two samples (obstacle_sweep=True)
     _vision = None                # the depth camera of vision_attributes=True (set by _watch_setup)
 
     # ------------------------------------------------------------------ construction
     def _watch_options(self, *, num_drones, freq, aggregate_phy_steps, dist, drone_watch, drone_watch_margin, obstacle_watch,
-                       obstacle_margin, vision_attributes, vision_scene, vision_drones, vision_res, vision_ground,
-                       vision_see_drones, vision_drone_range) -> None:
+                       obstacle_margin, obstacle_sweep, obstacle_sweep_sag, obstacle_sweep_travel, vision_attributes, vision_scene,
+                       vision_drones, vision_res, vision_ground, vision_see_drones, vision_drone_range) -> None:
         """The services' keywords of ``CtrlAviary.__init__``: checked and stashed (the set-up follows in _watch_setup, when the
         context and the storage order exist)."""
         # The reference's Bullet world lets the vehicles' collision shapes act on each other; here every drone is integrated
@@ -43,6 +44,21 @@ class StepWatches:
         # obstacle_offsets [N, 3] (the caller's numbering): the set lies in the frame of each drone's task, p_i - offset_i.
         # Set up at the end of __init__ (_obstacle_setup), when the context and the storage order exist.
         self._obst_set, self._obst_margin, self._obst = obstacle_watch, float(obstacle_margin), None
+        # obstacle_sweep=True: the query behind a launch is dsim_obstacle_sweep instead, the chord from the position the previous
+        # query saw (reset() primes it) to the state the launch left, as a sphere of radius R + obstacle_sweep_sag swept along it:
+        # with sag >= obstacles.sweep_sag(a_max, time between two queries) every sub-step state in between lies in the tested
+        # volume.  obstacle_sweep_travel [m]: the chord length one cell lookup serves (None: 10 m/s x one Env.step); it sizes the
+        # device set's reach and decides speed only.  Off by default: nothing new is allocated or launched.
+        if obstacle_sweep and obstacle_watch is None:
+            raise ValueError("obstacle_sweep=True without obstacle_watch=ObstacleSet")
+        if not obstacle_sweep and (obstacle_sweep_sag != 0.0 or obstacle_sweep_travel is not None):
+            raise ValueError("obstacle_sweep_sag / obstacle_sweep_travel without obstacle_sweep=True")
+        self._obst_sweep, self._obst_sag = bool(obstacle_sweep), float(obstacle_sweep_sag)
+        self._obst_travel = 10.0 * int(aggregate_phy_steps) / float(freq) if obstacle_sweep_travel is None else float(obstacle_sweep_travel)
+        if obstacle_sweep and (not np.isfinite(self._obst_sag) or self._obst_sag < 0.0):
+            raise ValueError("obstacle_sweep_sag must be >= 0")
+        if obstacle_sweep and (not np.isfinite(self._obst_travel) or not self._obst_travel >= 1e-3):
+            raise ValueError("obstacle_sweep_travel must be at least a millimetre")
         # BaseAviary(vision_attributes=True) keeps self.rgb / self.dep / self.seg per drone at IMG_RES = [64, 48] and refreshes them
         # from _getDroneImages whenever step_counter % IMG_CAPTURE_FREQ == 0 (BaseAviary.py:236-261, 453-502, 794-853).  Here:
         # env.dep / env.seg ([n, H, W] device tensors; no rgb) of the static world `vision_scene` (default: the obstacle_watch
@@ -108,11 +124,19 @@ class StepWatches:
             if offsets.shape != (self.NUM_DRONES, 3):
                 raise ValueError(f"obstacle_offsets must be [{self.NUM_DRONES}, 3]")
             self._obst_off = self._soa3(offsets)
-        self._obst = self._obst_set.to_device(self.ctx, obs.watch_reach(self.ctx.types, self._obst_margin))
+        reach = (obs.sweep_reach(self.ctx.types, self._obst_margin, self._obst_sag, self._obst_travel) if self._obst_sweep
+                 else obs.watch_reach(self.ctx.types, self._obst_margin))
+        self._obst = self._obst_set.to_device(self.ctx, reach)
         self._obst_clr = torch.empty((n_pad,), dtype=torch.float32, device=dev)
         self._obst_near = torch.empty((n_pad,), dtype=torch.int32, device=dev)
         self._obst_on_demand = torch.zeros((1,), dtype=torch.int64, device=dev)    # what on-demand queries counted
         self._obst_sampled = False
+        if self._obst_sweep:
+            # where the previous query saw every drone (storage order, fixed address: a captured sequence holds it), and how many
+            # drone x queries were point samples because they had no usable chord
+            self._obst_prev = torch.zeros((3, n_pad), dtype=torch.float32, device=dev)
+            self._obst_unswept = torch.zeros((1,), dtype=torch.int64, device=dev)
+            self._watch_placed()
 
     def _vision_setup(self, offsets) -> None:
         """vision_attributes=True: the camera, its device set (shared with the obstacle watch when both look at the same
@@ -132,6 +156,12 @@ class StepWatches:
     def _watch_reset(self) -> None:
         """_housekeeping: the step counter is back at zero, and so is the last one the camera's cadence saw."""
         self._vision_seen = 0
+
+    def _watch_placed(self) -> None:
+        """_housekeeping placed every drone: the swept watch's chords start there (the first step is swept from the start)."""
+        if self._obst is not None and self._obst_sweep:
+            from .. import obstacles as obs
+            obs.prime(self.ctx, self.state, self._obst, self._obst_prev)
 
     def _watch_close(self) -> None:
         if self._vision is not None:
@@ -171,8 +201,14 @@ class StepWatches:
         return clr, near
 
     def _watch_obstacles(self) -> None:
-        """One dsim_obstacle_clearance on the state the step just left, on the env's stream (also under capture)."""
+        """One dsim_obstacle_clearance on the state the step just left, on the env's stream (also under capture); with
+        obstacle_sweep=True one dsim_obstacle_sweep from the state the previous one saw."""
         from .. import obstacles as obs
+        if self._obst_sweep:
+            obs.sweep(self.ctx, self.state, self._obst, self._obst_margin, self._obst_sag, self._obst_prev, self._obst_clr,
+                      self._obst_near, self._obst_off, self._type_id, None, self._obst_unswept)
+            self._obst_sampled = True
+            return
         obs.query(self.ctx, self.state, self._obst, self._obst_margin, self._obst_clr, self._obst_near, self._obst_off,
                   self._type_id)
         self._obst_sampled = True
@@ -190,6 +226,11 @@ class StepWatches:
                                       "time to time, which a captured sequence cannot")
         if self._obst is not None:
             self.obstacle_clearance()     # (eager, not an Env.step: the watch's kernel is loaded before the capture starts)
+            if self._obst_sweep:          # (and the swept one's: prev stays, the contacts it counts go where on-demand ones go)
+                from .. import obstacles as obs
+                obs.sweep(self.ctx, self.state, self._obst, self._obst_margin, self._obst_sag, self._obst_prev,
+                          torch.empty_like(self._obst_clr), None, self._obst_off, self._type_id, self._obst_on_demand, None,
+                          keep_prev=True)
         if self._vision is not None:
             if self.IMG_CAPTURE_FREQ != self.AGGR_PHY_STEPS:
                 raise NotImplementedError(f"graph capture with vision_attributes: the images are due every "
@@ -257,10 +298,20 @@ class StepWatches:
         makes a vehicle collide with the static bodies loaded into it; here they act on nothing, and a non-zero count means
         part of the flight lies outside the domain in which trajectories are comparable with the reference.  One-sided:
         0 certifies that no bounding sphere touched a triangle at the sampled states; an overlapping sphere need not be a
-        touching shape.  A step_fused launch with n_steps > 1 is sampled once, at its end.  On-demand
+        touching shape.  A step_fused launch with n_steps > 1 is sampled once, at its end.  With ``obstacle_sweep=True`` the
+        count is of spheres swept along the chord between two sampled states, and 0 certifies the states in between as well
+        (obstacle_sweep_sag covers how far the path leaves the chord; rotation needs no cover: the sphere bounds it).  On-demand
         obstacle_clearance() calls are not Env.steps and are left out."""
         seen = self.ctx.query(nat.QUERY_OBSTACLE_CONTACTS)
         return seen - (int(self._obst_on_demand.item()) if self._obst is not None else 0)
+
+    def obstacle_unswept(self) -> int:
+        """Drones x queries so far of an ``obstacle_sweep=True`` env that were point samples instead of chords: a chord of more
+        than 32 pieces (a teleport) or a non-finite position on either end (cumulative; synchronises the stream).  0 for
+        a flight: every counted state was reached along a tested chord."""
+        if self._obst is None or not self._obst_sweep:
+            raise ValueError("obstacle_unswept() needs an env made with obstacle_sweep=True")
+        return int(self._obst_unswept.item())
 
     def obstacle_clearance(self, margin: Optional[float] = None):
         """Per-drone clearance of the CURRENT state to the ``obstacle_watch`` set (dsim_obstacle_clearance): (clearance [N]

@@ -232,3 +232,38 @@ def query(ctx, state, dev: DeviceObstacles, margin: float, clearance, nearest, o
         ctx.handle, ctx.stream_ptr(), state.n, state.view(), dev.handle, offset.data_ptr() if offset is not None else None,
         type_id.data_ptr() if type_id is not None else None, float(margin), clearance.data_ptr(),
         nearest.data_ptr() if nearest is not None else None, contacts_out.data_ptr() if contacts_out is not None else None))
+
+
+# ---- the swept watch (dsim_obstacle_sweep) ------------------------------------------------------------------------------------------
+def sweep_reach(types, margin: float, sag: float, travel: float) -> float:
+    """The ``reach`` of a set for swept queries of ``margin`` and ``sag`` over these drone types whose chords are up to ``travel``
+    metres long per lookup: fp32(R_max + sag + margin + travel / 2), a thousandth more as in :func:`watch_reach`.  A longer chord
+    is cut into pieces of that length (up to 32 of them), so ``travel`` decides speed, never results; it must be positive: the
+    library refuses a set whose reach leaves less than a 1024th of itself for the pieces."""
+    r_max = max(float(np.float32(t.collision_sphere)) for t in types)
+    s = r_max + float(np.float32(sag)) + float(np.float32(margin)) + 0.5 * float(travel)
+    return float(np.float32(s * (1.0 + 2.0 ** -10)))
+
+
+def sweep_sag(a_max: float, T: float) -> float:
+    """a_max T^2 / 8: how far a path whose acceleration never exceeds ``a_max`` [m/s^2] can leave the chord between its positions
+    a time ``T`` [s] apart (x(t) minus the chord vanishes at both ends and has a second derivative bounded by a_max: the
+    parabola a_max t (T - t) / 2 bounds it, with its maximum in the middle).  With ``sag`` at least this, every state between the
+    two samples lies in the volume the swept query tests."""
+    return float(a_max) * float(T) ** 2 / 8.0
+
+
+def sweep(ctx, state, dev: DeviceObstacles, margin: float, sag: float, prev, clearance, nearest, offset=None, type_id=None,
+          contacts_out=None, unswept_out=None, keep_prev: bool = False) -> None:
+    """dsim_obstacle_sweep on the current stream: the chord from ``prev`` ([3, n_pad] float32, world frame, updated unless
+    ``keep_prev``) to the current positions, into the given tensors ([n_pad] float32 / int32)."""
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    a = nat.SweepArgs(ptr(offset), ptr(type_id), float(margin), float(sag), prev.data_ptr(),
+                      nat.SWEEP_KEEP_PREV if keep_prev else 0, clearance.data_ptr(), ptr(nearest), ptr(contacts_out), ptr(unswept_out))
+    nat.check(ctx.lib.dsim_obstacle_sweep(ctx.handle, ctx.stream_ptr(), state.n, state.view(), dev.handle, ctypes.byref(a)))
+
+
+def prime(ctx, state, dev: DeviceObstacles, prev) -> None:
+    """``prev`` := the current positions (DSIM_SWEEP_PRIME): the next :func:`sweep` starts its chords here."""
+    a = nat.SweepArgs(None, None, 0.0, 0.0, prev.data_ptr(), nat.SWEEP_PRIME, None, None, None, None)
+    nat.check(ctx.lib.dsim_obstacle_sweep(ctx.handle, ctx.stream_ptr(), state.n, state.view(), dev.handle, ctypes.byref(a)))

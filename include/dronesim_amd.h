@@ -48,7 +48,7 @@ extern "C" {
                               DSIM_CAM_*, DSIM_SEG_GROUND; the other drones in the camera's images, dsim_depth_image_drones,
                               dsim_depth_image_drones_workspace, dsim_camera_drones, DSIM_SEG_DRONE; the trajectory bank,
                               dsim_trajgen, dsim_trajgen_workspace, dsim_traj_sample_bank, dsim_traj_bank, dsim_trajgen_args,
-                              DSIM_TRAJGEN_* */
+                              DSIM_TRAJGEN_*; the swept obstacle watch, dsim_obstacle_sweep, dsim_sweep_args, DSIM_SWEEP_* */
 #define DSIM_MAX_ACT 6     /* actuators per vehicle (quad 4, morphing hexa 6) */
 #define DSIM_MAX_TYPES 8
 
@@ -809,6 +809,47 @@ int dsim_obstacles_destroy(dsim_ctx* ctx, dsim_obstacles* set);
 int dsim_obstacle_clearance(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, const dsim_obstacles* set,
                             const float* offset, const uint8_t* type_id, float margin,
                             float* clearance_out, int32_t* nearest_out, uint64_t* contacts_out);
+
+/* The swept query: the clearance along the CHORD from the position the previous call saw to the current one, as a swept sphere.
+ * dsim_obstacle_clearance certifies the sampled states only; between two samples a vehicle a few m/s fast crosses a bar 0.14 m
+ * thick unseen.  Stream-ordered, allocates nothing, never synchronises (it may be captured).  For drone i of `state`,
+ *     q1 = p_i - offset_i, q0 = prev_i - offset_i        prev: SoA [3][n_pad] (device), WORLD frame like p, owned by the caller
+ *     Rs = collision_sphere of its type + sag            sag >= 0 [m]: how far the flown path may leave its chord; a path whose
+ *                                                        acceleration is bounded by a_max leaves it by at most a_max T^2 / 8 over T
+ *     c_i = min_t dist(segment q0 q1, triangle t) - Rs   exact segment-triangle distance, 0 where the chord pierces a triangle
+ *     clearance_out[i] = min(margin, c_i);  nearest_out[i] = the BODY that attains the minimum, -1 when c_i >= margin
+ * Every drone with c_i < 0 adds one to DSIM_Q_OBSTACLE_CONTACTS and to *contacts_out, as in the point query: the same quantity,
+ * measured better.  A type with collision_sphere = 0 takes no part (margin, -1, never counted), whatever the sag.  Then, unless
+ * DSIM_SWEEP_KEEP_PREV is set, prev_i := p_i for every drone i < n (also those of R = 0 and those outside the box): a captured
+ * and replayed call carries its own history.
+ *
+ * A chord is cut into K = ceil(|q1 - q0| / (2 half)) equal pieces, half = reach - (R_max + sag + margin), each looked up in the
+ * cell of its own midpoint: a triangle within Rs + margin of a piece is within reach of that midpoint, so the minimum over the
+ * pieces is the chord's and does not depend on K (half is taken 2^-10 shorter when K is chosen).  A piece whose midpoint lies
+ * outside the grown box reads no list.  A drone is UNSWEPT when K > 32 (a teleport: the caller's own reset) or when prev_i or p_i
+ * has a non-finite component: it is a point sample at q1, bit for bit what dsim_obstacle_clearance gives for the radius Rs, and
+ * adds one to *unswept_out (types with R = 0 are not counted).  A non-finite p_i gives (margin, -1) and leaves itself in prev.
+ *
+ * DSIM_SWEEP_PRIME: prev_i := p_i for i < n and nothing else; offset, type_id, margin, sag, the outputs and the counters are not
+ * looked at.  DSIM_E_ARG, nothing written: a null ctx / set / args / prev, n <= 0 or > n_pad, an unknown flag or both flags; and
+ * unless PRIME: more than one type without type_id, a null clearance_out, margin <= 0, sag < 0, either not finite, or half < reach / 1024
+ * (make the set with reach >= R_max + sag + margin + half the chord length one lookup should serve). */
+enum { DSIM_SWEEP_KEEP_PREV = 1,   /* do not write prev (on-demand queries, the eager call before a capture) */
+       DSIM_SWEEP_PRIME     = 2 }; /* prev := current position and nothing else: no outputs, no counters    */
+typedef struct dsim_sweep_args {
+  const float*   offset;        /* SoA [3][n_pad] or NULL, as dsim_obstacle_clearance                      */
+  const uint8_t* type_id;       /* [n_pad]; required with more than one type                               */
+  float          margin;        /* > 0                                                                      */
+  float          sag;           /* >= 0 [m]: added to every radius                                          */
+  float*         prev;          /* SoA [3][n_pad], WORLD frame, in-out; required                            */
+  int32_t        flags;
+  float*         clearance_out; /* [n_pad]; required unless PRIME                                           */
+  int32_t*       nearest_out;   /* [n_pad], nullable                                                        */
+  uint64_t*      contacts_out;  /* device counter, nullable                                                 */
+  uint64_t*      unswept_out;   /* device counter, nullable                                                 */
+} dsim_sweep_args;
+int dsim_obstacle_sweep(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, const dsim_obstacles* set,
+                        const dsim_sweep_args* args);
 
 /* Depth camera: per-drone depth and segmentation images of the obstacle set.  The reference's envs keep, with
  * vision_attributes=True, an rgb / depth / segmentation image per drone from p.getCameraImage (BaseAviary._getDroneImages,

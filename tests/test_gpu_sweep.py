@@ -1,0 +1,480 @@
+"""GPU tests of the swept obstacle watch (dsim_obstacle_sweep, obstacles.sweep / prime, the env's obstacle_sweep keywords) against a
+brute-force fp64 segment-triangle computation (tests/sweep_ref.py) on the fp32 positions, previous positions, offsets and vertices
+the device holds.  tests/README_sweep.md.
+
+Input rule, as tests/test_gpu_obstacles.py: GUARD = 1e-4 m, ATOL = 1e-5 m.  A chord is a midpoint uniform in the named box, a
+uniform direction and a length uniform in the named range; chords whose clearance lies within GUARD of 0 or of the margin are
+re-drawn, at most 1 % of them (asserted on the reference alone).  Counts and the -1 / not -1 status of `nearest` are then compared
+EXACTLY, clearances with atol ATOL, and a `nearest` body may differ only where two bodies' minima are within ATOL (at most 1 %).
+Every case prints the device's own worst difference before it asserts.  A flown state cannot be re-drawn: there the rule of
+test_gpu_obstacles.py's docstring holds (the decision exact wherever the reference's |c| >= ATOL, the counter equal to the device's
+own count of negative clearances)."""
+import functools
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from dronesim_amd import params
+from tests.obstacle_ref import brute
+from tests.sweep_ref import chords, pierces, seg_seg, sweep_brute
+from tests.test_gpu_obstacles import ATOL, GOLDEN, GUARD, _mixed_types, _positions, check, gate, load, soa3, soup
+from tests.util import f32
+
+pytestmark = pytest.mark.gpu
+
+GATE_BOX = ([-0.55, -1.05, -0.9], [0.55, 1.05, 0.9])              # the box of test_gpu_obstacles._gate_world
+
+
+@pytest.fixture(scope="module")
+def gpu():
+    if not torch.cuda.is_available():
+        pytest.fail("GPU tests need a HIP device; the product has no CPU fallback")
+    from dronesim_amd import _native as nat
+    from dronesim_amd import fleet
+    return nat, fleet
+
+
+def settle_chords(rng, draw, n, decide):
+    """The input rule: draws n chords with draw(rng, k) -> (prev, pos, offset or None), re-draws those whose raw clearance
+    decide(prev, pos, off) sits within GUARD of 0 or of the margin; returns (prev, pos, off, fraction re-drawn)."""
+    prev, pos, off = draw(rng, n)
+    redrawn = np.zeros(n, dtype=bool)
+    for _ in range(50):
+        c, margin = decide(prev, pos, off)
+        bad = (np.abs(c) < GUARD) | (np.abs(c - margin) < GUARD)
+        if not bad.any():
+            return prev, pos, off, redrawn.mean()
+        redrawn |= bad
+        a2, p2, o2 = draw(rng, int(bad.sum()))
+        prev[bad], pos[bad] = a2, p2
+        if off is not None:
+            off[bad] = o2
+    raise AssertionError("the input rule did not settle")
+
+
+def draw_chords(box, len_lo, len_hi, offsets=False):
+    def draw(rng, k):
+        q0, q1 = chords(rng, k, box[0], box[1], len_lo, len_hi)
+        if not offsets:
+            return f32(q0), f32(q1), None
+        off = f32(rng.uniform(-128.0, 128.0, (k, 3)))
+        return f32(q0 + off), f32(q1 + off), off
+    return draw
+
+
+def sweep_run(ctx, st, dev_set, margin, sag, prev, off=None, tid=None, counter=None, unswept=None, keep_prev=False):
+    from dronesim_amd import obstacles as obs
+    clr = torch.full((st.n_pad,), -7.0, dtype=torch.float32, device=ctx.device)
+    near = torch.full((st.n_pad,), -7, dtype=torch.int32, device=ctx.device)
+    obs.sweep(ctx, st, dev_set, margin, sag, prev, clr, near, off, tid, counter, unswept, keep_prev=keep_prev)
+    return clr[: st.n], near[: st.n]
+
+
+def counters(ctx):
+    return (torch.zeros((1,), dtype=torch.int64, device=ctx.device), torch.zeros((1,), dtype=torch.int64, device=ctx.device))
+
+
+def pieces(prev, pos, off, reach, r_max, sag, margin):
+    """The host formula of the piece count: K = ceil(|q1 - q0| / (2 half (1 - 2^-10))), half = reach - (R_max + sag + margin)."""
+    q0, q1 = prev.astype(np.float64), pos.astype(np.float64)
+    if off is not None:
+        q0, q1 = q0 - off, q1 - off
+    half = float(np.float32(reach)) - (float(np.float32(r_max)) + float(np.float32(sag)) + float(np.float32(margin)))
+    return np.maximum(np.ceil(np.linalg.norm(q1 - q0, axis=1) / (2 * half * (1 - 2.0 ** -10))), 1)
+
+
+# ---- 1. one triangle: piercing, minimum at an end, minimum inside the chord against an edge ----------------------------------------
+def test_one_triangle_every_class(gpu):
+    nat, fleet = gpu
+    from dronesim_amd.obstacles import ObstacleSet, sweep_reach
+    t = params.builtin_type("robobee")
+    R, margin, n = np.float32(t.collision_sphere), 0.5, 700
+    tri = np.array([[[0.0, 0.0, 1.0], [2.0, 0.0, 1.0], [0.5, 1.5, 1.3]]])
+    s = ObstacleSet(tri, 0)
+    rad = np.full(n, R)
+    decide = lambda a, p, o: (sweep_brute(a, p, s.triangles, s.body, rad[: len(p)], margin, 0.0, o)[4], margin)
+    prev, pos, _, frac = settle_chords(np.random.default_rng(3), draw_chords(([-0.5, -0.5, 0.6], [2.5, 2.0, 1.8]), 0.0, 0.8), n, decide)
+    assert frac <= 0.01, frac
+    ref = sweep_brute(prev, pos, s.triangles, s.body, rad, margin)
+    # the classes, on the reference: which candidate attains the chord's minimum
+    T = s.triangles.astype(np.float64)
+    hit = pierces(prev, pos, T)[:, 0]
+    d_end = np.minimum(brute(prev, s.triangles, s.body, rad, 9.0)[4], brute(pos, s.triangles, s.body, rad, 9.0)[4])
+    a, b, c = T[:, 0], T[:, 1], T[:, 2]
+    d_edge = np.minimum(np.minimum(seg_seg(prev, pos - prev, a, b - a), seg_seg(prev, pos - prev, a, c - a)),
+                        seg_seg(prev, pos - prev, b, c - b))[:, 0] - float(R)
+    reach_ = ref[1] >= 0
+    n_pierce = int((hit & reach_).sum())
+    n_end = int((~hit & reach_ & (d_end <= d_edge + 1e-12)).sum())
+    n_inner = int((~hit & reach_ & (d_edge < d_end - 1e-9)).sum())
+    print(f"one triangle: {n_pierce} chords pierce, {n_end} have their minimum at an end, {n_inner} inside the chord against an edge")
+    assert n_pierce >= 3 and n_end >= 3 and n_inner >= 3
+    ctx = fleet.Context([t])
+    dev = s.to_device(ctx, sweep_reach(ctx.types, margin, 0.0, 0.8))
+    st = load(fleet, ctx, pos)
+    cnt, uns = counters(ctx)
+    clr, near = sweep_run(ctx, st, dev, margin, 0.0, soa3(prev, st.n_pad, ctx.device), counter=cnt, unswept=uns)
+    check(clr, near, ref, margin, "swept, one triangle")
+    assert int(cnt.item()) == ref[3] == ctx.query(nat.QUERY_OBSTACLE_CONTACTS) and int(uns.item()) == 0
+    dev.close()
+    ctx.close()
+
+
+# ---- 2. the gate --------------------------------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def _gate_chords(offsets):
+    """Computed once per offsets: the chords and their reference (shared by both layouts, never written to)."""
+    t = params.builtin_type("robobee")
+    n, margin = 700, 1.0
+    s = gate()
+    rad = np.full(n, np.float32(t.collision_sphere))
+    decide = lambda a, p, o: (sweep_brute(a, p, s.triangles, s.body, rad[: len(p)], margin, 0.0, o)[4], margin)
+    prev, pos, off, frac = settle_chords(np.random.default_rng(11), draw_chords(GATE_BOX, 0.0, 0.3, offsets), n, decide)
+    assert frac <= 0.01, frac
+    ref = sweep_brute(prev, pos, s.triangles, s.body, rad, margin, 0.0, off)
+    ends = brute(pos, s.triangles, s.body, rad, margin, off)
+    return prev, pos, off, ref, ends
+
+
+@pytest.mark.parametrize("layout", ["soa", "tile64"])
+@pytest.mark.parametrize("offsets", [False, True])
+def test_gate_vs_bruteforce(gpu, layout, offsets):
+    nat, fleet = gpu
+    from dronesim_amd.obstacles import sweep_reach
+    t = params.builtin_type("robobee")
+    n, margin = 700, 1.0
+    s = gate()
+    prev, pos, off, ref, ends = _gate_chords(offsets)
+    missed = int(((ref[4] < 0) & ~(ends[4] < 0)).sum())
+    print(f"gate: {ref[3]} chords touch, the sample at their end sees {ends[3]} and misses {missed}")
+    assert missed >= 10 and 0.08 * n < ref[3] < 0.35 * n
+    ctx = fleet.Context([t])
+    dev = s.to_device(ctx, sweep_reach(ctx.types, margin, 0.0, 0.3))
+    st = load(fleet, ctx, pos, layout)
+    d_off = soa3(off, st.n_pad, ctx.device) if offsets else None
+    d_prev = soa3(prev, st.n_pad, ctx.device)
+    d_prev[:, n:] = -3.0                                            # (the padding is nobody's: it must stay)
+    keep = d_prev.clone()
+    cnt, uns = counters(ctx)
+    clr, near = sweep_run(ctx, st, dev, margin, 0.0, d_prev, d_off, None, cnt, uns)
+    check(clr, near, ref, margin, f"swept, gate {layout} offsets={offsets}")
+    assert int(cnt.item()) == ref[3] == ctx.query(nat.QUERY_OBSTACLE_CONTACTS) and int(uns.item()) == 0
+    # prev is now the current position, bit for bit
+    assert np.array_equal(d_prev[:, :n].cpu().numpy().T, pos.astype(np.float32))
+    assert bool((d_prev[:, n:] == -3.0).all())
+    # again on the restored prev with KEEP_PREV: the same outputs, the counters double, prev stays
+    d_prev.copy_(keep)
+    clr2, near2 = sweep_run(ctx, st, dev, margin, 0.0, d_prev, d_off, None, cnt, uns, keep_prev=True)
+    assert torch.equal(clr, clr2) and torch.equal(near, near2) and torch.equal(d_prev, keep)
+    assert int(cnt.item()) == 2 * ref[3] == ctx.query(nat.QUERY_OBSTACLE_CONTACTS)
+    dev.close()
+    ctx.close()
+
+
+# ---- 3. a mixed fleet with a type that takes no part, and a sag -------------------------------------------------------------------------
+def test_gate_mixed_fleet_with_the_ghost_type_and_a_sag(gpu):
+    nat, fleet = gpu
+    from dronesim_amd.obstacles import sweep_reach
+    types = _mixed_types()
+    n, margin, sag = 700, 0.75, 0.01
+    tid = (np.arange(n) % 4).astype(np.uint8)
+    s = gate()
+    rad_all = np.array([np.float32(t.collision_sphere) for t in types])[tid]
+    slot = {"rad": rad_all}
+
+    def decide(a, p, o):                                           # (re-drawn chords keep their slot's radius)
+        return sweep_brute(a, p, s.triangles, s.body, slot["rad"], margin, sag, o)[4], margin
+    rng = np.random.default_rng(13)
+    draw = draw_chords(GATE_BOX, 0.0, 0.3, True)
+    prev, pos, off = draw(rng, n)
+    redrawn = np.zeros(n, dtype=bool)
+    for _ in range(50):
+        c, _m = decide(prev, pos, off)
+        bad = (np.abs(c) < GUARD) | (np.abs(c - margin) < GUARD)
+        if not bad.any():
+            break
+        redrawn |= bad
+        prev[bad], pos[bad], off[bad] = draw(rng, int(bad.sum()))
+    assert not bad.any() and redrawn.mean() <= 0.01
+    ref = sweep_brute(prev, pos, s.triangles, s.body, rad_all, margin, sag, off)
+    assert ref[3] > 40 and (rad_all == 0).sum() == n // 4
+    ctx = fleet.Context(types)
+    dev = s.to_device(ctx, sweep_reach(ctx.types, margin, sag, 0.3))
+    st = load(fleet, ctx, pos)
+    t_id = torch.zeros((st.n_pad,), dtype=torch.uint8, device=ctx.device)
+    t_id[:n] = torch.from_numpy(tid).to(ctx.device)
+    d_prev, d_off = soa3(prev, st.n_pad, ctx.device), soa3(off, st.n_pad, ctx.device)
+    cnt, uns = counters(ctx)
+    clr, near = sweep_run(ctx, st, dev, margin, sag, d_prev, d_off, t_id, cnt, uns)
+    check(clr, near, ref, margin, "swept, gate, mixed fleet, sag 0.01")
+    c_, n_ = clr.cpu().numpy(), near.cpu().numpy()
+    assert np.all(c_[rad_all == 0] == np.float32(margin)) and np.all(n_[rad_all == 0] == -1)
+    assert ctx.query(nat.QUERY_OBSTACLE_CONTACTS) == ref[3] == int(cnt.item()) and int(uns.item()) == 0
+    assert np.array_equal(d_prev[:, :n].cpu().numpy().T, pos.astype(np.float32))      # (the ghosts' prev moved on too)
+    # more than one type and no type_id: refused, nothing written
+    before = d_prev.clone()
+    out = torch.full((st.n_pad,), -7.0, dtype=torch.float32, device=ctx.device)
+    a = nat.SweepArgs(None, None, margin, sag, d_prev.data_ptr(), 0, out.data_ptr(), None, None, None)
+    import ctypes
+    assert ctx.lib.dsim_obstacle_sweep(ctx.handle, ctx.stream_ptr(), n, st.view(), dev.handle, ctypes.byref(a)) == -1
+    torch.cuda.synchronize()
+    assert bool((out == -7.0).all()) and torch.equal(d_prev, before)
+    dev.close()
+    ctx.close()
+
+
+# ---- 4. the soup: records through L2, several pieces per chord, whole waves outside -------------------------------------------------
+def test_soup_results_do_not_depend_on_the_piece_count(gpu):
+    nat, fleet = gpu
+    from dronesim_amd.obstacles import sweep_reach
+    s = soup()
+    t = params.builtin_type("hexa_6DOF")
+    n, margin = 2048, 0.6
+    R = np.float32(t.collision_sphere)
+    rad = np.full(n, R)
+    reach_a, reach_b = sweep_reach([t], margin, 0.0, 0.5), sweep_reach([t], margin, 0.0, 3.0)
+    g, _, _ = s.grid(reach_b)
+    lo, hi = np.array(list(g.lo), dtype=np.float64), np.array(list(g.hi), dtype=np.float64)
+    assert np.abs(lo).max() < 14.0 and np.abs(hi).max() < 14.0 and s.n_tri == 3000
+
+    def draw_out(rng, k):                                          # midpoints 1.6 m or more outside the larger grown box
+        m = rng.uniform(-14.4, 14.4, (8 * k + 64, 3))
+        m = m[((m < lo - 1.6) | (m > hi + 1.6)).any(1)][:k]
+        assert len(m) == k
+        v = rng.normal(size=(k, 3))
+        h = 0.5 * rng.uniform(0.0, 3.0, (k, 1)) * v / np.linalg.norm(v, axis=1, keepdims=True)
+        return f32(m - h), f32(m + h), None
+    decide = lambda a, p, o: (sweep_brute(a, p, s.triangles, s.body, rad[: len(p)], margin, 0.0, o)[4], margin)
+    rng = np.random.default_rng(29)
+    a_in, p_in, _, frac = settle_chords(rng, draw_chords(([-10.0] * 3, [10.0] * 3), 0.0, 3.0), n // 2, decide)
+    assert frac <= 0.01, frac
+    a_out, p_out, _ = draw_out(rng, n // 2)
+    prev, pos = np.concatenate([a_in, a_out]), np.concatenate([p_in, p_out])
+    assert np.abs(prev).max() <= 16.0 and np.abs(pos).max() <= 16.0
+    ref = sweep_brute(prev, pos, s.triangles, s.body, rad, margin)
+    assert ref[3] > 30 and (ref[1][: n // 2] >= 0).sum() > 200 and np.all(ref[1][n // 2:] == -1)
+    K = pieces(prev, pos, None, reach_a, R, 0.0, margin)
+    print(f"soup: {ref[3]} chords touch; pieces at travel 0.5: max {int(K.max())}, {int((K >= 3).sum())} chords with 3 or more")
+    assert (K >= 3).sum() >= 50 and K.max() >= 4 and K.max() <= 32
+    ctx = fleet.Context([t])
+    got = []
+    for reach in (reach_a, reach_b):
+        dev = s.to_device(ctx, reach)
+        for layout in ("soa", "tile64") if reach == reach_a else ("soa",):
+            st = load(fleet, ctx, pos, layout)
+            cnt, uns = counters(ctx)
+            clr, near = sweep_run(ctx, st, dev, margin, 0.0, soa3(prev, st.n_pad, ctx.device), counter=cnt, unswept=uns)
+            check(clr, near, ref, margin, f"swept, soup {layout} reach {reach:.3f}")
+            assert int(cnt.item()) == ref[3] and int(uns.item()) == 0
+            assert bool((clr[n // 2:] == np.float32(margin)).all()) and bool((near[n // 2:] == -1).all())
+            got.append(clr.cpu().numpy().astype(np.float64))
+        dev.close()
+    # one lookup per chord against up to six: the same clearances
+    np.testing.assert_allclose(got[0], got[2], rtol=0, atol=ATOL)
+    print(f"soup: worst |travel 0.5 - travel 3.0| = {np.abs(got[0] - got[2]).max():.3e} m")
+    ctx.close()
+
+
+# ---- 5. unswept drones are point samples ------------------------------------------------------------------------------------------------
+def test_unswept_drones_equal_the_point_query_bit_for_bit(gpu):
+    nat, fleet = gpu
+    from dronesim_amd import obstacles as obs
+    t = params.builtin_type("robobee")
+    n, margin = 768, 1.0
+    s = gate()
+    rng = np.random.default_rng(17)
+    pos = f32(rng.uniform(GATE_BOX[0], GATE_BOX[1], (n, 3)))
+    v = rng.normal(size=(n, 3))
+    v /= np.linalg.norm(v, axis=1, keepdims=True)
+    prev = pos.copy()                                              # drones 512 ..: chords of length zero
+    prev[:256] = f32(pos[:256] + rng.uniform(40.0, 60.0, (256, 1)) * v[:256])       # teleports: K > 32
+    prev[256:512] = f32(pos[256:512] + 0.1 * v[256:512])
+    prev[np.arange(256, 512), rng.integers(0, 3, 256)] = np.nan   # NaN in one component
+    ctx = fleet.Context([t])
+    reach = obs.sweep_reach(ctx.types, margin, 0.0, 0.5)
+    K = pieces(prev[:256], pos[:256], None, reach, t.collision_sphere, 0.0, margin)
+    assert K.min() > 32
+    dev = s.to_device(ctx, reach)
+    st = load(fleet, ctx, pos)
+    d_prev = soa3(prev, st.n_pad, ctx.device)
+    cnt, uns = counters(ctx)
+    clr, near = sweep_run(ctx, st, dev, margin, 0.0, d_prev, counter=cnt, unswept=uns)
+    p_clr = torch.full((st.n_pad,), -7.0, dtype=torch.float32, device=ctx.device)
+    p_near = torch.full((st.n_pad,), -7, dtype=torch.int32, device=ctx.device)
+    p_cnt = torch.zeros((1,), dtype=torch.int64, device=ctx.device)
+    obs.query(ctx, st, dev, margin, p_clr, p_near, None, None, p_cnt)
+    assert torch.equal(clr[:512], p_clr[:512]) and torch.equal(near[:512], p_near[:512])
+    assert int((p_near[:512] >= 0).sum()) > 300 and int((p_clr[:512] < 0).sum()) > 30
+    assert int(uns.item()) == 512
+    z, pz = clr[512:].cpu().numpy().astype(np.float64), p_clr[512:n].cpu().numpy().astype(np.float64)
+    print(f"zero-length chords: worst |swept - point| = {np.abs(z - pz).max():.3e} m")
+    assert np.isfinite(z).all()
+    np.testing.assert_allclose(z, pz, rtol=0, atol=ATOL)
+    assert np.array_equal(d_prev[:, :n].cpu().numpy().T, pos.astype(np.float32))      # NaN and teleports are gone from prev
+    # a non-finite current position: (margin, -1), itself left in prev, so the next call is unswept
+    bad = pos.copy()
+    bad[5, 1] = np.nan
+    st2 = fleet.FleetState(ctx, n, "soa")
+    st2.set_fields(0, torch.from_numpy(np.ascontiguousarray(bad.T.astype(np.float32))).to(ctx.device))
+    uns.zero_()
+    clr2, near2 = sweep_run(ctx, st2, dev, margin, 0.0, d_prev, unswept=uns)
+    assert float(clr2[5].item()) == np.float32(margin) and int(near2[5].item()) == -1 and int(uns.item()) == 1
+    assert bool(torch.isnan(d_prev[1, 5]).item())
+    clr3, _ = sweep_run(ctx, st, dev, margin, 0.0, d_prev, unswept=uns)
+    assert int(uns.item()) == 2 and float(clr3[5].item()) == float(p_clr[5].item())
+    dev.close()
+    ctx.close()
+
+
+# ---- 6. refusals and PRIME ----------------------------------------------------------------------------------------------------------------
+def test_refusals_and_prime_leave_the_outputs_untouched(gpu):
+    import ctypes
+    nat, fleet = gpu
+    from dronesim_amd import obstacles as obs
+    t = params.builtin_type("robobee")
+    ctx = fleet.Context([t])
+    s = gate()
+    margin = 0.5
+    dev = s.to_device(ctx, obs.sweep_reach(ctx.types, margin, 0.01, 0.2))
+    tight = s.to_device(ctx, obs.watch_reach(ctx.types, margin))      # a point-watch set: no room for a piece
+    rng = np.random.default_rng(19)
+    pos = f32(rng.uniform(GATE_BOX[0], GATE_BOX[1], (64, 3)))
+    st = load(fleet, ctx, pos)
+    clr = torch.full((st.n_pad,), -7.0, dtype=torch.float32, device=ctx.device)
+    near = torch.full((st.n_pad,), -7, dtype=torch.int32, device=ctx.device)
+    prev = torch.full((3, st.n_pad), -5.0, dtype=torch.float32, device=ctx.device)
+    cnt, uns = counters(ctx)
+
+    def call(h=dev.handle, m=margin, sag=0.01, flags=0, p=prev.data_ptr(), out=clr.data_ptr(), n=st.n, c=ctx.handle, null_args=False):
+        a = nat.SweepArgs(None, None, m, sag, p, flags, out, near.data_ptr(), cnt.data_ptr(), uns.data_ptr())
+        return ctx.lib.dsim_obstacle_sweep(c, ctx.stream_ptr(), n, st.view(), h, None if null_args else ctypes.byref(a))
+    inf, nan = float("inf"), float("nan")
+    assert call(c=None) == -1 and call(h=None) == -1 and call(null_args=True) == -1 and call(p=None) == -1
+    assert call(m=0.0) == -1 and call(m=-1.0) == -1 and call(m=nan) == -1 and call(m=inf) == -1
+    assert call(sag=-1e-3) == -1 and call(sag=nan) == -1 and call(sag=inf) == -1
+    assert call(out=None) == -1
+    assert call(n=0) == -1 and call(n=st.n_pad + 1) == -1
+    assert call(flags=4) == -1 and call(flags=3) == -1
+    assert call(m=margin * 1.5) == -1 and call(sag=0.2) == -1      # R_max + sag + margin beyond what the set's reach leaves
+    assert call(h=tight.handle, sag=0.0) == -1                      # half < reach / 1024
+    torch.cuda.synchronize()
+    assert bool((clr == -7.0).all()) and bool((near == -7).all()) and bool((prev == -5.0).all())
+    assert int(cnt.item()) == 0 and int(uns.item()) == 0 and ctx.query(nat.QUERY_OBSTACLE_CONTACTS) == 0
+    # PRIME: prev and nothing else
+    assert call(flags=nat.SWEEP_PRIME, out=None, m=0.0) == 0
+    torch.cuda.synchronize()
+    assert np.array_equal(prev[:, : st.n].cpu().numpy().T, pos.astype(np.float32)) and bool((prev[:, st.n:] == -5.0).all())
+    assert bool((clr == -7.0).all()) and bool((near == -7).all())
+    assert int(cnt.item()) == 0 and int(uns.item()) == 0 and ctx.query(nat.QUERY_OBSTACLE_CONTACTS) == 0
+    prev.fill_(-5.0)
+    obs.prime(ctx, st, dev, prev)
+    assert np.array_equal(prev[:, : st.n].cpu().numpy().T, pos.astype(np.float32))
+    # and the call that is in order is served, also with a smaller margin on the same set
+    assert call() == 0 and call(m=0.25) == 0
+    torch.cuda.synchronize()
+    assert int(uns.item()) == 0 and not bool((clr[: st.n] == -7.0).any())
+    tight.close()
+    dev.close()
+    ctx.close()
+
+
+# ---- 7. the env -----------------------------------------------------------------------------------------------------------------------------
+def _column(n, z0=3.0):
+    """n tellos in a column above the top bar of gates of their own (the frames 1 m apart along x), 0.45 .. 1.0 m above its centre."""
+    from dronesim_amd.obstacles import ObstacleSet
+    s = ObstacleSet.from_urdf(os.path.join(GOLDEN, "gate_50_curved.urdf"), (0.0, 0.0, z0), (0, 0, 0))
+    off = np.stack([np.arange(n), np.zeros(n), np.zeros(n)], 1).astype(np.float64)
+    rng = np.random.default_rng(53)
+    q = np.stack([rng.uniform(-0.12, 0.12, n), rng.uniform(-0.2, 0.2, n), z0 + 0.45 + 0.55 * np.arange(n) / n], 1)
+    return s, q + off, off
+
+
+def test_env_dropped_column_sweeps_what_the_samples_miss(gpu):
+    nat, _ = gpu
+    from dronesim_amd.envs import CtrlAviary
+    from dronesim_amd.obstacles import sweep_sag
+    n, margin, steps = 64, 0.5, 24
+    sag = sweep_sag(9.8, 5 / 240)
+    s, xyz, off = _column(n)
+    kw = dict(initial_xyzs=xyz, aggregate_phy_steps=5, freq=240, obstacle_watch=s, obstacle_margin=margin, obstacle_offsets=off,
+              dict_io=False, noise_seed=0)
+    env = CtrlAviary(["tello"], n, obstacle_sweep=True, obstacle_sweep_sag=sag, **kw)
+    twin = CtrlAviary(["tello"], n, **kw)
+    rad = np.full(n, np.float32(env.ctx.types[0].collision_sphere))
+    zero = torch.zeros((n, 4), dtype=torch.float32, device=env.ctx.device)
+    off32 = f32(off)
+    assert env.obstacle_contacts() == 0 and env.obstacle_unswept() == 0 and env.last_obstacle_clearance is None
+
+    def swept_step(e, total, label):
+        before = _positions(e)
+        e.step(zero)
+        after = _positions(e)
+        ref = sweep_brute(before, after, s.triangles, s.body, rad, margin, sag, off32)
+        got = e.last_obstacle_clearance[0].cpu().numpy().astype(np.float64)
+        np.testing.assert_allclose(got, ref[0], rtol=0, atol=ATOL, err_msg=label)
+        inc = e.obstacle_contacts() - total
+        band = np.abs(ref[4]) < ATOL
+        assert inc == int((got < 0).sum())
+        np.testing.assert_array_equal((got < 0)[~band], (ref[4] < 0)[~band])
+        return inc, ref[3], np.abs(got - ref[0]).max(), after
+
+    total = ref_total = point_total = 0
+    worst = 0.0
+    for k in range(steps):
+        inc, r3, err, after = swept_step(env, total, f"step {k}")
+        total, ref_total, worst = total + inc, ref_total + r3, max(worst, err)
+        twin.step(zero)
+        assert np.array_equal(_positions(twin), after)              # (the watch acts on nothing: the same flight)
+        point_total += brute(after, s.triangles, s.body, rad, margin, off32)[3]
+        c2, _n2 = env.obstacle_clearance()                         # on demand: the POINT query of the current state, no Env.step
+        assert torch.equal(c2, twin.last_obstacle_clearance[0])
+    print(f"dropped column, {n} tellos x {steps} steps: swept {total} drone-steps in contact (reference {ref_total}), the samples "
+          f"{twin.obstacle_contacts()} (reference {point_total}); worst |swept - fp64| {worst:.2e} m")
+    assert ref_total > point_total > 0 and total > twin.obstacle_contacts()
+    assert env.obstacle_contacts() == total and env.obstacle_unswept() == 0
+    # after reset() the first step is swept from the reset positions: neither from where the flight ended, nor a point sample
+    env.reset()
+    assert np.array_equal(_positions(env), f32(xyz).astype(np.float32))
+    swept_step(env, total, "first step after reset")
+    assert env.obstacle_unswept() == 0
+    env.close()
+    twin.close()
+    with pytest.raises(ValueError):
+        CtrlAviary(["tello"], n, initial_xyzs=xyz, obstacle_sweep=True, dict_io=False, noise_seed=0)
+
+
+def test_env_eager_vs_captured_replay(gpu):
+    nat, _ = gpu
+    from dronesim_amd.envs import CtrlAviary
+    from dronesim_amd.fleet import Targets
+    from dronesim_amd.obstacles import sweep_sag
+    n, margin = 64, 0.5
+    sag = sweep_sag(9.8, 5 / 240)
+    s, xyz, off = _column(n)
+    below = xyz - np.array([0.0, 0.0, 1.5])
+    envs, tgts = [], []
+    for _ in range(2):
+        e = CtrlAviary(["tello"], n, initial_xyzs=xyz, aggregate_phy_steps=5, freq=240, obstacle_watch=s, obstacle_margin=margin,
+                       obstacle_offsets=off, obstacle_sweep=True, obstacle_sweep_sag=sag, dict_io=False, noise_seed=0)
+        tg = Targets(e.ctx, n)
+        tg.set(pos=f32(below).T, yaw=0.0)
+        envs.append(e)
+        tgts.append(tg)
+    eager = []
+    for k in range(24):
+        envs[0].step_fused(tgts[0])
+        if k % 4 == 3:
+            eager.append(tuple(x.clone() for x in envs[0].last_obstacle_clearance) + (envs[0].obstacle_contacts(),))
+    g = envs[1].capture_fused(tgts[1], 4)
+    for k in range(6):
+        g.replay()
+        c1, n1 = envs[1].last_obstacle_clearance
+        assert torch.equal(eager[k][0], c1) and torch.equal(eager[k][1], n1), k
+        assert envs[1].obstacle_contacts() == eager[k][2], k
+    assert torch.equal(envs[0].state.fields(0, 13), envs[1].state.fields(0, 13))
+    assert eager[-1][2] > 0 and envs[0].obstacle_unswept() == envs[1].obstacle_unswept() == 0
+    assert torch.equal(envs[0]._obst_prev, envs[1]._obst_prev)
+    for e in envs:
+        e.close()
