@@ -27,6 +27,7 @@ EXPORTS = (
     "dsim_depth_image_drones", "dsim_depth_image_drones_workspace",
     "dsim_trajgen", "dsim_trajgen_workspace", "dsim_traj_sample_bank",
     "dsim_obstacle_sweep",
+    "dsim_scenes_create", "dsim_scenes_destroy", "dsim_obstacle_clearance_scenes", "dsim_depth_image_scenes",
 )
 
 ABI_VERSION = 11
@@ -330,6 +331,10 @@ def load(path: str = None) -> ctypes.CDLL:
     lib.dsim_depth_image_drones_workspace.restype = ctypes.c_int64
     lib.dsim_depth_image_drones_workspace.argtypes = [i64, i32, i32]
     lib.dsim_depth_image_drones.argtypes = [vp, vp, View, vp, ctypes.POINTER(CameraParams), i64, vp, vp, vp, ctypes.POINTER(CameraDrones), vp, vp]
+    lib.dsim_scenes_create.argtypes = [vp, vp, vp, vp, i64, i32, ctypes.POINTER(vp)]
+    lib.dsim_scenes_destroy.argtypes = [vp, vp]
+    lib.dsim_obstacle_clearance_scenes.argtypes = [vp, vp, i64, View, vp, vp, vp, vp, ctypes.c_float, vp, vp, vp]
+    lib.dsim_depth_image_scenes.argtypes = [vp, vp, View, vp, vp, ctypes.POINTER(CameraParams), i64, vp, vp, vp, vp, vp]
     lib.dsim_trajgen_workspace.restype = ctypes.c_int64
     lib.dsim_trajgen_workspace.argtypes = [i64, i32]
     lib.dsim_trajgen.argtypes = [vp, vp, ctypes.POINTER(TrajBank), ctypes.POINTER(TrajGenArgs)]

@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from . import _native as nat
-from .obstacles import DeviceObstacles, ObstacleSet
+from .obstacles import DeviceObstacles, DeviceScenes, ObstacleScenes, ObstacleSet, scene_ids_tensor
 
 
 def camera_reach(types) -> float:
@@ -40,10 +40,15 @@ class DepthCamera:
     The fleet is binned per capture on an xy grid over its bounding box, re-measured every 256 captures like the contact
     watch's (one host sync; never under stream capture, where the box of the last eager capture stands), or over ``drone_box`` =
     (xmin, ymin, xmax, ymax); a drone outside the box is still drawn exactly, and :meth:`drones_outside` counts such drones.
-    ``obstacle_set`` may then be None: a world of drones and, with ``ground``, the plane."""
+    ``obstacle_set`` may then be None: a world of drones and, with ``ground``, the plane.
+
+    Obstacle scenes: ``obstacle_set`` may be an :class:`ObstacleScenes` (device scenes are made for it) or a
+    :class:`DeviceScenes` to share; the camera of drone i then sees the placements of scene ``scene_id[i]`` (dsim_depth_image_scenes;
+    ``scene_id`` [n] ints in the numbering ``offsets`` uses, required, an id outside [0, K) meaning no obstacles), and ``seg``
+    names a hit by the instance-major body index g n_bodies + body.  ``drones=True`` with scenes is not implemented."""
 
     def __init__(self, ctx, state, obstacle_set, res=(64, 48), fov=60.0, aspect=1.0, far=1000.0, ground=False, metric=False,
-                 cameras=None, offsets=None, type_id=None, drones=False, drone_range=None, drone_box=None):
+                 cameras=None, offsets=None, type_id=None, drones=False, drone_range=None, drone_box=None, scene_id=None):
         w, h = (int(v) for v in res)
         if not (1 <= w <= 1024 and 1 <= h <= 1024):
             raise ValueError(f"res must be (width, height) with 1 <= each <= 1024, got {res!r}")
@@ -68,14 +73,23 @@ class DepthCamera:
         if obstacle_set is None and not drones:
             raise TypeError("obstacle_set takes an ObstacleSet or a DeviceObstacles (None only with drones=True)")
         self.ctx, self.state = ctx, state
-        self._owns_set = isinstance(obstacle_set, ObstacleSet)
+        self.placed = isinstance(obstacle_set, (ObstacleScenes, DeviceScenes))
+        if self.placed and drones:
+            raise NotImplementedError("drones=True with obstacle scenes: there is no placed dsim_depth_image_drones (the other "
+                                      "drones in placed images are a follow-up)")
+        if self.placed and scene_id is None:
+            raise ValueError("scene_id is required with obstacle scenes")
+        if not self.placed and scene_id is not None:
+            raise ValueError("scene_id without obstacle scenes")
+        self._owns_set = isinstance(obstacle_set, (ObstacleSet, ObstacleScenes))
         if self._owns_set:
             obstacle_set = obstacle_set.to_device(ctx, camera_reach(ctx.types))
-        if obstacle_set is not None and not isinstance(obstacle_set, DeviceObstacles):
-            raise TypeError("obstacle_set takes an ObstacleSet or a DeviceObstacles")
+        if obstacle_set is not None and not isinstance(obstacle_set, (DeviceObstacles, DeviceScenes)):
+            raise TypeError("obstacle_set takes an ObstacleSet, a DeviceObstacles, an ObstacleScenes or a DeviceScenes")
         self.set = obstacle_set.enable_rays() if obstacle_set is not None else None
         order = getattr(state, "order", None) or getattr(ctx, "order", None)
         n, dev = state.n, ctx.device
+        self._scene_id = scene_ids_tensor(scene_id, n, state.n_pad, dev, order) if self.placed else None
         self._index = None
         if cameras is None:
             n_cam = n
@@ -118,7 +132,7 @@ class DepthCamera:
             self._dr.outside_out = self._outside.data_ptr()
 
     def capture(self, seg: bool = True):
-        """Enqueues one dsim_depth_image (``drones=True``: dsim_depth_image_drones) on the current stream (it may be captured into
+        """Enqueues one dsim_depth_image (``drones=True``: dsim_depth_image_drones; scenes: dsim_depth_image_scenes) on the current stream (it may be captured into
         a graph) and returns (dep, seg): the camera's own tensors, overwritten by the next capture.  ``seg=False`` leaves the
         segmentation image unwritten."""
         common = (self._index.data_ptr() if self._index is not None else None, self._off.data_ptr() if self._off is not None else None,
@@ -130,6 +144,11 @@ class DepthCamera:
                 self.ctx.handle, self.ctx.stream_ptr(), self.state.view(), self.set.handle if self.set is not None else None,
                 ctypes.byref(self.params), self.n_cam, *common, ctypes.byref(self._dr), self.dep.data_ptr(),
                 self.seg.data_ptr() if seg else None))
+            return self.dep, (self.seg if seg else None)
+        if self.placed:
+            nat.check(self.ctx.lib.dsim_depth_image_scenes(
+                self.ctx.handle, self.ctx.stream_ptr(), self.state.view(), self.set.handle, self._scene_id.data_ptr(),
+                ctypes.byref(self.params), self.n_cam, *common, self.dep.data_ptr(), self.seg.data_ptr() if seg else None))
             return self.dep, (self.seg if seg else None)
         nat.check(self.ctx.lib.dsim_depth_image(
             self.ctx.handle, self.ctx.stream_ptr(), self.state.view(), self.set.handle, ctypes.byref(self.params), self.n_cam,
@@ -155,7 +174,7 @@ class DepthCamera:
     def graph_keepalive(self):
         """What a captured capture() holds the addresses of, for the owner of the graph to keep alive: an eager capture that later
         re-measures the box and outgrows the drones' workspace makes a new one, and the old must outlive the graph."""
-        keep = [self.dep, self.seg, self._index, self._off, self._type_id]
+        keep = [self.dep, self.seg, self._index, self._off, self._type_id, self._scene_id]
         if self.drones:
             keep += [self._grid._ws, self._label, self._outside]
         return tuple(keep)

@@ -16,6 +16,14 @@ struct CamDr {
   float range;
 };
 
+// Obstacle scenes (dsim_depth_image_scenes): the placement table of dsim_scenes and the scene of every drone.
+struct CamPl {
+  const float4* place;             // [K][G][4] (dsim_obstacles.hip: struct dsim_scenes)
+  const int* scene_id;             // [n_pad], storage order
+  long long K;
+  int G, n_bodies;
+};
+
 struct CamK {
   KView st;
   long long n_pad;
@@ -40,7 +48,10 @@ struct CamK {
 #ifdef DSIM_CAM_COUNT
   unsigned long long* tests;              // triangle tests, summed over every ray (a measuring build: tools/bench_camera.py)
 #endif
-  CamDr dr;                               // DRONES instances only (at the end: the other instances' arguments lie where they lay)
+  union {                                 // (at the end: the other instances' arguments lie where they lay)
+    CamDr dr;                             // DRONES instances only
+    CamPl pl;                             // PLACED instances only (never both: scenes with drones are refused)
+  };
 };
 
 // One sphere (x, y, z, R) against the ray w + t d, cancellation-free: m = c - w, tc = m.d / d.d the parameter of the ray's closest
@@ -73,8 +84,10 @@ __device__ __forceinline__ void cam_sphere(const float4 p, const int* __restrict
 // spheres of the 3 x 3 block around the ray's cell are all that can be hit inside it — the whole block at the first cell, the
 // three newly adjacent cells after every step — and the walk stops as soon as best is not beyond the cell's exit.  The box the
 // ray is clipped to is the grid's grown by one ring of (empty) cells: a sphere of a border cell reaches outside the grid's box.
-// Then the outside list.  TRIS = false: no obstacle set (drones and, optionally, the plane).
-template <bool LDS, bool SEG, bool DRONES = false, bool TRIS = true>
+// Then the outside list.  TRIS = false: no obstacle set (drones and, optionally, the plane).  PLACED (dsim_depth_image_scenes): the set is
+// a prototype, walked once per placement of the camera's scene in that placement's frame (dsim_camera_walk.inc is the walk, as
+// text, for both); the plane stays in the task frame.
+template <bool LDS, bool SEG, bool DRONES = false, bool TRIS = true, bool PLACED = false>
 __global__ __launch_bounds__(256) void k_depth_image(CamK a) {
   extern __shared__ float4 s_cam_rec[];
   const unsigned cam = blockIdx.x / a.blocks_per_cam, blk = blockIdx.x - cam * a.blocks_per_cam;
@@ -141,65 +154,47 @@ __global__ __launch_bounds__(256) void k_depth_image(CamK a) {
     const float tg = -ez / dz;                                 // (dz = 0: +-inf or NaN, which fail the test)
     if (tg >= near && tg <= a.far) { best = tg; body = DSIM_SEG_GROUND; }
   }
-  // slab clip against [o, hi]; a zero component gives +-inf (or NaN at a face, which fminf / fmaxf drop)
-  const float ix_ = 1.0f / dx, iy_ = 1.0f / dy, iz_ = 1.0f / dz;
-  const float x0 = (a.ox - ex) * ix_, x1 = (a.hix - ex) * ix_;
-  const float y0 = (a.oy - ey) * iy_, y1 = (a.hiy - ey) * iy_;
-  const float z0 = (a.oz - ez) * iz_, z1 = (a.hiz - ez) * iz_;
-  const float t_in = fmaxf(fmaxf(fminf(x0, x1), fminf(y0, y1)), fmaxf(fminf(z0, z1), near));
-  const float t_out = fminf(fminf(fmaxf(x0, x1), fmaxf(y0, y1)), fminf(fmaxf(z0, z1), fminf(a.far, best)));
-  const bool inside_x = dx != 0.0f || (ex >= a.ox && ex <= a.hix);          // a ray parallel to a slab and outside it misses
-  const bool inside_y = dy != 0.0f || (ey >= a.oy && ey <= a.hiy);
-  const bool inside_z = dz != 0.0f || (ez >= a.oz && ez <= a.hiz);
 #ifdef DSIM_CAM_COUNT
   unsigned n_tests = 0u;
 #endif
-  if (TRIS && live && t_in <= t_out && inside_x && inside_y && inside_z) {
-    // the cell of the entry point, clamped; per axis the direction of travel, t at the next face and t per cell
-    const float qx = ex + t_in * dx, qy = ey + t_in * dy, qz = ez + t_in * dz;
-    int cx = min(max((int)floorf((qx - a.ox) * a.inv_cell), 0), a.nx - 1);
-    int cy = min(max((int)floorf((qy - a.oy) * a.inv_cell), 0), a.ny - 1);
-    int cz = min(max((int)floorf((qz - a.oz) * a.inv_cell), 0), a.nz - 1);
-    const int stx = dx > 0.0f ? 1 : -1, sty = dy > 0.0f ? 1 : -1, stz = dz > 0.0f ? 1 : -1;
-    const float dtx = dx != 0.0f ? a.cell * fabsf(ix_) : INFINITY;
-    const float dty = dy != 0.0f ? a.cell * fabsf(iy_) : INFINITY;
-    const float dtz = dz != 0.0f ? a.cell * fabsf(iz_) : INFINITY;
-    float tmx = dx != 0.0f ? (a.ox + (float)(cx + (dx > 0.0f ? 1 : 0)) * a.cell - ex) * ix_ : INFINITY;
-    float tmy = dy != 0.0f ? (a.oy + (float)(cy + (dy > 0.0f ? 1 : 0)) * a.cell - ey) * iy_ : INFINITY;
-    float tmz = dz != 0.0f ? (a.oz + (float)(cz + (dz > 0.0f ? 1 : 0)) * a.cell - ez) * iz_ : INFINITY;
-    const int max_cells = a.nx + a.ny + a.nz;                  // a walk visits fewer: every step moves one cell along one axis
-    for (int it = 0; it < max_cells; ++it) {
-      const int c = (cz * a.ny + cy) * a.nx + cx;
-      const int end = a.cell_start[c + 1];
-      for (int k = a.cell_start[c]; k < end; ++k) {
-        const float4* r = (LDS ? s_cam_rec : a.rec) + 4 * a.cell_tri[k];
-        const float4 r0 = r[0], r1 = r[1];
-        const float acz = r[2].x;
-        const int rb = __float_as_int(r[3].w);
-        const float ax = r0.x, ay = r0.y, az = r0.z, abx = r0.w, aby = r1.x, abz = r1.y, acx = r1.z, acy = r1.w;
-        const float pvx = dy * acz - dz * acy, pvy = dz * acx - dx * acz, pvz = dx * acy - dy * acx;      // d x ac
-        const float det = abx * pvx + aby * pvy + abz * pvz;
-        const float tx = ex - ax, ty = ey - ay, tz = ez - az;
-        const float idet = DSIM_RCP(det);                      // (det = 0, a ray in the triangle's plane: inf, nothing passes)
-        const float u = (tx * pvx + ty * pvy + tz * pvz) * idet;
-        const float qvx = ty * abz - tz * aby, qvy = tz * abx - tx * abz, qvz = tx * aby - ty * abx;      // (e - a) x ab
-        const float v = (dx * qvx + dy * qvy + dz * qvz) * idet;
-        const float t = (acx * qvx + acy * qvy + acz * qvz) * idet;
-        const bool hit = u >= 0.0f && v >= 0.0f && u + v <= 1.0f && t >= near && t <= a.far && t < best;
-        best = hit ? t : best;
-        body = hit ? rb : body;
-#ifdef DSIM_CAM_COUNT
-        ++n_tests;
-#endif
+  // the set in the task frame (every instance but the PLACED ones, of which nothing of this survives)
+#define CW_EX ex
+#define CW_EY ey
+#define CW_EZ ez
+#define CW_DX dx
+#define CW_DY dy
+#define CW_DZ dz
+#define CW_GATE (TRIS && !PLACED)
+#define CW_BODY(rb) rb
+#include "dsim_camera_walk.inc"
+  if (PLACED) {
+    // The camera's scene is uniform: its placements are read through the scalar path, the eye and the basis go into each
+    // placement's frame once (subtract first, then rotate), and a lane forms its ray from the rotated basis.  t is eye-space depth
+    // in every frame, so best and body carry across placements and bound every later walk.  A scene outside [0, K): no obstacles.
+    const int sid = a.pl.scene_id[i];
+    if (sid >= 0 && (long long)sid < a.pl.K) {
+      const float4* pl = a.pl.place + 4 * ((size_t)sid * (size_t)a.pl.G);
+      for (int g = 0; g < a.pl.G; ++g) {
+        const float4 w0 = pl[4 * g];
+        if (!(w0.w >= 0.0f)) continue;                         // a slot at or above the scene's count
+        const float4 c0 = pl[4 * g + 1], c1 = pl[4 * g + 2], c2 = pl[4 * g + 3];
+        const float tx = ex - c0.w, ty = ey - c1.w, tz = ez - c2.w;
+        const float lex = c0.x * tx + c0.y * ty + c0.z * tz, ley = c1.x * tx + c1.y * ty + c1.z * tz, lez = c2.x * tx + c2.y * ty + c2.z * tz;
+        const float lfx = c0.x * fx + c0.y * fy + c0.z * fz, lfy = c1.x * fx + c1.y * fy + c1.z * fz, lfz = c2.x * fx + c2.y * fy + c2.z * fz;
+        const float lsx = c0.x * sx + c0.y * sy, lsy = c1.x * sx + c1.y * sy, lsz = c2.x * sx + c2.y * sy;
+        const float lux = c0.x * ux + c0.y * uy + c0.z * uz, luy = c1.x * ux + c1.y * uy + c1.z * uz, luz = c2.x * ux + c2.y * uy + c2.z * uz;
+        const float ldx = lfx + ca * lsx + cb * lux, ldy = lfy + ca * lsy + cb * luy, ldz = lfz + ca * lsz + cb * luz;
+        const int body_add = g * a.pl.n_bodies;
+#define CW_EX lex
+#define CW_EY ley
+#define CW_EZ lez
+#define CW_DX ldx
+#define CW_DY ldy
+#define CW_DZ ldz
+#define CW_GATE true
+#define CW_BODY(rb) (rb + body_add)
+#include "dsim_camera_walk.inc"
       }
-      const float t_exit = fminf(tmx, fminf(tmy, tmz));
-      if (best <= t_exit || t_exit >= t_out) break;            // nothing nearer can lie in a later cell / the ray leaves the box
-      const bool gx = tmx <= tmy && tmx <= tmz;
-      const bool gy = !gx && tmy <= tmz;
-      const bool gz = !gx && !gy;
-      cx += gx ? stx : 0; cy += gy ? sty : 0; cz += gz ? stz : 0;
-      tmx += gx ? dtx : 0.0f; tmy += gy ? dty : 0.0f; tmz += gz ? dtz : 0.0f;
-      if (cx < 0 || cx >= a.nx || cy < 0 || cy >= a.ny || cz < 0 || cz >= a.nz) break;
     }
   }
   if (DRONES) {

@@ -23,6 +23,18 @@ struct dsim_obstacles {
   int* ray_tri;
   dsim_obstacle_grid ray_grid;
   std::vector<float> tri_host;
+  int n_bodies;                  // 1 + the largest body index (obstacle scenes number a hit g * n_bodies + body)
+};
+
+// Obstacle scenes (dsim_scenes_create; dsim_scenes.hip): K scenes of up to G placements of one prototype set.  One 64-byte record
+// per slot: (c_task.xyz, r_cull) — the centre of the prototype's box placed into the task frame and the radius outside which the
+// placement is out of every query's reach, -inf for a slot at or above its scene's count — then R's three columns, each
+// followed by one component of t: the local point is (col_k . (q - t))_k = R^T (q - t).
+struct dsim_scenes {
+  const dsim_obstacles* proto;
+  float4* place;                 // [K][G][4]
+  long long K;
+  int G;
 };
 
 struct ObsK {
@@ -83,6 +95,26 @@ __device__ __forceinline__ float tri_dist2(const float4 r0, const float4 r1, con
   return mode == 6 ? h * h : ex * ex + ey * ey + ez * ez;
 }
 
+// The cell of q and the walk of its list (both clearance kernels: the set's frame, and a placement's): the least squared distance
+// below `best` and the body of the triangle that attains it.  The records come from LDS when the whole set was staged.
+template <bool LDS>
+__device__ __forceinline__ void obs_cell_walk(const ObsK& a, const float4* s_rec, float qx, float qy, float qz, int& body, float& best) {
+  const int cx = min(max((int)floorf((qx - a.ox) * a.inv_cell), 0), a.nx - 1);
+  const int cy = min(max((int)floorf((qy - a.oy) * a.inv_cell), 0), a.ny - 1);
+  const int cz = min(max((int)floorf((qz - a.oz) * a.inv_cell), 0), a.nz - 1);
+  const int c = (cz * a.ny + cy) * a.nx + cx;
+  const int end = a.cell_start[c + 1];
+  for (int k = a.cell_start[c]; k < end; ++k) {
+    const int t = a.cell_tri[k];
+    const float4* r = (LDS ? s_rec : a.rec) + 4 * t;
+    const float4 r0 = r[0], r1 = r[1], r2 = r[2], r3 = r[3];
+    const float d2 = tri_dist2(r0, r1, r2, r3, qx, qy, qz);
+    const bool better = d2 < best;
+    best = better ? d2 : best;
+    body = better ? __float_as_int(r3.w) : body;
+  }
+}
+
 // One drone per lane, tiles of 256 drones grid-stride.  A tile none of whose drones lies in the grown box reads its positions
 // (and offsets) and writes (margin, -1); of a tile that has some, the waves that have none do the same.  The others look up
 // their cell and walk its list: the records come from LDS when the whole set fits (staged by the workgroup before its first
@@ -112,22 +144,7 @@ __global__ __launch_bounds__(256) void k_obstacle_clearance(ObsK a) {
     }
     float best = INFINITY;
     int body = -1;
-    if (inbox) {                       // (a wave with no such lane skips the block: the per-wave reject)
-      const int cx = min(max((int)floorf((qx - a.ox) * a.inv_cell), 0), a.nx - 1);
-      const int cy = min(max((int)floorf((qy - a.oy) * a.inv_cell), 0), a.ny - 1);
-      const int cz = min(max((int)floorf((qz - a.oz) * a.inv_cell), 0), a.nz - 1);
-      const int c = (cz * a.ny + cy) * a.nx + cx;
-      const int end = a.cell_start[c + 1];
-      for (int k = a.cell_start[c]; k < end; ++k) {
-        const int t = a.cell_tri[k];
-        const float4* r = (LDS ? s_rec : a.rec) + 4 * t;
-        const float4 r0 = r[0], r1 = r[1], r2 = r[2], r3 = r[3];
-        const float d2 = tri_dist2(r0, r1, r2, r3, qx, qy, qz);
-        const bool better = d2 < best;
-        best = better ? d2 : best;
-        body = better ? __float_as_int(r3.w) : body;
-      }
-    }
+    if (inbox) obs_cell_walk<LDS>(a, s_rec, qx, qy, qz, body, best);   // (a wave with no such lane skips it: the per-wave reject)
     const float c_i = DSIM_SQRT(best) - R;
     const bool in = inbox && c_i < a.margin;
     if (live) {
@@ -190,7 +207,8 @@ int dsim_obstacles_create(dsim_ctx* ctx, const float* tri_host, const int32_t* b
   dsim_obstacles* s = new (std::nothrow) dsim_obstacles();
   if (!s) return (int)hipErrorOutOfMemory;
   s->rec = nullptr; s->cell_start = nullptr; s->cell_tri = nullptr; s->n_tri = (int)n_tri; s->grid = g;
-  s->ray_start = nullptr; s->ray_tri = nullptr;
+  s->ray_start = nullptr; s->ray_tri = nullptr; s->n_bodies = 1;
+  if (body_host) for (int64_t t = 0; t < n_tri; ++t) if (body_host[t] >= s->n_bodies) s->n_bodies = body_host[t] + 1;
   try { s->tri_host.assign(tri_host, tri_host + 9 * n_tri); } catch (const std::bad_alloc&) { delete s; return (int)hipErrorOutOfMemory; }
   hipError_t e = hipSetDevice(ctx->device);           // (as dsim_dev_alloc: the set lives where the ctx's streams run)
   if (e == hipSuccess) e = hipMalloc((void**)&s->rec, rec.size() * sizeof(float));
@@ -245,3 +263,6 @@ int dsim_obstacle_clearance(dsim_ctx* ctx, void* stream, int64_t n, dsim_view st
 
 // the swept watch: the chord between two samples against the same set (it shares the record, tri_dist2 and the LDS threshold)
 #include "dsim_sweep.hip"
+
+// obstacle scenes: per-drone placements of one set for the watch and the camera (they share the cell walk and the camera's kernel)
+#include "dsim_scenes.hip"

@@ -1,0 +1,196 @@
+// Obstacle scenes (dsim_scenes_create, dsim_obstacle_clearance_scenes, dsim_depth_image_scenes): K scenes of up to G rigid
+// placements of ONE prototype set, and a scene per drone.  Distances and ray parameters do not change under a rotation and a shift,
+// so the prototype's grids, records and LDS staging serve every placement: only the query point, or the ray, goes into the
+// placement's frame.  Compiled as part of dsim_obstacles.hip, which includes this file: it shares the watch's cell walk
+// (obs_cell_walk), its arguments (ObsK, obs_kargs) and the camera's kernel (k_depth_image<.., PLACED>, cam_fill).
+#pragma once
+
+#define SCN_MAX_G 32                     // one bit per placement in a lane's mask
+#define SCN_MAX_SLOTS (1LL << 22)
+
+struct ScnK {
+  const float4* place;                   // [K][G][4] (struct dsim_scenes)
+  const int* scene_id;                   // [n_pad]
+  long long K;
+  int G, n_bodies;
+};
+
+// k_obstacle_clearance with the set placed: one drone per lane, tiles of 256 grid-stride, the prototype's records staged in LDS
+// once per workgroup.  Scene ids differ per lane, so placement records are per-lane vector loads: a lane reads the first 16 bytes
+// of each of its scene's G slots, (c_task, r_cull), and the other 48 only of a slot whose sphere it is within reach of — the bound
+// is widened (1e-4 relative, 1e-5 m) well beyond the fp32 rounding of q - c and of an R that is orthonormal to 1e-5, so it decides
+// speed only.  Then q goes into the placement's frame, subtract first, then rotate: R^T q - R^T t cancels digits at offsets of
+// 128 m, R^T (q - t) does not.  There the grown-box test and the cell walk are the unplaced kernel's.  The minimum runs over the
+// placements in slot order with a strict <, and the body is g * n_bodies + the triangle's.
+template <bool LDS>
+__global__ __launch_bounds__(256) void k_obstacle_clearance_scenes(ObsK a, ScnK s) {
+  extern __shared__ float4 s_rec[];
+  bool staged = false;
+  for (long long tile = blockIdx.x; tile < a.tiles; tile += gridDim.x) {
+    const long long i = tile * 256 + threadIdx.x;
+    const bool live = i < a.n;
+    float qx = 0.0f, qy = 0.0f, qz = 0.0f, R = 0.0f;
+    int sid = -1;
+    if (live) {
+      const long long o = kv_off(a.st, i);
+      qx = a.st.base[o]; qy = a.st.base[o + a.st.field_stride]; qz = a.st.base[o + 2 * a.st.field_stride];
+      if (a.offset) { qx -= a.offset[i]; qy -= a.offset[a.n_pad + i]; qz -= a.offset[2 * a.n_pad + i]; }
+      R = a.types[a.type_id ? min((int)a.type_id[i], a.n_types - 1) : 0].coll_sphere;
+      sid = s.scene_id[i];
+    }
+    // the placements within reach, one bit each (a NaN position fails every comparison; a scene outside [0, K) has none)
+    unsigned near = 0u;
+    const float4* pl = s.place;
+    if (live && R > 0.0f && sid >= 0 && (long long)sid < s.K) {
+      pl += 4 * ((size_t)sid * (size_t)s.G);
+      for (int g = 0; g < s.G; ++g) {
+        const float4 w = pl[4 * g];
+        const float ux = qx - w.x, uy = qy - w.y, uz = qz - w.z;
+        const float b = (w.w + R + a.margin) * 1.0001f + 1e-5f;                // (-inf for a slot at or above the count)
+        near |= (b >= 0.0f && ux * ux + uy * uy + uz * uz <= b * b) ? (1u << g) : 0u;
+      }
+    }
+    if (LDS) {
+      if (!staged && __syncthreads_or(near != 0u ? 1 : 0)) {
+        for (int k = threadIdx.x; k < 4 * a.n_tri; k += 256) s_rec[k] = a.rec[k];
+        __syncthreads();
+        staged = true;
+      }
+    }
+    float best = INFINITY;
+    int body = -1;
+    while (near != 0u) {                   // (a wave with no such lane skips the loop: the per-wave reject)
+      const int g = __ffs((int)near) - 1;
+      near &= near - 1u;
+      const float4 c0 = pl[4 * g + 1], c1 = pl[4 * g + 2], c2 = pl[4 * g + 3];
+      const float tx = qx - c0.w, ty = qy - c1.w, tz = qz - c2.w;
+      const float lx = c0.x * tx + c0.y * ty + c0.z * tz, ly = c1.x * tx + c1.y * ty + c1.z * tz, lz = c2.x * tx + c2.y * ty + c2.z * tz;
+      // (the grown box of the prototype, in its own frame: outside it no triangle is within reach)
+      if (lx >= a.lox && lx <= a.hix && ly >= a.loy && ly <= a.hiy && lz >= a.loz && lz <= a.hiz) {
+        float b2 = best;
+        int bd = -1;
+        obs_cell_walk<LDS>(a, s_rec, lx, ly, lz, bd, b2);
+        if (bd >= 0) { best = b2; body = g * s.n_bodies + bd; }
+      }
+    }
+    const float c_i = DSIM_SQRT(best) - R;
+    const bool in = body >= 0 && c_i < a.margin;
+    if (live) {
+      a.clearance[i] = in ? c_i : a.margin;
+      if (a.nearest) a.nearest[i] = in ? body : -1;
+    }
+    const unsigned long long hit = __ballot(in && c_i < 0.0f);
+    if (hit != 0ULL && (threadIdx.x & 63u) == 0u) {
+      const unsigned long long cnt = (unsigned long long)__popcll(hit);
+      atomicAdd(&a.counters[8 + DSIM_GROUND_SHARDS + DSIM_DRONE_SHARDS + (tile & (DSIM_OBST_SHARDS - 1))], cnt);
+      if (a.contacts_out) atomicAdd(a.contacts_out, cnt);
+    }
+  }
+}
+
+extern "C" {
+
+int dsim_scenes_create(dsim_ctx* ctx, const dsim_obstacles* proto, const float* place_host, const int32_t* count_host, int64_t K,
+                       int32_t G, dsim_scenes** out) {
+  if (!ctx || !proto || !place_host || !out || K < 1 || G < 1 || G > SCN_MAX_G || K > SCN_MAX_SLOTS / G) return DSIM_E_ARG;
+  // the prototype's own box: its centre and half its diagonal
+  double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+  for (size_t k = 0; k < proto->tri_host.size(); ++k) {
+    lo[k % 3] = fmin(lo[k % 3], (double)proto->tri_host[k]); hi[k % 3] = fmax(hi[k % 3], (double)proto->tri_host[k]);
+  }
+  double c[3], hd = 0.0, cn = 0.0;
+  for (int k = 0; k < 3; ++k) { c[k] = 0.5 * (lo[k] + hi[k]); hd += 0.25 * (hi[k] - lo[k]) * (hi[k] - lo[k]); cn += c[k] * c[k]; }
+  hd = sqrt(hd); cn = sqrt(cn);
+  std::vector<float> rec;
+  try { rec.assign((size_t)K * G * 16, 0.0f); } catch (const std::bad_alloc&) { return (int)hipErrorOutOfMemory; }
+  for (int64_t s = 0; s < K; ++s) {
+    const int cnt = count_host ? count_host[s] : G;
+    if (cnt < 0 || cnt > G) return DSIM_E_ARG;
+    for (int g = 0; g < G; ++g) {
+      float* r = rec.data() + ((size_t)s * G + g) * 16;
+      if (g >= cnt) { r[3] = -INFINITY; continue; }            // (the host's entry is not looked at)
+      const float* p = place_host + ((size_t)s * G + g) * 12;  // R row-major, then t
+      for (int k = 0; k < 12; ++k) if (!isfinite(p[k])) return DSIM_E_ARG;
+      for (int i = 0; i < 3; ++i)                              // R^T R = I to 1e-5
+        for (int j = 0; j < 3; ++j) {
+          const double d = (double)p[i] * p[j] + (double)p[3 + i] * p[3 + j] + (double)p[6 + i] * p[6 + j];
+          if (!(fabs(d - (i == j ? 1.0 : 0.0)) <= 1e-5)) return DSIM_E_ARG;
+        }
+      const double det = (double)p[0] * ((double)p[4] * p[8] - (double)p[5] * p[7]) - (double)p[1] * ((double)p[3] * p[8] - (double)p[5] * p[6]) +
+                         (double)p[2] * ((double)p[3] * p[7] - (double)p[4] * p[6]);
+      if (!(det > 0.0)) return DSIM_E_ARG;
+      for (int i = 0; i < 3; ++i) r[i] = (float)((double)p[3 * i] * c[0] + (double)p[3 * i + 1] * c[1] + (double)p[3 * i + 2] * c[2] + (double)p[9 + i]);
+      // half the diagonal, and what an R that is orthonormal to 1e-5 only can move the box's centre by; rounded up
+      r[3] = nextafterf((float)(hd * (1.0 + 1e-4) + 4e-5 * cn + 1e-5), INFINITY);
+      for (int col = 0; col < 3; ++col) {                      // column `col` of R, then t[col]
+        r[4 + 4 * col] = p[col]; r[5 + 4 * col] = p[3 + col]; r[6 + 4 * col] = p[6 + col]; r[7 + 4 * col] = p[9 + col];
+      }
+      if (!isfinite(r[0]) || !isfinite(r[1]) || !isfinite(r[2])) return DSIM_E_ARG;
+    }
+  }
+  dsim_scenes* sc = new (std::nothrow) dsim_scenes();
+  if (!sc) return (int)hipErrorOutOfMemory;
+  sc->proto = proto; sc->place = nullptr; sc->K = K; sc->G = G;
+  hipError_t e = hipSetDevice(ctx->device);
+  if (e == hipSuccess) e = hipMalloc((void**)&sc->place, rec.size() * sizeof(float));
+  if (e == hipSuccess) e = hipMemcpy(sc->place, rec.data(), rec.size() * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e != hipSuccess) { (void)dsim_scenes_destroy(ctx, sc); return (int)e; }
+  *out = sc;
+  return DSIM_OK;
+}
+
+int dsim_scenes_destroy(dsim_ctx* ctx, dsim_scenes* scenes) {
+  (void)ctx;                                          // (may be NULL, as for dsim_obstacles_destroy)
+  if (!scenes) return DSIM_OK;
+  hipError_t e = hipSuccess;                          // (hipFree waits for the work that may still read the table)
+  if (scenes->place) e = hipFree(scenes->place);
+  delete scenes;
+  return (int)e;
+}
+
+int dsim_obstacle_clearance_scenes(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, const dsim_scenes* scenes,
+                                   const int32_t* scene_id, const float* offset, const uint8_t* type_id, float margin,
+                                   float* clearance_out, int32_t* nearest_out, uint64_t* contacts_out) {
+  if (!ctx || !scenes || !scene_id || !clearance_out || !(margin > 0.0f) || n <= 0 || n > state.n_pad) return DSIM_E_ARG;
+  if (ctx->n_types > 1 && !type_id) return DSIM_E_ARG;
+  const dsim_obstacles* set = scenes->proto;
+  float r_max = 0.0f;
+  for (int t = 0; t < ctx->n_types; ++t) r_max = fmaxf(r_max, (float)ctx->h_types[t].collision_sphere);
+  if ((double)r_max + (double)margin > (double)set->grid.reach) return DSIM_E_ARG;
+  ObsK a;
+  const int rc = obs_kargs(ctx, n, state, set, offset, type_id, margin, clearance_out, nearest_out, contacts_out, &a);
+  if (rc) return rc;
+  ScnK s;
+  s.place = scenes->place; s.scene_id = scene_id; s.K = scenes->K; s.G = scenes->G; s.n_bodies = set->n_bodies;
+  const unsigned blocks = (unsigned)(a.tiles < OBS_MAX_BLOCKS ? a.tiles : OBS_MAX_BLOCKS);
+  const hipStream_t st_ = (hipStream_t)stream;
+  if (set->n_tri <= OBS_LDS_TRI)
+    hipLaunchKernelGGL((k_obstacle_clearance_scenes<true>), dim3(blocks), dim3(256), (size_t)set->n_tri * 64, st_, a, s);
+  else
+    hipLaunchKernelGGL((k_obstacle_clearance_scenes<false>), dim3(blocks), dim3(256), 0, st_, a, s);
+  return (int)hipGetLastError();
+}
+
+int dsim_depth_image_scenes(dsim_ctx* ctx, void* stream, dsim_view state, const dsim_scenes* scenes, const int32_t* scene_id,
+                            const dsim_camera_params* params, int64_t n_cam, const int32_t* cam_index, const float* offset,
+                            const uint8_t* type_id, float* depth_out, int32_t* seg_out) {
+  if (!scenes || !scene_id) return DSIM_E_ARG;
+  const dsim_obstacles* set = scenes->proto;
+  CamK a;
+  int64_t blocks;
+  const int rc = cam_fill(ctx, state, set, params, n_cam, cam_index, offset, type_id, depth_out, seg_out, &a, &blocks);
+  if (rc) return rc;
+  a.pl.place = scenes->place; a.pl.scene_id = scene_id; a.pl.K = scenes->K; a.pl.G = scenes->G; a.pl.n_bodies = set->n_bodies;
+  const hipStream_t st_ = (hipStream_t)stream;
+  const bool lds = set->n_tri <= OBS_LDS_TRI;
+  const size_t shm = lds ? (size_t)set->n_tri * 64 : 0;
+  const dim3 gr((unsigned)blocks), tb(256);
+  if (lds && seg_out) hipLaunchKernelGGL((k_depth_image<true, true, false, true, true>), gr, tb, shm, st_, a);
+  else if (lds) hipLaunchKernelGGL((k_depth_image<true, false, false, true, true>), gr, tb, shm, st_, a);
+  else if (seg_out) hipLaunchKernelGGL((k_depth_image<false, true, false, true, true>), gr, tb, 0, st_, a);
+  else hipLaunchKernelGGL((k_depth_image<false, false, false, true, true>), gr, tb, 0, st_, a);
+  return (int)hipGetLastError();
+}
+
+}  // extern "C"

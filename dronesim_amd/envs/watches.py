@@ -17,12 +17,13 @@ class StepWatches:
     _drone_watch = False          # the drone-drone contact watch behind every step (set by _watch_options)
     _obst = None                  # the static-obstacle watch's device set (set by _watch_setup)
     _obst_sweep = False           # ... queried along the chord between two samples (obstacle_sweep=True)
+    _obst_placed = False          # ... an ObstacleScenes: per-drone placements of one prototype (obstacle_scene_id)
     _vision = None                # the depth camera of vision_attributes=True (set by _watch_setup)
 
     # ------------------------------------------------------------------ construction
     def _watch_options(self, *, num_drones, freq, aggregate_phy_steps, dist, drone_watch, drone_watch_margin, obstacle_watch,
                        obstacle_margin, obstacle_sweep, obstacle_sweep_sag, obstacle_sweep_travel, vision_attributes, vision_scene,
-                       vision_drones, vision_res, vision_ground, vision_see_drones, vision_drone_range) -> None:
+                       vision_drones, vision_res, vision_ground, vision_see_drones, vision_drone_range, obstacle_scene_id=None) -> None:
         """The services' keywords of ``CtrlAviary.__init__``: checked and stashed (the set-up follows in _watch_setup, when the
         context and the storage order exist)."""
         # The reference's Bullet world lets the vehicles' collision shapes act on each other; here every drone is integrated
@@ -44,6 +45,29 @@ class StepWatches:
         # obstacle_offsets [N, 3] (the caller's numbering): the set lies in the frame of each drone's task, p_i - offset_i.
         # Set up at the end of __init__ (_obstacle_setup), when the context and the storage order exist.
         self._obst_set, self._obst_margin, self._obst = obstacle_watch, float(obstacle_margin), None
+        # Obstacle scenes: obstacle_watch= and vision_scene= also take an ObstacleScenes, K scenes of up to G placements of one
+        # prototype set, with obstacle_scene_id [N] (ints, the caller's numbering; required with scenes, refused without): drone i
+        # is watched against, and sees, the placements of scene obstacle_scene_id[i] in the frame p_i - offset_i, an id outside
+        # [0, K) meaning no obstacles.  `nearest` and seg then hold the instance-major body index g n_bodies + body.  Two deliberate
+        # cuts: the swept watch and the other drones in the images are not implemented on scenes (the unplaced forms are).
+        from ..obstacles import ObstacleScenes
+        placed = [x for x in (obstacle_watch, vision_scene) if isinstance(x, ObstacleScenes)]
+        if placed and obstacle_scene_id is None:
+            raise ValueError("obstacle_scene_id [N] is required with an ObstacleScenes")
+        if not placed and obstacle_scene_id is not None:
+            raise ValueError("obstacle_scene_id without an ObstacleScenes (obstacle_watch= or vision_scene=)")
+        if placed:
+            ids = np.asarray(obstacle_scene_id)
+            if ids.shape != (num_drones,) or not np.issubdtype(ids.dtype, np.integer):
+                raise ValueError(f"obstacle_scene_id must be [{num_drones}] ints")
+            if isinstance(obstacle_watch, ObstacleScenes) and obstacle_sweep:
+                raise NotImplementedError("obstacle_sweep=True with an ObstacleScenes: the swept watch on scenes is a follow-up, "
+                                          "the chord in the placement's frame (both ends through R^T (q - t))")
+            if vision_attributes and vision_see_drones and isinstance(obstacle_watch if vision_scene is None else vision_scene,
+                                                                      ObstacleScenes):
+                raise NotImplementedError("vision_see_drones=True with an ObstacleScenes: the other drones in placed images are a "
+                                          "follow-up (there is no placed dsim_depth_image_drones)")
+        self._scene_ids = obstacle_scene_id
         # obstacle_sweep=True: the query behind a launch is dsim_obstacle_sweep instead, the chord from the position the previous
         # query saw (reset() primes it) to the state the launch left, as a sphere of radius R + obstacle_sweep_sag swept along it:
         # with sag >= obstacles.sweep_sag(a_max, time between two queries) every sub-step state in between lies in the tested
@@ -113,8 +137,9 @@ class StepWatches:
                 raise ValueError("obstacle_offsets without obstacle_watch")
             return
         from .. import obstacles as obs
-        if not isinstance(self._obst_set, obs.ObstacleSet):
-            raise TypeError("obstacle_watch takes an ObstacleSet")
+        if not isinstance(self._obst_set, (obs.ObstacleSet, obs.ObstacleScenes)):
+            raise TypeError("obstacle_watch takes an ObstacleSet or an ObstacleScenes")
+        self._obst_placed = isinstance(self._obst_set, obs.ObstacleScenes)
         if not self._obst_margin > 0.0:
             raise ValueError("obstacle_margin must be positive")
         dev, n_pad = self.ctx.device, self.state.n_pad
@@ -127,6 +152,9 @@ class StepWatches:
         reach = (obs.sweep_reach(self.ctx.types, self._obst_margin, self._obst_sag, self._obst_travel) if self._obst_sweep
                  else obs.watch_reach(self.ctx.types, self._obst_margin))
         self._obst = self._obst_set.to_device(self.ctx, reach)
+        # the scene of every drone in storage order (a type-major fleet and a sharded rank's slice see their own ids)
+        self._obst_ids = (obs.scene_ids_tensor(self._scene_ids, self.NUM_DRONES, n_pad, dev, self.order) if self._obst_placed
+                          else None)
         self._obst_clr = torch.empty((n_pad,), dtype=torch.float32, device=dev)
         self._obst_near = torch.empty((n_pad,), dtype=torch.int32, device=dev)
         self._obst_on_demand = torch.zeros((1,), dtype=torch.int64, device=dev)    # what on-demand queries counted
@@ -146,9 +174,12 @@ class StepWatches:
         from ..camera import DepthCamera
         scene, drones, ground, see_drones, drone_range = self._vision_args
         shared = self._obst is not None and (scene is None or scene is self._obst_set)
-        self._vision = DepthCamera(self.ctx, self.state, self._obst if shared else scene, res=tuple(int(v) for v in self.IMG_RES),
+        from ..obstacles import DeviceScenes, ObstacleScenes
+        world = self._obst if shared else scene
+        self._vision = DepthCamera(self.ctx, self.state, world, res=tuple(int(v) for v in self.IMG_RES),
                                    ground=ground, cameras=drones, offsets=offsets, type_id=self._type_id, drones=see_drones,
-                                   drone_range=drone_range)
+                                   drone_range=drone_range,
+                                   scene_id=self._scene_ids if isinstance(world, (ObstacleScenes, DeviceScenes)) else None)
         self.dep, self.seg = self._vision.dep, self._vision.seg
         self.dep.fill_(1.0)                # nothing seen yet (BaseAviary.py:245 starts from ones too)
         self.seg.fill_(-1)
@@ -209,9 +240,17 @@ class StepWatches:
                       self._obst_near, self._obst_off, self._type_id, None, self._obst_unswept)
             self._obst_sampled = True
             return
-        obs.query(self.ctx, self.state, self._obst, self._obst_margin, self._obst_clr, self._obst_near, self._obst_off,
-                  self._type_id)
+        self._obst_query(self._obst_margin, self._obst_clr, self._obst_near, None)
         self._obst_sampled = True
+
+    def _obst_query(self, margin, clr, near, contacts_out) -> None:
+        """The point query of the watch's world: dsim_obstacle_clearance, or dsim_obstacle_clearance_scenes on scenes."""
+        from .. import obstacles as obs
+        if self._obst_placed:
+            obs.query_scenes(self.ctx, self.state, self._obst, self._obst_ids, margin, clr, near, self._obst_off, self._type_id,
+                             contacts_out)
+        else:
+            obs.query(self.ctx, self.state, self._obst, margin, clr, near, self._obst_off, self._type_id, contacts_out)
 
     def _vision_capture(self):
         if self._vision.drones and self._downwash is not None:
@@ -320,11 +359,10 @@ class StepWatches:
         (default: the env's obstacle_margin, which is also the largest the device set serves).  Not counted as an Env.step."""
         if self._obst is None:
             raise ValueError("obstacle_clearance() needs an env made with obstacle_watch=ObstacleSet")
-        from .. import obstacles as obs
         margin = self._obst_margin if margin is None else float(margin)
         clr = torch.empty((self.state.n_pad,), dtype=torch.float32, device=self.ctx.device)
         near = torch.empty((self.state.n_pad,), dtype=torch.int32, device=self.ctx.device)
-        obs.query(self.ctx, self.state, self._obst, margin, clr, near, self._obst_off, self._type_id, self._obst_on_demand)
+        self._obst_query(margin, clr, near, self._obst_on_demand)
         return self._obst_to_caller(clr, near)
 
     def drone_images(self):

@@ -234,6 +234,154 @@ def query(ctx, state, dev: DeviceObstacles, margin: float, clearance, nearest, o
         nearest.data_ptr() if nearest is not None else None, contacts_out.data_ptr() if contacts_out is not None else None))
 
 
+# ---- obstacle scenes: per-drone placements of one set (dsim_scenes_create) --------------------------------------------------------
+SCENES_MAX_G, SCENES_MAX_SLOTS = 32, 1 << 22
+
+
+class DeviceScenes:
+    """The library's device copy of an :class:`ObstacleScenes` (dsim_scenes_create): the placement table, and the prototype's
+    device set, which it makes for ``reach`` and owns unless ``prototype_dev`` hands it one to share."""
+
+    def __init__(self, ctx, scenes: "ObstacleScenes", reach: float = None, prototype_dev: DeviceObstacles = None):
+        if prototype_dev is None and reach is None:
+            raise ValueError("reach, or a device set of the prototype to share")
+        self.ctx, self.scenes, self.K, self.G, self.n_bodies = ctx, scenes, scenes.K, scenes.G, scenes.n_bodies
+        self._owns_set = prototype_dev is None
+        self.set = scenes.prototype.to_device(ctx, reach) if self._owns_set else prototype_dev
+        self.reach = self.set.reach
+        self._h = ctypes.c_void_p()
+        place, count = scenes.place, scenes.count
+        nat.check(ctx.lib.dsim_scenes_create(ctx.handle, self.set.handle, place.ctypes.data, count.ctypes.data, self.K, self.G,
+                                             ctypes.byref(self._h)))
+
+    @property
+    def handle(self):
+        return self._h
+
+    def enable_rays(self) -> "DeviceScenes":
+        """The prototype's ray grid for the depth camera (DeviceObstacles.enable_rays)."""
+        self.set.enable_rays()
+        return self
+
+    def close(self) -> None:
+        if self._h:
+            self.ctx.lib.dsim_scenes_destroy(None, self._h)
+            self._h = ctypes.c_void_p()
+            if self._owns_set:
+                self.set.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class ObstacleScenes:
+    """K scenes of up to G rigid placements of ONE prototype :class:`ObstacleSet`; a drone looks at the scene its ``scene_id``
+    names.  ``position`` and ``rpy`` [K, G, 3]: placement g of scene k maps the prototype's frame into the task frame,
+    x_task = R(rpy) x_proto + position with R = :func:`_rot` — the convention of ``ObstacleSet.from_urdf(path, position, rpy)``.
+    ``count`` [K] ints in 0 .. G (default: G everywhere): the slots of a scene that are used; a scene may be empty, and the
+    entries of the other slots are never looked at.  1 <= G <= 32, K G <= 2^22, finite entries in every used slot.
+
+    Every output names a hit triangle by the instance-major body index g n_bodies + body: g the placement's slot in the scene.
+    ``place`` is what the device is given: float32 [K, G, 12], R row-major, then the position."""
+
+    def __init__(self, prototype: ObstacleSet, position, rpy, count=None):
+        if not isinstance(prototype, ObstacleSet):
+            raise TypeError("prototype takes an ObstacleSet")
+        pos, rpy = np.asarray(position, dtype=np.float64), np.asarray(rpy, dtype=np.float64)
+        if pos.ndim != 3 or pos.shape[2] != 3 or rpy.shape != pos.shape:
+            raise ValueError("position and rpy must both be [K, G, 3]")
+        K, G = int(pos.shape[0]), int(pos.shape[1])
+        if K < 1 or not 1 <= G <= SCENES_MAX_G:
+            raise ValueError(f"K >= 1 scenes of 1 <= G <= {SCENES_MAX_G} placements, got K = {K}, G = {G}")
+        if K * G > SCENES_MAX_SLOTS:
+            raise ValueError(f"K G = {K * G} placements exceed 2^22")
+        if count is None:
+            cnt = np.full(K, G, dtype=np.int32)
+        else:
+            cnt = np.asarray(count)
+            if cnt.shape != (K,) or not np.issubdtype(cnt.dtype, np.integer) or cnt.min() < 0 or cnt.max() > G:
+                raise ValueError(f"count must be [{K}] ints in 0 .. {G}")
+            cnt = np.ascontiguousarray(cnt, dtype=np.int32)
+        used = np.arange(G)[None, :] < cnt[:, None]
+        if not (np.isfinite(pos[used]).all() and np.isfinite(rpy[used]).all()):
+            raise ValueError("non-finite placement")
+        self.prototype, self.position, self.rpy, self.count = prototype, pos, rpy, cnt
+        place = np.full((K, G, 12), np.nan, dtype=np.float32)
+        r, p, y = (rpy[used][:, k] for k in range(3))              # _rot for every used slot at once
+        cr, sr, cp, sp, cy, sy = np.cos(r), np.sin(r), np.cos(p), np.sin(p), np.cos(y), np.sin(y)
+        with np.errstate(over="ignore"):
+            place[used] = np.stack([cy * cp, cy * sp * sr - sy * cr, cy * sp * cr + sy * sr,
+                                    sy * cp, sy * sp * sr + cy * cr, sy * sp * cr - cy * sr,
+                                    -sp, cp * sr, cp * cr, *pos[used].T], 1)
+        if not np.isfinite(place[used]).all():
+            raise ValueError("a placement is not finite in float32")
+        self.place = np.ascontiguousarray(place)
+
+    @property
+    def K(self) -> int:
+        return int(self.place.shape[0])
+
+    @property
+    def G(self) -> int:
+        return int(self.place.shape[1])
+
+    @property
+    def n_bodies(self) -> int:
+        return self.prototype.n_bodies
+
+    def flatten(self, k: int) -> ObstacleSet:
+        """Scene k's placed triangles as one plain set, body g n_bodies + body (placed with the float32 R and t the device holds).
+        An empty scene has no triangles and is a ValueError."""
+        k = int(k)
+        if not 0 <= k < self.K:
+            raise ValueError(f"scene {k} outside [0, {self.K})")
+        if self.count[k] == 0:
+            raise ValueError(f"scene {k} is empty")
+        tri, body = [], []
+        proto = self.prototype.triangles.astype(np.float64)
+        for g in range(int(self.count[k])):
+            R, t = self.place[k, g, :9].astype(np.float64).reshape(3, 3), self.place[k, g, 9:].astype(np.float64)
+            tri.append(proto @ R.T + t)
+            body.append(self.prototype.body + g * self.n_bodies)
+        return ObstacleSet(np.concatenate(tri), np.concatenate(body))
+
+    def to_device(self, ctx, reach: float = None, prototype_dev: DeviceObstacles = None) -> DeviceScenes:
+        """The library's device scenes for queries with R_max + margin <= ``reach`` (allocates, uploads, synchronises: not inside
+        a graph capture); ``prototype_dev``: a device set of the prototype to share instead of making one."""
+        return DeviceScenes(ctx, self, reach, prototype_dev)
+
+
+def query_scenes(ctx, state, dev_scenes: DeviceScenes, scene_id, margin: float, clearance, nearest, offset=None, type_id=None,
+                 contacts_out=None) -> None:
+    """dsim_obstacle_clearance_scenes on the current stream into the given tensors ([n_pad] float32 / int32); ``scene_id``: int32
+    device tensor [n_pad] in storage order, an id outside [0, K) meaning no obstacles."""
+    if scene_id is None:
+        raise ValueError("scene_id is required")
+    nat.check(ctx.lib.dsim_obstacle_clearance_scenes(
+        ctx.handle, ctx.stream_ptr(), state.n, state.view(), dev_scenes.handle, scene_id.data_ptr(),
+        offset.data_ptr() if offset is not None else None, type_id.data_ptr() if type_id is not None else None, float(margin),
+        clearance.data_ptr(), nearest.data_ptr() if nearest is not None else None,
+        contacts_out.data_ptr() if contacts_out is not None else None))
+
+
+def scene_ids_tensor(scene_id, n: int, n_pad: int, device, order=None):
+    """``scene_id`` [n] ints in the caller's numbering as the int32 device tensor [n_pad] in storage order the calls take (-1, no
+    obstacles, behind n)."""
+    ids = np.asarray(scene_id)
+    if ids.shape != (n,) or not np.issubdtype(ids.dtype, np.integer):
+        raise ValueError(f"scene ids must be [{n}] ints")
+    ids = np.clip(ids.astype(np.int64), -1, 2 ** 31 - 1)
+    if order is not None:
+        ids = order.to_storage_np(ids)
+    import torch
+    t = torch.full((n_pad,), -1, dtype=torch.int32)
+    t[:n] = torch.from_numpy(np.ascontiguousarray(ids.astype(np.int32)))
+    return t.to(device)
+
+
 # ---- the swept watch (dsim_obstacle_sweep) ------------------------------------------------------------------------------------------
 def sweep_reach(types, margin: float, sag: float, travel: float) -> float:
     """The ``reach`` of a set for swept queries of ``margin`` and ``sag`` over these drone types whose chords are up to ``travel``

@@ -9,6 +9,11 @@ call on the host, 5-60 ms each, is one launch for the whole fleet here (fleet.Tr
 each drone's own course (fleet.BankTrajectoryTargets).  240 Hz physics, 2 physics steps per control step, every drone offset on
 a 10 m grid.  A course made here is exactly at rest at t = 0, where the reference's yaw-from-velocity rule has no heading (NaN);
 the flight starts one control step into the course.
+
+--gates: the committed gate stands at each drone's own three waypoints (obstacles.ObstacleScenes: one prototype on the device, a
+scene of three placements per drone), yawed so that its normal lies along the xy direction of the course's velocity there; the
+flight is watched (obstacle_watch=scenes) and the run prints obstacle_contacts() and the least clearance per gate slot.  With
+--vision every drone also carries a camera that sees its own gates, and one depth frame is saved (--out).
 """
 import argparse
 import os
@@ -33,6 +38,24 @@ def random_gates(n, seed):
     return g
 
 
+def gate_scenes(ctx, bank, gates, dt):
+    """One scene per drone: the gate prototype at the drone's three waypoints, its normal (the prototype's x axis) along the xy
+    direction of the course's velocity there.  The velocity comes from the bank's coefficients through its own sampler; a course
+    is at rest at both ends, so the first and last gate take the direction a control step inside the course."""
+    from dronesim_amd.obstacles import ObstacleScenes, ObstacleSet
+    n = gates.shape[0]
+    proto = ObstacleSet.from_urdf(os.path.join(ROOT, "tests", "golden", "gate_50_curved.urdf"), (0, 0, 0), (0, 0, 0))
+    TS = bank.ts[:3, :n].T.cpu().numpy()                                   # [n, 3]: when course k passes its waypoints
+    rpy = np.zeros((n, 3, 3))
+    for j in range(3):
+        t = np.clip(TS[:, j], dt, np.maximum(TS[:, 2] - dt, dt))
+        probe = BankTrajectoryTargets(ctx, n, bank, t0=t)
+        probe.sample(0.0)
+        v = probe.fields(3, 3).T.cpu().numpy()
+        rpy[:, j, 2] = np.arctan2(v[:, 1], v[:, 0])
+    return ObstacleScenes(proto, gates, rpy)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--num_drones", type=int, default=4096)
@@ -40,12 +63,30 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--times", default="optimize", choices=["optimize", "tmin"],
                     help="optimize: the reference's behaviour (segment times searched per course); tmin: distance / max_vel")
+    ap.add_argument("--gates", action="store_true", help="stand a gate at each drone's own waypoints and watch it (ObstacleScenes)")
+    ap.add_argument("--vision", action="store_true", help="with --gates: every drone carries a camera; one depth frame is saved")
+    ap.add_argument("--out", default="courses_depth.npy", help="where --vision saves its frame")
+    ap.add_argument("--margin", type=float, default=1.0, help="obstacle_margin of --gates [m]")
     A = ap.parse_args(argv)
+    if A.vision and not A.gates:
+        ap.error("--vision needs --gates")
     n, AGGR, FREQ = A.num_drones, 2, 240                                   # fly_INDI_TrajectoryTrack.py:108,162-164
     side = int(np.ceil(np.sqrt(n)))
     off = 10.0 * np.stack([np.arange(n) % side, np.arange(n) // side, np.zeros(n)], 1).astype(np.float64)
     gates = random_gates(n, A.seed)
-    env = CtrlAviary(["robobee"], n, initial_xyzs=gates[:, 0, :] + off, aggregate_phy_steps=AGGR, freq=FREQ, dict_io=False)
+    if A.gates:
+        # the scenes need the courses and the env's keywords need the scenes: the bank is made on a context of its own first
+        from dronesim_amd.fleet import Context
+        from dronesim_amd.params import builtin_type
+        ctx0 = Context([builtin_type("robobee")])
+        scenes = gate_scenes(ctx0, TrajectoryBank(ctx0, gates, max_vel=0.7, gamma=1e6, times=A.times), gates, AGGR / FREQ)
+        ctx0.close()
+        watch = dict(obstacle_watch=scenes, obstacle_scene_id=np.arange(n), obstacle_offsets=off, obstacle_margin=A.margin)
+        if A.vision:
+            watch["vision_attributes"] = True
+    else:
+        watch = {}
+    env = CtrlAviary(["robobee"], n, initial_xyzs=gates[:, 0, :] + off, aggregate_phy_steps=AGGR, freq=FREQ, dict_io=False, **watch)
     t_gen = time.time()
     bank = TrajectoryBank(env.ctx, gates, max_vel=0.7, gamma=1e6, times=A.times)
     status, evals = bank.status, bank.evals                                # (host copies: the launch has finished after this)
@@ -55,16 +96,31 @@ def main(argv=None):
     dt_ctrl = AGGR / FREQ
     tgt = BankTrajectoryTargets(env.ctx, n, bank, t0=np.full(n, dt_ctrl), offsets=off)
     steps = int(A.duration_sec * FREQ / AGGR)
+    least = np.full((n, 3), np.inf) if A.gates else None
+    frame = None
     START = time.time()
     for k in range(steps):
         tgt.sample(dt_ctrl)
         env.step_fused(tgt, control_timestep=dt_ctrl, action=np.full((n, 4), 0.4, dtype=np.float32) if k == 0 else None)
+        if A.gates:
+            clr, near = (x.cpu().numpy() for x in env.last_obstacle_clearance)
+            seen = near >= 0                                               # (one body per gate: `nearest` is the gate's slot)
+            np.minimum.at(least, (np.nonzero(seen)[0], near[seen]), clr[seen])
+        if A.vision and frame is None and bool((env.seg >= 0).any()):
+            frame = env.dep.clone()
     pos = env.state.pos.T.cpu().numpy()
     el = time.time() - START
     want = tgt.fields(0, 3).T.cpu().numpy()
     err = np.linalg.norm(pos - want, axis=1)
     print(f"{n} drones x {steps} env steps in {el:.2f} s wall ({n * steps / el:.3e} drone-steps/s incl. host loop); "
           f"distance to the own target: median {np.median(err):.3f} m, worst {err.max():.3f} m")
+    if A.gates:
+        per_slot = [f"gate {j}: {least[:, j].min():.3f} m ({int(np.isfinite(least[:, j]).sum())} drones within {A.margin} m)" for j in range(3)]
+        print(f"obstacle_contacts() = {env.obstacle_contacts()} drone x steps with the bounding sphere on a gate; least clearance per "
+              f"gate slot: " + "; ".join(per_slot))
+    if A.vision:
+        np.save(A.out, (frame if frame is not None else env.dep).cpu().numpy())
+        print(f"depth frame [{n}, 48, 64] saved to {A.out}" + ("" if frame is not None else " (no gate came into view)"))
     env.close()
     return pos - off, gates
 

@@ -48,7 +48,8 @@ extern "C" {
                               DSIM_CAM_*, DSIM_SEG_GROUND; the other drones in the camera's images, dsim_depth_image_drones,
                               dsim_depth_image_drones_workspace, dsim_camera_drones, DSIM_SEG_DRONE; the trajectory bank,
                               dsim_trajgen, dsim_trajgen_workspace, dsim_traj_sample_bank, dsim_traj_bank, dsim_trajgen_args,
-                              DSIM_TRAJGEN_*; the swept obstacle watch, dsim_obstacle_sweep, dsim_sweep_args, DSIM_SWEEP_* */
+                              DSIM_TRAJGEN_*; the swept obstacle watch, dsim_obstacle_sweep, dsim_sweep_args, DSIM_SWEEP_*; obstacle
+                              scenes, dsim_scenes_create / _destroy, dsim_obstacle_clearance_scenes, dsim_depth_image_scenes */
 #define DSIM_MAX_ACT 6     /* actuators per vehicle (quad 4, morphing hexa 6) */
 #define DSIM_MAX_TYPES 8
 
@@ -941,6 +942,49 @@ int dsim_depth_image_drones(dsim_ctx* ctx, void* stream, dsim_view state, const 
                             const dsim_camera_params* params, int64_t n_cam, const int32_t* cam_index,
                             const float* offset, const uint8_t* type_id, const dsim_camera_drones* drones,
                             float* depth_out, int32_t* seg_out);
+
+/* Obstacle scenes: per-drone placements of ONE prototype set, for the watch and the camera.  A set is one soup in one frame, which
+ * serves any number of replicas of one task; a fleet whose drones fly courses of their own has its gates at each drone's own
+ * waypoints.  Distances and ray parameters do not change under a rotation and a shift, so one prototype is instanced at any number
+ * of poses: its grids, records and LDS staging stay as they are, and only the query point, or the ray, goes into the placement's
+ * frame.  K scenes hold up to G placements each (1 <= G <= 32, K G <= 2^22); drone i looks at scene scene_id[i].
+ *
+ * dsim_scenes_create: place_host [K][G][12] (host) is R row-major, then t, of the map x_task = R x_proto + t of each placement;
+ * count_host [K] (host, each 0 .. G; NULL: G everywhere) says how many slots of a scene are used — a scene may be empty, and the
+ * entries of slots at or above the count are never looked at.  Every used R must be finite and orthonormal to 1e-5 with det > 0,
+ * every t finite: DSIM_E_ARG otherwise, as for a null pointer or K, G outside their limits.  Allocates, uploads and SYNCHRONISES
+ * (not inside a capture; neither is dsim_scenes_destroy, which waits for the work that may still read the table).  The prototype
+ * must outlive the scenes.
+ *
+ * Every output names a hit triangle by the INSTANCE-MAJOR body index g n_bodies + body >= 0: g the placement's slot in the drone's
+ * scene, n_bodies = 1 + the largest body index of the prototype.  -1 (none) and DSIM_SEG_GROUND keep their meaning.
+ *
+ * dsim_obstacle_clearance_scenes is dsim_obstacle_clearance on the placed set: with q_i = p_i - offset_i and s = scene_id[i],
+ *     clearance_out[i] = min(margin, min over placements g < count[s] of min_t dist(R_g^T (q_i - t_g), triangle t) - R_i)
+ *     nearest_out[i]   = the instance-major body that attains the minimum (the lowest slot among equals), -1 when none is below
+ *                        margin
+ * (subtract first, then rotate: R^T q - R^T t cancels digits at offsets of 128 m, R^T (q - t) does not).  Ownership, stream
+ * ordering, "allocates nothing, never synchronises, may be captured" and the counters (DSIM_Q_OBSTACLE_CONTACTS, contacts_out) are
+ * dsim_obstacle_clearance's; scene_id is int32 [n_pad] (device, storage order like offset).  A scene_id[i] outside [0, K) means no
+ * obstacles — (margin, -1), a defined case: a drone may have no gates.  DSIM_E_ARG, nothing enqueued: everything
+ * dsim_obstacle_clearance refuses (R_max + margin > reach of the PROTOTYPE's grid among it), a null scenes or scene_id.  A drone
+ * that is out of reach of every placement of its scene reads its position (offset, type), its id and the first 16 bytes of each
+ * of the scene's G slots, and writes its two outputs.
+ *
+ * dsim_depth_image_scenes is dsim_depth_image on the placed set: the camera of drone i sees the placements of scene scene_id[i]
+ * (an id outside [0, K): the plane or the background only); the plane z = 0 stays in the task frame.  The arguments behind
+ * `params` are dsim_depth_image's.  DSIM_E_ARG, nothing enqueued: everything dsim_depth_image refuses (a prototype without rays
+ * enabled among it), a null scenes or scene_id.  The other drones are not drawn: there is no placed dsim_depth_image_drones. */
+typedef struct dsim_scenes dsim_scenes;
+int dsim_scenes_create(dsim_ctx* ctx, const dsim_obstacles* proto, const float* place_host, const int32_t* count_host, int64_t K,
+                       int32_t G, dsim_scenes** out);
+int dsim_scenes_destroy(dsim_ctx* ctx, dsim_scenes* scenes);
+int dsim_obstacle_clearance_scenes(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, const dsim_scenes* scenes,
+                                   const int32_t* scene_id, const float* offset, const uint8_t* type_id, float margin,
+                                   float* clearance_out, int32_t* nearest_out, uint64_t* contacts_out);
+int dsim_depth_image_scenes(dsim_ctx* ctx, void* stream, dsim_view state, const dsim_scenes* scenes, const int32_t* scene_id,
+                            const dsim_camera_params* params, int64_t n_cam, const int32_t* cam_index,
+                            const float* offset, const uint8_t* type_id, float* depth_out, int32_t* seg_out);
 
 /* The rotor-noise normals the step kernels draw (diagnostics / distribution studies; no counterpart in the reference, whose
  * draws come from numpy's global generator): for drones [0, n) and the physics sub-steps [0, substeps) of Env.step number

@@ -1,0 +1,132 @@
+"""Times obstacle scenes against the unplaced calls they stand beside, on the same fleet and margin.
+
+Watch: A = dsim_obstacle_clearance on the gate, B = dsim_obstacle_clearance_scenes with G = 1 identity (the same work plus the
+placement layer), C = the placed watch with G = 3 (64 scenes of three random gates, scene_id = i mod 64).  N robobees, "far" (the
+fleet stands 100 m away: every drone is culled) and "near" (the fleet about the gates).  Camera: 4 096 cameras at 64 x 48 looking at
+the gate, unplaced against G = 1 identity and G = 3.  Device events around batches of --iters calls behind a warm-up, the variants
+interleaved round by round; prints one JSON line per case with the median and the range of each and of the paired ratios.
+
+    python tools/bench_scenes.py [--drones 65536 4194304] [--cameras 4096] [--iters 50] [--warmup 20] [--pairs 9]
+
+The bytes a far drone must move: A reads 12 (position) and writes 8; the placed watch reads 4 (scene id) + 16 G (cull words) more.
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--drones", type=int, nargs="+", default=[65536, 4194304])
+    ap.add_argument("--cameras", type=int, default=4096)
+    ap.add_argument("--margin", type=float, default=0.5)
+    ap.add_argument("--iters", type=int, default=50)
+    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--pairs", type=int, default=9)
+    a = ap.parse_args()
+    import torch
+    from dronesim_amd import fleet, params
+    from dronesim_amd import obstacles as obs
+    from dronesim_amd.camera import DepthCamera
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_scenes needs a HIP device")
+    ctx = fleet.Context([params.builtin_type("robobee")])
+    gate = obs.ObstacleSet.from_urdf(os.path.join(ROOT, "tests", "golden", "gate_50_curved.urdf"), (0, 0, 0), (0, 0, 0))
+    K = 64
+    rng = np.random.default_rng(11)
+    pos3 = rng.uniform([-2.0, -2.0, 1.0], [2.0, 2.0, 3.0], (K, 3, 3))
+    rpy3 = rng.uniform([-0.5, -0.5, -np.pi], [0.5, 0.5, np.pi], (K, 3, 3))
+    dev = gate.to_device(ctx, obs.watch_reach(ctx.types, a.margin)).enable_rays()
+    one = obs.ObstacleScenes(gate, np.zeros((1, 1, 3)), np.zeros((1, 1, 3))).to_device(ctx, prototype_dev=dev)
+    three = obs.ObstacleScenes(gate, pos3, rpy3).to_device(ctx, prototype_dev=dev)
+    r = lambda x: round(float(x), 2)
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(a.iters):
+            fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1) * 1e3 / a.iters
+
+    def rounds(fns):
+        for _ in range(a.warmup):
+            for f in fns:
+                f()
+        torch.cuda.synchronize()
+        t = [[] for _ in fns]
+        for _ in range(a.pairs):
+            for k, f in enumerate(fns):
+                t[k].append(timed(f))
+        return [np.array(x) for x in t]
+
+    def report(head, names, t):
+        out = dict(head)
+        for nm, x in zip(names, t):
+            out[nm + "_us_median"], out[nm + "_us_min_max"] = r(np.median(x)), [r(x.min()), r(x.max())]
+        for nm, x in zip(names[1:], t[1:]):
+            q = x / t[0]
+            out[nm + "_over_" + names[0] + "_median"] = round(float(np.median(q)), 3)
+            out[nm + "_over_" + names[0] + "_min_max"] = [round(float(q.min()), 3), round(float(q.max()), 3)]
+        print(json.dumps(out), flush=True)
+
+    for n in a.drones:
+        for case in ("far", "near"):
+            rg = np.random.default_rng(7)
+            # about the placements of the drone's own G = 3 scene (the identity gate stands at the origin: fewer of them reach it)
+            p = pos3[np.arange(n) % K, rg.integers(0, 3, n)] + rg.uniform(-1.5, 1.5, (n, 3))
+            p[::4] = rg.uniform(-0.6, 0.6, (len(p[::4]), 3))
+            if case == "far":
+                p[:, 0] += 100.0
+            st = fleet.FleetState(ctx, n, "soa")
+            st.set_fields(0, torch.from_numpy(np.ascontiguousarray(p.astype(np.float32).T)))
+            clr = torch.empty((st.n_pad,), dtype=torch.float32, device=ctx.device)
+            near = torch.empty((st.n_pad,), dtype=torch.int32, device=ctx.device)
+            id1 = torch.zeros((st.n_pad,), dtype=torch.int32, device=ctx.device)
+            id3 = (torch.arange(st.n_pad, dtype=torch.int32) % K).to(ctx.device)
+            fa = lambda: obs.query(ctx, st, dev, a.margin, clr, near)
+            fb = lambda: obs.query_scenes(ctx, st, one, id1, a.margin, clr, near)
+            fc = lambda: obs.query_scenes(ctx, st, three, id3, a.margin, clr, near)
+            t = rounds([fa, fb, fc])
+            share = []
+            for f in (fa, fb, fc):
+                f()
+                share.append(round(float((near[:n] >= 0).float().mean().item()), 4))
+            report({"what": "watch", "case": case, "drones": n, "n_tri": gate.n_tri, "margin": a.margin, "in_reach_share_A_B_C": share,
+                    "far_bytes_per_drone_A_B_C": [20, 40, 72]}, ["A_unplaced", "B_placed_G1", "C_placed_G3"], t)
+            del st, clr, near, id1, id3
+
+    # the camera: a grid of cameras two metres in front of the gate, looking at it (+x), each in a frame of its own
+    n = a.cameras
+    rg = np.random.default_rng(9)
+    p = np.stack([np.full(n, -2.0), rg.uniform(-0.3, 0.3, n), rg.uniform(-0.2, 0.2, n)], 1)
+    st = fleet.FleetState(ctx, n, "soa")
+    state = np.zeros((7, n), dtype=np.float32)
+    state[:3], state[6] = p.T, 1.0
+    st.set_fields(0, torch.from_numpy(state))
+    # (the G = 3 scenes stand about (0, 0, 2): those cameras look from (-4, 0, 2) instead, through an offset of their own)
+    off3 = np.tile(np.array([2.0, 0.0, -2.0]), (n, 1))
+    cams = [DepthCamera(ctx, st, dev, ground=True),
+            DepthCamera(ctx, st, one, ground=True, scene_id=np.zeros(n, dtype=int)),
+            DepthCamera(ctx, st, three, ground=True, scene_id=np.arange(n) % K, offsets=off3)]
+    t = rounds([c.capture for c in cams])
+    hit = []
+    for c in cams:
+        hit.append(round(float((c.capture()[1] >= 0).float().mean().item()), 4))
+    report({"what": "camera", "cameras": n, "res": [64, 48], "n_tri": gate.n_tri, "pixels_on_obstacles_share_A_B_C": hit},
+           ["A_unplaced", "B_placed_G1", "C_placed_G3"], t)
+    one.close()
+    three.close()
+    dev.close()
+    ctx.close()
+
+
+if __name__ == "__main__":
+    main()
