@@ -100,7 +100,7 @@ class CameraDrones(ctypes.Structure):
 
 TRAJGEN_GIVEN, TRAJGEN_TMIN, TRAJGEN_OPTIMIZE = 0, 1, 2     # dsim_trajgen_args.mode
 TRAJGEN_LMAX = 9                                              # DSIM_TRAJGEN_LMAX: waypoints per course
-TRAJGEN_BAD_COUNT, TRAJGEN_BAD_WAYPOINT, TRAJGEN_BAD_SEGMENT, TRAJGEN_BAD_TIME = 1, 2, 3, 4    # status of a course
+TRAJGEN_BAD_COUNT, TRAJGEN_BAD_WAYPOINT, TRAJGEN_BAD_SEGMENT, TRAJGEN_BAD_TIME, TRAJGEN_BAD_CONDITION = 1, 2, 3, 4, 5    # status of a course
 
 
 class TrajBank(ctypes.Structure):

@@ -5,12 +5,19 @@
 // ---- generator ------------------------------------------------------------------------------------------------------
 // One lane per course.  The only per-lane arrays indexed at run time are the segment times, their lower bounds and the
 // position steps: they live in LDS, one column per lane (a lane touches its own column only: no barrier anywhere).  The
-// 4 x 4 blocks of the solve are indexed by unrolled loops and stay in registers; what the sweep back needs of the sweep
-// along (per interior waypoint the Cholesky factor of its block, 10, and z = L^-1 w for three axes, 12) goes through the
-// caller's workspace, course-minor like the bank.
+// blocks of the solve are indexed by unrolled loops and stay in registers; what the sweep back needs of the sweep along
+// (per interior waypoint R_a, 10, R_ab, 16, and z_a for three axes, 12: R_a a = z_a - R_ab b) goes through the caller's
+// workspace, course-minor like the bank.
+// The sweep is in square-root form.  A segment's cost is |F e^|^2 / T^7 (F: DSIM_TG_F, 6 x 10, F^T F = M), so the
+// cost-so-far is carried as |R a - s|^2 with R upper triangular, and a segment joins it by Householder reflections.  The
+// block Cholesky sweep this replaces formed K_bb - Y^T Y, a difference of nearly equal numbers where a short leg follows
+// a long one (tests/README_trajgen.md).
 #define DSIM_TG_LANES 64
 #define DSIM_TG_SEGS (DSIM_TRAJGEN_LMAX - 1)
-#define DSIM_TG_KEEP 22
+#define DSIM_TG_KEEP 38
+// A pivot of the carried factor smaller than its column was by more than this has lost the digits the published accuracy
+// needs (the error goes like 0.2 eps cond^2: tests/README_trajgen.md); squared, because the squares are what is at hand.
+#define DSIM_TG_COND_MAX2 (16384.0 * 16384.0)
 struct TrajGenK {
   const double* wp; const int* n_wp;
   double *coeffs, *ts; int* n_seg;
@@ -22,167 +29,163 @@ struct TrajGenK {
   double max_vel, gamma;
 };
 
-__device__ __forceinline__ constexpr int tg_sym(int r, int c) { return r >= c ? r * (r + 1) / 2 + c : c * (c + 1) / 2 + r; }
-
-// T, T^2, T^3, T^4 in u; g = u / T^7; returns 1 / T^7
-__device__ __forceinline__ double tg_scales(double T, double u[4], double g[4]) {
+// T, T^2, T^3, T^4 in u; h = u T^-3.5; returns T^-3.5
+__device__ __forceinline__ double tg_scales(double T, double u[4], double h[4]) {
   u[0] = T; u[1] = T * T; u[2] = u[1] * T; u[3] = u[1] * u[1];
-  const double i7 = 1.0 / (u[3] * u[2]);
+  const double w = 1.0 / (u[2] * sqrt(T));
 #pragma unroll
-  for (int r = 0; r < 4; ++r) g[r] = u[r] * i7;
-  return i7;
+  for (int r = 0; r < 4; ++r) h[r] = u[r] * w;
+  return w;
 }
 
 // the sweep along the course: the snap cost at the best interior derivatives.  sT, sD: this lane's LDS columns; segment
 // ci takes the time cv instead of its stored one (ci = -1: none).  KEEP: ws (already at this course) receives the factors.
+// lost: set where a block that a later segment goes on from has lost its digits (DSIM_TG_COND_MAX2).
 template <bool KEEP>
-__device__ __forceinline__ double tg_sweep(int n, const double* sT, int ci, double cv, const double* sD, double* ws, long long K_pad) {
-  double P[10], q[3][4], c;
+__device__ __forceinline__ double tg_sweep(int n, const double* sT, int ci, double cv, const double* sD, double* ws, long long K_pad,
+                                           bool& lost) {
+  double top[4][11], c = 0.0;             // columns: R (upper triangular) | what the elimination leaves of b | s, three axes
+#pragma unroll
+  for (int r = 0; r < 4; ++r)
+#pragma unroll
+    for (int e = 0; e < 11; ++e) top[r][e] = 0.0;
   for (int m = 0; m < n; ++m) {
     const double T = (m == ci) ? cv : sT[m * DSIM_TG_LANES];
-    double u[4], g[4], d[3];
-    const double i7 = tg_scales(T, u, g);
+    double u[4], h[4], D[6][11];           // columns: F_a U w | F_b U w | -F_d w d, three axes
+    const double w = tg_scales(T, u, h);
 #pragma unroll
-    for (int x = 0; x < 3; ++x) d[x] = sD[(m * 3 + x) * DSIM_TG_LANES];
-    const double dd = DSIM_TG_M[5][5] * i7 * (d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-    if (m == 0) {                                  // at rest at the start: the cost so far is the segment's own, in its end derivatives
+    for (int i = 0; i < 6; ++i) {
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
+      for (int r = 0; r < 4; ++r) { D[i][r] = DSIM_TG_F[i][1 + r] * h[r]; D[i][4 + r] = DSIM_TG_F[i][6 + r] * h[r]; }
 #pragma unroll
-        for (int s = 0; s <= r; ++s) P[tg_sym(r, s)] = DSIM_TG_M[6 + r][6 + s] * g[r] * u[s];
-#pragma unroll
-        for (int x = 0; x < 3; ++x) q[x][r] = DSIM_TG_M[6 + r][5] * g[r] * d[x];
-      }
-      c = dd;
-      continue;
+      for (int x = 0; x < 3; ++x) D[i][8 + x] = -(DSIM_TG_F[i][5] * w) * sD[(m * 3 + x) * DSIM_TG_LANES];
     }
-    // S = P + K_aa = L L^T
-    double L[10], Li[4];
+    if (m >= 1) {                                   // (at rest at the start: the first segment has no a)
 #pragma unroll
-    for (int r = 0; r < 4; ++r)
+      for (int r = 0; r < 4; ++r)
 #pragma unroll
-      for (int s = 0; s <= r; ++s) L[tg_sym(r, s)] = P[tg_sym(r, s)] + DSIM_TG_M[1 + r][1 + s] * g[r] * u[s];
+        for (int e = 4; e < 8; ++e) top[r][e] = 0.0;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {                 // the reflection on (top[j], D[:]) that zeroes D[:][j]
+        double v0 = top[j][j], nn = v0 * v0;
+#pragma unroll
+        for (int i = 0; i < 6; ++i) nn += D[i][j] * D[i][j];
+        const double norm = sqrt(nn), alpha = v0 >= 0.0 ? -norm : norm;
+        v0 -= alpha;
+        const double beta = -1.0 / (alpha * v0);
+#pragma unroll
+        for (int e = j + 1; e < 11; ++e) {
+          double dot = v0 * top[j][e];
+#pragma unroll
+          for (int i = 0; i < 6; ++i) dot += D[i][j] * D[i][e];
+          const double f = dot * beta;
+          top[j][e] -= f * v0;
+#pragma unroll
+          for (int i = 0; i < 6; ++i) D[i][e] -= f * D[i][j];
+        }
+        top[j][j] = alpha;
+      }
+      if (KEEP) {
+        double* o = ws + (long long)(m - 1) * DSIM_TG_KEEP * K_pad;
+        int e = 0;
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+#pragma unroll
+          for (int s = r; s < 4; ++s) o[(e++) * K_pad] = top[r][s];
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+#pragma unroll
+          for (int s = 4; s < 11; ++s) o[(e++) * K_pad] = top[r][s];
+      }
+    }
+    if (m == n - 1) {                               // at rest at the end: b = 0, what is left of the right-hand sides is cost
+#pragma unroll
+      for (int i = 0; i < 6; ++i)
+#pragma unroll
+        for (int x = 0; x < 3; ++x) c += D[i][8 + x] * D[i][8 + x];
+      break;
+    }
+    // the six rows left, in b: four reflections make them the next R and s; their last two rows are cost
+    double n0[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      double s = L[tg_sym(j, j)];
+      n0[j] = 0.0;
 #pragma unroll
-      for (int k = 0; k < j; ++k) s -= L[tg_sym(j, k)] * L[tg_sym(j, k)];
-      s = sqrt(s);
-      L[tg_sym(j, j)] = s;
-      Li[j] = 1.0 / s;
-#pragma unroll
-      for (int i = j + 1; i < 4; ++i) {
-        double t = L[tg_sym(i, j)];
-#pragma unroll
-        for (int k = 0; k < j; ++k) t -= L[tg_sym(i, k)] * L[tg_sym(j, k)];
-        L[tg_sym(i, j)] = t * Li[j];
-      }
+      for (int i = 0; i < 6; ++i) n0[j] += D[i][4 + j] * D[i][4 + j];
     }
-    // z = L^-1 (q + K_ad d) per axis; the cost drops by |z|^2
-    double z[3][4];
 #pragma unroll
-    for (int x = 0; x < 3; ++x)
+    for (int j = 0; j < 4; ++j) {
+      double v0 = D[j][4 + j], nn = 0.0;
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        double t = q[x][r] + DSIM_TG_M[1 + r][5] * g[r] * d[x];
+      for (int i = j; i < 6; ++i) nn += D[i][4 + j] * D[i][4 + j];
+      const double norm = sqrt(nn), alpha = v0 >= 0.0 ? -norm : norm;
+      v0 -= alpha;
+      const double beta = -1.0 / (alpha * v0);
 #pragma unroll
-        for (int k = 0; k < r; ++k) t -= L[tg_sym(r, k)] * z[x][k];
-        z[x][r] = t * Li[r];
+      for (int e = j + 1; e < 7; ++e) {
+        double dot = v0 * D[j][4 + e];
+#pragma unroll
+        for (int i = j + 1; i < 6; ++i) dot += D[i][4 + j] * D[i][4 + e];
+        const double f = dot * beta;
+        D[j][4 + e] -= f * v0;
+#pragma unroll
+        for (int i = j + 1; i < 6; ++i) D[i][4 + e] -= f * D[i][4 + j];
       }
-    double zz = 0.0;
+      if (!(n0[j] <= DSIM_TG_COND_MAX2 * nn)) lost = true;
 #pragma unroll
-    for (int x = 0; x < 3; ++x)
+      for (int s = 0; s < 4; ++s) top[j][s] = s < j ? 0.0 : (s == j ? alpha : D[j][4 + s]);
 #pragma unroll
-      for (int r = 0; r < 4; ++r) zz += z[x][r] * z[x][r];
-    c += dd - zz;
-    if (KEEP) {
-      double* w = ws + (long long)(m - 1) * DSIM_TG_KEEP * K_pad;
-#pragma unroll
-      for (int e = 0; e < 10; ++e) w[e * K_pad] = L[e];
-#pragma unroll
-      for (int x = 0; x < 3; ++x)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) w[(10 + x * 4 + r) * K_pad] = z[x][r];
+      for (int x = 0; x < 3; ++x) top[j][8 + x] = D[j][8 + x];
     }
-    // Y = L^-1 K_ab; P' = K_bb - Y^T Y; q' = K_bd d - Y^T z
-    double Y[4][4];
 #pragma unroll
-    for (int s = 0; s < 4; ++s)
+    for (int i = 4; i < 6; ++i)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        double t = DSIM_TG_M[1 + r][6 + s] * g[r] * u[s];
-#pragma unroll
-        for (int k = 0; k < r; ++k) t -= L[tg_sym(r, k)] * Y[k][s];
-        Y[r][s] = t * Li[r];
-      }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-#pragma unroll
-      for (int s = 0; s <= r; ++s) {
-        double t = DSIM_TG_M[6 + r][6 + s] * g[r] * u[s];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) t -= Y[k][r] * Y[k][s];
-        P[tg_sym(r, s)] = t;
-      }
-#pragma unroll
-      for (int x = 0; x < 3; ++x) {
-        double t = DSIM_TG_M[6 + r][5] * g[r] * d[x];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) t -= Y[k][r] * z[x][k];
-        q[x][r] = t;
-      }
-    }
+      for (int x = 0; x < 3; ++x) c += D[i][8 + x] * D[i][8 + x];
   }
   return c;
 }
 
-// the sweep back: interior derivatives from the kept factors, then every segment's ten coefficients per axis and its cost
+// the sweep back: interior derivatives from the kept factors, then every segment's ten coefficients per axis and its cost.
+// NaN where a coefficient is not finite.
 __device__ __forceinline__ double tg_back(int n, const double* sT, const double* sD, const double* ws, long long K_pad,
                                           const double* wp, double* coeffs) {
   double b[3][4], cost = 0.0;
+  bool finite = true;
 #pragma unroll
   for (int x = 0; x < 3; ++x)
 #pragma unroll
     for (int r = 0; r < 4; ++r) b[x][r] = 0.0;                     // at rest at the end
   for (int m = n - 1; m >= 0; --m) {
     const double T = sT[m * DSIM_TG_LANES];
-    double u[4], g[4], a[3][4];
-    const double i7 = tg_scales(T, u, g);
+    double u[4], h[4], a[3][4];
+    const double w = tg_scales(T, u, h);
 #pragma unroll
     for (int x = 0; x < 3; ++x)
 #pragma unroll
       for (int r = 0; r < 4; ++r) a[x][r] = 0.0;                   // at rest at the start
-    if (m >= 1) {                                                   // a = -L^-T (z + L^-1 K_ab b)
-      const double* w = ws + (long long)(m - 1) * DSIM_TG_KEEP * K_pad;
-      double L[10], Li[4];
+    if (m >= 1) {                                                   // R_a a = z_a - R_ab b
+      const double* o = ws + (long long)(m - 1) * DSIM_TG_KEEP * K_pad;
+      double Ra[4][4], rest[4][7];
+      int e = 0;
 #pragma unroll
-      for (int e = 0; e < 10; ++e) L[e] = w[e * K_pad];
+      for (int r = 0; r < 4; ++r)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) Li[r] = 1.0 / L[tg_sym(r, r)];
+        for (int s = r; s < 4; ++s) Ra[r][s] = o[(e++) * K_pad];
 #pragma unroll
-      for (int x = 0; x < 3; ++x) {
-        double y[4];
+      for (int r = 0; r < 4; ++r)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          double t = 0.0;
+        for (int s = 0; s < 7; ++s) rest[r][s] = o[(e++) * K_pad];
 #pragma unroll
-          for (int s = 0; s < 4; ++s) t += DSIM_TG_M[1 + r][6 + s] * g[r] * u[s] * b[x][s];
-#pragma unroll
-          for (int k = 0; k < r; ++k) t -= L[tg_sym(r, k)] * y[k];
-          y[r] = t * Li[r];
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) y[r] += w[(10 + x * 4 + r) * K_pad];
+      for (int x = 0; x < 3; ++x)
 #pragma unroll
         for (int r = 3; r >= 0; --r) {
-          double t = y[r];
+          double t = rest[r][4 + x];
 #pragma unroll
-          for (int k = r + 1; k < 4; ++k) t -= L[tg_sym(k, r)] * a[x][k];
-          a[x][r] = t * Li[r];
+          for (int s = 0; s < 4; ++s) t -= rest[r][s] * b[x][s];
+#pragma unroll
+          for (int k = r + 1; k < 4; ++k) t -= Ra[r][k] * a[x][k];
+          a[x][r] = t / Ra[r][r];
         }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) a[x][r] = -a[x][r];
-      }
     }
     double ip[10];
     ip[0] = 1.0; ip[1] = 1.0 / T;
@@ -196,20 +199,22 @@ __device__ __forceinline__ double tg_back(int n, const double* sT, const double*
       for (int r = 0; r < 4; ++r) { e[1 + r] = a[x][r] * u[r]; e[6 + r] = b[x][r] * u[r]; }
       double en = 0.0;
 #pragma unroll
-      for (int r = 1; r < 10; ++r) {
+      for (int i = 0; i < 6; ++i) {
         double t = 0.0;
 #pragma unroll
-        for (int s = 1; s < 10; ++s) t += DSIM_TG_M[r][s] * e[s];
-        en += e[r] * t;
+        for (int s = 1; s < 10; ++s) t += DSIM_TG_F[i][s] * e[s];
+        en += t * t;
       }
-      cost += en * i7;
+      cost += en * (w * w);
       coeffs[((long long)(m * 10) * 3 + x) * K_pad] = wp[(long long)(m * 3 + x) * K_pad];
 #pragma unroll
       for (int j = 1; j < 10; ++j) {
         double t = 0.0;
 #pragma unroll
         for (int s = 1; s < 10; ++s) t += DSIM_TG_AINV[j][s] * e[s];
-        coeffs[((long long)(m * 10 + j) * 3 + x) * K_pad] = t * ip[j];
+        t *= ip[j];
+        finite = finite && isfinite(t);
+        coeffs[((long long)(m * 10 + j) * 3 + x) * K_pad] = t;
       }
     }
 #pragma unroll
@@ -217,7 +222,16 @@ __device__ __forceinline__ double tg_back(int n, const double* sT, const double*
 #pragma unroll
       for (int r = 0; r < 4; ++r) b[x][r] = a[x][r];
   }
-  return cost;
+  return finite ? cost : __builtin_nan("");
+}
+
+// a course that cannot be made: NaN everywhere, n_seg 0 (this course only)
+__device__ __forceinline__ void tg_refuse(const TrajGenK& a, long long k, int status, int evals) {
+  const double qnan = __builtin_nan("");
+  for (int e = 0; e < (a.L_max - 1) * 30; ++e) a.coeffs[(long long)e * a.K_pad + k] = qnan;
+  for (int l = 0; l < a.L_max; ++l) a.ts[(long long)l * a.K_pad + k] = qnan;
+  if (a.seg_times) for (int m = 0; m < a.L_max - 1; ++m) a.seg_times[(long long)m * a.K_pad + k] = qnan;
+  a.cost[k] = qnan; a.evals[k] = evals; a.status[k] = status; a.n_seg[k] = 0;
 }
 
 __global__ __launch_bounds__(DSIM_TG_LANES) void k_trajgen(TrajGenK a) {
@@ -254,20 +268,15 @@ __global__ __launch_bounds__(DSIM_TG_LANES) void k_trajgen(TrajGenK a) {
     }
     sT[m * DSIM_TG_LANES] = T;
   }
-  if (bad) {                                        // this course only: NaN everywhere, n_seg 0
-    for (int e = 0; e < (a.L_max - 1) * 30; ++e) coeffs[(long long)e * a.K_pad] = qnan;
-    for (int l = 0; l < a.L_max; ++l) ts[(long long)l * a.K_pad] = qnan;
-    if (a.seg_times) for (int m = 0; m < a.L_max - 1; ++m) a.seg_times[(long long)m * a.K_pad + k] = qnan;
-    a.cost[k] = qnan; a.evals[k] = 0; a.status[k] = bad; a.n_seg[k] = 0;
-    return;
-  }
+  if (bad) { tg_refuse(a, k, bad, 0); return; }
   int evals = 0;
+  bool lost = false;
   if (a.mode == DSIM_TRAJGEN_OPTIMIZE) {
     // greedy multiplicative pattern search (include/dronesim_amd.h); one pass of the loop is at most one evaluation, so lanes
     // at different points of their own searches still share the sweep's instructions
     double sum = 0.0;
     for (int m = 0; m < n; ++m) sum += sT[m * DSIM_TG_LANES];
-    double Jx = tg_sweep<false>(n, sT, -1, 0.0, sD, nullptr, 0) + a.gamma * sum;
+    double Jx = tg_sweep<false>(n, sT, -1, 0.0, sD, nullptr, 0, lost) + a.gamma * sum;
     evals = 1;
     double step = 0.5;
     int i = 0, dir = 0;
@@ -279,7 +288,7 @@ __global__ __launch_bounds__(DSIM_TG_LANES) void k_trajgen(TrajGenK a) {
       if (yi != xi) {
         sum = 0.0;
         for (int m = 0; m < n; ++m) sum += (m == i) ? yi : sT[m * DSIM_TG_LANES];
-        const double Jy = tg_sweep<false>(n, sT, i, yi, sD, nullptr, 0) + a.gamma * sum;
+        const double Jy = tg_sweep<false>(n, sT, i, yi, sD, nullptr, 0, lost) + a.gamma * sum;
         ++evals;
         if (Jy < Jx) { sT[i * DSIM_TG_LANES] = yi; Jx = Jy; accepted = true; took = true; }
       }
@@ -291,6 +300,13 @@ __global__ __launch_bounds__(DSIM_TG_LANES) void k_trajgen(TrajGenK a) {
       }
     }
   }
+  // what the search met on its way does not count: the course is judged at the times it is made for.  T^9 and T^-9 scale
+  // its coefficients and must be normal numbers
+  lost = false;
+  for (int m = 0; m < n; ++m) {
+    const double T = sT[m * DSIM_TG_LANES], T3 = T * T * T, T9 = T3 * T3 * T3;
+    if (!(T9 >= 0x1p-1000 && T9 <= 0x1p1000)) lost = true;
+  }
   if (a.mode != DSIM_TRAJGEN_GIVEN) {               // TS[1:] = cumsum(T), trajGen.py:42
     double acc = 0.0;
     ts[0] = 0.0;
@@ -299,8 +315,9 @@ __global__ __launch_bounds__(DSIM_TG_LANES) void k_trajgen(TrajGenK a) {
   for (int l = n + 1; l < a.L_max; ++l) ts[(long long)l * a.K_pad] = qnan;
   if (a.seg_times) for (int m = 0; m < a.L_max - 1; ++m) a.seg_times[(long long)m * a.K_pad + k] = m < n ? sT[m * DSIM_TG_LANES] : qnan;
   double* ws = a.ws ? a.ws + k : nullptr;           // (null only at L_max = 2, where no course has an interior waypoint)
-  tg_sweep<true>(n, sT, -1, 0.0, sD, ws, a.K_pad);
+  tg_sweep<true>(n, sT, -1, 0.0, sD, ws, a.K_pad, lost);
   const double cost = tg_back(n, sT, sD, ws, a.K_pad, wp, coeffs);
+  if (lost || !isfinite(cost)) { tg_refuse(a, k, DSIM_TRAJGEN_BAD_CONDITION, evals); return; }
   for (int e = n * 30; e < (a.L_max - 1) * 30; ++e) coeffs[(long long)e * a.K_pad] = qnan;
   a.cost[k] = cost; a.evals[k] = evals; a.status[k] = 0; a.n_seg[k] = n;
 }
@@ -404,6 +421,7 @@ int dsim_trajgen(dsim_ctx* ctx, void* stream, const dsim_traj_bank* bank, const 
   if (!(args->max_vel > 0.0) || !isfinite(args->max_vel) || !isfinite(args->gamma)) return DSIM_E_ARG;
   if (args->mode != DSIM_TRAJGEN_GIVEN && args->mode != DSIM_TRAJGEN_TMIN && args->mode != DSIM_TRAJGEN_OPTIMIZE) return DSIM_E_ARG;
   if (args->max_evals < 1) return DSIM_E_ARG;
+  if (args->mode == DSIM_TRAJGEN_OPTIMIZE && !(args->gamma > 0.0)) return DSIM_E_ARG;     // J has no minimum: T runs off to infinity
   const int64_t need = dsim_trajgen_workspace(bank->K_pad, bank->L_max);
   if (need > 0 && (!args->workspace || args->workspace_len < need)) return DSIM_E_ARG;
   TrajGenK a;

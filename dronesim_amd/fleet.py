@@ -594,7 +594,9 @@ class TrajectoryBank:
     at most ``max_evals`` evaluations per course), "tmin" (T = Tmin = distance / max_vel), or the cumulative times themselves,
     [K, L] or a list of [L_k] like ``trajGenerator.TS``.  ``L_max``: the bank's room in waypoints per course (default: the longest
     course).  A course that cannot be made (a non-finite waypoint, two equal consecutive waypoints, fewer than 2 or more than
-    L_max waypoints) has ``status != 0`` and NaN coefficients; the others are not affected."""
+    L_max waypoints, or — ``TRAJGEN_BAD_CONDITION`` — segment times at which the solve cannot keep its accuracy: a leg about 1 000
+    times shorter in time than those around it, as a near-duplicate waypoint gives) has ``status != 0`` and NaN coefficients; the
+    others are not affected.  ``gamma`` must be positive with "optimize" (the cost has no minimum otherwise): ``DsimError``."""
 
     def __init__(self, ctx: Context, waypoints, max_vel: float = 5, gamma: float = 100, times="optimize", max_evals: int = 2000,
                  L_max: Optional[int] = None):

@@ -48,7 +48,7 @@ extern "C" {
                               DSIM_CAM_*, DSIM_SEG_GROUND; the other drones in the camera's images, dsim_depth_image_drones,
                               dsim_depth_image_drones_workspace, dsim_camera_drones, DSIM_SEG_DRONE; the trajectory bank,
                               dsim_trajgen, dsim_trajgen_workspace, dsim_traj_sample_bank, dsim_traj_bank, dsim_trajgen_args,
-                              DSIM_TRAJGEN_*; the swept obstacle watch, dsim_obstacle_sweep, dsim_sweep_args, DSIM_SWEEP_*; obstacle
+                              DSIM_TRAJGEN_* (DSIM_TRAJGEN_BAD_CONDITION among them); the swept obstacle watch, dsim_obstacle_sweep, dsim_sweep_args, DSIM_SWEEP_*; obstacle
                               scenes, dsim_scenes_create / _destroy, dsim_obstacle_clearance_scenes, dsim_depth_image_scenes */
 #define DSIM_MAX_ACT 6     /* actuators per vehicle (quad 4, morphing hexa 6) */
 #define DSIM_MAX_TYPES 8
@@ -521,10 +521,12 @@ typedef struct dsim_traj_bank {
  *   coeffs = MinimizeSnap(T) (trajGen.py:45-106): order 10, positions at both ends of every segment, derivatives 1-4
  *   continuous, at rest at both ends, the 4 (L - 2) interior derivatives free and chosen to minimise the cost; L = 2 has none.
  * The reference inverts the dense 10 n_seg-square constraint matrix.  Here a segment's cost is the quadratic form of its
- * scaled end values in ONE constant 10 x 10 matrix (a table, exact rationals rounded once) over T^7, and the interior
- * derivatives solve a symmetric positive definite block-tridiagonal system of 4 x 4 blocks: one sweep along the course in
- * registers gives J (that is an evaluation of the search: a few hundred flops per segment), a second sweep back gives the
- * coefficients.  Each segment is solved for p(t) - wp[seg], which costs the same.
+ * scaled end values in ONE constant 10 x 10 matrix M over T^7, held as its 6 x 10 factor F (M = F^T F; tables, exact
+ * rationals rounded once), and the interior derivatives solve a least-squares problem with a block-bidiagonal matrix of
+ * 6 x 4 blocks: one sweep along the course in registers, by Householder reflections, gives J (that is an evaluation of the
+ * search: about a thousand flops per segment), a second sweep back gives the coefficients.  Each segment is solved for
+ * p(t) - wp[seg], which costs the same.  No difference of nearly equal numbers is formed, so a short leg beside a long one
+ * keeps its digits up to a ratio of about 1 000 in their times; beyond that the course is refused, see below.
  * The reference searches T with scipy's COBYLA; this search is a greedy multiplicative pattern search, deterministic and
  * derivative-free: from x = Tmin and step = 0.5, sweep i and try y_i = max(Tmin_i, x_i (1 + step)), then
  * max(Tmin_i, x_i / (1 + step)) (a y_i equal to x_i is skipped); J(y) < J(x) is accepted at once and the sweep moves to
@@ -534,15 +536,23 @@ typedef struct dsim_traj_bank {
  * Out: bank->coeffs, ->ts (not in GIVEN), ->n_seg; cost[k] = trace(P^T Q P) without the gamma term (trajGenerator.cost);
  * evals[k] = evaluations of J the search spent (0 in GIVEN / TMIN); status[k] = 0, or DSIM_TRAJGEN_BAD_* for a course that
  * cannot be made — n_wp[k] out of [2, L_max], a non-finite waypoint, a zero-length segment (the reference's matrix is singular
- * there), in GIVEN a time step that is not positive and finite — whose coeffs, ts and cost are NaN and n_seg 0.  The other
- * courses of the launch are not affected.  cost, evals, status: [K_pad].  seg_times (nullable) receives the segment times
+ * there), in GIVEN a time step that is not positive and finite, or (DSIM_TRAJGEN_BAD_CONDITION) segment times at which
+ * the solve cannot keep the published accuracy (tests/README_trajgen.md) — whose coeffs, ts, seg_times and cost are NaN
+ * and n_seg 0.  DSIM_TRAJGEN_BAD_CONDITION is reported where a pivot of the carried triangular factor is more than
+ * 2^14 times smaller than its column was and a later segment goes on from it (a leg whose time is about 1 000 times
+ * shorter than those around it; measured error of the course 0.2 eps (ratio)^2), where T^9 or T^-9 of a segment is no
+ * normal fp64 number (T outside about 1e-33 .. 1e33 s), and where a coefficient or the cost comes out not finite; it is
+ * judged at the times the course is made for, and evals[k] still counts what the search spent.  The other courses of the
+ * launch are not affected.  cost, evals, status: [K_pad].  seg_times (nullable) receives the segment times
  * the coefficients were made for, NaN past n_seg and for such a course: T >= Tmin holds for them exactly.
- * workspace: dsim_trajgen_workspace(K_pad, L_max) fp64 entries (22 (L_max - 2) K_pad: what the sweep back needs of the
+ * workspace: dsim_trajgen_workspace(K_pad, L_max) fp64 entries (38 (L_max - 2) K_pad: what the sweep back needs of the
  * sweep along), the call's until it has run; may be NULL at L_max = 2.  Stream-ordered, allocates and synchronises nothing.
  * DSIM_E_ARG, nothing enqueued: a null pointer, K < 1, K_pad < K or no multiple of 64, L_max outside [2, DSIM_TRAJGEN_LMAX],
- * max_vel / gamma not finite or max_vel <= 0, an unknown mode, max_evals < 1, a workspace too small.                    */
+ * max_vel / gamma not finite or max_vel <= 0, gamma <= 0 in DSIM_TRAJGEN_OPTIMIZE (J has no minimum then; GIVEN and TMIN
+ * do not read gamma), an unknown mode, max_evals < 1, a workspace too small.                                            */
 enum { DSIM_TRAJGEN_GIVEN = 0, DSIM_TRAJGEN_TMIN = 1, DSIM_TRAJGEN_OPTIMIZE = 2 };
-enum { DSIM_TRAJGEN_BAD_COUNT = 1, DSIM_TRAJGEN_BAD_WAYPOINT = 2, DSIM_TRAJGEN_BAD_SEGMENT = 3, DSIM_TRAJGEN_BAD_TIME = 4 };
+enum { DSIM_TRAJGEN_BAD_COUNT = 1, DSIM_TRAJGEN_BAD_WAYPOINT = 2, DSIM_TRAJGEN_BAD_SEGMENT = 3, DSIM_TRAJGEN_BAD_TIME = 4,
+       DSIM_TRAJGEN_BAD_CONDITION = 5 };
 typedef struct dsim_trajgen_args {
   const double*  wp;
   const int32_t* n_wp;

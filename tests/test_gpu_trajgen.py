@@ -210,9 +210,12 @@ def test_bad_courses_do_not_touch_their_neighbours(gpu, ctx, courses):
 
 
 def test_arguments_refused(gpu, ctx, courses):
+    """(gamma <= 0 has no minimum under "optimize", the default mode here; "tmin" and given times do not read gamma:
+    tests/test_gpu_trajgen_exact.py)"""
     nat, fleet = gpu
     wps = [courses[3]["waypoints"]]
-    for kw in (dict(max_vel=0.0), dict(max_vel=float("nan")), dict(gamma=float("inf")), dict(max_evals=0), dict(L_max=1)):
+    for kw in (dict(max_vel=0.0), dict(max_vel=float("nan")), dict(gamma=float("inf")), dict(max_evals=0), dict(L_max=1),
+               dict(gamma=0.0), dict(gamma=-1.0), dict(gamma=float("nan"))):
         with pytest.raises(nat.DsimError):
             fleet.TrajectoryBank(ctx, wps, **kw)
 

@@ -93,7 +93,8 @@ def test_two_waypoints_is_the_closed_form(courses):
 
 def test_library_tables_are_the_exact_rationals():
     """dsim_trajgen_tables.h holds exact_tables() rounded once: A^^-1 is the inverse of the Hermite matrix, M is symmetric and costs a
-    constant nothing, and the committed header is what tools/gen_trajgen_tables.py writes."""
+    constant nothing; factor_table() rounded once: F^T F = M to the bits its square roots were taken to; and the committed header is
+    what tools/gen_trajgen_tables.py writes."""
     from fractions import Fraction
     Ainv, M = R.exact_tables()
     for i in range(10):
@@ -106,7 +107,13 @@ def test_library_tables_are_the_exact_rationals():
     assert [Ainv[k][k] for k in range(5)] == [Fraction(1, f) for f in (1, 1, 2, 6, 24)]
     txt = open(os.path.join(ROOT, "dronesim_amd", "csrc", "dsim_trajgen_tables.h")).read()
     got = [float.fromhex(h) for h in re.findall(r"-?0x[0-9a-f.]+p[+-]?\d+", txt)]
-    want = [float(v) for t in (Ainv, M) for row in t for v in row]
+    F = R.factor_table()
+    assert len(F) == 6 and all(len(row) == 10 for row in F)
+    for i in range(10):
+        for j in range(10):
+            FtF = sum(F[k][i] * F[k][j] for k in range(6))
+            assert abs(FtF - M[i][j]) <= Fraction(1, 2 ** (R.FACTOR_BITS - 40)) * max(abs(M[i][i]), abs(M[j][j])), (i, j)
+    want = [float(v) for t in (Ainv, M, F) for row in t for v in row]
     assert got == want
     import importlib.util
     spec = importlib.util.spec_from_file_location("gen_trajgen_tables", os.path.join(ROOT, "tools", "gen_trajgen_tables.py"))
@@ -136,7 +143,7 @@ def test_new_symbols_and_struct_sizes(nat, tmp_path):
     consts = {"DSIM_TRAJGEN_GIVEN": nat.TRAJGEN_GIVEN, "DSIM_TRAJGEN_TMIN": nat.TRAJGEN_TMIN, "DSIM_TRAJGEN_OPTIMIZE": nat.TRAJGEN_OPTIMIZE,
               "DSIM_TRAJGEN_LMAX": nat.TRAJGEN_LMAX, "DSIM_TRAJGEN_BAD_COUNT": nat.TRAJGEN_BAD_COUNT,
               "DSIM_TRAJGEN_BAD_WAYPOINT": nat.TRAJGEN_BAD_WAYPOINT, "DSIM_TRAJGEN_BAD_SEGMENT": nat.TRAJGEN_BAD_SEGMENT,
-              "DSIM_TRAJGEN_BAD_TIME": nat.TRAJGEN_BAD_TIME}
+              "DSIM_TRAJGEN_BAD_TIME": nat.TRAJGEN_BAD_TIME, "DSIM_TRAJGEN_BAD_CONDITION": nat.TRAJGEN_BAD_CONDITION}
     lines = [f'printf("{c} %d\\n", (int){c});' for c in consts]
     for cname, cls in mirrors.items():
         lines.append(f'printf("{cname} %zu\\n", sizeof({cname}));')
@@ -153,8 +160,9 @@ def test_new_symbols_and_struct_sizes(nat, tmp_path):
         assert int(got[cname]) == ctypes.sizeof(cls), cname
         for fname, _ in cls._fields_:
             assert int(got[f"{cname}.{fname}"]) == getattr(cls, fname).offset, (cname, fname)
-    # the workspace rule needs no device: 22 fp64 per interior waypoint and course
-    assert lib.dsim_trajgen_workspace(64, 2) == 0 and lib.dsim_trajgen_workspace(128, 9) == 22 * 7 * 128
+    # the workspace rule needs no device: 38 fp64 per interior waypoint and course (the square-root sweep keeps R_a, R_ab and z_a)
+    assert nat.TRAJGEN_BAD_CONDITION == 5
+    assert lib.dsim_trajgen_workspace(64, 2) == 0 and lib.dsim_trajgen_workspace(128, 9) == 38 * 7 * 128
     assert lib.dsim_trajgen_workspace(64, 10) == 0 and lib.dsim_trajgen_workspace(0, 4) == 0
 
 
