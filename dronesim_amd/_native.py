@@ -28,6 +28,7 @@ EXPORTS = (
     "dsim_trajgen", "dsim_trajgen_workspace", "dsim_traj_sample_bank",
     "dsim_obstacle_sweep",
     "dsim_scenes_create", "dsim_scenes_destroy", "dsim_obstacle_clearance_scenes", "dsim_depth_image_scenes",
+    "dsim_clearance_sweep", "dsim_clearance_sweep_workspace",
 )
 
 ABI_VERSION = 11
@@ -164,6 +165,21 @@ class SweepArgs(ctypes.Structure):
         ("clearance_out", ctypes.c_void_p),
         ("nearest_out", ctypes.c_void_p),
         ("contacts_out", ctypes.c_void_p),
+        ("unswept_out", ctypes.c_void_p),
+    ]
+
+
+class ClearanceSweepArgs(ctypes.Structure):
+    """dsim_clearance_sweep_args (dsim_clearance_sweep); flags as dsim_sweep_args'."""
+    _fields_ = [
+        ("prev", ctypes.c_void_p),
+        ("margin", ctypes.c_float),
+        ("sag", ctypes.c_float),
+        ("travel", ctypes.c_float),
+        ("flags", ctypes.c_int32),
+        ("clearance_out", ctypes.c_void_p),
+        ("nearest_out", ctypes.c_void_p),
+        ("pairs_out", ctypes.c_void_p),
         ("unswept_out", ctypes.c_void_p),
     ]
 
@@ -324,6 +340,9 @@ def load(path: str = None) -> ctypes.CDLL:
     lib.dsim_obstacles_destroy.argtypes = [vp, vp]
     lib.dsim_obstacle_clearance.argtypes = [vp, vp, i64, View, vp, vp, vp, ctypes.c_float, vp, vp, vp]
     lib.dsim_obstacle_sweep.argtypes = [vp, vp, i64, View, vp, ctypes.POINTER(SweepArgs)]
+    lib.dsim_clearance_sweep_workspace.restype = ctypes.c_int64
+    lib.dsim_clearance_sweep_workspace.argtypes = [i64, i32, i32]
+    lib.dsim_clearance_sweep.argtypes = [vp, vp, i64, View, ctypes.POINTER(DownwashArgs), ctypes.POINTER(ClearanceSweepArgs)]
     lib.dsim_obstacle_ray_grid_plan.argtypes = [vp, i64, ctypes.POINTER(ObstacleGrid)]
     lib.dsim_obstacle_ray_grid_build.argtypes = [vp, i64, ctypes.POINTER(ObstacleGrid), vp, vp]
     lib.dsim_obstacles_enable_rays.argtypes = [vp, vp]

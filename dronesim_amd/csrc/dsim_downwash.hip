@@ -1741,3 +1741,6 @@ int dsim_sphere_grid_build(dsim_ctx* ctx, hipStream_t st_, int64_t n, const dsim
   out->local_offset = g->local_offset;
   return (int)hipGetLastError();
 }
+
+// the swept drone-drone contact watch (dsim_clearance_sweep): part of this translation unit, it shares DwK, ClrK, grid_build, sort_ws and WsWalk
+#include "dsim_clearance_sweep.hip"

@@ -723,6 +723,59 @@ class Downwash:
                                      pairs_out.data_ptr() if pairs_out is not None else None))
         return clr[: st.n], near[: st.n]
 
+    def _single_rank_only(self, what: str) -> None:
+        if self.halo is not None or (self.dist is not None and self.dist.is_initialized() and self.dist.get_world_size() > 1):
+            raise NotImplementedError(f"{what} on a sharded fleet: prev would have to hold every world entry, the other ranks' too")
+
+    def clearance_prime(self, prev: torch.Tensor) -> None:
+        """``prev`` [3, n_pad] float32 := the current positions, and nothing else (dsim_clearance_sweep, DSIM_SWEEP_PRIME): the
+        next clearance_sweep's chords start here."""
+        self._single_rank_only("clearance_prime")
+        st = self.state
+        if prev.dtype != torch.float32 or tuple(prev.shape) != (3, st.n_pad) or not prev.is_contiguous():
+            raise ValueError(f"prev must be a contiguous float32 [3, {st.n_pad}]")
+        a = nat.ClearanceSweepArgs(prev.data_ptr(), 0.0, 0.0, 0.0, nat.SWEEP_PRIME, None, None, None, None)
+        nat.check(self.ctx.lib.dsim_clearance_sweep(self.ctx.handle, self.ctx.stream_ptr(), st.n, st.view(), None, ctypes.byref(a)))
+
+    def clearance_sweep(self, margin: float, sag: float, travel: float, prev: torch.Tensor, pairs_out: Optional[torch.Tensor] = None,
+                        unswept_out: Optional[torch.Tensor] = None, keep_prev: bool = False, box=None):
+        """The swept drone-drone contact watch (dsim_clearance_sweep): as clearance(), with every drone a sphere of radius
+        R + ``sag`` that moves linearly from ``prev`` [3, n_pad] (float32, storage order: where the previous call saw it) to its
+        current position, both drones of a pair at the same parameter.  (clearance [n] float32, nearest [n] int32); overlapping
+        pairs go into the context's counter and ``pairs_out`` as clearance()'s do.  A drone whose chord is longer than ``travel``
+        or has a non-finite end is a point sample and is counted in ``unswept_out`` (int64 [1] on the device).  ``prev`` is moved
+        on to the current positions unless ``keep_prev``.  The grid is chosen as clearance() chooses its own, for the radius
+        r_max + sag and the margin margin + 2 travel, which is the library's cell rule.  Single rank only."""
+        self._single_rank_only("clearance_sweep")
+        st, lib = self.state, self.ctx.lib
+        margin, sag, travel = float(margin), float(sag), float(travel)
+        if prev.dtype != torch.float32 or tuple(prev.shape) != (3, st.n_pad) or not prev.is_contiguous():
+            raise ValueError(f"prev must be a contiguous float32 [3, {st.n_pad}]")
+        key = ("sweep", margin, sag, travel, None if box is None else tuple(float(v) for v in box))
+        if self._box is None or (box is None and self._box_age >= self._box_refresh) or getattr(self, "_clr_key", None) != key:
+            if box is not None:
+                lo, hi = key[4][:2], key[4][2:]
+            else:
+                src = torch.nan_to_num(st.raw_fields(0, 2), nan=0.0, posinf=0.0, neginf=0.0)      # (a lost drone does not stretch the box)
+                lo, hi = src.min(dim=1).values.cpu(), src.max(dim=1).values.cpu()
+            r_max = max(float(t.collision_sphere) for t in self.ctx.types)
+            self.cell, *grid = clearance_grid(lo, hi, r_max + sag, margin + 2.0 * travel, st.n)
+            self._box, self._box_age, self._clr_key = tuple(grid), 0, key
+        elif self._box_age >= self._box_refresh:
+            self._box_age = 0                      # a pinned box stands (_grid_box would measure one of its own)
+        self._auto_cell = False
+        self._prebin_version = None
+        a = self._grid_args(None, 0)
+        self._workspace(a, lib.dsim_clearance_sweep_workspace(a.m, a.nx, a.ny))
+        clr = torch.empty((st.n_pad,), dtype=torch.float32, device=self.ctx.device)
+        near = torch.empty((st.n_pad,), dtype=torch.int32, device=self.ctx.device)
+        s = nat.ClearanceSweepArgs(prev.data_ptr(), margin, sag, travel, nat.SWEEP_KEEP_PREV if keep_prev else 0, clr.data_ptr(),
+                                   near.data_ptr(), pairs_out.data_ptr() if pairs_out is not None else None,
+                                   unswept_out.data_ptr() if unswept_out is not None else None)
+        self._clr_args, self._sweep_args = a, s
+        nat.check(lib.dsim_clearance_sweep(self.ctx.handle, self.ctx.stream_ptr(), st.n, st.view(), ctypes.byref(a), ctypes.byref(s)))
+        return clr[: st.n], near[: st.n]
+
     def sphere_grid(self, box=None) -> nat.DownwashArgs:
         """The grid argument of dsim_depth_image_drones (DepthCamera(drones=True)): the fleet's xy grid with cells of 2 R_max or
         more, chosen as clearance() chooses its own (clearance_grid: at most CLEARANCE_CELLS_PER_DRONE cells per drone) over the

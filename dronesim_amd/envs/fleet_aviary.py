@@ -127,6 +127,9 @@ class CtrlAviary(PlacedFleetArrays, FleetObservation, StepWatches):
         mem_hint: bool = True,
         drone_watch: bool = False,
         drone_watch_margin: float = 1.0,
+        drone_sweep: bool = False,
+        drone_sweep_sag: float = 0.0,
+        drone_sweep_travel: Optional[float] = None,
         obstacle_watch=None,
         obstacle_margin: float = 1.0,
         obstacle_offsets=None,
@@ -150,7 +153,8 @@ class CtrlAviary(PlacedFleetArrays, FleetObservation, StepWatches):
                             obstacle_sweep_travel=obstacle_sweep_travel, vision_attributes=vision_attributes, vision_scene=vision_scene,
                             vision_drones=vision_drones, vision_res=vision_res, vision_ground=vision_ground,
                             vision_see_drones=vision_see_drones, vision_drone_range=vision_drone_range,
-                            obstacle_scene_id=obstacle_scene_id)
+                            obstacle_scene_id=obstacle_scene_id, drone_sweep=drone_sweep, drone_sweep_sag=drone_sweep_sag,
+                            drone_sweep_travel=drone_sweep_travel)
         # the add-on terms of the PYB_* modes (dead code in the reference fork, intended formulas); Physics.DYN: the
         # reference's own explicit model, BaseAviary._dynamics (BaseAviary.py:1767-1828; DSIM_OPT_DYN)
         self._phys_options = {Physics.PYB: 0, Physics.PYB_DW: 0, Physics.PYB_GND: nat.OPT_GROUND,

@@ -15,6 +15,8 @@ from .. import _native as nat
 class StepWatches:
     # (class-level "nothing on": an env made without __init__ steps with no service behind it)
     _drone_watch = False          # the drone-drone contact watch behind every step (set by _watch_options)
+    _drone_sweep = False          # ... queried along the chords between two samples (drone_sweep=True)
+    _drone_prev = None            # ... from where the previous query saw every drone (set by _watch_setup)
     _obst = None                  # the static-obstacle watch's device set (set by _watch_setup)
     _obst_sweep = False           # ... queried along the chord between two samples (obstacle_sweep=True)
     _obst_placed = False          # ... an ObstacleScenes: per-drone placements of one prototype (obstacle_scene_id)
@@ -23,7 +25,8 @@ class StepWatches:
     # ------------------------------------------------------------------ construction
     def _watch_options(self, *, num_drones, freq, aggregate_phy_steps, dist, drone_watch, drone_watch_margin, obstacle_watch,
                        obstacle_margin, obstacle_sweep, obstacle_sweep_sag, obstacle_sweep_travel, vision_attributes, vision_scene,
-                       vision_drones, vision_res, vision_ground, vision_see_drones, vision_drone_range, obstacle_scene_id=None) -> None:
+                       vision_drones, vision_res, vision_ground, vision_see_drones, vision_drone_range, obstacle_scene_id=None,
+                       drone_sweep=False, drone_sweep_sag=0.0, drone_sweep_travel=None) -> None:
         """The services' keywords of ``CtrlAviary.__init__``: checked and stashed (the set-up follows in _watch_setup, when the
         context and the storage order exist)."""
         # The reference's Bullet world lets the vehicles' collision shapes act on each other; here every drone is integrated
@@ -38,6 +41,23 @@ class StepWatches:
         self.last_clearance = None
         self._clearance = None    # grid for drone_clearance(), built on first use
         self._clr_on_demand = None    # int64 [1]: pairs the on-demand queries counted (not Env.steps: drone_contacts() leaves them out)
+        # drone_sweep=True: the query behind a launch is dsim_clearance_sweep instead, every drone a sphere of radius
+        # R + drone_sweep_sag that moves along the chord from the position the previous query saw (reset() primes it) to the state
+        # the launch left, both drones of a pair at the same parameter: with sag >= obstacles.sweep_sag(a_max, time between two
+        # queries) and drone_unswept() == 0, drone_contacts() == 0 certifies every state in between as well.
+        # drone_sweep_travel [m]: the longest chord that is swept (None: 10 m/s x one Env.step); a longer one is a point sample and is
+        # counted by drone_unswept(); the grid's cells grow by twice the travel.  Off by default: nothing new is allocated or launched.
+        if not drone_watch and (drone_sweep or drone_sweep_sag != 0.0 or drone_sweep_travel is not None):
+            raise ValueError("drone_sweep / drone_sweep_sag / drone_sweep_travel without drone_watch=True")
+        if not drone_sweep and (drone_sweep_sag != 0.0 or drone_sweep_travel is not None):
+            raise ValueError("drone_sweep_sag / drone_sweep_travel without drone_sweep=True")
+        self._drone_sweep, self._drone_sag = bool(drone_sweep), float(drone_sweep_sag)
+        self._drone_travel = 10.0 * int(aggregate_phy_steps) / float(freq) if drone_sweep_travel is None else float(drone_sweep_travel)
+        if drone_sweep and (not np.isfinite(self._drone_sag) or self._drone_sag < 0.0):
+            raise ValueError("drone_sweep_sag must be >= 0")
+        if drone_sweep and (not np.isfinite(self._drone_travel) or not self._drone_travel >= 1e-3):
+            raise ValueError("drone_sweep_travel must be at least a millimetre")
+        self._drone_prev = self._drone_unswept = None
         # The reference's Bullet world also holds static bodies (p.loadURDF of a gate); here they act on nothing.
         # obstacle_watch=ObstacleSet: every step / step_fused / adaptor step is followed, on the env's stream, by one
         # dsim_obstacle_clearance on the state it left (once per LAUNCH: a step_fused with n_steps > 1 is sampled once, at its end);
@@ -126,6 +146,12 @@ class StepWatches:
 
     def _watch_setup(self, offsets) -> None:
         """At the end of __init__: the obstacle set first, because the camera shares its device set."""
+        if self._drone_sweep:
+            # where the previous query saw every drone (storage order), and how many drone x queries were point samples
+            dev, n_pad = self.ctx.device, self.state.n_pad
+            self._drone_prev = torch.zeros((3, n_pad), dtype=torch.float32, device=dev)
+            self._drone_unswept = torch.zeros((1,), dtype=torch.int64, device=dev)
+            self._drone_grid().clearance_prime(self._drone_prev)     # (the first _housekeeping ran before this tensor existed)
         self._obstacle_setup(offsets)
         self._vision_setup(offsets)
 
@@ -193,6 +219,8 @@ class StepWatches:
         if self._obst is not None and self._obst_sweep:
             from .. import obstacles as obs
             obs.prime(self.ctx, self.state, self._obst, self._obst_prev)
+        if self._drone_prev is not None:
+            self._drone_grid().clearance_prime(self._drone_prev)
 
     def _watch_close(self) -> None:
         if self._vision is not None:
@@ -208,7 +236,7 @@ class StepWatches:
         self.step_counter += self.AGGR_PHY_STEPS * n_steps
         self._env_steps += n_steps
         if self._drone_watch:
-            self.last_clearance = self._drone_query(self._drone_watch_margin, None)
+            self.last_clearance = self._drone_query(self._drone_watch_margin, None, self._drone_sweep)
         if self._obst is not None:
             self._watch_obstacles()
         if self._vision is not None:
@@ -220,13 +248,23 @@ class StepWatches:
             if due:
                 self._vision_capture()
 
-    def _drone_query(self, margin: float, pairs_out):
+    def _drone_grid(self):
         from ..downwash import Downwash
         if self._clearance is None:
             self._clearance = Downwash(self.ctx, self.state, self._type_id, None)
+        return self._clearance
+
+    def _drone_query(self, margin: float, pairs_out, swept: bool = False):
+        """The point query of the current state, or (``swept``: the watch behind a launch of a drone_sweep=True env) the swept one
+        from the state the previous swept query saw."""
+        dw = self._drone_grid()
         if self._downwash is not None:
             self._downwash.invalidate_prebin()            # the clearance pass re-uses the ctx's grid bookkeeping
-        clr, near = self._clearance.clearance(margin, pairs_out=pairs_out)
+        if swept:
+            clr, near = dw.clearance_sweep(margin, self._drone_sag, self._drone_travel, self._drone_prev, pairs_out=pairs_out,
+                                           unswept_out=self._drone_unswept)
+        else:
+            clr, near = dw.clearance(margin, pairs_out=pairs_out)
         if self.order is not None:
             clr, near = self.order.to_caller(clr, 0), self.order.indices_to_caller(near, 0)
         return clr, near
@@ -313,9 +351,20 @@ class StepWatches:
         Bullet world lets the vehicles' collision shapes act on each other; here contact between drones is not modelled,
         and a non-zero count means part of the flight lies outside the domain in which trajectories are comparable with
         the reference.  One-sided: 0 certifies that no two vehicles touched; overlapping spheres need not be touching
-        shapes.  On-demand drone_clearance() calls are not Env.steps and are left out."""
+        shapes.  That 0 is about the sampled states, one per launch; with ``drone_sweep=True`` the count is of spheres moved along
+        the chords between two sampled states, and with drone_sweep_sag >= obstacles.sweep_sag(a_max, time between two queries) and
+        drone_unswept() == 0 it certifies the states in between as well.  On-demand drone_clearance() calls are not Env.steps and
+        are left out."""
         seen = self.ctx.query(nat.QUERY_DRONE_CONTACTS)
         return seen - (int(self._clr_on_demand.item()) if self._clr_on_demand is not None else 0)
+
+    def drone_unswept(self) -> int:
+        """Drones x queries so far of a ``drone_sweep=True`` env that were point samples instead of chords: a chord longer than
+        drone_sweep_travel (a teleport, or a launch of more Env.steps than the travel was sized for) or a non-finite position on
+        either end (cumulative; synchronises the stream).  0 for a flight: every counted state was reached along a tested chord."""
+        if not self._drone_sweep:
+            raise ValueError("drone_unswept() needs an env made with drone_watch=True, drone_sweep=True")
+        return int(self._drone_unswept.item()) if self._drone_unswept is not None else 0
 
     @property
     def last_obstacle_clearance(self):

@@ -49,7 +49,9 @@ extern "C" {
                               dsim_depth_image_drones_workspace, dsim_camera_drones, DSIM_SEG_DRONE; the trajectory bank,
                               dsim_trajgen, dsim_trajgen_workspace, dsim_traj_sample_bank, dsim_traj_bank, dsim_trajgen_args,
                               DSIM_TRAJGEN_* (DSIM_TRAJGEN_BAD_CONDITION among them); the swept obstacle watch, dsim_obstacle_sweep, dsim_sweep_args, DSIM_SWEEP_*; obstacle
-                              scenes, dsim_scenes_create / _destroy, dsim_obstacle_clearance_scenes, dsim_depth_image_scenes */
+                              scenes, dsim_scenes_create / _destroy, dsim_obstacle_clearance_scenes, dsim_depth_image_scenes; the
+                              swept drone-drone watch, dsim_clearance_sweep, dsim_clearance_sweep_workspace,
+                              dsim_clearance_sweep_args */
 #define DSIM_MAX_ACT 6     /* actuators per vehicle (quad 4, morphing hexa 6) */
 #define DSIM_MAX_TYPES 8
 
@@ -861,6 +863,49 @@ typedef struct dsim_sweep_args {
 } dsim_sweep_args;
 int dsim_obstacle_sweep(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, const dsim_obstacles* set,
                         const dsim_sweep_args* args);
+
+/* The swept drone-drone query: dsim_clearance along the CHORDS from the positions the previous call saw to the current ones.
+ * dsim_clearance certifies the sampled states only; two vehicles that close at a few m/s, or any fleet sampled once per several
+ * Env.steps, pass through each other between two samples.  Stream-ordered, allocates nothing, never synchronises.  Each drone is
+ * a sphere of radius R + sag that moves linearly from p0 = prev to p1 = its current position, both drones of a pair at the same
+ * parameter s in [0, 1]:
+ *     d0 = p0_j - p0_i,  d1 = p1_j - p1_i,  Delta = d1 - d0
+ *     s* = clamp(-d0.Delta / Delta.Delta, 0, 1)            (0 where Delta.Delta = 0)
+ *     dist^2 = min(|d0|^2, |d1|^2, |d0 + s* Delta|^2)       never above the point query's distance at either end
+ *     c_ij = sqrt(dist^2) - (R_i + sag) - (R_j + sag)
+ *     clearance_out[i] = min(margin, min_j c_ij);  nearest_out[i] = the j that attains it, -1 when no c_ij < margin
+ * sag >= 0 [m]: how far a flown path may leave the interpolation AT EQUAL TIMES; with |a| <= a_max over the time T between two
+ * calls that is a_max T^2 / 8 per drone, hence 2 sag per pair.  A type with collision_sphere = 0 takes no part (margin, -1, never
+ * counted), whatever the sag.  Every unordered pair with c_ij < 0 is counted once per call, by the lower index, into
+ * DSIM_Q_DRONE_CONTACTS and *pairs_out, as in dsim_clearance: the same quantity, measured better.  Then, unless
+ * DSIM_SWEEP_KEEP_PREV is set, prev_i := p_i for every i < n.
+ *
+ * The drones are binned at their CURRENT positions on the counting-sort grid of `grid`, as dsim_clearance bins them.  grid->cell
+ * must be >= 2 (R_max + sag) + margin + 2 travel: a pair with c_ij < margin has |d1| <= |d(s*)| + |Delta| < 2 (R_max + sag) +
+ * margin + 2 travel as long as no chord is longer than `travel`, so its current positions lie in the same or adjacent cells
+ * (clamping into a border cell is monotone).  The library enforces the bound: a drone whose chord is longer than travel (by a
+ * comparison 2^-20 on the safe side), or whose prev_i or p_i has a non-finite component, is UNSWEPT — p0 := p1, a point sample —
+ * and adds one to *unswept_out when its R > 0.  Workspace: at least dsim_clearance_sweep_workspace(m, nx, ny) int32 entries (the
+ * clearance layout and one 16-byte aligned float4 [m]).
+ *
+ * DSIM_SWEEP_PRIME: prev_i := p_i for i < n and nothing else; grid (may be NULL), margin, sag, travel, the outputs and the
+ * counters are not looked at.  Refused with nothing enqueued: a NULL args or prev, an unknown flag or both flags (DSIM_E_ARG);
+ * grid->pos_all or a halo plan (DSIM_E_UNSUPPORTED: a sharded world would need prev for every world entry); and DSIM_E_ARG for a
+ * NULL ctx, n <= 0 or > n_pad, and unless PRIME: a NULL grid or clearance_out, margin <= 0, sag < 0, travel <= 0, any of them not
+ * finite, more than one type without grid->type_id, the cell rule, a workspace that is too short, and what dsim_clearance refuses
+ * of the grid. */
+typedef struct dsim_clearance_sweep_args {
+  float*    prev;           /* [3][n_pad] SoA, world frame; updated to the current positions unless KEEP_PREV */
+  float     margin, sag, travel;
+  int32_t   flags;
+  float*    clearance_out;  /* [n_pad] */
+  int32_t*  nearest_out;    /* nullable [n_pad] */
+  uint64_t* pairs_out;      /* nullable device counter */
+  uint64_t* unswept_out;    /* nullable device counter */
+} dsim_clearance_sweep_args;
+int64_t dsim_clearance_sweep_workspace(int64_t m, int32_t nx, int32_t ny);
+int dsim_clearance_sweep(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, const dsim_downwash_args* grid,
+                         const dsim_clearance_sweep_args* args);
 
 /* Depth camera: per-drone depth and segmentation images of the obstacle set.  The reference's envs keep, with
  * vision_attributes=True, an rgb / depth / segmentation image per drone from p.getCameraImage (BaseAviary._getDroneImages,
