@@ -238,6 +238,11 @@ class CtrlAviary(PlacedFleetArrays, FleetObservation, StepWatches):
         # None -> fresh seed per env, 0 -> noise off (parity runs), k -> reproducible
         self.noise_seed = int.from_bytes(os.urandom(7), "little") | 1 if noise_seed is None else int(noise_seed)
         self.dict_io = (num_drones <= DICT_IO_MAX_DRONES) if dict_io is None else dict_io
+        if self._phys_options & (nat.OPT_GROUND | nat.OPT_DRAG) and any(t.n_act != 4 for t in types):
+            # (the library refuses every step of such a fleet with DSIM_E_UNSUPPORTED: say so here, in a sentence)
+            raise NotImplementedError(f"Physics.{physics.name}: the drag and ground-effect add-on formulas are written for "
+                                      "four-rotor types (BaseAviary._drag / _groundEffect read the four rotor links, "
+                                      "BaseAviary.py:1648-1732) — not for a type table that holds a six-actuator type")
 
         self.ctx = Context(types, device)
         # Storage order.  Drones are independent on the path, so a heterogeneous fleet in ARBITRARY order (BASELINE

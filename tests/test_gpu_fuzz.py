@@ -24,7 +24,7 @@ from dronesim_amd import params  # noqa: E402
 from oracle import oracle as orc  # noqa: E402
 from tests.test_gpu_parity import _check_obs_rows  # noqa: E402
 from tests.test_gpu_two_call_loop import _downwash_part, _noise_by_id  # noqa: E402
-from tests.util import K_ULP, assert_control_parity, assert_step_parity, f32, noise_terms  # noqa: E402
+from tests.util import K_ULP, aero_boost, aero_terms, assert_control_parity, assert_step_parity, f32, noise_terms  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DT = float(np.float32(1.0 / 240.0))
@@ -52,28 +52,45 @@ OPS = st.lists(st.one_of(
 
 
 class Loop:
-    """One env + bound controller + the oracle-driven model of both."""
+    """One env + bound controller + the oracle-driven model of both.
 
-    def __init__(self, kind, seed):
+    kind: a key of FLEETS, or (with fleet=) any label.  fleet = (models, type ids, sub-steps, downwash, chained) as in FLEETS;
+    type ids "per_drone": the env is handed one model name per drone (models x n / len(models), the reference's own form) and
+    makes the table itself.  physics: the env's mode (default: PYB, or PYB_DW for a downwash fleet); with the add-on modes
+    (PYB_GND, PYB_DRAG, PYB_GND_DRAG_DW: tests/test_gpu_aero_env.py) the model hands the oracle the option bits, and the bar
+    gets the ground-effect boost and the drag's magnitude as tests/test_gpu_aero_edges.py builds them.  xyz / vels: the
+    initial positions and velocities; noise_seed 0: no rotor noise."""
+
+    def __init__(self, kind, seed, physics=None, fleet=None, n=300, xyz=None, vels=None, noise_seed=5):
         from dronesim_amd.control import INDIControl
         from dronesim_amd.envs import CtrlAviary, Physics
         from dronesim_amd.fleet import Targets
-        models, tids, self.sub, self.dw, chained = FLEETS[kind]
+        models, tids, self.sub, self.dw, chained = FLEETS[kind] if fleet is None else fleet
+        if physics is None:
+            physics = Physics.PYB_DW if self.dw else Physics.PYB
+        self.physics = physics
+        self.dw = physics in (Physics.PYB_DW, Physics.PYB_GND_DRAG_DW)
+        self.opts = {Physics.PYB_DRAG: 1, Physics.PYB_GND: 2, Physics.PYB_GND_DRAG_DW: 3}.get(physics, 0)    # DSIM_OPT_DRAG | _GROUND
         self.kind = kind
         self.rng = np.random.default_rng(seed)
-        self.n = n = 300
+        self.n = n
         self.types = [params.builtin_type(m) for m in models]
         self.tid = None
-        if tids == "interleaved":
-            self.tid = (np.arange(n) % 2).astype(np.uint8)
+        if tids in ("interleaved", "per_drone"):
+            self.tid = (np.arange(n) % len(models)).astype(np.uint8)
         elif tids == "random":
             self.tid = self.rng.integers(0, 2, n).astype(np.uint8)
-        self.xyz = np.stack([self.rng.uniform(0, 14, n), self.rng.uniform(0, 14, n), self.rng.uniform(2, 9, n)], 1)
-        self.noise_seed = 5
-        self.env = CtrlAviary(models, n, initial_xyzs=self.xyz, aggregate_phy_steps=self.sub, noise_seed=self.noise_seed,
-                              dict_io=False, type_ids=self.tid, chained=chained, neighbourhood_radius=1.5,
-                              physics=Physics.PYB_DW if self.dw else Physics.PYB)
+        self.xyz = (np.stack([self.rng.uniform(0, 14, n), self.rng.uniform(0, 14, n), self.rng.uniform(2, 9, n)], 1) if xyz is None
+                    else np.asarray(xyz, dtype=np.float64))
+        self.vels = vels
+        self.noise_seed = noise_seed
+        per_drone = tids == "per_drone"
+        self.env = CtrlAviary(list(models) * (n // len(models)) if per_drone else models, n, initial_xyzs=self.xyz,
+                              initial_vels=vels, aggregate_phy_steps=self.sub, noise_seed=self.noise_seed,
+                              dict_io=False, type_ids=None if per_drone else self.tid, chained=chained, neighbourhood_radius=1.5,
+                              physics=physics)
         self.na = self.env.n_act
+        self.prefix = "aero env" if self.opts else "fuzz"                    # (the label of this loop's entries in WORST)
         self.ctrl = INDIControl(models[-1], env=self.env)
         self.env.reset()                                  # (the controller's own reset wrote controller memory: start over)
         self.O = orc.Oracle(self.types)
@@ -93,23 +110,40 @@ class Loop:
         return self.env.state.rigid_aos(), self.env.state.mem_aos()
 
     def noise(self, step_index):
+        if self.noise_seed == 0:
+            return None
         return _noise_by_id(self.O, self.types, self.tid, np.arange(self.n), self.noise_seed, step_index, self.sub)
 
     def model_physics(self, r, m, a6, track_last):
         last = self.last if track_last else None
         nz = self.noise(self.env_steps)
         if self.dw:
-            assert self.O.physics_downwash(r, m, self.sub, DT, action=a6, noise=nz, type_id=self.tid, last_action=last) == 0
+            assert self.O.physics_downwash(r, m, self.sub, DT, action=a6, noise=nz, options=self.opts, type_id=self.tid,
+                                           last_action=last) == 0
         else:
-            self.O.physics(r, m, self.sub, DT, action=a6, noise=nz, type_id=self.tid, last_action=last)
+            self.O.physics(r, m, self.sub, DT, action=a6, noise=nz, options=self.opts, type_id=self.tid, last_action=last)
         self.env_steps += 1
 
-    def check_step(self, label, r0, m0, r, m, control, applied, k=None):
+    def check_step(self, label, r0, m0, r, m, control, applied, k=None, last=None):
+        """last [n, n_act]: the previous action where the drag of the step's first sub-step used it (Env.step)."""
         gr, gm = self.dev_state()
         part = _downwash_part(self.O, self.types, self.tid, r0, r, self.sub) if self.dw else None
-        assert_step_parity(f"fuzz {self.kind} {label}", self.types, self.tid, r0, m0, self.tgt, gr, gm if control else None, r,
+        extra = noise_terms(self.types, self.tid, self.n, DT, self.sub) if self.noise_seed else None
+        if self.opts:
+            # (tests/test_gpu_aero_edges.py: the boost at the height clip on the wrench's roundings, the drag among the magnitudes)
+            k = (K_ULP * self.sub if k is None else k) * aero_boost(self.types, self.opts)
+            rpm_cmd = applied if last is None else np.maximum(applied, last)
+            at = aero_terms(self.types, self.tid, r0, rpm_cmd, DT, self.sub, self.opts)
+            extra = at if extra is None else (extra[0] + at[0], extra[1] + at[1])
+            if self.opts & 2:
+                # the ground-effect gate (|roll|, |pitch| < pi/2) is open beyond doubt, in fp32 as in fp64, while the body z axis
+                # stays within 1.3 rad of the vertical: cos(roll) cos(pitch) = cos(tilt) > 0.26 (no drone is excluded: a fleet
+                # that tumbles further is a badly built one and fails here)
+                for q in (r0[:, 3:7], r[:, 3:7]):
+                    assert (1.0 - 2.0 * (q[:, 0] ** 2 + q[:, 1] ** 2) > np.cos(1.3)).all(), (self.kind, label, "a drone tumbled to the gate")
+        assert_step_parity(f"{self.prefix} {self.kind} {label}", self.types, self.tid, r0, m0, self.tgt, gr, gm if control else None, r,
                            m if control else None, DT, self.dtc, self.sub, control=control, action=applied, k=k, part_rigid=part,
-                           extra_terms=noise_terms(self.types, self.tid, self.n, DT, self.sub))
+                           extra_terms=extra)
 
     def action6(self, a):
         a6 = np.zeros((self.n, 6)); a6[:, :self.na] = a
@@ -153,25 +187,31 @@ class Loop:
         assert np.abs(m - self.O.reset_mem(self.n, self.tid)).max() < 1e-7          # (0.3 as an fp32)
         self.graphs.clear()                               # (a graph captured before holds a noise counter of its own)
 
-    def op_step(self, how):
+    def op_step(self, how, tensor=None):
+        """tensor: a device tensor of the action's shape that receives the drawn action IN PLACE and is handed to step() (the
+        same object call after call: the env's prepared launch)."""
         n, na = self.n, self.na
         if how == "last_cmd" and self.cmd is not None:
             act = self.cmd                                # the very tensor computeControl returned (zero-copy paths)
             a = act.double().cpu().numpy()
         else:
-            lo, hi = (-0.3, 1.3) if how == "out_of_range" else (0.3, 0.6)
+            lo, hi = {"out_of_range": (-0.3, 1.3), "tight": (0.43, 0.47)}.get(how, (0.3, 0.6))
             a = f32(self.rng.uniform(lo, hi, (n, na)))
             if self.tid is not None:
                 for k, t in enumerate(self.types):
                     a[self.tid == k, t.n_act:] = 0.0
             act = torch.from_numpy(a.astype(np.float32)).to(self.env.ctx.device)
+            if tensor is not None:
+                tensor.copy_(act)
+                act = tensor
         r0, m0 = self.dev_state()
         obs, _, _, _ = self.env.step(act)
         r, a6 = r0.copy(), self.action6(a)
+        last0 = self.last[:, :na].copy()
         self.model_physics(r, m0, a6, True)
         self.use_last = True
-        self.check_step("step", r0, m0, r, None, False, self.applied(a6, m0))
-        _check_obs_rows(f"fuzz {self.kind} step rows", self.O, obs.double().cpu().numpy(), self.dev_state()[0], self.last, self.tid,
+        self.check_step("step", r0, m0, r, None, False, self.applied(a6, m0), last=last0)
+        _check_obs_rows(f"{self.prefix} {self.kind} step rows", self.O, obs.double().cpu().numpy(), self.dev_state()[0], self.last, self.tid,
                         self.types)
 
     def op_step_fused(self, with_action, n_steps):
@@ -198,6 +238,21 @@ class Loop:
             self.check_step("step_fused", r0, m0, r, m, True, self.applied(a6, m0))
         else:
             self.check_step("step_fused x3", rp, mp, r, m, True, mp[:, 7:7 + self.na], k=K_ULP * self.sub * 4 * n_steps)
+
+    def op_step_fused_run(self, count):
+        """`count` step_fused() calls with nothing in between — no host access, so from the second call on the env replays its
+        prepared launch and hands it the memory hint — judged like a captured graph of that many steps."""
+        r0, m0 = self.dev_state()
+        for _ in range(count):
+            self.env.step_fused(self.tg)
+        r, m = r0.copy(), m0.copy()
+        rp, mp = r0, m0
+        for _ in range(count):
+            rp, mp = r.copy(), m.copy()
+            self.model_physics(r, m, None, False)
+            assert self.O.control(r, m, self.tgt, self.dtc, type_id=self.tid)[0] == 0
+        self.use_last = False
+        self.check_step(f"step_fused run x{count}", rp, mp, r, m, True, mp[:, 7:7 + self.na], k=K_ULP * self.sub * 4 * count)
 
     def op_observe(self):
         rows = self.env.observe().double().cpu().numpy()

@@ -265,10 +265,12 @@ def plane_terms(types, type_id, rigid, dt_ctrl, dt_phys=1.0 / 240.0):
 
 
 def assert_step_parity(label, types, type_id, prev_rigid, prev_mem, tgt, got_rigid, got_mem, ref_rigid, ref_mem,
-                       dt_phys, dt_ctrl, substeps, control=True, k=None, action=None, extra_terms=None, part_rigid=None, noise=False):
+                       dt_phys, dt_ctrl, substeps, control=True, k=None, action=None, extra_terms=None, part_rigid=None, noise=False,
+                       part_mem=None):
     """One step of the HIP path against one step of the oracle from the same (fp32-representable) state,
     judged on the increments (module docstring).  got_mem / ref_mem may be None (physics only); action [n, n_act] =
-    the explicit action of this step where it is not the stored cmd."""
+    the explicit action of this step where it is not the stored cmd.  part_mem [n,13]: like part_rigid, for the controller
+    memory itself (control_rounding_part)."""
     k = (K_ULP_NOISE if noise else K_ULP) * max(1, substeps) if k is None else k
     tr, tm = step_terms(types, type_id, prev_rigid, prev_mem, tgt, dt_phys, dt_ctrl, max(1, substeps), control, action)
     if extra_terms is not None:
@@ -283,7 +285,7 @@ def assert_step_parity(label, types, type_id, prev_rigid, prev_mem, tgt, got_rig
         kk = k * tilt_gain(types, type_id, ref_rigid)
         # (the controller memory copies the new velocity into last_vel: what is only known to REL_TOL in the velocity — the
         # part of its increment that came from the neighbour-downwash force — is only known to REL_TOL there too)
-        part_mem = None
+        part_mem_given, part_mem = part_mem, None
         if part_rigid is not None:
             # ... and the law differentiates it: (v - last_vel) / dt_ctrl is the measured acceleration (INDIControl.py:285-291,
             # INDIControl_6DOF.py:399-413), which goes into the thrust state and, through the allocation, into the commands
@@ -297,6 +299,8 @@ def assert_step_parity(label, types, type_id, prev_rigid, prev_mem, tgt, got_rig
                 A_ = np.abs(np.asarray(t_.alloc, dtype=np.float64))
                 col = A_[: t_.n_act, 3] if t_.kind != 1 else A_[:6, 3:6].sum(1)
                 part_mem[np.ix_(s_, 7 + np.arange(t_.n_act))] = pa[s_, None] * col[None, :]
+        if part_mem_given is not None:
+            part_mem = part_mem_given if part_mem is None else part_mem + part_mem_given
         rm = increment_ratio(got_mem, ref_mem, prev_mem, tm, kk, part_mem)
         if rm.max() > worst:
             worst = float(rm.max())
@@ -717,3 +721,310 @@ def bounds_expected(rigid):
     with np.errstate(all="ignore"):
         return np.array([np.nanmin(r[:, 0]), np.nanmin(r[:, 1]), np.nanmax(r[:, 0]), np.nanmax(r[:, 1]), np.abs(r[:, 7:10]).max()],
                         dtype=np.float32)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# drag (P6) and ground effect (P7) at their edges: seeded inputs, built once here for tests/test_gpu_aero_edges.py (the
+# device) and tests/test_aero_inputs_cpu.py (the properties the device tests rely on, and their power)
+# ---------------------------------------------------------------------------------------------------------------------
+AERO_DELTA = 1e-3                                   # rad: how far the gate cases sit from a threshold of the ground-effect gate
+AERO_GATE_ULPS = 16.0                               # ... and the least distance, in fp32 ulps of the operands, the CPU file demands
+AERO_PITCH_GATE = math.asin(EULER_CLAMP)            # the pitch at which Bullet's Euler helper switches to its gimbal branch
+AERO_GATE_RATE = 5.0                                # rad/s: the gate cases turn away from their threshold at this rate
+AERO_CLASSES = ("gate", "height", "drag")
+OPT_DRAG, OPT_GROUND = 1, 2                         # DSIM_OPT_DRAG, DSIM_OPT_GROUND
+
+
+def _aero_pack(rng, rpy, pos, vel, om, cmd_lo=0.3, cmd_hi=0.9, equal_rotors=False):
+    """dict(rigid [m,13], mem [m,13], tgt [m,10], act [m,4], prev [m,4]), fp32-representable, from attitudes, positions,
+    velocities and rates: commands (stored, explicit and previous) in [cmd_lo, cmd_hi] — no rotor at idle —, targets within a
+    metre of the drone."""
+    m = len(rpy)
+    quat = np.stack([orc.quat_from_euler(r) for r in rpy])
+    rigid = f32(np.concatenate([pos, quat, vel, om], 1))
+    mem = np.zeros((m, 13))
+    mem[:, 0:3] = rigid[:, 7:10]
+    mem[:, 6] = rng.uniform(0.2, 0.8, m)
+    draw = (lambda: np.repeat(rng.uniform(cmd_lo, cmd_hi, (m, 1)), 4, 1)) if equal_rotors else (lambda: rng.uniform(cmd_lo, cmd_hi, (m, 4)))
+    mem[:, 7:11] = draw()
+    act, prev = f32(draw()), f32(draw())
+    tgt = np.concatenate([rigid[:, 0:3] + rng.uniform(-1, 1, (m, 3)), rng.uniform(-0.5, 0.5, (m, 6)), rng.uniform(-3, 3, (m, 1))], 1)
+    return dict(rigid=rigid, mem=f32(mem), tgt=f32(tgt), act=act, prev=prev)
+
+
+def aero_gate_cases(t, seed=7100):
+    """States 0.05-0.3 m above the ground on both sides of every threshold of the ground-effect gate (|roll| < pi/2 and
+    |pitch| < pi/2, BaseAviary.py:1648-1699), AERO_DELTA away from it:
+      roll  = +-(pi/2 -+ delta)               at pitch 0, +0.7, -0.7
+      pitch = +-(asin(0.99999) -+ delta)      at roll 0, +0.5, -0.5  (beyond it Bullet's helper reports |pitch| = pi/2: gate shut)
+      roll  = 0, +pi, -pi                     plain members
+    each at two yaws.  Cases come in PAIRS that differ in the side of the threshold only (`partner`: the index of the other one;
+    the plain members: roll 0 is the partner of +-pi, +pi that of 0) and `open` says on which side a case lies.  The gate is
+    evaluated again at every later sub-step, on an attitude the step itself has moved: the four rotors of a drone get ONE
+    command (no torque but the ground effect's own) and the body turns at AERO_GATE_RATE AWAY from its threshold — the Euler
+    angle in question moves 0.02 rad per sub-step, where one that lingers would sooner or later sit within fp32 rounding of
+    the threshold (sin(pitch) moves 4e-6 per milliradian there).  Checked, not assumed: aero_gate_margins along
+    aero_substep_starts in tests/test_aero_inputs_cpu.py and in front of every device launch."""
+    rng = np.random.default_rng(seed + sum(map(ord, t.name)))
+    rpy, is_open, partner, away = [], [], [], []
+    for yaw_k in range(2):
+        for s in (1.0, -1.0):
+            for pitch in (0.0, 0.7, -0.7):
+                yaw = rng.uniform(-math.pi, math.pi)
+                for d in (-AERO_DELTA, AERO_DELTA):
+                    rpy.append([s * (math.pi / 2 + d), pitch, yaw]); is_open.append(d < 0); away.append([s * np.sign(d), 0.0, 0.0])
+                partner += [len(rpy) - 1, len(rpy) - 2]
+            for roll in (0.0, 0.5, -0.5):
+                yaw = rng.uniform(-math.pi, math.pi)
+                for d in (-AERO_DELTA, AERO_DELTA):
+                    rpy.append([roll, s * (AERO_PITCH_GATE + d), yaw]); is_open.append(d < 0); away.append([0.0, s * np.sign(d), 0.0])
+                partner += [len(rpy) - 1, len(rpy) - 2]
+        yaw, k = rng.uniform(-math.pi, math.pi), len(rpy)
+        rpy += [[0.0, 0.1, yaw], [math.pi, 0.1, yaw], [-math.pi, 0.1, yaw]]; is_open += [True, False, False]
+        partner += [k + 1, k, k]
+        away += [[0.0] * 3] * 3
+    rpy, partner, away = np.array(rpy), np.array(partner), np.array(away)
+    m = len(rpy)
+    state = rng.uniform(size=(m, 6))
+    state = state[np.minimum(np.arange(m), partner)]                   # a pair shares everything but the side
+    pos = np.stack([-5 + 10 * state[:, 0], -5 + 10 * state[:, 1], 0.05 + 0.25 * state[:, 2]], 1)
+    vel = -1 + 2 * state[:, 3:6]
+    # the world-frame angular velocity that moves the Euler angles at `away` x AERO_GATE_RATE: w = 2 (dq / dt) q^-1, by a
+    # central difference of the half-angle product (Bullet integrates q <- dq(w dt) q: the increment acts from the left)
+    om, h = np.zeros((m, 3)), 1e-6
+    for i in range(m):
+        q, dq = orc.quat_from_euler(rpy[i]), (orc.quat_from_euler(rpy[i] + h * away[i]) - orc.quat_from_euler(rpy[i] - h * away[i])) / (2 * h)
+        qi = np.array([-q[0], -q[1], -q[2], q[3]])
+        om[i] = 2 * AERO_GATE_RATE * np.array([dq[3] * qi[0] + dq[0] * qi[3] + dq[1] * qi[2] - dq[2] * qi[1],
+                                               dq[3] * qi[1] + dq[1] * qi[3] + dq[2] * qi[0] - dq[0] * qi[2],
+                                               dq[3] * qi[2] + dq[2] * qi[3] + dq[0] * qi[1] - dq[1] * qi[0]])
+    c = _aero_pack(rng, rpy, pos, vel, om, equal_rotors=True)
+    for key in ("mem", "tgt", "act", "prev"):
+        c[key] = c[key][np.minimum(np.arange(m), partner)]
+    c.update(open=np.array(is_open), partner=partner, rpy=rpy)
+    return c
+
+
+def aero_gate_margins(quat):
+    """For quaternions [n,4] as the state block holds them (fp32-representable): (open32, open64, clear, strict).
+      open64  the oracle's gate: orc_euler_from_quat, then |roll| < pi/2 and |pitch| < pi/2 (oracle/dsim_oracle.c:orc_ground_effect)
+      open32  the kernel's gate restated in fp32 numpy: sarg = -2 (x z - w y), rb = w w - x x - y y + z z,
+              |sarg| < 0.99999f and rb > 0 (dsim_device.h:ground_effect_quad)
+      strict  | |sarg| - 0.99999 | and |rb| are both at least AERO_GATE_ULPS fp32 ulps of their operands away from zero.  The
+              operands are products of two components and their sums, bounded by |q|^2: whichever way the compiler contracts
+              or orders the four products (two roundings or fused multiply-adds), the result moves by a few of those ulps.
+      clear   the predicate's VALUE cannot flip: strict, or one of the two comparisons is false by that margin (a shut roll
+              gate hides the pitch threshold and the reverse) — what a state reached DURING a run is asked for."""
+    q64 = np.asarray(quat, dtype=np.float64)
+    rpy = np.stack([orc.euler_from_quat(q) for q in q64])
+    open64 = (np.abs(rpy[:, 0]) < math.pi / 2) & (np.abs(rpy[:, 1]) < math.pi / 2)
+    x, y, z, w = (q64[:, k].astype(np.float32) for k in range(4))
+    sarg = np.float32(-2.0) * (x * z - w * y)
+    rb = w * w - x * x - y * y + z * z
+    open32 = (np.abs(sarg) < np.float32(EULER_CLAMP)) & (rb > np.float32(0.0))
+    u = ulp32(np.maximum((q64 ** 2).sum(1), 1.0))
+    far_s = np.abs(np.abs(sarg.astype(np.float64)) - EULER_CLAMP) >= AERO_GATE_ULPS * u
+    far_r = np.abs(rb.astype(np.float64)) >= AERO_GATE_ULPS * u
+    shut_s = far_s & (np.abs(sarg) >= np.float32(EULER_CLAMP))
+    shut_r = far_r & (rb <= 0)
+    return open32, open64, (far_s & far_r) | shut_s | shut_r, far_s & far_r
+
+
+def aero_height_cases(t, seed=7200):
+    """The per-rotor height clip h_i = max(z + (R r_i)_z, gnd_eff_h_clip) at its edges.  `group`:
+      0  z = the clip exactly (its fp32 image)      1  one fp32 ulp above      2  one fp32 ulp below
+      3  z = -0.2 (every rotor under the clip)      4  z = 100 (the term is 1e-7 of the thrust: the far end of 1 / h^2)
+      5  tilted 0.5-1.2 rad about a random horizontal axis, z placed so that the clip lies between the lowest and the
+         highest rotor: some rotors clipped, some not
+    Groups 0-4 fly level (any yaw): R's third row is (0, 0, 1) exactly and h_i = z + r_i,z."""
+    rng = np.random.default_rng(seed + sum(map(ord, t.name)))
+    clip32 = np.float32(t.gnd_eff_h_clip)
+    zs = [clip32, np.nextafter(clip32, np.float32(np.inf)), np.nextafter(clip32, np.float32(-np.inf)), np.float32(-0.2), np.float32(100.0)]
+    counts = [4, 4, 4, 6, 3]
+    group = np.concatenate([np.full(c, g) for g, c in enumerate(counts)] + [np.full(36, 5)])
+    m = len(group)
+    rpy = np.zeros((m, 3))
+    rpy[:, 2] = rng.uniform(-math.pi, math.pi, m)
+    tilted = np.flatnonzero(group == 5)
+    ang, axis = rng.uniform(0.5, 1.2, len(tilted)), rng.uniform(-math.pi, math.pi, len(tilted))
+    rpy[tilted, 0], rpy[tilted, 1] = ang * np.cos(axis) * 0.95, ang * np.sin(axis) * 0.95
+    z = np.zeros(m)
+    for g, zg in enumerate(zs):
+        z[group == g] = float(zg)
+    rel = aero_rotor_rel_heights(t, np.stack([f32(orc.quat_from_euler(r)) for r in rpy]))
+    lo, hi = rel[tilted].min(1), rel[tilted].max(1)
+    z[tilted] = t.gnd_eff_h_clip - (0.5 * (lo + hi) + rng.uniform(-0.25, 0.25, len(tilted)) * (hi - lo))
+    pos = np.stack([rng.uniform(-5, 5, m), rng.uniform(-5, 5, m), z], 1)
+    c = _aero_pack(rng, rpy, pos, rng.uniform(-1, 1, (m, 3)), rng.uniform(-0.3, 0.3, (m, 3)))
+    # the drones 100 m up also carry the out-of-range actions of the set (the echo is clip(action, 0, 1), CtrlAviary.py:258-263)
+    c["act"][group == 4, 0], c["act"][group == 4, 2] = np.float32(-0.25), np.float32(1.5)
+    c.update(group=group)
+    return c
+
+
+def aero_rotor_rel_heights(t, quat):
+    """[n, 4] the height of every rotor above the drone's own z, (R r_i)_z, in fp64 from the given quaternions."""
+    out = np.zeros((len(quat), 4))
+    r = np.asarray(t.rotor_pos, dtype=np.float64)[:4]
+    for i, q in enumerate(np.asarray(quat, dtype=np.float64)):
+        out[i] = r @ orc.matrix_from_quat(q)[2]
+    return out
+
+
+AERO_DRAG_SPEEDS = (0.0, 0.5, 5.0, 30.0)
+
+
+def aero_drag_cases(t, seed=7300):
+    """Drag = R (-c sum(2 pi rpm / 60) v) with the PREVIOUS action's rotor speeds on sub-step 0 (BaseAviary.py:531-532, 1705-1732).
+    `speed` [m]: |v| = 0 exactly (3 drones), 0.5 (4), 5 (24), 30 m/s (40), in random directions, the body tilted up to 0.8 rad
+    at any yaw, 1-5 m up.  `far` [m]: the previous action is a world away from this step's — every rotor at 0.28-0.32 now and
+    at 0.9-0.95 before, or, for every third drone at 30 m/s, the other way round (`act_high`); every fifth drone has
+    prev == act bit for bit (`far` False): the control group of the previous-action rule.
+    (Why not more drones with a LOW previous action, and none of them at 5 m/s: the drag of the 0.75 kg type at 5 m/s with its
+    rotors at 0.3 is 4e-5 m/s per sub-step, a few times the 1e-4-relative bar on the thrust's own 0.14 m/s — such a drone
+    tells little, whatever the kernel does; tests/test_aero_inputs_cpu.py measures what each drone tells.)"""
+    rng = np.random.default_rng(seed + sum(map(ord, t.name)))
+    speed = np.concatenate([np.full(c, s) for s, c in zip(AERO_DRAG_SPEEDS, (3, 4, 24, 40))])
+    m = len(speed)
+    d = rng.normal(size=(m, 3)); d /= np.linalg.norm(d, axis=1, keepdims=True)
+    rpy = np.stack([rng.uniform(-0.8, 0.8, m), rng.uniform(-0.8, 0.8, m), rng.uniform(-math.pi, math.pi, m)], 1)
+    pos = np.stack([rng.uniform(-5, 5, m), rng.uniform(-5, 5, m), rng.uniform(1, 5, m)], 1)
+    c = _aero_pack(rng, rpy, pos, d * speed[:, None], rng.uniform(-0.3, 0.3, (m, 3)))
+    lo, hi = f32(rng.uniform(0.28, 0.32, (m, 4))), f32(rng.uniform(0.9, 0.95, (m, 4)))
+    act_high = (speed == 30.0) & (np.arange(m) % 3 == 0)
+    c["act"], c["prev"] = np.where(act_high[:, None], hi, lo), np.where(act_high[:, None], lo, hi)
+    c["mem"][:, 7:11] = c["act"]                                  # (the stored command: the action of a call without one)
+    far = np.arange(m) % 5 != 4
+    c["prev"][~far] = c["act"][~far]
+    c.update(speed=speed, far=far, act_high=act_high)
+    return c
+
+
+_AERO_SETS = {}
+
+
+def aero_sets(t):
+    """{class: cases} of one type, built once per session and never modified (callers copy what they change)."""
+    if t.name not in _AERO_SETS:
+        _AERO_SETS[t.name] = dict(gate=aero_gate_cases(t), height=aero_height_cases(t), drag=aero_drag_cases(t))
+    return _AERO_SETS[t.name]
+
+
+def aero_fleet(types, n):
+    """The fleet the device tests fly: dict(rigid, mem, tgt, act, prev [n, .], tid [n] uint8 or None, cls [n] index into
+    AERO_CLASSES, case [n] index into that class's set).  One type: the concatenation of its three sets, cycled to n.  Two
+    types: interleaved (even drones type 0, odd drones type 1, the caller's order: every tile holds both), and the j-th drone
+    of a type takes case (3 j + type) mod m of its type's concatenation — a third of the list, spread over all three sets, so
+    that the hundred drones a type has in the smallest fleet still reach every class."""
+    cat = []
+    for t in types:
+        s = aero_sets(t)
+        c = {k: np.concatenate([s[cl][k] for cl in AERO_CLASSES]) for k in ("rigid", "mem", "tgt", "act", "prev")}
+        c["cls"] = np.concatenate([np.full(len(s[cl]["rigid"]), i) for i, cl in enumerate(AERO_CLASSES)])
+        c["case"] = np.concatenate([np.arange(len(s[cl]["rigid"])) for cl in AERO_CLASSES])
+        cat.append(c)
+    tid = None if len(types) == 1 else (np.arange(n) % len(types)).astype(np.uint8)
+    out = {k: np.zeros((n,) + cat[0][k].shape[1:], dtype=cat[0][k].dtype) for k in cat[0]}
+    for k_, c in enumerate(cat):
+        sel = np.arange(n) if tid is None else np.flatnonzero(tid == k_)
+        j = np.arange(len(sel))
+        idx = (j if tid is None else 3 * j + k_) % len(c["cls"])
+        for key in out:
+            out[key][sel] = c[key][idx]
+    out["tid"] = tid
+    return out
+
+
+def aero_boost(types, options):
+    """The factor the ground effect puts on a rotor's thrust at the height clip, 1 + coeff (r / 4 h_clip)^2 (4 / 15 above one for
+    the built-in quads): charged to the roundings of the wrench, K_ULP x sub-steps x boost, as
+    tests/test_gpu_parity.py::test_drag_and_ground_effect_vs_oracle does."""
+    if not options & OPT_GROUND:
+        return 1.0
+    return max(1.0 + t.gnd_eff_coeff * (t.prop_radius / (4 * t.gnd_eff_h_clip)) ** 2 for t in types)
+
+
+def aero_terms(types, type_id, rigid, rpm_cmd, dt_phys, substeps, options, ext_force=None):
+    """([n,13], [n,13]) what the add-on forces put among the operands of the velocity update, for step_terms' magnitudes
+    (extra_terms of assert_step_parity; nothing here comes from a device result):
+      drag        |F| <= max(c) sum_i(2 pi rpm_i / 60) |v|, from the type's constants, the state in front of the step and
+                  rpm_cmd [n,4], the LARGER of the previous and the current command per rotor; over the mass, times dt
+      ext_force   |F| / m dt of the given body-frame force [n,3]
+    Both are single products like the thrusts step_terms sums: they join M, the magnitude whose fp32 ulp the bar counts."""
+    n = rigid.shape[0]
+    tr, tm = np.zeros((n, 13)), np.zeros((n, 13))
+    tid = np.zeros(n, dtype=np.int64) if type_id is None else np.asarray(type_id).astype(np.int64)
+    vn = np.linalg.norm(rigid[:, 7:10], axis=1)
+    for k, t in enumerate(types):
+        s = tid == k
+        acc = np.zeros(int(s.sum()))
+        if options & OPT_DRAG:
+            rpm = np.asarray(t.pwm2rpm_scale)[:4] * np.asarray(rpm_cmd)[s, :4] + np.asarray(t.pwm2rpm_const)[:4]
+            acc = acc + max(t.drag_coeff) * (2 * math.pi * rpm / 60).sum(1) * vn[s] / t.mass
+        if ext_force is not None:
+            acc = acc + np.linalg.norm(ext_force[s], axis=1) / t.mass
+        tr[s, 7:10] = (acc * dt_phys)[:, None]
+        tr[s, 0:3] = (acc * dt_phys * substeps * dt_phys)[:, None]
+        tm[s, 0:3] = tr[s, 7:10]
+    return tr, tm
+
+
+def aero_substep_starts(O, type_id, rigid, mem, substeps, dt, action=None, options=0, last_action=None, ext_force=None):
+    """The oracle's Env.step taken one sub-step at a time: (states [substeps, n, 13] at the START of every sub-step, the
+    state after the last).  Bit-equal to O.physics(rigid, ..., substeps): that call runs this very loop (orc_physics_batch:
+    sub-step 0 with the previous action, the later ones with the current one)."""
+    r = rigid.copy()
+    starts = []
+    last = None if last_action is None else last_action.copy()
+    for s_ in range(substeps):
+        starts.append(r.copy())
+        O.physics(r, mem, 1, dt, action=action, options=options, type_id=type_id, last_action=last if s_ == 0 else None,
+                  ext_force=ext_force)
+    return np.array(starts), r
+
+
+def aero_fused_starts(O, type_id, rigid, mem, tgt, substeps, dt, dt_ctrl, options, n_steps, action=None):
+    """The oracle's fused loop body (Env.step with the current command's rotor speeds in the drag, then computeControl), n_steps
+    times, one sub-step at a time: (states at the start of every sub-step [n_steps x substeps, n, 13], rigid and mem in front of
+    the LAST Env.step, rigid and mem after it).  action [n,6]: the explicit action of the first Env.step."""
+    r, m = rigid.copy(), mem.copy()
+    starts, rp, mp = [], r, m
+    for k in range(n_steps):
+        rp, mp = r.copy(), m.copy()
+        s_, r = aero_substep_starts(O, type_id, r, m, substeps, dt, action=action if k == 0 else None, options=options)
+        starts.append(s_)
+        assert O.control(r, m, tgt, dt_ctrl, type_id=type_id)[0] == 0
+    return np.concatenate(starts), rp, mp, r, m
+
+
+def aero_power(types, type_id, before, mem, tgt, ref, alt, dt, substeps, options, applied, rpm_cmd, ext_force=None):
+    """[n] how many times the bar of the device tests (assert_step_parity with K_ULP x sub-steps x aero_boost and aero_terms)
+    a result `alt` lies from the oracle's `ref`, in its worst rigid field: the POWER of that comparison against the fault
+    that turns ref into alt."""
+    tr, _ = step_terms(types, type_id, before, mem, tgt, dt, dt, substeps, False, applied)
+    tr = tr + aero_terms(types, type_id, before, rpm_cmd, dt, substeps, options, ext_force)[0]
+    return increment_ratio(alt, ref, before, tr, K_ULP * substeps * aero_boost(types, options)).max(1)
+
+
+def control_rounding_part(O, type_id, rigid, mem, tgt, dt_ctrl):
+    """[n,13] (part_mem of assert_step_parity): how far the oracle's OWN command and thrust state move when one component of the
+    quaternion it is given moves by two fp32 ulps, up or down (the largest of the eight moves), over REL_TOL — the construction
+    of the neighbour term's sensitivity in tests/test_gpu_two_call_loop.py:_downwash_part.  The quad law reads roll, pitch and yaw
+    off the quaternion (INDIControl.py:301: pitch = asin(sarg), roll and yaw = atan2 of terms that vanish with cos(pitch)) and
+    builds its attitude target on them: beside the gimbal point a rounding of sarg — the device forms it from four fp32 products —
+    is a rounding of the ANGLE 1 / sqrt(1 - sarg^2) times as large (60-130 times for a drone that hovers at sarg = -0.9999, as the
+    gate cases of aero_gate_cases do), where the step's bar counts ulps of the terms themselves and tilt_gain knows of
+    cos(roll) only.  In gentle flight the eight moves change the command by an ulp or two and the term adds nothing.
+    rigid: the state the law evaluates (behind the physics); mem: the controller memory in front of it."""
+    base = mem.copy()
+    assert O.control(rigid, base, tgt, dt_ctrl, type_id=type_id)[0] == 0
+    sens = np.zeros_like(base)
+    step = 2.0 * ulp32(np.linalg.norm(rigid[:, 3:7], axis=1))
+    for k in range(4):
+        for sign in (1.0, -1.0):
+            rr, mm = rigid.copy(), mem.copy()
+            rr[:, 3 + k] += sign * step
+            O.control(rr, mm, tgt, dt_ctrl, type_id=type_id)
+            sens = np.maximum(sens, np.abs(mm - base))
+    sens[:, 0:6] = 0.0                   # (last_vel is a copy; last_rates = R^T w is charged to its own terms)
+    return sens / REL_TOL
