@@ -29,6 +29,7 @@ EXPORTS = (
     "dsim_obstacle_sweep",
     "dsim_scenes_create", "dsim_scenes_destroy", "dsim_obstacle_clearance_scenes", "dsim_depth_image_scenes",
     "dsim_clearance_sweep", "dsim_clearance_sweep_workspace",
+    "dsim_range_scan",
 )
 
 ABI_VERSION = 11
@@ -96,6 +97,27 @@ class CameraDrones(ctypes.Structure):
         ("label", ctypes.c_void_p),
         ("range", ctypes.c_float),
         ("outside_out", ctypes.c_void_p),
+    ]
+
+
+SCAN_GROUND, SCAN_CLAMP = 1, 2   # dsim_scan_args.flags
+
+
+class ScanArgs(ctypes.Structure):
+    """dsim_scan_args (dsim_range_scan)."""
+    _fields_ = [
+        ("beams", ctypes.c_void_p),
+        ("n_beams", ctypes.c_int32),
+        ("t_min", ctypes.c_float),
+        ("t_max", ctypes.c_float),
+        ("flags", ctypes.c_uint32),
+        ("offset", ctypes.c_void_p),
+        ("type_id", ctypes.c_void_p),
+        ("scenes", ctypes.c_void_p),
+        ("scene_id", ctypes.c_void_p),
+        ("drones", ctypes.c_void_p),
+        ("range_out", ctypes.c_void_p),
+        ("hit_out", ctypes.c_void_p),
     ]
 
 
@@ -354,6 +376,7 @@ def load(path: str = None) -> ctypes.CDLL:
     lib.dsim_scenes_destroy.argtypes = [vp, vp]
     lib.dsim_obstacle_clearance_scenes.argtypes = [vp, vp, i64, View, vp, vp, vp, vp, ctypes.c_float, vp, vp, vp]
     lib.dsim_depth_image_scenes.argtypes = [vp, vp, View, vp, vp, ctypes.POINTER(CameraParams), i64, vp, vp, vp, vp, vp]
+    lib.dsim_range_scan.argtypes = [vp, vp, i64, View, vp, ctypes.POINTER(ScanArgs)]
     lib.dsim_trajgen_workspace.restype = ctypes.c_int64
     lib.dsim_trajgen_workspace.argtypes = [i64, i32]
     lib.dsim_trajgen.argtypes = [vp, vp, ctypes.POINTER(TrajBank), ctypes.POINTER(TrajGenArgs)]

@@ -266,3 +266,6 @@ int dsim_obstacle_clearance(dsim_ctx* ctx, void* stream, int64_t n, dsim_view st
 
 // obstacle scenes: per-drone placements of one set for the watch and the camera (they share the cell walk and the camera's kernel)
 #include "dsim_scenes.hip"
+
+// the range scanner: per-drone beam fans against the set, the scenes, the plane and the drones (it shares the camera's walk and records)
+#include "dsim_scan.hip"

@@ -144,6 +144,14 @@ class CtrlAviary(PlacedFleetArrays, FleetObservation, StepWatches):
         vision_ground: bool = True,
         vision_see_drones: bool = False,
         vision_drone_range: Optional[float] = None,
+        range_scan=None,
+        range_scene=None,
+        range_min: float = 0.0,
+        range_max: float = 10.0,
+        range_ground: bool = True,
+        range_clamp: bool = False,
+        range_see_drones: bool = False,
+        range_drone_range: Optional[float] = None,
     ):
         if gui or record or obstacles:
             raise NotImplementedError("gui/record/obstacles are rendering features outside the hot path")
@@ -154,7 +162,9 @@ class CtrlAviary(PlacedFleetArrays, FleetObservation, StepWatches):
                             vision_drones=vision_drones, vision_res=vision_res, vision_ground=vision_ground,
                             vision_see_drones=vision_see_drones, vision_drone_range=vision_drone_range,
                             obstacle_scene_id=obstacle_scene_id, drone_sweep=drone_sweep, drone_sweep_sag=drone_sweep_sag,
-                            drone_sweep_travel=drone_sweep_travel)
+                            drone_sweep_travel=drone_sweep_travel, range_scan=range_scan, range_scene=range_scene,
+                            range_min=range_min, range_max=range_max, range_ground=range_ground, range_clamp=range_clamp,
+                            range_see_drones=range_see_drones, range_drone_range=range_drone_range)
         # the add-on terms of the PYB_* modes (dead code in the reference fork, intended formulas); Physics.DYN: the
         # reference's own explicit model, BaseAviary._dynamics (BaseAviary.py:1767-1828; DSIM_OPT_DYN)
         self._phys_options = {Physics.PYB: 0, Physics.PYB_DW: 0, Physics.PYB_GND: nat.OPT_GROUND,

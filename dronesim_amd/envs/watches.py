@@ -1,5 +1,5 @@
 """The services that follow every step of the fleet env on its stream: the drone-drone contact watch (``drone_watch``), the
-static-obstacle watch (``obstacle_watch``) and the depth camera (``vision_attributes``).  Their keywords, set-up, state and public
+static-obstacle watch (``obstacle_watch``), the depth camera (``vision_attributes``) and the range scanner (``range_scan``).  Their keywords, set-up, state and public
 calls, the one epilogue of a launch (``_stepped``) and the four hooks a captured sequence goes through (``_capture_prepare``,
 ``_captured_step``, ``_capture_keepalive``, ``_replayed``).  A mix-in of ``CtrlAviary``: it uses the env's attributes as they are."""
 from __future__ import annotations
@@ -21,12 +21,16 @@ class StepWatches:
     _obst_sweep = False           # ... queried along the chord between two samples (obstacle_sweep=True)
     _obst_placed = False          # ... an ObstacleScenes: per-drone placements of one prototype (obstacle_scene_id)
     _vision = None                # the depth camera of vision_attributes=True (set by _watch_setup)
+    _scan = None                  # the range scanner of range_scan= (set by _watch_setup)
+    _scan_args = None
 
     # ------------------------------------------------------------------ construction
     def _watch_options(self, *, num_drones, freq, aggregate_phy_steps, dist, drone_watch, drone_watch_margin, obstacle_watch,
                        obstacle_margin, obstacle_sweep, obstacle_sweep_sag, obstacle_sweep_travel, vision_attributes, vision_scene,
                        vision_drones, vision_res, vision_ground, vision_see_drones, vision_drone_range, obstacle_scene_id=None,
-                       drone_sweep=False, drone_sweep_sag=0.0, drone_sweep_travel=None) -> None:
+                       drone_sweep=False, drone_sweep_sag=0.0, drone_sweep_travel=None, range_scan=None, range_scene=None,
+                       range_min=0.0, range_max=10.0, range_ground=True, range_clamp=False, range_see_drones=False,
+                       range_drone_range=None) -> None:
         """The services' keywords of ``CtrlAviary.__init__``: checked and stashed (the set-up follows in _watch_setup, when the
         context and the storage order exist)."""
         # The reference's Bullet world lets the vehicles' collision shapes act on each other; here every drone is integrated
@@ -71,11 +75,11 @@ class StepWatches:
         # [0, K) meaning no obstacles.  `nearest` and seg then hold the instance-major body index g n_bodies + body.  Two deliberate
         # cuts: the swept watch and the other drones in the images are not implemented on scenes (the unplaced forms are).
         from ..obstacles import ObstacleScenes
-        placed = [x for x in (obstacle_watch, vision_scene) if isinstance(x, ObstacleScenes)]
+        placed = [x for x in (obstacle_watch, vision_scene, range_scene) if isinstance(x, ObstacleScenes)]
         if placed and obstacle_scene_id is None:
             raise ValueError("obstacle_scene_id [N] is required with an ObstacleScenes")
         if not placed and obstacle_scene_id is not None:
-            raise ValueError("obstacle_scene_id without an ObstacleScenes (obstacle_watch= or vision_scene=)")
+            raise ValueError("obstacle_scene_id without an ObstacleScenes (obstacle_watch=, vision_scene= or range_scene=)")
         if placed:
             ids = np.asarray(obstacle_scene_id)
             if ids.shape != (num_drones,) or not np.issubdtype(ids.dtype, np.integer):
@@ -143,6 +147,36 @@ class StepWatches:
             self._vision_args = (vision_scene, vision_drones, bool(vision_ground), bool(vision_see_drones), vision_drone_range)
         elif vision_scene is not None or vision_drones is not None:
             raise ValueError("vision_scene / vision_drones without vision_attributes=True")
+        # range_scan=beams [B, 3] (body frame; RangeScanner.fan(...) builds the usual tables): every drone carries that fan of
+        # range beams, cast behind every launch, on the env's stream, against range_scene (default: the obstacle_watch world,
+        # whose device set the scanner then shares; an ObstacleScenes goes by obstacle_scene_id), the plane z = 0 (range_ground)
+        # and, with range_see_drones=True, the other drones as their bounding spheres up to range_drone_range metres (None:
+        # range_max).  env.ranges / env.range_hits [B, N] hold the last scan in the caller's numbering (None before the first
+        # step); a beam reports hits with range_min <= t <= range_max, a miss +inf or, with range_clamp, range_max.  The world
+        # lies in the frame of obstacle_offsets.  Off by default: nothing is allocated or launched.
+        self._scan_args = None
+        self._scan_sampled = False
+        if range_scan is None:
+            if (range_scene is not None or range_min != 0.0 or range_max != 10.0 or range_ground is not True or range_clamp
+                    or range_see_drones or range_drone_range is not None):
+                raise ValueError("range_scene / range_min / range_max / range_ground / range_clamp / range_see_drones / "
+                                 "range_drone_range without range_scan=beams")
+        else:
+            from ..scanner import check_range, unit_beams
+            beams = unit_beams(range_scan)
+            check_range(range_min, range_max)
+            if range_see_drones and dist is not None and dist.is_initialized() and dist.get_world_size() > 1:
+                raise NotImplementedError("range_see_drones on a sharded fleet: the radii of the other ranks' drones would have to "
+                                          "travel with their positions (dsim_depth_image_drones takes pos_all / radius_all)")
+            if range_drone_range is not None and not range_see_drones:
+                raise ValueError("range_drone_range without range_see_drones=True")
+            if range_drone_range is not None and not float(range_drone_range) > 0.0:
+                raise ValueError("range_drone_range must be positive")
+            if range_scene is None and obstacle_watch is None and not range_see_drones and not range_ground:
+                raise ValueError("range_scan needs a world to range against: range_scene=ObstacleSet (or obstacle_watch), "
+                                 "range_ground=True or range_see_drones=True")
+            self._scan_args = (beams, range_scene, float(range_min), float(range_max), bool(range_ground), bool(range_clamp),
+                               bool(range_see_drones), range_drone_range)
 
     def _watch_setup(self, offsets) -> None:
         """At the end of __init__: the obstacle set first, because the camera shares its device set."""
@@ -154,12 +188,13 @@ class StepWatches:
             self._drone_grid().clearance_prime(self._drone_prev)     # (the first _housekeeping ran before this tensor existed)
         self._obstacle_setup(offsets)
         self._vision_setup(offsets)
+        self._scan_setup(offsets)
 
     def _obstacle_setup(self, offsets) -> None:
         """obstacle_watch: the device set for reach = R_max + margin, the offsets in storage order and the tensors every
         per-step query writes (fixed addresses: a captured sequence holds them)."""
         if self._obst_set is None:
-            if offsets is not None and self._vision_args is None:
+            if offsets is not None and self._vision_args is None and self._scan_args is None:
                 raise ValueError("obstacle_offsets without obstacle_watch")
             return
         from .. import obstacles as obs
@@ -210,6 +245,19 @@ class StepWatches:
         self.dep.fill_(1.0)                # nothing seen yet (BaseAviary.py:245 starts from ones too)
         self.seg.fill_(-1)
 
+    def _scan_setup(self, offsets) -> None:
+        """range_scan=beams: the scanner and its device set (shared with the obstacle watch when both look at the same world)."""
+        if self._scan_args is None:
+            return
+        from ..obstacles import DeviceScenes, ObstacleScenes
+        from ..scanner import RangeScanner
+        beams, scene, t_min, t_max, ground, clamp, see_drones, drone_range = self._scan_args
+        shared = self._obst is not None and (scene is None or scene is self._obst_set)
+        world = self._obst if shared else scene
+        self._scan = RangeScanner(self.ctx, self.state, world, beams, t_min=t_min, t_max=t_max, ground=ground, clamp=clamp,
+                                  offsets=offsets, type_id=self._type_id, drones=see_drones, drone_range=drone_range,
+                                  scene_id=self._scene_ids if isinstance(world, (ObstacleScenes, DeviceScenes)) else None)
+
     def _watch_reset(self) -> None:
         """_housekeeping: the step counter is back at zero, and so is the last one the camera's cadence saw."""
         self._vision_seen = 0
@@ -225,6 +273,8 @@ class StepWatches:
     def _watch_close(self) -> None:
         if self._vision is not None:
             self._vision.close()
+        if self._scan is not None:
+            self._scan.close()
         if self._obst is not None:
             self._obst.close()
 
@@ -247,6 +297,8 @@ class StepWatches:
             self._vision_seen = self.step_counter
             if due:
                 self._vision_capture()
+        if self._scan is not None:
+            self._scan_now()
 
     def _drone_grid(self):
         from ..downwash import Downwash
@@ -290,6 +342,13 @@ class StepWatches:
         else:
             obs.query(self.ctx, self.state, self._obst, margin, clr, near, self._obst_off, self._type_id, contacts_out)
 
+    def _scan_now(self):
+        """One dsim_range_scan on the state the launch just left, on the env's stream (also under capture)."""
+        if self._scan.drones and self._downwash is not None:
+            self._downwash.invalidate_prebin()            # the drones' binning drops the ctx's grid bookkeeping
+        self._scan.scan()
+        self._scan_sampled = True
+
     def _vision_capture(self):
         if self._vision.drones and self._downwash is not None:
             self._downwash.invalidate_prebin()            # the drones' binning drops the ctx's grid bookkeeping
@@ -318,24 +377,59 @@ class StepWatches:
             if self._vision.drones:
                 self._vision.refresh_drone_box()
             self._vision_capture()
+        if self._scan is not None:
+            # (eager: the scanner's kernel is loaded before the capture starts; with range_see_drones this scan also measures the box
+            # of the drones' grid and makes its workspace, which stand for the whole graph.  Not an Env.step: what env.ranges shows
+            # does not change kind, it is the current state's scan)
+            if self._scan.drones:
+                self._scan.refresh_drone_box()
+            sampled = self._scan_sampled
+            self._scan_now()
+            self._scan_sampled = sampled
 
     def _captured_step(self) -> None:
-        """Behind every captured step, as in eager mode: the obstacle watch's query, then the camera at its cadence of 1."""
+        """Behind every captured step, as in eager mode: the obstacle watch's query, the camera at its cadence of 1, the scan."""
         if self._obst is not None:
             self._watch_obstacles()
         if self._vision is not None:
             self._vision_capture()
+        if self._scan is not None:
+            self._scan_now()
 
     def _capture_keepalive(self):
         """After the capture: what the graph must keep alive.  The captured captures hold the camera's addresses, among them the
         workspace of the drones' grid: an eager capture that later re-measures the box and outgrows it allocates a new one."""
-        return self._vision.graph_keepalive() if self._vision is not None else ()
+        keep = self._vision.graph_keepalive() if self._vision is not None else ()
+        return keep + (self._scan.graph_keepalive() if self._scan is not None else ())
 
     def _replayed(self) -> None:
         """After a replay (the env's counters moved on already): the camera saw every step of it."""
         self._vision_seen = self.step_counter
+        if self._scan is not None:
+            self._scan_sampled = True
 
     # ------------------------------------------------------------------ public surface
+    @property
+    def ranges(self):
+        """[B, N] float32: what every beam of the ``range_scan`` fan read behind the last step, in the caller's numbering; None
+        before the first step (and without range_scan)."""
+        return self._scan.ranges if self._scan is not None and self._scan_sampled else None
+
+    @property
+    def range_hits(self):
+        """[B, N] int32: what every beam hit behind the last step (body index, -1 nothing, -2 the plane, -3 - k drone k:
+        RangeScanner.hit_drone); None before the first step."""
+        return self._scan.hits if self._scan is not None and self._scan_sampled else None
+
+    def range_scan(self):
+        """(ranges, hits) [B, N] of the CURRENT state, scanned now on the env's stream (not counted as an Env.step)."""
+        if self._scan is None:
+            raise ValueError("range_scan() needs an env made with range_scan=beams")
+        if self._scan.drones and self._downwash is not None:
+            self._downwash.invalidate_prebin()
+        self._scan.scan()
+        return self._scan.ranges, self._scan.hits
+
     def drone_clearance(self, margin: float = 1.0):
         """Per-drone clearance of the CURRENT state between the vehicles' bounding spheres (dsim_clearance; no counterpart in
         the reference, whose Bullet world makes the vehicles collide instead): (clearance [N] float32, nearest [N] int32) in

@@ -13,7 +13,9 @@ the flight starts one control step into the course.
 --gates: the committed gate stands at each drone's own three waypoints (obstacles.ObstacleScenes: one prototype on the device, a
 scene of three placements per drone), yawed so that its normal lies along the xy direction of the course's velocity there; the
 flight is watched (obstacle_watch=scenes) and the run prints obstacle_contacts() and the least clearance per gate slot.  With
---vision every drone also carries a camera that sees its own gates, and one depth frame is saved (--out).
+--vision every drone also carries a camera that sees its own gates, and one depth frame is saved (--out).  With --scan N every
+drone carries a ring of N range beams (scanner.RangeScanner through the env's range_scan=) against its own gates, scanned behind
+every step, and the fleet's least range per gate slot is printed beside the clearances.
 """
 import argparse
 import os
@@ -21,6 +23,7 @@ import sys
 import time
 
 import numpy as np
+import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -67,9 +70,15 @@ def main(argv=None):
     ap.add_argument("--vision", action="store_true", help="with --gates: every drone carries a camera; one depth frame is saved")
     ap.add_argument("--out", default="courses_depth.npy", help="where --vision saves its frame")
     ap.add_argument("--margin", type=float, default=1.0, help="obstacle_margin of --gates [m]")
+    ap.add_argument("--scan", type=int, default=0, metavar="N",
+                    help="with --gates: every drone carries a ring of N range beams (1 .. 64) against its own gates")
     A = ap.parse_args(argv)
     if A.vision and not A.gates:
         ap.error("--vision needs --gates")
+    if A.scan and not A.gates:
+        ap.error("--scan needs --gates")
+    if not 0 <= A.scan <= 64:
+        ap.error("--scan takes 1 .. 64 beams")
     n, AGGR, FREQ = A.num_drones, 2, 240                                   # fly_INDI_TrajectoryTrack.py:108,162-164
     side = int(np.ceil(np.sqrt(n)))
     off = 10.0 * np.stack([np.arange(n) % side, np.arange(n) // side, np.zeros(n)], 1).astype(np.float64)
@@ -84,6 +93,10 @@ def main(argv=None):
         watch = dict(obstacle_watch=scenes, obstacle_scene_id=np.arange(n), obstacle_offsets=off, obstacle_margin=A.margin)
         if A.vision:
             watch["vision_attributes"] = True
+        if A.scan:
+            # (the scanner shares the watch's device scenes; the plane is left out: the least range is then a gate's)
+            from dronesim_amd.scanner import RangeScanner
+            watch.update(range_scan=RangeScanner.fan(A.scan), range_max=10.0, range_ground=False)
     else:
         watch = {}
     env = CtrlAviary(["robobee"], n, initial_xyzs=gates[:, 0, :] + off, aggregate_phy_steps=AGGR, freq=FREQ, dict_io=False, **watch)
@@ -97,6 +110,7 @@ def main(argv=None):
     tgt = BankTrajectoryTargets(env.ctx, n, bank, t0=np.full(n, dt_ctrl), offsets=off)
     steps = int(A.duration_sec * FREQ / AGGR)
     least = np.full((n, 3), np.inf) if A.gates else None
+    least_range = np.full(3, np.inf)                                       # --scan: the fleet's least range per gate slot
     frame = None
     START = time.time()
     for k in range(steps):
@@ -106,6 +120,10 @@ def main(argv=None):
             clr, near = (x.cpu().numpy() for x in env.last_obstacle_clearance)
             seen = near >= 0                                               # (one body per gate: `nearest` is the gate's slot)
             np.minimum.at(least, (np.nonzero(seen)[0], near[seen]), clr[seen])
+        if A.scan:
+            rng_, hit = env.ranges, env.range_hits                         # [N beams, n]; one body per gate: a hit is the gate's slot
+            for j in range(3):
+                least_range[j] = min(least_range[j], float(torch.where(hit == j, rng_, torch.full_like(rng_, float("inf"))).min()))
         if A.vision and frame is None and bool((env.seg >= 0).any()):
             frame = env.dep.clone()
     pos = env.state.pos.T.cpu().numpy()
@@ -115,7 +133,8 @@ def main(argv=None):
     print(f"{n} drones x {steps} env steps in {el:.2f} s wall ({n * steps / el:.3e} drone-steps/s incl. host loop); "
           f"distance to the own target: median {np.median(err):.3f} m, worst {err.max():.3f} m")
     if A.gates:
-        per_slot = [f"gate {j}: {least[:, j].min():.3f} m ({int(np.isfinite(least[:, j]).sum())} drones within {A.margin} m)" for j in range(3)]
+        per_slot = [f"gate {j}: {least[:, j].min():.3f} m ({int(np.isfinite(least[:, j]).sum())} drones within {A.margin} m)"
+                    + (f", least range of {A.scan} beams {least_range[j]:.3f} m" if A.scan else "") for j in range(3)]
         print(f"obstacle_contacts() = {env.obstacle_contacts()} drone x steps with the bounding sphere on a gate; least clearance per "
               f"gate slot: " + "; ".join(per_slot))
     if A.vision:

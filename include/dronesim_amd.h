@@ -51,7 +51,7 @@ extern "C" {
                               DSIM_TRAJGEN_* (DSIM_TRAJGEN_BAD_CONDITION among them); the swept obstacle watch, dsim_obstacle_sweep, dsim_sweep_args, DSIM_SWEEP_*; obstacle
                               scenes, dsim_scenes_create / _destroy, dsim_obstacle_clearance_scenes, dsim_depth_image_scenes; the
                               swept drone-drone watch, dsim_clearance_sweep, dsim_clearance_sweep_workspace,
-                              dsim_clearance_sweep_args */
+                              dsim_clearance_sweep_args; the range scanner, dsim_range_scan, dsim_scan_args, DSIM_SCAN_* */
 #define DSIM_MAX_ACT 6     /* actuators per vehicle (quad 4, morphing hexa 6) */
 #define DSIM_MAX_TYPES 8
 
@@ -1040,6 +1040,55 @@ int dsim_obstacle_clearance_scenes(dsim_ctx* ctx, void* stream, int64_t n, dsim_
 int dsim_depth_image_scenes(dsim_ctx* ctx, void* stream, dsim_view state, const dsim_scenes* scenes, const int32_t* scene_id,
                             const dsim_camera_params* params, int64_t n_cam, const int32_t* cam_index,
                             const float* offset, const uint8_t* type_id, float* depth_out, int32_t* seg_out);
+
+/* Range scanner: a fan of range beams per drone, for EVERY drone — the sensor real vehicles carry (a ToF ring, a downward altimeter,
+ * a small lidar fan).  A watch gives one scalar per drone and no direction; the camera gives direction at thousands of rays per
+ * drone, which is why it serves a few carriers.  dsim_range_scan casts n_beams rays per drone, one drone per lane.
+ *
+ * The ray.  For drone i < n and beam b the origin is e = p_i - offset_i, the drone's centre in its task frame, and the direction
+ * d = R(quat_i) beam_b, R formed from the unnormalised quaternion exactly as the camera forms it (s = 2 / |q|^2).  d is NOT
+ * normalised: t is in units of |beam_b|, metres for a unit beam.  The beam takes the nearest hit with t_min <= t <= t_max over
+ *   - both faces of every triangle of `set`;
+ *   - with `scenes`, every placement of scene scene_id[i], the ray taken into the placement's frame (subtract first, then rotate,
+ *     as dsim_depth_image_scenes does); an id outside [0, K): no obstacles;
+ *   - with DSIM_SCAN_GROUND, the plane z = 0 of the task frame: analytic, also for rays that never enter a box;
+ *   - with `drones`, the bounding sphere of every OTHER drone j with R_j > 0, as dsim_depth_image_drones draws it: the ray starts
+ *     at the STORED position p_i in the world frame with the same d, the first root is taken unless it lies below t_min (then the
+ *     second), and the hit must satisfy t <= min(t_max, drones->range).  A drone never sees itself.  Scenes and drones together
+ *     are served (the camera refuses that pair).
+ *     range_out[b][i] = t of the nearest hit; +inf on a miss, or t_max with DSIM_SCAN_CLAMP
+ *     hit_out[b][i]   = the body index; the instance-major g n_bodies + body on scenes; DSIM_SEG_GROUND; DSIM_SEG_DRONE(k) with
+ *                       drones->label applied as the camera applies it; -1 on a miss.  Nullable.
+ * Both are beam-major [n_beams][n_pad] (device, storage order like offset).  Lanes i >= n are not written.
+ *
+ * Undefined poses: a non-finite position or quaternion, |q|^2 = 0, a zero or non-finite beam — those beams miss and nothing faults.
+ * The drone's type plays no part in its own scan (a type with collision_sphere = 0 still scans; it is merely not a target);
+ * type_id is what the drones' grid is binned with.
+ *
+ * Stream-ordered, allocates nothing, never synchronises; may be captured.  With `drones` the fleet is binned per call through the
+ * grid of drones->grid (dsim_depth_image_drones has the rules: workspace, outside_out, the box that need not hold every drone) and
+ * the call drops the context's record of the downwash grid, as that call does.  DSIM_E_ARG, nothing enqueued: a null ctx, args,
+ * beams or range_out; n <= 0 or n > n_pad; n_beams outside 1 .. 64; t_min < 0, t_max <= t_min, either not finite; an unknown flag;
+ * a set (or the scenes' prototype) without rays enabled; scenes without scene_id or the reverse; scenes together with a non-NULL
+ * set; no world at all (no set, scenes, drones or ground); several types with drones and no type_id; everything
+ * dsim_depth_image_drones refuses about `drones` (a halo plan: DSIM_E_UNSUPPORTED). */
+enum { DSIM_SCAN_GROUND = 1u << 0,    /* the plane z = 0 of the task frame, body DSIM_SEG_GROUND              */
+       DSIM_SCAN_CLAMP  = 1u << 1 };  /* a beam that hits nothing reports t_max instead of +inf               */
+typedef struct dsim_scan_args {
+  const float*   beams;       /* device [n_beams][3]: beam directions in the BODY frame, used as given        */
+  int32_t        n_beams;     /* 1 .. 64                                                                      */
+  float          t_min, t_max;/* 0 <= t_min < t_max, both finite                                              */
+  uint32_t       flags;       /* DSIM_SCAN_*                                                                  */
+  const float*   offset;      /* SoA [3][n_pad] or NULL, as dsim_obstacle_clearance                           */
+  const uint8_t* type_id;     /* [n_pad]; required with more than one type when `drones` is given             */
+  const dsim_scenes* scenes;  /* nullable: the placed world; then `set` must be NULL (the prototype is its)   */
+  const int32_t* scene_id;    /* [n_pad] storage order; with `scenes`, and only with it                       */
+  const dsim_camera_drones* drones;   /* nullable: the other drones as their bounding spheres                 */
+  float*         range_out;   /* [n_beams][n_pad]: t of the nearest hit                                       */
+  int32_t*       hit_out;     /* nullable, same shape: what was hit                                           */
+} dsim_scan_args;
+int dsim_range_scan(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, const dsim_obstacles* set,
+                    const dsim_scan_args* args);
 
 /* The rotor-noise normals the step kernels draw (diagnostics / distribution studies; no counterpart in the reference, whose
  * draws come from numpy's global generator): for drones [0, n) and the physics sub-steps [0, substeps) of Env.step number
