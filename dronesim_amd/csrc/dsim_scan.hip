@@ -113,7 +113,9 @@ __global__ __launch_bounds__(256) void k_range_scan(ScanK a) {
     const int b_lo = (int)blockIdx.y * a.beams_per_block, b_hi = min(b_lo + a.beams_per_block, a.n_beams);
     for (int b = b_lo; b < b_hi; ++b) {
       const float bx = a.beams[3 * b], by = a.beams[3 * b + 1], bz = a.beams[3 * b + 2];
-      const bool beam_ok = fabsf(bx) <= 3.0e38f && fabsf(by) <= 3.0e38f && fabsf(bz) <= 3.0e38f && (bx != 0.0f || by != 0.0f || bz != 0.0f);
+      // (a beam whose squared length overflows float32 is a non-finite beam: the reach above never counted it)
+      const bool beam_ok = fabsf(bx) <= 3.0e38f && fabsf(by) <= 3.0e38f && fabsf(bz) <= 3.0e38f && (bx != 0.0f || by != 0.0f || bz != 0.0f) &&
+                           bx * bx + by * by + bz * bz <= 3.0e38f;
       const float dx = r00 * bx + r01 * by + r02 * bz, dy = r10 * bx + r11 * by + r12 * bz, dz = r20 * bx + r21 * by + r22 * bz;
       const bool ray = defined && beam_ok && fabsf(dx) <= 3.0e38f && fabsf(dy) <= 3.0e38f && fabsf(dz) <= 3.0e38f;
       float best = INFINITY;

@@ -798,8 +798,16 @@ class Downwash:
             if box is not None:
                 lo, hi = key[1][:2], key[1][2:]
             else:
-                src = torch.nan_to_num(st.raw_fields(0, 2), nan=0.0, posinf=0.0, neginf=0.0)      # (a lost drone does not stretch the box)
-                lo, hi = src.min(dim=1).values.cpu(), src.max(dim=1).values.cpu()
+                # the box of the drones whose position is finite: a lost drone does not stretch it, to the origin neither
+                # (nobody finite: the box of the positions with zeros for what is not finite).  One read-back.
+                src = st.raw_fields(0, 3)
+                finite = torch.isfinite(src).all(dim=0, keepdim=True)
+                src = src[:2]
+                zeroed = torch.nan_to_num(src, nan=0.0, posinf=0.0, neginf=0.0)
+                lo_hi = torch.stack([torch.where(finite, src, float("inf")).min(dim=1).values,
+                                     torch.where(finite, src, float("-inf")).max(dim=1).values,
+                                     zeroed.min(dim=1).values, zeroed.max(dim=1).values]).cpu()
+                lo, hi = (lo_hi[0], lo_hi[1]) if bool(torch.isfinite(lo_hi[:2]).all()) else (lo_hi[2], lo_hi[3])
             r_max = max(float(t.collision_sphere) for t in self.ctx.types)
             # margin: what makes the cell 0.25 m at least (a fleet of points still gets a grid)
             self.cell, *grid = clearance_grid(lo, hi, r_max, max(0.25 - 2.0 * r_max, 0.0), st.n)

@@ -1061,7 +1061,8 @@ int dsim_depth_image_scenes(dsim_ctx* ctx, void* stream, dsim_view state, const 
  *                       drones->label applied as the camera applies it; -1 on a miss.  Nullable.
  * Both are beam-major [n_beams][n_pad] (device, storage order like offset).  Lanes i >= n are not written.
  *
- * Undefined poses: a non-finite position or quaternion, |q|^2 = 0, a zero or non-finite beam — those beams miss and nothing faults.
+ * Undefined poses: a non-finite position or quaternion, |q|^2 = 0, a zero or non-finite beam, a beam whose squared length is not
+ * finite in float32 (longer than about 1.8e19) — those beams miss and nothing faults.
  * The drone's type plays no part in its own scan (a type with collision_sphere = 0 still scans; it is merely not a target);
  * type_id is what the drones' grid is binned with.
  *

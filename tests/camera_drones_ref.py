@@ -36,7 +36,8 @@ def cast_spheres(centre, radius, eye, d, near, tmax, own=-1):
         drawn[own] = False
     sel = np.nonzero(drawn)[0]
     m_all = centre[sel] - eye[None, :]
-    b = D @ m_all.T                                                      # [P, S]
+    b = D[:, 0:1] * m_all[None, :, 0] + D[:, 1:2] * m_all[None, :, 1] + D[:, 2:3] * m_all[None, :, 2]    # [P, S] (a matmul with an
+    #                                                                      inner size of 3 is ten times slower at 65 536 spheres)
     rho2 = (m_all * m_all).sum(1)[None, :] - b * b / a[:, None]
     pi, sj = np.nonzero(rho2 <= (1.01 * radius[sel])[None, :] ** 2)
     si = sel[sj]
@@ -160,13 +161,20 @@ def restated_spheres(stored, radius, cam, quat, L, W, H, far=FAR, rng=None, chun
     return best.astype(np.float64)
 
 
-def walked_spheres(stored, radius, cam, quat, L, W, H, grid, far=FAR, rng=None):
-    """t [H, W] by the kernel's own route in float32, ray by ray: the drones binned on grid = (cell, xmin, ymin, nx, ny) as the
-    scatter pass bins them (a drone outside the box on the outside list), the 2-D walk over the box grown by one ring with the
-    kernel's selects — the 3 x 3 block at the first cell, the newly adjacent column or row after a step — the early stop, then
-    the outside list.  Slow (a Python loop per ray).  Also returns the mean cell steps and sphere tests per ray."""
+def walk_rays(stored, radius, grid, origin, d, own, near, tmax):
+    """The walker the camera and the range scanner share: t [P] (inf: none) of rays (origin [P, 3] or [3], d [P, 3], own [P] or one
+    index: the drone a ray never sees) by the kernels' own route in float32, ray by ray: the drones binned on grid = (cell, xmin,
+    ymin, nx, ny) as the scatter pass bins them (a drone outside the box on the outside list, one whose position is not finite on
+    no list), the 2-D walk over the box grown by one ring with the kernels' selects — s_in / s_out with fmin / fmax semantics, the
+    3 x 3 block at the first cell, the newly adjacent column or row after a step — the early stop, then the outside list.  A ray
+    whose origin or direction is not finite casts nothing.  Slow (a Python loop per ray).  -> (t, cell steps, sphere tests)."""
     f32 = np.float32
-    stored, radius = np.asarray(stored, f32), np.asarray(radius, f32).copy()
+    stored, radius = np.asarray(stored, f32)[:, :3], np.asarray(radius, f32).copy()
+    d = np.asarray(d, f32).reshape(-1, 3)
+    P = d.shape[0]
+    origin = np.broadcast_to(np.asarray(origin, f32), (P, 3))
+    own = np.broadcast_to(np.asarray(own, np.int64), (P,))
+    near, tmax = f32(near), f32(tmax)
     cell, xmin, ymin = (f32(v) for v in grid[:3])
     nx, ny = int(grid[3]), int(grid[4])
     icell = f32(1.0) / cell
@@ -178,15 +186,13 @@ def walked_spheres(stored, radius, cam, quat, L, W, H, grid, far=FAR, rng=None):
     for j in np.nonzero(inside)[0]:
         cells.setdefault((int(fx[j]), int(fy[j])), []).append(j)
     outside = [j for j in np.nonzero(finite & ~inside)[0] if radius[j] > 0]
-    e, d = rays32(stored[cam], quat, L, W, H)
-    near, tmax = f32(L), min(f32(far), f32(far if rng is None else rng))
     gx0, gx1 = xmin - cell, xmin + f32(nx + 1) * cell
     gy0, gy1 = ymin - cell, ymin + f32(ny + 1) * cell
-    out = np.full((H, W), np.inf)
+    out = np.full(P, np.inf)
     steps = tests = 0
 
-    def sphere(j, dv, inv_a, best):
-        if j == cam or not radius[j] > 0:
+    def sphere(j, e, me, dv, inv_a, best):
+        if j == me or not radius[j] > 0:
             return best
         m = stored[j] - e
         tc = (m[0] * dv[0] + m[1] * dv[1] + m[2] * dv[2]) * inv_a
@@ -198,50 +204,65 @@ def walked_spheres(stored, radius, cam, quat, L, W, H, grid, far=FAR, rng=None):
         return t if (disc >= 0 and near <= t <= tmax and t < best) else best
 
     with np.errstate(all="ignore"):
-        for r in range(H):
-            for c in range(W):
-                dv = d[r, c]
-                inv_a = f32(1.0) / (dv[0] * dv[0] + dv[1] * dv[1] + dv[2] * dv[2])
-                best = f32(np.inf)
-                ix, iy = f32(1.0) / dv[0], f32(1.0) / dv[1]
-                sx0, sx1, sy0, sy1 = (gx0 - e[0]) * ix, (gx1 - e[0]) * ix, (gy0 - e[1]) * iy, (gy1 - e[1]) * iy
-                s_in = np.fmax(np.fmax(np.fmin(sx0, sx1), np.fmin(sy0, sy1)), near)
-                s_out = np.fmin(np.fmin(np.fmax(sx0, sx1), np.fmax(sy0, sy1)), np.fmin(tmax, best))
-                in_x = dv[0] != 0 or gx0 <= e[0] <= gx1
-                in_y = dv[1] != 0 or gy0 <= e[1] <= gy1
-                if s_in <= s_out and in_x and in_y:
-                    qx, qy = e[0] + s_in * dv[0], e[1] + s_in * dv[1]
-                    cx = min(max(int(np.floor((qx - gx0) * icell)), 0), nx + 1) - 1
-                    cy = min(max(int(np.floor((qy - gy0) * icell)), 0), ny + 1) - 1
-                    stx, sty = (1 if dv[0] > 0 else -1), (1 if dv[1] > 0 else -1)
-                    dtx = cell * abs(ix) if dv[0] != 0 else f32(np.inf)
-                    dty = cell * abs(iy) if dv[1] != 0 else f32(np.inf)
-                    tmx = (gx0 + f32(cx + 1 + (1 if dv[0] > 0 else 0)) * cell - e[0]) * ix if dv[0] != 0 else f32(np.inf)
-                    tmy = (gy0 + f32(cy + 1 + (1 if dv[1] > 0 else 0)) * cell - e[1]) * iy if dv[1] != 0 else f32(np.inf)
-                    bx0, bx1, by0, by1 = cx - 1, cx + 1, cy - 1, cy + 1
-                    for it in range(nx + ny + 4):
-                        for yy in range(max(by0, 0), min(by1, ny - 1) + 1):
-                            for xx in range(max(bx0, 0), min(bx1, nx - 1) + 1):
-                                for j in cells.get((xx, yy), ()):
-                                    best = sphere(j, dv, inv_a, best)
-                                    tests += 1
-                        t_exit = min(tmx, tmy)
-                        if best <= t_exit or t_exit >= s_out:
-                            break
-                        gx = tmx <= tmy
-                        if gx:
-                            cx += stx; tmx = f32(tmx + dtx)
-                        else:
-                            cy += sty; tmy = f32(tmy + dty)
-                        steps += 1
-                        if cx < -1 or cx > nx or cy < -1 or cy > ny:
-                            break
-                        bx0, bx1 = (cx + stx, cx + stx) if gx else (cx - 1, cx + 1)
-                        by0, by1 = (cy - 1, cy + 1) if gx else (cy + sty, cy + sty)
-                for j in outside:
-                    best = sphere(j, dv, inv_a, best)
-                out[r, c] = best
-    return out, steps / (W * H), tests / (W * H)
+        for r in range(P):
+            e, dv, me = origin[r], d[r], int(own[r])
+            if not (np.isfinite(e).all() and np.isfinite(dv).all()):
+                continue
+            inv_a = f32(1.0) / (dv[0] * dv[0] + dv[1] * dv[1] + dv[2] * dv[2])
+            best = f32(np.inf)
+            ix, iy = f32(1.0) / dv[0], f32(1.0) / dv[1]
+            sx0, sx1, sy0, sy1 = (gx0 - e[0]) * ix, (gx1 - e[0]) * ix, (gy0 - e[1]) * iy, (gy1 - e[1]) * iy
+            s_in = np.fmax(np.fmax(np.fmin(sx0, sx1), np.fmin(sy0, sy1)), near)
+            s_out = np.fmin(np.fmin(np.fmax(sx0, sx1), np.fmax(sy0, sy1)), np.fmin(tmax, best))
+            in_x = dv[0] != 0 or gx0 <= e[0] <= gx1
+            in_y = dv[1] != 0 or gy0 <= e[1] <= gy1
+            if s_in <= s_out and in_x and in_y:
+                qx, qy = e[0] + s_in * dv[0], e[1] + s_in * dv[1]
+                cx = min(max(int(np.floor((qx - gx0) * icell)), 0), nx + 1) - 1
+                cy = min(max(int(np.floor((qy - gy0) * icell)), 0), ny + 1) - 1
+                stx, sty = (1 if dv[0] > 0 else -1), (1 if dv[1] > 0 else -1)
+                dtx = cell * abs(ix) if dv[0] != 0 else f32(np.inf)
+                dty = cell * abs(iy) if dv[1] != 0 else f32(np.inf)
+                tmx = (gx0 + f32(cx + 1 + (1 if dv[0] > 0 else 0)) * cell - e[0]) * ix if dv[0] != 0 else f32(np.inf)
+                tmy = (gy0 + f32(cy + 1 + (1 if dv[1] > 0 else 0)) * cell - e[1]) * iy if dv[1] != 0 else f32(np.inf)
+                bx0, bx1, by0, by1 = cx - 1, cx + 1, cy - 1, cy + 1
+                for it in range(nx + ny + 4):
+                    for yy in range(max(by0, 0), min(by1, ny - 1) + 1):
+                        for xx in range(max(bx0, 0), min(bx1, nx - 1) + 1):
+                            for j in cells.get((xx, yy), ()):
+                                best = sphere(j, e, me, dv, inv_a, best)
+                                tests += 1
+                    t_exit = min(tmx, tmy)
+                    if best <= t_exit or t_exit >= s_out:
+                        break
+                    gx = tmx <= tmy
+                    if gx:
+                        cx += stx; tmx = f32(tmx + dtx)
+                    else:
+                        cy += sty; tmy = f32(tmy + dty)
+                    steps += 1
+                    if cx < -1 or cx > nx or cy < -1 or cy > ny:
+                        break
+                    bx0, bx1 = (cx + stx, cx + stx) if gx else (cx - 1, cx + 1)
+                    by0, by1 = (cy - 1, cy + 1) if gx else (cy + sty, cy + sty)
+            for j in outside:
+                best = sphere(j, e, me, dv, inv_a, best)
+            out[r] = best
+    return out, steps, tests
+
+
+def walked_spheres(stored, radius, cam, quat, L, W, H, grid, far=FAR, rng=None):
+    """t [H, W] by the kernel's own route in float32, ray by ray (walk_rays, which the range scanner's reference shares, with the
+    camera's rays): the drones binned on grid = (cell, xmin, ymin, nx, ny) as the scatter pass bins them (a drone outside the box
+    on the outside list), the 2-D walk over the box grown by one ring with the kernel's selects — the 3 x 3 block at the first
+    cell, the newly adjacent column or row after a step — the early stop, then the outside list.  Slow (a Python loop per ray).
+    Also returns the mean cell steps and sphere tests per ray."""
+    f32 = np.float32
+    stored = np.asarray(stored, f32)
+    e, d = rays32(stored[cam], quat, L, W, H)
+    near, tmax = f32(L), min(f32(far), f32(far if rng is None else rng))
+    t, steps, tests = walk_rays(stored, radius, grid, e, d.reshape(-1, 3), cam, near, tmax)
+    return t.reshape(H, W), steps / (W * H), tests / (W * H)
 
 
 # ---- the tests' scenes ---------------------------------------------------------------------------------------------------------------

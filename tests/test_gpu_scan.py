@@ -66,6 +66,9 @@ def check(label, t, hit, ref, tol=None, miss=np.inf):
     wrong_id = int((hit != ref["hit"])[ok].sum()) if hit is not None else 0
     print(f"{label}: worst t_error {err:.3e} (tol {tol:.3e}), {wrong} hit / no-hit and {wrong_id} ids differ outside the mask of "
           f"{int(ref['ambiguous'].sum())} of {ref['t'].size} rays")
+    differ = ok & ((got != np.isfinite(ref["t"])) | ((hit != ref["hit"]) if hit is not None else False))
+    for b, i in np.argwhere(differ)[:8]:                       # the first few rays that differ: (beam, drone, got, reference)
+        print(f"  beam {b}, drone {i}: got ({t[b, i]!r}, {hit[b, i] if hit is not None else None}), reference ({ref['t'][b, i]!r}, {ref['hit'][b, i]})")
     assert wrong == 0 and wrong_id == 0
     assert err <= tol
     if np.isfinite(miss):
@@ -343,6 +346,26 @@ def test_a_mixed_fleet_stored_type_major_names_drones_as_the_caller_does(gpu):
 
 
 # ---- case 8: refusals ---------------------------------------------------------------------------------------------------------------
+def raw_call(nat, ctx, st, table, rng_out, hit_out, h=None, c_="ctx", n=None, null_args=False, drones=None, grid=None, outside=None, **kw):
+    """dsim_range_scan through the raw ABI: table [B, 3] a device tensor of beams used as they are, t in [0.05, 8] and no flags unless kw (fields
+    of dsim_scan_args) says otherwise; h the set's handle or None; drones: None, or fields of dsim_camera_drones over grid (range 6,
+    outside_out = outside).  Returns the call's status."""
+    a = nat.ScanArgs()
+    a.beams, a.n_beams, a.t_min, a.t_max, a.flags = table.data_ptr(), table.shape[0], 0.05, 8.0, 0
+    a.range_out, a.hit_out = rng_out.data_ptr(), hit_out.data_ptr()
+    for k, v in kw.items():
+        setattr(a, k, v)
+    d = None
+    if drones is not None:
+        d = nat.CameraDrones()
+        d.grid, d.range, d.outside_out = ctypes.addressof(grid), 6.0, outside.data_ptr()
+        for k, v in drones.items():
+            setattr(d, k, v)
+        a.drones = ctypes.addressof(d)
+    return ctx.lib.dsim_range_scan(ctx.handle if c_ == "ctx" else c_, ctx.stream_ptr(), st.n if n is None else n, st.view(), h,
+                                   None if null_args else ctypes.byref(a))
+
+
 def test_refusals_leave_the_outputs_untouched(gpu):
     nat, fleet = gpu
     from dronesim_amd.downwash import Downwash
@@ -362,21 +385,8 @@ def test_refusals_leave_the_outputs_untouched(gpu):
     grid = Downwash(ctx, st, tid, None).sphere_grid(None)
     before = [ctx.query(q) for q in (nat.QUERY_DRONE_CONTACTS, nat.QUERY_OBSTACLE_CONTACTS)]
 
-    def call(h="set", c_=ctx.handle, n=st.n, null_args=False, drones=None, **kw):
-        a = nat.ScanArgs()
-        a.beams, a.n_beams, a.t_min, a.t_max, a.flags = beams.data_ptr(), 18, 0.05, 8.0, 0
-        a.range_out, a.hit_out = rng_out.data_ptr(), hit_out.data_ptr()
-        for k, v in kw.items():
-            setattr(a, k, v)
-        d = None
-        if drones is not None:
-            d = nat.CameraDrones()
-            d.grid, d.range, d.outside_out = ctypes.addressof(grid), 6.0, outside.data_ptr()
-            for k, v in drones.items():
-                setattr(d, k, v)
-            a.drones = ctypes.addressof(d)
-        handle = dev.handle if h == "set" else h
-        return ctx.lib.dsim_range_scan(c_, ctx.stream_ptr(), n, st.view(), handle, None if null_args else ctypes.byref(a))
+    def call(h="set", **kw):
+        return raw_call(nat, ctx, st, beams, rng_out, hit_out, h=dev.handle if h == "set" else h, grid=grid, outside=outside, **kw)
     inf, nan = float("inf"), float("nan")
     assert call(c_=None) == -1 and call(null_args=True) == -1 and call(beams=None) == -1 and call(range_out=None) == -1
     assert call(n=0) == -1 and call(n=-3) == -1 and call(n=st.n_pad + 1) == -1

@@ -178,3 +178,91 @@ def test_scan_args_mirror_matches_c(nat, tmp_path):
         assert int(got[fname]) == getattr(nat.ScanArgs, fname).offset, fname
     assert (int(got["GROUND"]), int(got["CLAMP"])) == (nat.SCAN_GROUND, nat.SCAN_CLAMP)
     assert "dsim_range_scan" in nat.EXPORTS
+
+
+# ---- the drones' walk at its edges: what tests/test_gpu_scan_edges.py takes for granted ---------------------------------------------
+def test_edge_cases_are_what_the_gpu_tests_need():
+    """Every case of scan_ref.restated_edge_inputs, on the references alone: the mask covers at most 1 % of the case's own rays,
+    outside it the float32 restatement hits exactly what the reference hits, its worst t_error is the recorded
+    SCAN_EDGE_RESTATED_WORST (not above it, the record not padded), which is not above SCAN_RESTATED_WORST: SCAN_EDGE_TOL is
+    SCAN_TOL.  Then the floors: what each case must contain to be worth running."""
+    worst = 0.0
+    for name, t32, ref in sf.restated_edge_inputs():
+        share = float(ref["ambiguous"].mean())
+        err = sf.t_error(t32, ref)
+        print(f"{name}: restated t_error {err:.3e}, mask {share:.4%}")
+        assert share <= sf.MASK_CAP, name
+        assert not ((np.isfinite(t32) != np.isfinite(ref["t"])) & ~ref["ambiguous"]).any(), name
+        worst = max(worst, err)
+    print(f"restated worst over the edge cases {worst:.3e}")
+    assert worst <= sf.SCAN_EDGE_RESTATED_WORST <= 1.02 * worst, worst
+    assert sf.SCAN_EDGE_RESTATED_WORST <= sf.SCAN_RESTATED_WORST and sf.SCAN_EDGE_TOL == sf.SCAN_TOL
+    t_min, t_max, rng = sf.STACK_LIMITS
+    # the stack: level drones, beams along the axes
+    near, far = sf.case_stack(), sf.case_stack(sf.FAR_SHIFT)
+    h = near["ref"]["hit"]
+    assert near["st"].shape[0] == 300 and not near["ref"]["ambiguous"].any()
+    assert int((h[4] <= -3).sum()) == 200 and int((h[5] <= -3).sum()) == 200         # up: layers 0 and 1; down: layers 1 and 2
+    assert all(int((h[b] <= -3).sum()) >= 260 for b in range(4)) and int((h <= -3).sum()) >= 2000
+    _, _, d = sf._rays32(near["st"], near["beams"], None)
+    assert int((d == 0.0).sum()) == 4800 and d.size == 9000
+    assert np.array_equal(far["ref"]["hit"], h) and np.abs(far["ref"]["t"][h <= -3] - near["ref"]["t"][h <= -3]).max() < 1e-9
+    who = -3 - h
+    assert not ((h <= -3) & (who == np.arange(300)[None, :])).any() and int(((h <= -3) & (who >= 256)).sum()) >= 200
+    for shift in ((0.0, 0.0), sf.FAR_SHIFT):
+        sf.stack_pinned_box(shift)                             # (asserts its construction)
+    # offsets: the set and the plane from p - offset, the spheres from p
+    c = sf.case_stack_offsets(0)
+    ref, alt = c["ref"], sf.stack_offsets_partial()
+    h = ref["hit"]
+    assert int((h >= 0).sum()) >= 30 and int((h == -2).sum()) >= 150 and int((h <= -3).sum()) >= 2000
+    bare = sf.scan_brute(c["st"], c["beams"], t_min, t_max, c["sc"].triangles, c["sc"].body, ground=True, offsets=c["off"])
+    alone = sf.scan_brute(c["st"], c["beams"], t_min, t_max, radius=c["rad"], drone_range=rng)
+    assert int(((h >= 0) & (alone["hit"] <= -3)).sum()) >= 20                    # a triangle in front of a sphere
+    assert int(((h <= -3) & (bare["hit"] != -1)).sum()) >= 200                   # a sphere in front of a triangle or the plane
+    both = ~ref["ambiguous"] & ~alt["ambiguous"]
+    gap = np.abs(np.where(np.isfinite(ref["t"]), ref["t"], 1e9) - np.where(np.isfinite(alt["t"]), alt["t"], 1e9))
+    differ = int((both & ((h != alt["hit"]) | (gap > 1e-3))).sum())
+    print(f"beams that tell the spheres met from p from those met with part of the offset applied: {differ}")
+    assert differ >= 20
+    assert int((sf.case_stack_offsets(2)["ref"]["hit"] >= 0).sum()) >= 30
+    # lost drones
+    lost = sf.case_stack_lost()
+    hb, hl = lost["before"]["hit"], lost["ref"]["hit"]
+    saw = (hb <= -3) & np.isin(-3 - hb, sf.STACK_LOST[:2])
+    saw[:, list(sf.STACK_LOST)] = False
+    assert int(saw.sum()) >= 10 and not ((hl <= -3) & np.isin(-3 - hl, sf.STACK_LOST[:2])).any()
+    assert int(((hl <= -3) & (-3 - hl == 255)).sum()) >= 5
+    assert np.isinf(lost["ref"]["t"][:, list(sf.STACK_LOST)]).all() and (hl[:, list(sf.STACK_LOST)] == -1).all()
+    # the sparse layer: a doubled cell
+    sp = sf.case_sparse()
+    assert sf.scan_grid(sp["st"])[0] >= 4.0 * sf.scan_grid(near["st"])[0] and int((sp["ref"]["hit"] <= -3).sum()) >= 200
+    # the big fleet's sample
+    big = sf.case_big()
+    assert np.isin([0, 255, 256, sf.BIG_N - 256, sf.BIG_N - 1], big["sample"]).all() and big["sample"].size == 512
+    assert int((big["ref"]["hit"] <= -3).sum()) >= 2000 and int((-3 - big["ref"]["hit"]).max()) > 65000
+    # the raw table
+    raw = sf.case_raw_beams()
+    hr = raw["ref"]["hit"]
+    assert int((hr >= 0).sum()) >= 50 and int((hr == -2).sum()) >= 500 and all((hr[k] != -1).any() for k in (0, 1, 2, 3, 5, 6))
+
+
+def test_the_scanners_walk_finds_what_brute_force_finds():
+    """walked_scan — the DRONES route of k_range_scan restated in float32 through the walker the camera's reference uses: the
+    binning, s_in / s_out, the INFINITY branches of a zero dx or dy, the 3 x 3 block, the newly adjacent column or row, the early
+    stop, the outside list — is restated_scan over all spheres BIT FOR BIT: the walk as designed loses no sphere, on axis beams,
+    with centres on cell borders, 4 km out, with lost drones on no list and over a doubled cell."""
+    t_min, t_max, rng = sf.STACK_LIMITS
+    for shift in ((0.0, 0.0), sf.FAR_SHIFT):
+        c = sf.case_stack(shift)
+        t32 = sf.restated_scan(c["st"], c["beams"], t_min, t_max, radius=c["rad"], drone_range=rng)
+        assert int(np.isfinite(t32).sum()) >= 2000
+        for box in (None, sf.stack_pinned_box(shift)):
+            assert np.array_equal(sf.walked_scan(c["st"], c["beams"], c["rad"], sf.scan_grid(c["st"], box), t_min, t_max, rng), t32), (shift, box)
+    c = sf.case_stack_lost()
+    t32 = sf.restated_scan(c["st"], c["beams"], t_min, t_max, radius=c["rad"], drone_range=rng)
+    assert np.isinf(t32[:, list(sf.STACK_LOST)]).all()
+    assert np.array_equal(sf.walked_scan(c["st"], c["beams"], c["rad"], sf.scan_grid(c["st"]), t_min, t_max, rng), t32)
+    c = sf.case_sparse()
+    t32 = sf.restated_scan(c["st"], c["beams"], t_min, sf.SPARSE_RANGE, radius=c["rad"], drone_range=sf.SPARSE_RANGE)
+    assert np.array_equal(sf.walked_scan(c["st"], c["beams"], c["rad"], sf.scan_grid(c["st"]), t_min, sf.SPARSE_RANGE, sf.SPARSE_RANGE), t32)
