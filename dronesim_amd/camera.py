@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from . import _native as nat
+from .drone_targets import DroneTargets, check_drone_args, offsets_tensor, require_targets
 from .obstacles import DeviceObstacles, DeviceScenes, ObstacleScenes, ObstacleSet, scene_ids_tensor
 
 
@@ -62,14 +63,7 @@ class DepthCamera:
             raise ValueError("every drone type needs arm > 0: it is the camera's height above the drone and its near plane")
         if len(ctx.types) > 1 and type_id is None:
             raise ValueError("type_id is required with several drone types")
-        if not drones and (drone_range is not None or drone_box is not None):
-            raise ValueError("drone_range / drone_box without drones=True")
-        if drone_range is not None and not float(drone_range) > 0.0:
-            raise ValueError("drone_range must be positive")
-        if drone_box is not None:
-            drone_box = tuple(float(v) for v in drone_box)
-            if len(drone_box) != 4 or not all(np.isfinite(drone_box)) or not (drone_box[0] <= drone_box[2] and drone_box[1] <= drone_box[3]):
-                raise ValueError("drone_box must be (xmin, ymin, xmax, ymax)")
+        drone_box = check_drone_args(drones, drone_range, drone_box)
         if obstacle_set is None and not drones:
             raise TypeError("obstacle_set takes an ObstacleSet or a DeviceObstacles (None only with drones=True)")
         self.ctx, self.state = ctx, state
@@ -102,34 +96,16 @@ class DepthCamera:
             n_cam = int(cams.size)
             self._index = torch.from_numpy((order.slot_np[cams] if order is not None else cams).astype(np.int32)).to(dev)
         self.n_cam = n_cam
-        self._off = None
-        if offsets is not None:
-            off = np.asarray(offsets, dtype=np.float64)
-            if off.shape != (n, 3):
-                raise ValueError(f"offsets must be [{n}, 3]")
-            if order is not None:
-                off = order.to_storage_np(off)
-            t = torch.zeros((3, state.n_pad), dtype=torch.float32)
-            t[:, :n] = torch.from_numpy(np.ascontiguousarray(off.T)).float()
-            self._off = t.to(dev)
+        self._off = offsets_tensor(offsets, n, state.n_pad, order, dev)
         self._type_id = type_id
         self.params = nat.CameraParams(w, h, float(fov), float(aspect), float(far),
                                        (nat.CAM_GROUND if ground else 0) | (nat.CAM_METRIC if metric else 0))
         self.dep = torch.empty((n_cam, h, w), dtype=torch.float32, device=dev)
         self.seg = torch.empty((n_cam, h, w), dtype=torch.int32, device=dev)
         self.drones = bool(drones)
-        if self.drones:
-            from .downwash import Downwash
-            self._grid = Downwash(ctx, state, type_id, None)     # the helper the contact watch bins with
-            self._drone_box = drone_box
-            # storage slot -> the caller's number (a type-major fleet): what seg names a drone by
-            self._label = torch.from_numpy(order.drone_np.astype(np.int32)).to(dev) if order is not None else None
-            self._outside = torch.zeros((1,), dtype=torch.int64, device=dev)
-            self._dr = nat.CameraDrones()
-            self._dr.radius_all = None
-            self._dr.label = self._label.data_ptr() if self._label is not None else None
-            self._dr.range = float(far if drone_range is None else drone_range)
-            self._dr.outside_out = self._outside.data_ptr()
+        self._targets = DroneTargets(ctx, state, type_id, order, far if drone_range is None else drone_range, drone_box) if drones else None
+        if drones:                                 # (kept under the names the tests reach for)
+            self._grid, self._outside, self._dr = self._targets.grid, self._targets.outside_count, self._targets.dr
 
     def capture(self, seg: bool = True):
         """Enqueues one dsim_depth_image (``drones=True``: dsim_depth_image_drones; scenes: dsim_depth_image_scenes) on the current stream (it may be captured into
@@ -138,8 +114,7 @@ class DepthCamera:
         common = (self._index.data_ptr() if self._index is not None else None, self._off.data_ptr() if self._off is not None else None,
                   self._type_id.data_ptr() if self._type_id is not None else None)
         if self.drones:
-            self._grid_args = self._grid.sphere_grid(self._drone_box)          # (kept: the struct outlives the call)
-            self._dr.grid = ctypes.addressof(self._grid_args)
+            self._grid_args = self._targets.grid_args()
             nat.check(self.ctx.lib.dsim_depth_image_drones(
                 self.ctx.handle, self.ctx.stream_ptr(), self.state.view(), self.set.handle if self.set is not None else None,
                 ctypes.byref(self.params), self.n_cam, *common, ctypes.byref(self._dr), self.dep.data_ptr(),
@@ -167,24 +142,20 @@ class DepthCamera:
     def refresh_drone_box(self) -> None:
         """Has the next eager capture re-measure the box of the drones' grid (no-op with ``drone_box``): for a caller that is about
         to capture a graph, whose captures keep the box and the workspace of the last eager one."""
-        if not self.drones:
-            raise ValueError("refresh_drone_box() needs a camera made with drones=True")
-        self._grid._box = None
+        require_targets(self._targets, "refresh_drone_box", "camera").refresh_box()
 
     def graph_keepalive(self):
         """What a captured capture() holds the addresses of, for the owner of the graph to keep alive: an eager capture that later
         re-measures the box and outgrows the drones' workspace makes a new one, and the old must outlive the graph."""
         keep = [self.dep, self.seg, self._index, self._off, self._type_id, self._scene_id]
         if self.drones:
-            keep += [self._grid._ws, self._label, self._outside]
+            keep += self._targets.keepalive()
         return tuple(keep)
 
     def drones_outside(self) -> int:
         """Drones x captures so far that were binned outside the grid's box (synchronises the stream): drawn all the same, but
         tested by every ray — a count that grows says the box (``drone_box``, or the one a graph was captured with) is stale."""
-        if not self.drones:
-            raise ValueError("drones_outside() needs a camera made with drones=True")
-        return int(self._outside.item())
+        return require_targets(self._targets, "drones_outside", "camera").outside()
 
     def close(self) -> None:
         if self._owns_set:

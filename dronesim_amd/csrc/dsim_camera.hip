@@ -1,7 +1,10 @@
 // Depth camera (dsim_depth_image, dsim_depth_image_drones): per-drone depth and segmentation images of the static obstacle set —
 // and, with the second entry point, of the other drones as their bounding spheres — one ray per pixel against
 // the set's RAY grid (dsim_obstacle_grid.h: ray_plan; include/dronesim_amd.h has the camera model).  Compiled as part of
-// dsim_obstacles.hip, which includes this file: it reads the set's private record (struct dsim_obstacles) and shares OBS_LDS_TRI.
+// dsim_obstacles.hip, which includes this file: it reads the set's private record (struct dsim_obstacles) and shares OBS_LDS_TRI and
+// obs_stage.  What the range scanner (dsim_scan.hip) shares with the camera is stated here once: the ray grid's record (RayGridK,
+// ray_grid_fill), the triangle walk (dsim_camera_walk.inc) and the walk of the drones' grid (dsim_camera_drones.inc), both as
+// text, the drone targets' record and host set-up (CamDr, cam_drones_fill) and the sphere test (cam_sphere).
 #pragma once
 
 #include <stdlib.h>
@@ -24,6 +27,17 @@ struct CamPl {
   int G, n_bodies;
 };
 
+// The set's ray grid as a kernel reads it (dsim_camera_walk.inc; zeroed: no set).  Its box is [o, hi].
+struct RayGridK {
+  const float4* rec;
+  const int* cell_start;
+  const int* cell_tri;
+  int n_tri;
+  float ox, oy, oz, cell, inv_cell;
+  int nx, ny, nz;
+  float hix, hiy, hiz;
+};
+
 struct CamK {
   KView st;
   long long n_pad;
@@ -32,13 +46,7 @@ struct CamK {
   const uint8_t* type_id;          // or null: type 0
   const DevType* types;
   int n_types;
-  const float4* rec;
-  const int* cell_start;
-  const int* cell_tri;
-  int n_tri;
-  float ox, oy, oz, cell, inv_cell;       // the ray grid
-  int nx, ny, nz;
-  float hix, hiy, hiz;                    // its box is [o, hi]
+  RayGridK rg;
   int W, H, bx;                           // image size; 16 x 16 blocks per image row
   unsigned blocks_per_cam;
   float inv_w, inv_h, th, tha, far;       // 1 / W, 1 / H, tan(fov / 2), ... x aspect
@@ -48,7 +56,7 @@ struct CamK {
 #ifdef DSIM_CAM_COUNT
   unsigned long long* tests;              // triangle tests, summed over every ray (a measuring build: tools/bench_camera.py)
 #endif
-  union {                                 // (at the end: the other instances' arguments lie where they lay)
+  union {
     CamDr dr;                             // DRONES instances only
     CamPl pl;                             // PLACED instances only (never both: scenes with drones are refused)
   };
@@ -78,13 +86,9 @@ __device__ __forceinline__ void cam_sphere(const float4 p, const int* __restrict
 // A lane slab-clips its ray against the grid's box, walks the cells by 3-D DDA (Amanatides & Woo, three named scalars per
 // quantity and selects: an array indexed by the stepping axis would live in scratch), tests the list of every cell with
 // Moller-Trumbore from the records (a, ab, ac; body in r3.w) and stops as soon as its best t is not beyond the cell's exit.
-// DRONES: behind the triangle walk the same lane walks the drone grid's xy cells by 2-D DDA from the eye in the WORLD frame
+// DRONES: behind the triangle walk the same lane walks the drones' grid (dsim_camera_drones.inc) from the eye in the WORLD frame
 // (p_i + (0, 0, L): the triangles and the plane keep the task frame p_i - offset_i; d is the same, so both t are eye-space depth
-// and share `best`).  Cells are 2 R_max or more: a sphere whose centre lies in a cell reaches into adjacent cells only, so the
-// spheres of the 3 x 3 block around the ray's cell are all that can be hit inside it — the whole block at the first cell, the
-// three newly adjacent cells after every step — and the walk stops as soon as best is not beyond the cell's exit.  The box the
-// ray is clipped to is the grid's grown by one ring of (empty) cells: a sphere of a border cell reaches outside the grid's box.
-// Then the outside list.  TRIS = false: no obstacle set (drones and, optionally, the plane).  PLACED (dsim_depth_image_scenes): the set is
+// and share `best`).  TRIS = false: no obstacle set (drones and, optionally, the plane).  PLACED (dsim_depth_image_scenes): the set is
 // a prototype, walked once per placement of the camera's scene in that placement's frame (dsim_camera_walk.inc is the walk, as
 // text, for both); the plane stays in the task frame.
 template <bool LDS, bool SEG, bool DRONES = false, bool TRIS = true, bool PLACED = false>
@@ -139,10 +143,7 @@ __global__ __launch_bounds__(256) void k_depth_image(CamK a) {
     return;
   }
   const float ux = sy * fz, uy = -(sx * fz), uz = sx * fy - sy * fx;        // u = s x f, s = (sx, sy, 0)
-  if (LDS) {                                                   // the whole set's records, once per workgroup (as the watch does)
-    for (int k = threadIdx.x; k < 4 * a.n_tri; k += 256) s_cam_rec[k] = a.rec[k];
-    __syncthreads();
-  }
+  if (LDS) obs_stage(s_cam_rec, a.rg.rec, a.rg.n_tri);         // the whole set's records, once per workgroup (as the watch does)
 
   // ---- the ray of this pixel -------------------------------------------------------------------------------------------------
   const float ca = (2.0f * ((float)col + 0.5f) * a.inv_w - 1.0f) * a.tha;
@@ -198,59 +199,8 @@ __global__ __launch_bounds__(256) void k_depth_image(CamK a) {
     }
   }
   if (DRONES) {
-    const SphereGrid& g = a.dr.g;
-    const float tmax = fminf(a.far, a.dr.range);
-    const float inv_a = 1.0f / (dx * dx + dy * dy + dz * dz);
-    const long long i_w = i + g.local_offset;
-    const int own = i_w < 0x7fffffffLL ? (int)i_w : -1;
-    const float gx0 = g.xmin - g.cell, gx1 = g.xmin + (float)(g.nx + 1) * g.cell;
-    const float gy0 = g.ymin - g.cell, gy1 = g.ymin + (float)(g.ny + 1) * g.cell;
-    const float sx0 = (gx0 - wx) * ix_, sx1 = (gx1 - wx) * ix_;
-    const float sy0 = (gy0 - wy) * iy_, sy1 = (gy1 - wy) * iy_;
-    const float s_in = fmaxf(fmaxf(fminf(sx0, sx1), fminf(sy0, sy1)), near);
-    const float s_out = fminf(fminf(fmaxf(sx0, sx1), fmaxf(sy0, sy1)), fminf(tmax, best));   // (starts from the triangle hit)
-    const bool in_x = dx != 0.0f || (wx >= gx0 && wx <= gx1);
-    const bool in_y = dy != 0.0f || (wy >= gy0 && wy <= gy1);
-    if (live && s_in <= s_out && in_x && in_y) {
-      // cell indices -1 .. nx (ny): the ring included; the blocks below are clamped to the cells that exist
-      const float qx = wx + s_in * dx, qy = wy + s_in * dy;
-      int cx = min(max((int)floorf((qx - gx0) * g.inv_cell), 0), g.nx + 1) - 1;
-      int cy = min(max((int)floorf((qy - gy0) * g.inv_cell), 0), g.ny + 1) - 1;
-      const int stx = dx > 0.0f ? 1 : -1, sty = dy > 0.0f ? 1 : -1;
-      const float dtx = dx != 0.0f ? g.cell * fabsf(ix_) : INFINITY;
-      const float dty = dy != 0.0f ? g.cell * fabsf(iy_) : INFINITY;
-      float tmx = dx != 0.0f ? (gx0 + (float)(cx + 1 + (dx > 0.0f ? 1 : 0)) * g.cell - wx) * ix_ : INFINITY;
-      float tmy = dy != 0.0f ? (gy0 + (float)(cy + 1 + (dy > 0.0f ? 1 : 0)) * g.cell - wy) * iy_ : INFINITY;
-      int bx0 = cx - 1, bx1 = cx + 1, by0 = cy - 1, by1 = cy + 1;           // the block to test: 3 x 3 at the first cell
-      const int max_cells = g.nx + g.ny + 4;
-      for (int it = 0; it < max_cells; ++it) {
-        const int xlo = max(bx0, 0), xhi = min(bx1, g.nx - 1), yhi = min(by1, g.ny - 1);
-        if (xlo <= xhi) {
-          for (int yy = max(by0, 0); yy <= yhi; ++yy) {                      // a row of the block is one run of sorted[]
-            const int end = g.cell_start[yy * g.nx + xhi + 1];
-            for (int k = g.cell_start[yy * g.nx + xlo]; k < end; ++k) {
-              cam_sphere(g.sorted[k], g.sidx, k, own, wx, wy, wz, dx, dy, dz, inv_a, near, tmax, best, body);
-#ifdef DSIM_CAM_COUNT
-              ++n_tests;
-#endif
-            }
-          }
-        }
-        const float t_exit = fminf(tmx, tmy);
-        if (best <= t_exit || t_exit >= s_out) break;          // nothing nearer can lie in a later cell / the ray leaves the box (dx = dy = 0: at once)
-        const bool gx = tmx <= tmy;
-        cx += gx ? stx : 0; cy += gx ? 0 : sty;
-        tmx += gx ? dtx : 0.0f; tmy += gx ? 0.0f : dty;
-        if (cx < -1 || cx > g.nx || cy < -1 || cy > g.ny) break;
-        bx0 = gx ? cx + stx : cx - 1; bx1 = gx ? cx + stx : cx + 1;          // the newly adjacent column or row
-        by0 = gx ? cy - 1 : cy + sty; by1 = gx ? cy + 1 : cy + sty;
-      }
-    }
-    if (live) {                                                // drones outside the grid's box: every ray, the list is short
-      const int n_out = *g.outside_n;
-      for (int k = 0; k < n_out; ++k)
-        cam_sphere(g.outside[k], g.outside_idx, k, own, wx, wy, wz, dx, dy, dz, inv_a, near, tmax, best, body);
-    }
+#define CD_GATE live
+#include "dsim_camera_drones.inc"
   }
   if (live) {
     const bool got = best < INFINITY;
@@ -270,6 +220,29 @@ __global__ __launch_bounds__(256) void k_depth_image(CamK a) {
 static unsigned long long* g_cam_tests = nullptr;              // device counter of the measuring build
 #endif
 
+// the ray grid of a set with rays enabled, as the kernels read it
+static void ray_grid_fill(const dsim_obstacles* set, RayGridK* r) {
+  const dsim_obstacle_grid& g = set->ray_grid;
+  r->rec = set->rec; r->cell_start = set->ray_start; r->cell_tri = set->ray_tri; r->n_tri = set->n_tri;
+  r->ox = g.origin[0]; r->oy = g.origin[1]; r->oz = g.origin[2]; r->cell = g.cell; r->inv_cell = 1.0f / g.cell;
+  r->nx = g.nx; r->ny = g.ny; r->nz = g.nz; r->hix = g.hi[0]; r->hiy = g.hi[1]; r->hiz = g.hi[2];
+}
+
+// The drone targets of a call (dsim_depth_image_drones, dsim_range_scan): the caller's record checked, the fleet binned on the
+// stream (dsim_sphere_grid_build) and the kernel's record filled.  Called once the sensor's own arguments have passed: a call that is
+// refused for them has binned nothing.
+static int cam_drones_fill(dsim_ctx* ctx, hipStream_t st_, const dsim_view& state, const dsim_camera_drones* drones, CamDr* out) {
+  if (!drones || !drones->grid || !(drones->range > 0.0f)) return DSIM_E_ARG;
+  const dsim_downwash_args* g = drones->grid;
+  if (g->halo) return DSIM_E_UNSUPPORTED;
+  // the drones of the state block among the world's: all of them (pos_all NULL), or those from local_offset on
+  const int64_t m = g->pos_all ? (g->m - g->local_offset < state.n_pad ? g->m - g->local_offset : state.n_pad) : g->m;
+  const int rc = dsim_sphere_grid_build(ctx, st_, m, state, g, drones->radius_all, (unsigned long long*)drones->outside_out, &out->g);
+  if (rc) return rc;
+  out->label = drones->label; out->range = drones->range;
+  return DSIM_OK;
+}
+
 // the arguments both entry points share, checked and laid out for the kernel; set = null (dsim_depth_image_drones): no triangles
 static int cam_fill(dsim_ctx* ctx, const dsim_view& state, const dsim_obstacles* set, const dsim_camera_params* params, int64_t n_cam,
                     const int32_t* cam_index, const float* offset, const uint8_t* type_id, float* depth_out, int32_t* seg_out,
@@ -288,12 +261,7 @@ static int cam_fill(dsim_ctx* ctx, const dsim_view& state, const dsim_obstacles*
   if (rc) return rc;
   a.n_pad = state.n_pad; a.cam_index = cam_index; a.offset = offset; a.type_id = type_id;
   a.types = ctx->d_types; a.n_types = ctx->n_types;
-  if (set) {
-    const dsim_obstacle_grid& g = set->ray_grid;
-    a.rec = set->rec; a.cell_start = set->ray_start; a.cell_tri = set->ray_tri; a.n_tri = set->n_tri;
-    a.ox = g.origin[0]; a.oy = g.origin[1]; a.oz = g.origin[2]; a.cell = g.cell; a.inv_cell = 1.0f / g.cell;
-    a.nx = g.nx; a.ny = g.ny; a.nz = g.nz; a.hix = g.hi[0]; a.hiy = g.hi[1]; a.hiz = g.hi[2];
-  }
+  if (set) ray_grid_fill(set, &a.rg);
   a.W = p.width; a.H = p.height; a.bx = (p.width + 15) / 16;
   a.blocks_per_cam = (unsigned)(a.bx * ((p.height + 15) / 16));
   a.inv_w = 1.0f / (float)p.width; a.inv_h = 1.0f / (float)p.height;
@@ -379,19 +347,13 @@ int64_t dsim_depth_image_drones_workspace(int64_t m, int32_t nx, int32_t ny) {
 int dsim_depth_image_drones(dsim_ctx* ctx, void* stream, dsim_view state, const dsim_obstacles* set, const dsim_camera_params* params,
                             int64_t n_cam, const int32_t* cam_index, const float* offset, const uint8_t* type_id,
                             const dsim_camera_drones* drones, float* depth_out, int32_t* seg_out) {
-  if (!drones || !drones->grid || !(drones->range > 0.0f)) return DSIM_E_ARG;
   CamK a;
   int64_t blocks;
   int rc = cam_fill(ctx, state, set, params, n_cam, cam_index, offset, type_id, depth_out, seg_out, &a, &blocks);
   if (rc) return rc;
-  const dsim_downwash_args* g = drones->grid;
-  if (g->halo) return DSIM_E_UNSUPPORTED;
-  // the drones of the state block among the world's: all of them (pos_all NULL), or those from local_offset on
-  const int64_t n = g->pos_all ? (g->m - g->local_offset < state.n_pad ? g->m - g->local_offset : state.n_pad) : g->m;
   const hipStream_t st_ = (hipStream_t)stream;
-  rc = dsim_sphere_grid_build(ctx, st_, n, state, g, drones->radius_all, (unsigned long long*)drones->outside_out, &a.dr.g);
+  rc = cam_drones_fill(ctx, st_, state, drones, &a.dr);
   if (rc) return rc;
-  a.dr.label = drones->label; a.dr.range = drones->range;
   const bool tris = set != nullptr, lds = tris && set->n_tri <= OBS_LDS_TRI;
   const size_t shm = lds ? (size_t)set->n_tri * 64 : 0;
   const dim3 gr((unsigned)blocks), tb(256);

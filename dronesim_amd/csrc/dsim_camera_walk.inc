@@ -1,37 +1,40 @@
-// The triangle walk of k_depth_image (dsim_camera.hip), as text: the kernel includes it once at its own scope for the set in the task
-// frame and once per placement of a scene (PLACED), so that one walk serves both and the unplaced instances keep the very
-// statements they were compiled from.  The includer defines the ray CW_EX .. CW_DZ (origin and direction in the frame the grid lies
-// in: t is eye-space depth in every frame), CW_GATE (the compile-time part of the walk's condition) and CW_BODY(rb) (what a hit
-// reports for the triangle's body rb); `a`, `live`, `near`, `best`, `body`, `s_cam_rec` and LDS are the kernel's.
+// The triangle walk of k_depth_image (dsim_camera.hip) and k_range_scan (dsim_scan.hip), as text: a kernel includes it once for the
+// set in the task frame and once per placement of a scene (PLACED).  Text, not a function: as a function it compiled to other
+// branch and compare sequences (DESIGN.md, "Placed camera").  The includer defines the ray CW_EX .. CW_DZ (origin and direction in
+// the frame the grid lies in: t is the same in every frame), CW_GATE (the compile-time part of the walk's condition) and
+// CW_BODY(rb) (what a hit reports for the triangle's body rb); `a.rg` (RayGridK), `a.far`, `live`, `near`, `best`, `body`,
+// `s_cam_rec` and LDS are the kernel's (and `n_tests` in the counting build).  It is a block of its own: it declares nothing that
+// outlives it, and it undefines the CW_ names.
+{
   // slab clip against [o, hi]; a zero component gives +-inf (or NaN at a face, which fminf / fmaxf drop)
   const float ix_ = 1.0f / CW_DX, iy_ = 1.0f / CW_DY, iz_ = 1.0f / CW_DZ;
-  const float x0 = (a.ox - CW_EX) * ix_, x1 = (a.hix - CW_EX) * ix_;
-  const float y0 = (a.oy - CW_EY) * iy_, y1 = (a.hiy - CW_EY) * iy_;
-  const float z0 = (a.oz - CW_EZ) * iz_, z1 = (a.hiz - CW_EZ) * iz_;
+  const float x0 = (a.rg.ox - CW_EX) * ix_, x1 = (a.rg.hix - CW_EX) * ix_;
+  const float y0 = (a.rg.oy - CW_EY) * iy_, y1 = (a.rg.hiy - CW_EY) * iy_;
+  const float z0 = (a.rg.oz - CW_EZ) * iz_, z1 = (a.rg.hiz - CW_EZ) * iz_;
   const float t_in = fmaxf(fmaxf(fminf(x0, x1), fminf(y0, y1)), fmaxf(fminf(z0, z1), near));
   const float t_out = fminf(fminf(fmaxf(x0, x1), fmaxf(y0, y1)), fminf(fmaxf(z0, z1), fminf(a.far, best)));
-  const bool inside_x = CW_DX != 0.0f || (CW_EX >= a.ox && CW_EX <= a.hix);          // a ray parallel to a slab and outside it misses
-  const bool inside_y = CW_DY != 0.0f || (CW_EY >= a.oy && CW_EY <= a.hiy);
-  const bool inside_z = CW_DZ != 0.0f || (CW_EZ >= a.oz && CW_EZ <= a.hiz);
+  const bool inside_x = CW_DX != 0.0f || (CW_EX >= a.rg.ox && CW_EX <= a.rg.hix);    // a ray parallel to a slab and outside it misses
+  const bool inside_y = CW_DY != 0.0f || (CW_EY >= a.rg.oy && CW_EY <= a.rg.hiy);
+  const bool inside_z = CW_DZ != 0.0f || (CW_EZ >= a.rg.oz && CW_EZ <= a.rg.hiz);
   if (CW_GATE && live && t_in <= t_out && inside_x && inside_y && inside_z) {
     // the cell of the entry point, clamped; per axis the direction of travel, t at the next face and t per cell
     const float qx = CW_EX + t_in * CW_DX, qy = CW_EY + t_in * CW_DY, qz = CW_EZ + t_in * CW_DZ;
-    int cx = min(max((int)floorf((qx - a.ox) * a.inv_cell), 0), a.nx - 1);
-    int cy = min(max((int)floorf((qy - a.oy) * a.inv_cell), 0), a.ny - 1);
-    int cz = min(max((int)floorf((qz - a.oz) * a.inv_cell), 0), a.nz - 1);
+    int cx = min(max((int)floorf((qx - a.rg.ox) * a.rg.inv_cell), 0), a.rg.nx - 1);
+    int cy = min(max((int)floorf((qy - a.rg.oy) * a.rg.inv_cell), 0), a.rg.ny - 1);
+    int cz = min(max((int)floorf((qz - a.rg.oz) * a.rg.inv_cell), 0), a.rg.nz - 1);
     const int stx = CW_DX > 0.0f ? 1 : -1, sty = CW_DY > 0.0f ? 1 : -1, stz = CW_DZ > 0.0f ? 1 : -1;
-    const float dtx = CW_DX != 0.0f ? a.cell * fabsf(ix_) : INFINITY;
-    const float dty = CW_DY != 0.0f ? a.cell * fabsf(iy_) : INFINITY;
-    const float dtz = CW_DZ != 0.0f ? a.cell * fabsf(iz_) : INFINITY;
-    float tmx = CW_DX != 0.0f ? (a.ox + (float)(cx + (CW_DX > 0.0f ? 1 : 0)) * a.cell - CW_EX) * ix_ : INFINITY;
-    float tmy = CW_DY != 0.0f ? (a.oy + (float)(cy + (CW_DY > 0.0f ? 1 : 0)) * a.cell - CW_EY) * iy_ : INFINITY;
-    float tmz = CW_DZ != 0.0f ? (a.oz + (float)(cz + (CW_DZ > 0.0f ? 1 : 0)) * a.cell - CW_EZ) * iz_ : INFINITY;
-    const int max_cells = a.nx + a.ny + a.nz;                  // a walk visits fewer: every step moves one cell along one axis
+    const float dtx = CW_DX != 0.0f ? a.rg.cell * fabsf(ix_) : INFINITY;
+    const float dty = CW_DY != 0.0f ? a.rg.cell * fabsf(iy_) : INFINITY;
+    const float dtz = CW_DZ != 0.0f ? a.rg.cell * fabsf(iz_) : INFINITY;
+    float tmx = CW_DX != 0.0f ? (a.rg.ox + (float)(cx + (CW_DX > 0.0f ? 1 : 0)) * a.rg.cell - CW_EX) * ix_ : INFINITY;
+    float tmy = CW_DY != 0.0f ? (a.rg.oy + (float)(cy + (CW_DY > 0.0f ? 1 : 0)) * a.rg.cell - CW_EY) * iy_ : INFINITY;
+    float tmz = CW_DZ != 0.0f ? (a.rg.oz + (float)(cz + (CW_DZ > 0.0f ? 1 : 0)) * a.rg.cell - CW_EZ) * iz_ : INFINITY;
+    const int max_cells = a.rg.nx + a.rg.ny + a.rg.nz;         // a walk visits fewer: every step moves one cell along one axis
     for (int it = 0; it < max_cells; ++it) {
-      const int c = (cz * a.ny + cy) * a.nx + cx;
-      const int end = a.cell_start[c + 1];
-      for (int k = a.cell_start[c]; k < end; ++k) {
-        const float4* r = (LDS ? s_cam_rec : a.rec) + 4 * a.cell_tri[k];
+      const int c = (cz * a.rg.ny + cy) * a.rg.nx + cx;
+      const int end = a.rg.cell_start[c + 1];
+      for (int k = a.rg.cell_start[c]; k < end; ++k) {
+        const float4* r = (LDS ? s_cam_rec : a.rg.rec) + 4 * a.rg.cell_tri[k];
         const float4 r0 = r[0], r1 = r[1];
         const float acz = r[2].x;
         const int rb = __float_as_int(r[3].w);
@@ -58,9 +61,10 @@
       const bool gz = !gx && !gy;
       cx += gx ? stx : 0; cy += gy ? sty : 0; cz += gz ? stz : 0;
       tmx += gx ? dtx : 0.0f; tmy += gy ? dty : 0.0f; tmz += gz ? dtz : 0.0f;
-      if (cx < 0 || cx >= a.nx || cy < 0 || cy >= a.ny || cz < 0 || cz >= a.nz) break;
+      if (cx < 0 || cx >= a.rg.nx || cy < 0 || cy >= a.rg.ny || cz < 0 || cz >= a.rg.nz) break;
     }
   }
+}
 #undef CW_EX
 #undef CW_EY
 #undef CW_EZ

@@ -58,6 +58,13 @@ struct ObsK {
   unsigned long long* contacts_out;
 };
 
+// The whole set's records into LDS, by the 256 lanes of a workgroup (the watches, the camera and the scanner: sets of up to
+// OBS_LDS_TRI triangles).  Every lane of the workgroup calls it, under a uniform condition that is the caller's: it ends in a barrier.
+__device__ __forceinline__ void obs_stage(float4* s_rec, const float4* rec, int n_tri) {
+  for (int k = threadIdx.x; k < 4 * n_tri; k += 256) s_rec[k] = rec[k];
+  __syncthreads();
+}
+
 // Squared distance from q to one triangle record (Ericson, Real-Time Collision Detection 5.1.5, without branches: every lane of a
 // wave meets another region).  The vertex and edge regions give barycentric (v, w) of the closest point and the distance to it;
 // in the face region the distance is |n . ap| with the record's unit normal, which does not lose digits in the quotient
@@ -137,8 +144,7 @@ __global__ __launch_bounds__(256) void k_obstacle_clearance(ObsK a) {
     const bool inbox = live && R > 0.0f && qx >= a.lox && qx <= a.hix && qy >= a.loy && qy <= a.hiy && qz >= a.loz && qz <= a.hiz;
     if (LDS) {
       if (!staged && __syncthreads_or(inbox ? 1 : 0)) {
-        for (int k = threadIdx.x; k < 4 * a.n_tri; k += 256) s_rec[k] = a.rec[k];
-        __syncthreads();
+        obs_stage(s_rec, a.rec, a.n_tri);
         staged = true;
       }
     }

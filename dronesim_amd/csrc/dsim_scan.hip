@@ -3,21 +3,16 @@
 // the ray).  The camera's kernel maps a workgroup onto a 16 x 16 pixel block of ONE camera and keeps the pose in scalar registers:
 // at 8 .. 64 rays per drone that is 256 lanes for at most 64 rays and one pose read per workgroup.  Here the mapping is the
 // watches': one drone per lane, tiles of 256 walked grid-stride, the pose loaded coalesced once, the lane loops over the beams.
-// Compiled as part of dsim_obstacles.hip, which includes this file: it reads the set's and the scenes' private records, the
-// camera's triangle walk (dsim_camera_walk.inc, as it is), its sphere test (cam_sphere) and its argument records CamPl / CamDr.
+// Compiled as part of dsim_obstacles.hip, which includes this file: it reads the set's and the scenes' private records and uses
+// what dsim_camera.hip states for both sensors: the ray grid's record, the triangle walk (dsim_camera_walk.inc), the walk of the
+// drones' grid (dsim_camera_drones.inc), the drone targets' host set-up (cam_drones_fill) and the argument records CamPl / CamDr.
 #pragma once
 
 struct ScanK {
   KView st;
   long long n, n_pad, tiles;
   const float* offset;             // SoA [3][n_pad] or null
-  const float4* rec;
-  const int* cell_start;
-  const int* cell_tri;
-  int n_tri;
-  float ox, oy, oz, cell, inv_cell;       // the ray grid (the names dsim_camera_walk.inc reads)
-  int nx, ny, nz;
-  float hix, hiy, hiz;
+  RayGridK rg;
   float far, t_min;                       // t_max (`far`: the walk's name for it) and t_min
   unsigned flags;
   const float* beams;                     // [n_beams][3]
@@ -32,8 +27,8 @@ struct ScanK {
 // One drone per lane.  Per tile a lane reads its position, quaternion and offset through the view (coalesced in both layouts),
 // forms R(q) once (nine registers) and walks the beams: the table is wave-uniform and comes through the scalar path, d = R beam,
 // and outputs are beam-major, so every store is a coalesced row.  Per beam: the plane, then the triangle walk of the camera
-// (dsim_camera_walk.inc) — once in the task frame, or once per placement of the lane's scene — then the 2-D walk of the drones'
-// grid from the WORLD-frame origin, as k_depth_image<DRONES> does it; `best` and `body` carry through all of them.
+// (dsim_camera_walk.inc) — once in the task frame, or once per placement of the lane's scene — then the camera's walk of the
+// drones' grid (dsim_camera_drones.inc) from the WORLD-frame origin; `best` and `body` carry through all of them.
 // A lane whose pose is undefined (a non-finite position or R: every such value fails a comparison) casts nothing and reports
 // misses; so does a beam that is zero or not finite.  No lane returns early: the workgroup meets at the staging barrier.
 // A fleet too small to fill the device with one workgroup per tile spreads chunks of the beams over blockIdx.y (scan_beams_per_block: the
@@ -45,6 +40,9 @@ template <bool LDS, bool PLACED, bool DRONES, bool TRIS>
 __global__ __launch_bounds__(256) void k_range_scan(ScanK a) {
   extern __shared__ float4 s_cam_rec[];
   const float near = a.t_min;
+#ifdef DSIM_CAM_COUNT
+  unsigned n_tests = 0u;           // the walk's text counts into it; the measuring build reports the camera's tests only
+#endif
   const float miss = (a.flags & DSIM_SCAN_CLAMP) != 0u ? a.far : INFINITY;
   const bool ground = (a.flags & DSIM_SCAN_GROUND) != 0u;
   // how far a beam reaches (uniform): t_max times the longest beam of the table (a non-finite beam casts nothing)
@@ -88,8 +86,8 @@ __global__ __launch_bounds__(256) void k_range_scan(ScanK a) {
     unsigned reach_pl = 0u;                                    // PLACED: one bit per placement of the lane's scene
     const float4* pl = a.pl.place;
     if (TRIS && !PLACED && defined) {
-      const float bx = fmaxf(fmaxf(a.ox - ex, ex - a.hix), 0.0f), by = fmaxf(fmaxf(a.oy - ey, ey - a.hiy), 0.0f);
-      const float bz = fmaxf(fmaxf(a.oz - ez, ez - a.hiz), 0.0f);
+      const float bx = fmaxf(fmaxf(a.rg.ox - ex, ex - a.rg.hix), 0.0f), by = fmaxf(fmaxf(a.rg.oy - ey, ey - a.rg.hiy), 0.0f);
+      const float bz = fmaxf(fmaxf(a.rg.oz - ez, ez - a.rg.hiz), 0.0f);
       const float rr = reach + 1e-4f * (fabsf(ex) + fabsf(ey) + fabsf(ez));
       reach_set = bx * bx + by * by + bz * bz <= rr * rr;
     }
@@ -104,8 +102,7 @@ __global__ __launch_bounds__(256) void k_range_scan(ScanK a) {
     }
     if (LDS) {
       if (!staged && __syncthreads_or((reach_set || reach_pl != 0u) ? 1 : 0)) {
-        for (int k = threadIdx.x; k < 4 * a.n_tri; k += 256) s_cam_rec[k] = a.rec[k];
-        __syncthreads();
+        obs_stage(s_cam_rec, a.rg.rec, a.rg.n_tri);
         staged = true;
       }
     }
@@ -124,9 +121,8 @@ __global__ __launch_bounds__(256) void k_range_scan(ScanK a) {
         const float tg = -ez / dz;                             // (dz = 0: +-inf or NaN, which fail the test)
         if (tg >= near && tg <= a.far) { best = tg; body = DSIM_SEG_GROUND; }
       }
-      {
-        const bool live = ray && reach_set;
-        // the set in the task frame (every instance with triangles but the PLACED ones)
+      const bool live = ray && reach_set;
+      // the set in the task frame (every instance with triangles but the PLACED ones)
 #define CW_EX ex
 #define CW_EY ey
 #define CW_EZ ez
@@ -136,7 +132,6 @@ __global__ __launch_bounds__(256) void k_range_scan(ScanK a) {
 #define CW_GATE (TRIS && !PLACED)
 #define CW_BODY(rb) rb
 #include "dsim_camera_walk.inc"
-      }
       if (PLACED) {
         // The ray into each placement's frame, subtract first, then rotate; t does not change, so best and body carry across
         // placements and bound every later walk.  A ray that passes the placement's cull sphere by (widened: speed only) is
@@ -169,59 +164,9 @@ __global__ __launch_bounds__(256) void k_range_scan(ScanK a) {
 #include "dsim_camera_walk.inc"
         }
       }
-      if (DRONES) {
-        // the 2-D walk of k_depth_image's DRONES block, from the stored position in the world frame (see there for why the 3 x 3
-        // block at the first cell and the newly adjacent column or row after every step are all that can be hit)
-        const SphereGrid& g = a.dr.g;
-        const float tmax = fminf(a.far, a.dr.range);
-        const float inv_a = 1.0f / (dx * dx + dy * dy + dz * dz);
-        const float jx_ = 1.0f / dx, jy_ = 1.0f / dy;
-        const long long i_w = i + g.local_offset;
-        const int own = i_w < 0x7fffffffLL ? (int)i_w : -1;
-        const float gx0 = g.xmin - g.cell, gx1 = g.xmin + (float)(g.nx + 1) * g.cell;
-        const float gy0 = g.ymin - g.cell, gy1 = g.ymin + (float)(g.ny + 1) * g.cell;
-        const float sx0 = (gx0 - wx) * jx_, sx1 = (gx1 - wx) * jx_;
-        const float sy0 = (gy0 - wy) * jy_, sy1 = (gy1 - wy) * jy_;
-        const float s_in = fmaxf(fmaxf(fminf(sx0, sx1), fminf(sy0, sy1)), near);
-        const float s_out = fminf(fminf(fmaxf(sx0, sx1), fmaxf(sy0, sy1)), fminf(tmax, best));   // (starts from the triangle hit)
-        const bool in_x = dx != 0.0f || (wx >= gx0 && wx <= gx1);
-        const bool in_y = dy != 0.0f || (wy >= gy0 && wy <= gy1);
-        if (ray && s_in <= s_out && in_x && in_y) {
-          // cell indices -1 .. nx (ny): the ring included; the blocks below are clamped to the cells that exist
-          const float px = wx + s_in * dx, py = wy + s_in * dy;
-          int cx = min(max((int)floorf((px - gx0) * g.inv_cell), 0), g.nx + 1) - 1;
-          int cy = min(max((int)floorf((py - gy0) * g.inv_cell), 0), g.ny + 1) - 1;
-          const int stx = dx > 0.0f ? 1 : -1, sty = dy > 0.0f ? 1 : -1;
-          const float dtx = dx != 0.0f ? g.cell * fabsf(jx_) : INFINITY;
-          const float dty = dy != 0.0f ? g.cell * fabsf(jy_) : INFINITY;
-          float tmx = dx != 0.0f ? (gx0 + (float)(cx + 1 + (dx > 0.0f ? 1 : 0)) * g.cell - wx) * jx_ : INFINITY;
-          float tmy = dy != 0.0f ? (gy0 + (float)(cy + 1 + (dy > 0.0f ? 1 : 0)) * g.cell - wy) * jy_ : INFINITY;
-          int bx0 = cx - 1, bx1 = cx + 1, by0 = cy - 1, by1 = cy + 1;           // the block to test: 3 x 3 at the first cell
-          const int max_cells = g.nx + g.ny + 4;
-          for (int it = 0; it < max_cells; ++it) {
-            const int xlo = max(bx0, 0), xhi = min(bx1, g.nx - 1), yhi = min(by1, g.ny - 1);
-            if (xlo <= xhi) {
-              for (int yy = max(by0, 0); yy <= yhi; ++yy) {                      // a row of the block is one run of sorted[]
-                const int end = g.cell_start[yy * g.nx + xhi + 1];
-                for (int k = g.cell_start[yy * g.nx + xlo]; k < end; ++k)
-                  cam_sphere(g.sorted[k], g.sidx, k, own, wx, wy, wz, dx, dy, dz, inv_a, near, tmax, best, body);
-              }
-            }
-            const float t_exit = fminf(tmx, tmy);
-            if (best <= t_exit || t_exit >= s_out) break;      // nothing nearer can lie in a later cell / the ray leaves the box
-            const bool gx = tmx <= tmy;
-            cx += gx ? stx : 0; cy += gx ? 0 : sty;
-            tmx += gx ? dtx : 0.0f; tmy += gx ? 0.0f : dty;
-            if (cx < -1 || cx > g.nx || cy < -1 || cy > g.ny) break;
-            bx0 = gx ? cx + stx : cx - 1; bx1 = gx ? cx + stx : cx + 1;          // the newly adjacent column or row
-            by0 = gx ? cy - 1 : cy + sty; by1 = gx ? cy + 1 : cy + sty;
-          }
-        }
-        if (ray) {                                             // drones outside the grid's box: every ray, the list is short
-          const int n_out = *g.outside_n;
-          for (int k = 0; k < n_out; ++k)
-            cam_sphere(g.outside[k], g.outside_idx, k, own, wx, wy, wz, dx, dy, dz, inv_a, near, tmax, best, body);
-        }
+      if (DRONES) {                                            // from the stored position in the world frame
+#define CD_GATE ray
+#include "dsim_camera_drones.inc"
       }
       if (lane) {
         const bool got = best < INFINITY;
@@ -261,36 +206,20 @@ int dsim_range_scan(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, con
   const dsim_obstacles* tris = s.scenes ? s.scenes->proto : set;
   if (tris && !tris->ray_start) return DSIM_E_ARG;
   if (!tris && !s.drones && !(s.flags & DSIM_SCAN_GROUND)) return DSIM_E_ARG;
-  if (s.drones) {
-    if (!s.drones->grid || !(s.drones->range > 0.0f)) return DSIM_E_ARG;
-    if (ctx->n_types > 1 && !s.type_id) return DSIM_E_ARG;
-    if (s.drones->grid->halo) return DSIM_E_UNSUPPORTED;
-  }
+  if (s.drones && ctx->n_types > 1 && !s.type_id) return DSIM_E_ARG;
   ScanK a;
   memset(&a, 0, sizeof(a));
   int rc = make_kview(state, 7, &a.st);
   if (rc) return rc;
   a.n = n; a.n_pad = state.n_pad; a.tiles = (n + 255) / 256; a.offset = s.offset;
-  if (tris) {
-    const dsim_obstacle_grid& g = tris->ray_grid;
-    a.rec = tris->rec; a.cell_start = tris->ray_start; a.cell_tri = tris->ray_tri; a.n_tri = tris->n_tri;
-    a.ox = g.origin[0]; a.oy = g.origin[1]; a.oz = g.origin[2]; a.cell = g.cell; a.inv_cell = 1.0f / g.cell;
-    a.nx = g.nx; a.ny = g.ny; a.nz = g.nz; a.hix = g.hi[0]; a.hiy = g.hi[1]; a.hiz = g.hi[2];
-  }
+  if (tris) ray_grid_fill(tris, &a.rg);
   a.far = s.t_max; a.t_min = s.t_min; a.flags = s.flags; a.beams = s.beams; a.n_beams = s.n_beams;
   a.range = s.range_out; a.hit = s.hit_out;
   if (s.scenes) {
     a.pl.place = s.scenes->place; a.pl.scene_id = s.scene_id; a.pl.K = s.scenes->K; a.pl.G = s.scenes->G; a.pl.n_bodies = tris->n_bodies;
   }
   const hipStream_t st_ = (hipStream_t)stream;
-  if (s.drones) {
-    // the drones of the state block among the world's: all of them (pos_all NULL), or those from local_offset on
-    const dsim_downwash_args* g = s.drones->grid;
-    const int64_t m = g->pos_all ? (g->m - g->local_offset < state.n_pad ? g->m - g->local_offset : state.n_pad) : g->m;
-    rc = dsim_sphere_grid_build(ctx, st_, m, state, g, s.drones->radius_all, (unsigned long long*)s.drones->outside_out, &a.dr.g);
-    if (rc) return rc;
-    a.dr.label = s.drones->label; a.dr.range = s.drones->range;
-  }
+  if (s.drones && (rc = cam_drones_fill(ctx, st_, state, s.drones, &a.dr)) != 0) return rc;
   const bool placed = s.scenes != nullptr, dr = s.drones != nullptr, lds = tris && tris->n_tri <= OBS_LDS_TRI;
   const size_t shm = lds ? (size_t)tris->n_tri * 64 : 0;
   a.beams_per_block = scan_beams_per_block(a.tiles, a.n_beams);

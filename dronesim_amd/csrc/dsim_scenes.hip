@@ -52,8 +52,7 @@ __global__ __launch_bounds__(256) void k_obstacle_clearance_scenes(ObsK a, ScnK 
     }
     if (LDS) {
       if (!staged && __syncthreads_or(near != 0u ? 1 : 0)) {
-        for (int k = threadIdx.x; k < 4 * a.n_tri; k += 256) s_rec[k] = a.rec[k];
-        __syncthreads();
+        obs_stage(s_rec, a.rec, a.n_tri);
         staged = true;
       }
     }

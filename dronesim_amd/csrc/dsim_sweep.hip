@@ -111,8 +111,7 @@ __global__ __launch_bounds__(256) void k_obstacle_sweep(SweepK w) {
                           fmaxf(q0y, q1y) >= a.loy && fminf(q0z, q1z) <= a.hiz && fmaxf(q0z, q1z) >= a.loz;
     if (LDS) {
       if (!staged && __syncthreads_or(near_box ? 1 : 0)) {
-        for (int k = threadIdx.x; k < 4 * a.n_tri; k += 256) s_rec[k] = a.rec[k];
-        __syncthreads();
+        obs_stage(s_rec, a.rec, a.n_tri);
         staged = true;
       }
     }

@@ -14,6 +14,7 @@ import torch
 
 from . import _native as nat
 from .camera import camera_reach
+from .drone_targets import DroneTargets, check_drone_args, offsets_tensor, require_targets
 from .obstacles import DeviceObstacles, DeviceScenes, ObstacleScenes, ObstacleSet, scene_ids_tensor
 
 MAX_BEAMS = 64
@@ -55,14 +56,7 @@ class RangeScanner:
                  scene_id=None, drones=False, drone_range=None, drone_box=None):
         b32 = unit_beams(beams)
         check_range(t_min, t_max)
-        if not drones and (drone_range is not None or drone_box is not None):
-            raise ValueError("drone_range / drone_box without drones=True")
-        if drone_range is not None and not float(drone_range) > 0.0:
-            raise ValueError("drone_range must be positive")
-        if drone_box is not None:
-            drone_box = tuple(float(v) for v in drone_box)
-            if len(drone_box) != 4 or not all(np.isfinite(drone_box)) or not (drone_box[0] <= drone_box[2] and drone_box[1] <= drone_box[3]):
-                raise ValueError("drone_box must be (xmin, ymin, xmax, ymax)")
+        drone_box = check_drone_args(drones, drone_range, drone_box)
         if world is None and not (drones or ground):
             raise ValueError("no world at all: world=None needs drones=True or ground=True")
         if world is not None and not isinstance(world, (ObstacleSet, DeviceObstacles, ObstacleScenes, DeviceScenes)):
@@ -86,34 +80,16 @@ class RangeScanner:
         self.beams = b32
         self._beams = torch.from_numpy(b32).to(dev)
         self._scene_id = scene_ids_tensor(scene_id, n, state.n_pad, dev, order) if self.placed else None
-        self._off = None
-        if offsets is not None:
-            off = np.asarray(offsets, dtype=np.float64)
-            if off.shape != (n, 3):
-                raise ValueError(f"offsets must be [{n}, 3]")
-            if order is not None:
-                off = order.to_storage_np(off)
-            t = torch.zeros((3, state.n_pad), dtype=torch.float32)
-            t[:, :n] = torch.from_numpy(np.ascontiguousarray(off.T)).float()
-            self._off = t.to(dev)
+        self._off = offsets_tensor(offsets, n, state.n_pad, order, dev)
         self._type_id = type_id
         self._slot = torch.from_numpy(order.slot_np.astype(np.int64)).to(dev) if order is not None else None
         self.range_out = torch.full((self.n_beams, state.n_pad), float("inf"), dtype=torch.float32, device=dev)
         self.hit_out = torch.full((self.n_beams, state.n_pad), -1, dtype=torch.int32, device=dev)
         self.drones = bool(drones)
         self._dr = None
-        if self.drones:
-            from .downwash import Downwash
-            self._grid = Downwash(ctx, state, type_id, None)     # the helper the contact watch bins with
-            self._drone_box = drone_box
-            # storage slot -> the caller's number (a type-major fleet): what hit_out names a drone by
-            self._label = torch.from_numpy(order.drone_np.astype(np.int32)).to(dev) if order is not None else None
-            self._outside = torch.zeros((1,), dtype=torch.int64, device=dev)
-            self._dr = nat.CameraDrones()
-            self._dr.radius_all = None
-            self._dr.label = self._label.data_ptr() if self._label is not None else None
-            self._dr.range = float(t_max if drone_range is None else drone_range)
-            self._dr.outside_out = self._outside.data_ptr()
+        self._targets = DroneTargets(ctx, state, type_id, order, t_max if drone_range is None else drone_range, drone_box) if drones else None
+        if drones:                                 # (kept under the names the tests reach for)
+            self._grid, self._outside, self._dr = self._targets.grid, self._targets.outside_count, self._targets.dr
         a = self.args = nat.ScanArgs()
         a.beams, a.n_beams, a.t_min, a.t_max = self._beams.data_ptr(), self.n_beams, float(t_min), float(t_max)
         a.flags = (nat.SCAN_GROUND if ground else 0) | (nat.SCAN_CLAMP if clamp else 0)
@@ -157,8 +133,7 @@ class RangeScanner:
         a = self.args
         a.hit_out = self.hit_out.data_ptr() if hits else None
         if self.drones:
-            self._grid_args = self._grid.sphere_grid(self._drone_box)          # (kept: the struct outlives the call)
-            self._dr.grid = ctypes.addressof(self._grid_args)
+            self._grid_args = self._targets.grid_args()
         nat.check(self.ctx.lib.dsim_range_scan(
             self.ctx.handle, self.ctx.stream_ptr(), self.state.n, self.state.view(),
             self.set.handle if (self.set is not None and not self.placed) else None, ctypes.byref(a)))
@@ -187,23 +162,19 @@ class RangeScanner:
     def refresh_drone_box(self) -> None:
         """Has the next eager scan re-measure the box of the drones' grid (no-op with ``drone_box``): for a caller that is about to
         capture a graph, whose scans keep the box and the workspace of the last eager one."""
-        if not self.drones:
-            raise ValueError("refresh_drone_box() needs a scanner made with drones=True")
-        self._grid._box = None
+        require_targets(self._targets, "refresh_drone_box", "scanner").refresh_box()
 
     def graph_keepalive(self):
         """What a captured scan() holds the addresses of, for the owner of the graph to keep alive."""
         keep = [self.range_out, self.hit_out, self._beams, self._off, self._type_id, self._scene_id]
         if self.drones:
-            keep += [self._grid._ws, self._label, self._outside]
+            keep += self._targets.keepalive()
         return tuple(keep)
 
     def drones_outside(self) -> int:
         """Drones x scans so far that were binned outside the grid's box (synchronises the stream): targets all the same, but
         tested by every beam — a count that grows says the box is stale."""
-        if not self.drones:
-            raise ValueError("drones_outside() needs a scanner made with drones=True")
-        return int(self._outside.item())
+        return require_targets(self._targets, "drones_outside", "scanner").outside()
 
     def close(self) -> None:
         if self._owns_set:

@@ -1,13 +1,13 @@
 """The range scanner where it meets OTHER DRONES, at the edges case_lattice never shows it (tests/README_scan.md): the DRONES block of
-k_range_scan is a hand copy of the camera's 2-D grid walk, and this is its edge suite.  Level drones whose axis beams have
-components of d that are exactly 0, drones stacked above one another, a second and ragged tile, cell borders through the drones'
+k_range_scan is the camera's 2-D grid walk (dsim_camera_drones.inc, included by both), and this is its edge suite.  Level drones
+whose axis beams have components of d that are exactly 0, drones stacked above one another, a second and ragged tile, cell borders through the drones'
 centres, a fleet 4 km from the origin, task offsets beside a set, lost drones as targets, a doubled cell, beam chunks over
 blockIdx.y, and beams "used as given" through the raw ABI.
 
 The references are scan_ref.scan_brute (fp64, no grid); the rule is test_gpu_scan.py's: outside the mask (at most 1 % of each case's
 rays, asserted on the CPU) hit / no-hit and ids EXACTLY, t within SCAN_EDGE_TOL (= SCAN_TOL: the edge cases' restated error is not
 above the recorded one).  tests/test_scan_cpu.py shows without a device that the walk AS DESIGNED finds every sphere on these very
-inputs (walked_scan == restated_scan bit for bit); what is tested here is whether the HIP copy does what the design says."""
+inputs (walked_scan == restated_scan bit for bit); what is tested here is whether the HIP text does what the design says."""
 import numpy as np
 import pytest
 import torch

@@ -3,7 +3,7 @@
 stands in front of the gate at (2, 0, 1) of ITS task frame and is stored at that place plus its own offset, 8 m apart on a square
 lattice.  One JSON line per fleet size: us per scan and rays per second.
 
-    python tools/bench_scan.py [--sizes 65536 1048576] [--beams 16] [--subdiv 0] [--iters 200] [--warmup 50]
+    python tools/bench_scan.py [--sizes 65536 1048576] [--beams 16] [--subdiv 0] [--iters 200] [--warmup 50] [--lib PATH]
 
 For the camera's time at the same 16 rays per drone run tools/bench_camera.py --cameras 65536 --res 4 4: the only other way to
 get 16 rays per drone.
@@ -47,8 +47,12 @@ def main():
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--lib", default=None, help="another build of the library (an A/B against the one in the tree)")
     ap.add_argument("--drones", action="store_true", help="the drones case (see above)")
     a = ap.parse_args()
+    from dronesim_amd import _native as nat
+    if a.lib:
+        nat.load(a.lib)
     import torch
     from dronesim_amd.envs import CtrlAviary
     from dronesim_amd.scanner import RangeScanner
