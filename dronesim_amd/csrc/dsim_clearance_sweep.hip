@@ -149,8 +149,7 @@ extern "C" int dsim_clearance_sweep(dsim_ctx* ctx, void* stream, int64_t n, dsim
       !isfinite(travel))
     return DSIM_E_ARG;
   if (ctx->n_types > 1 && !g->type_id) return DSIM_E_ARG;
-  float r_max = 0.0f;
-  for (int t = 0; t < ctx->n_types; ++t) r_max = fmaxf(r_max, (float)ctx->h_types[t].collision_sphere);
+  const float r_max = ctx_r_max(ctx);
   if (g->nx < 1 || g->ny < 1 || g->m < 1 || g->workspace_len < dsim_clearance_sweep_workspace(g->m, g->nx, g->ny)) return DSIM_E_ARG;
   DwK a;
   // (the cell rule is grid_build's test of cell against min_cell)

@@ -1676,8 +1676,7 @@ int dsim_clearance(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, cons
   if (g->halo) return DSIM_E_UNSUPPORTED;
   if ((g->pos_all != nullptr) != (radius_all != nullptr)) return DSIM_E_ARG;     // the world's radii travel with its positions
   if (ctx->n_types > 1 && !g->type_id && !radius_all) return DSIM_E_ARG;
-  float r_max = 0.0f;
-  for (int t = 0; t < ctx->n_types; ++t) r_max = fmaxf(r_max, (float)ctx->h_types[t].collision_sphere);
+  const float r_max = ctx_r_max(ctx);
   if (g->nx < 1 || g->ny < 1 || g->m < 1 || g->workspace_len < dsim_clearance_workspace(g->m, g->nx, g->ny)) return DSIM_E_ARG;
   DwK a;
   const hipStream_t st_ = (hipStream_t)stream;
@@ -1714,8 +1713,7 @@ int dsim_sphere_grid_build(dsim_ctx* ctx, hipStream_t st_, int64_t n, const dsim
   if (g->halo) return DSIM_E_UNSUPPORTED;
   if ((g->pos_all != nullptr) != (radius_all != nullptr)) return DSIM_E_ARG;     // the world's radii travel with its positions
   if (ctx->n_types > 1 && !g->type_id && !radius_all) return DSIM_E_ARG;
-  float r_max = 0.0f;
-  for (int t = 0; t < ctx->n_types; ++t) r_max = fmaxf(r_max, (float)ctx->h_types[t].collision_sphere);
+  const float r_max = ctx_r_max(ctx);
   if (g->nx < 1 || g->ny < 1 || g->m < 1 || !(g->cell > 0.0f) || !isfinite(g->cell) || !isfinite(g->xmin) || !isfinite(g->ymin) ||
       g->workspace_len < dsim_sphere_grid_workspace(g->m, g->nx, g->ny))
     return DSIM_E_ARG;

@@ -88,6 +88,13 @@ struct dsim_ctx {
   dsim_type_params h_types[DSIM_MAX_TYPES];
 };
 
+// the largest bounding sphere of the type table (what a watch's reach or cell must cover)
+static inline float ctx_r_max(const dsim_ctx* ctx) {
+  float r_max = 0.0f;
+  for (int t = 0; t < ctx->n_types; ++t) r_max = fmaxf(r_max, (float)ctx->h_types[t].collision_sphere);
+  return r_max;
+}
+
 // a DSIM_KIND_HEXA_QUADLAW type in the table: served by the per-run kernels (k_step_run), whose step kernel never refreshes kept lists
 static inline bool has_quadlaw6(const dsim_ctx* ctx) {
   for (int t = 0; t < ctx->n_types; ++t) if (ctx->h_types[t].kind == DSIM_KIND_HEXA_QUADLAW) return true;

@@ -102,10 +102,56 @@ __device__ __forceinline__ float tri_dist2(const float4 r0, const float4 r1, con
   return mode == 6 ? h * h : ex * ex + ey * ey + ez * ez;
 }
 
-// The cell of q and the walk of its list (both clearance kernels: the set's frame, and a placement's): the least squared distance
-// below `best` and the body of the triangle that attains it.  The records come from LDS when the whole set was staged.
+// ---- the tile frame of the three watch kernels (k_obstacle_clearance, k_obstacle_clearance_scenes, k_obstacle_sweep) ----------------
+// One drone per lane, tiles of 256 drones grid-stride.  Per tile every kernel loads its lane's drone (the point kernels: obs_lane),
+// decides per lane what it has to look at, stages the records once the workgroup meets a tile that needs them (obs_stage_once),
+// searches, and hands the lane's answer to obs_lane_store.  The search is each kernel's own; where it walks a cell's list it is
+// obs_cell_walk.
+
+// A live lane's drone for the point kernels: the query point q = position - offset and the bounding sphere's radius.  Called
+// inside the kernel's `if (live)`, beside the loads that are the kernel's own; a dead lane keeps the zeros.  (The swept kernel
+// reads and writes prev between the position and the offset and keeps its own load: dsim_sweep.hip.)
+struct ObsLane { float qx, qy, qz, R; };
+__device__ __forceinline__ ObsLane obs_lane(const ObsK& a, long long i) {
+  ObsLane l;
+  const long long o = kv_off(a.st, i);
+  l.qx = a.st.base[o]; l.qy = a.st.base[o + a.st.field_stride]; l.qz = a.st.base[o + 2 * a.st.field_stride];
+  if (a.offset) { l.qx -= a.offset[i]; l.qy -= a.offset[a.n_pad + i]; l.qz -= a.offset[2 * a.n_pad + i]; }
+  l.R = a.types[a.type_id ? min((int)a.type_id[i], a.n_types - 1) : 0].coll_sphere;
+  return l;
+}
+
+// The records into LDS before the workgroup's first tile with a lane that wants them (`want` is the caller's; every lane calls).
 template <bool LDS>
-__device__ __forceinline__ void obs_cell_walk(const ObsK& a, const float4* s_rec, float qx, float qy, float qz, int& body, float& best) {
+__device__ __forceinline__ void obs_stage_once(const ObsK& a, float4* s_rec, bool& staged, bool want) {
+  if (LDS) {
+    if (!staged && __syncthreads_or(want ? 1 : 0)) {
+      obs_stage(s_rec, a.rec, a.n_tri);
+      staged = true;
+    }
+  }
+}
+
+// The lane's answer — (c_i, body) within the margin, else (margin, -1) — and the wave's contacts: one ballot, one atomic per
+// counter (the ctx's shard of the tile, and contacts_out).
+__device__ __forceinline__ void obs_lane_store(const ObsK& a, long long tile, long long i, bool live, bool in, float c_i, int body) {
+  if (live) {
+    a.clearance[i] = in ? c_i : a.margin;
+    if (a.nearest) a.nearest[i] = in ? body : -1;
+  }
+  const unsigned long long hit = __ballot(in && c_i < 0.0f);
+  if (hit != 0ULL && (threadIdx.x & 63u) == 0u) {
+    const unsigned long long cnt = (unsigned long long)__popcll(hit);
+    atomicAdd(&a.counters[8 + DSIM_GROUND_SHARDS + DSIM_DRONE_SHARDS + (tile & (DSIM_OBST_SHARDS - 1))], cnt);
+    if (a.contacts_out) atomicAdd(a.contacts_out, cnt);
+  }
+}
+
+// The cell of q and the walk of its list (the set's frame, or a placement's): the least dist2(r0, r1, r2, r3) below `best` over
+// the list's records and the body of the triangle that attains it.  The records come from LDS when the whole set was staged.
+template <bool LDS, class Dist2>
+__device__ __forceinline__ void obs_cell_walk(const ObsK& a, const float4* s_rec, float qx, float qy, float qz, Dist2 dist2, int& body,
+                                              float& best) {
   const int cx = min(max((int)floorf((qx - a.ox) * a.inv_cell), 0), a.nx - 1);
   const int cy = min(max((int)floorf((qy - a.oy) * a.inv_cell), 0), a.ny - 1);
   const int cz = min(max((int)floorf((qz - a.oz) * a.inv_cell), 0), a.nz - 1);
@@ -115,17 +161,24 @@ __device__ __forceinline__ void obs_cell_walk(const ObsK& a, const float4* s_rec
     const int t = a.cell_tri[k];
     const float4* r = (LDS ? s_rec : a.rec) + 4 * t;
     const float4 r0 = r[0], r1 = r[1], r2 = r[2], r3 = r[3];
-    const float d2 = tri_dist2(r0, r1, r2, r3, qx, qy, qz);
+    const float d2 = dist2(r0, r1, r2, r3);
     const bool better = d2 < best;
     best = better ? d2 : best;
     body = better ? __float_as_int(r3.w) : body;
   }
 }
 
-// One drone per lane, tiles of 256 drones grid-stride.  A tile none of whose drones lies in the grown box reads its positions
-// (and offsets) and writes (margin, -1); of a tile that has some, the waves that have none do the same.  The others look up
-// their cell and walk its list: the records come from LDS when the whole set fits (staged by the workgroup before its first
-// tile that needs them), else through L2 — the set is read-only and small next to the fleet.
+// ... for the point q itself (both point kernels)
+template <bool LDS>
+__device__ __forceinline__ void obs_point_walk(const ObsK& a, const float4* s_rec, float qx, float qy, float qz, int& body, float& best) {
+  obs_cell_walk<LDS>(a, s_rec, qx, qy, qz,
+                     [=](const float4 r0, const float4 r1, const float4 r2, const float4 r3) { return tri_dist2(r0, r1, r2, r3, qx, qy, qz); },
+                     body, best);
+}
+
+// The point watch.  A tile none of whose drones lies in the grown box reads its positions (and offsets) and writes (margin, -1);
+// of a tile that has some, the waves that have none do the same.  The others look up their cell and walk its list: the records
+// come from LDS when the whole set fits, else through L2 — the set is read-only and small next to the fleet.
 template <bool LDS>
 __global__ __launch_bounds__(256) void k_obstacle_clearance(ObsK a) {
   extern __shared__ float4 s_rec[];
@@ -133,36 +186,17 @@ __global__ __launch_bounds__(256) void k_obstacle_clearance(ObsK a) {
   for (long long tile = blockIdx.x; tile < a.tiles; tile += gridDim.x) {
     const long long i = tile * 256 + threadIdx.x;
     const bool live = i < a.n;
-    float qx = 0.0f, qy = 0.0f, qz = 0.0f, R = 0.0f;
-    if (live) {
-      const long long o = kv_off(a.st, i);
-      qx = a.st.base[o]; qy = a.st.base[o + a.st.field_stride]; qz = a.st.base[o + 2 * a.st.field_stride];
-      if (a.offset) { qx -= a.offset[i]; qy -= a.offset[a.n_pad + i]; qz -= a.offset[2 * a.n_pad + i]; }
-      R = a.types[a.type_id ? min((int)a.type_id[i], a.n_types - 1) : 0].coll_sphere;
-    }
+    ObsLane l = {};
+    if (live) l = obs_lane(a, i);
+    const float qx = l.qx, qy = l.qy, qz = l.qz, R = l.R;
     // (a NaN position fails every comparison: not in the box, clearance = margin)
     const bool inbox = live && R > 0.0f && qx >= a.lox && qx <= a.hix && qy >= a.loy && qy <= a.hiy && qz >= a.loz && qz <= a.hiz;
-    if (LDS) {
-      if (!staged && __syncthreads_or(inbox ? 1 : 0)) {
-        obs_stage(s_rec, a.rec, a.n_tri);
-        staged = true;
-      }
-    }
+    obs_stage_once<LDS>(a, s_rec, staged, inbox);
     float best = INFINITY;
     int body = -1;
-    if (inbox) obs_cell_walk<LDS>(a, s_rec, qx, qy, qz, body, best);   // (a wave with no such lane skips it: the per-wave reject)
+    if (inbox) obs_point_walk<LDS>(a, s_rec, qx, qy, qz, body, best);   // (a wave with no such lane skips it: the per-wave reject)
     const float c_i = DSIM_SQRT(best) - R;
-    const bool in = inbox && c_i < a.margin;
-    if (live) {
-      a.clearance[i] = in ? c_i : a.margin;
-      if (a.nearest) a.nearest[i] = in ? body : -1;
-    }
-    const unsigned long long hit = __ballot(in && c_i < 0.0f);
-    if (hit != 0ULL && (threadIdx.x & 63u) == 0u) {
-      const unsigned long long cnt = (unsigned long long)__popcll(hit);
-      atomicAdd(&a.counters[8 + DSIM_GROUND_SHARDS + DSIM_DRONE_SHARDS + (tile & (DSIM_OBST_SHARDS - 1))], cnt);
-      if (a.contacts_out) atomicAdd(a.contacts_out, cnt);
-    }
+    obs_lane_store(a, tile, i, live, inbox && c_i < a.margin, c_i, body);
   }
 }
 
@@ -182,6 +216,29 @@ static int obs_kargs(dsim_ctx* ctx, int64_t n, const dsim_view& state, const dsi
   a.margin = margin; a.clearance = clearance_out; a.nearest = nearest_out;
   a.counters = ctx->d_counters; a.contacts_out = (unsigned long long*)contacts_out;
   return DSIM_OK;
+}
+
+// what the three watch launchers refuse alike (`extra` widens every radius: the swept watch's sag)
+static int obs_refuse(const dsim_ctx* ctx, int64_t n, const dsim_view& state, const dsim_obstacles* set, const uint8_t* type_id,
+                      float margin, float extra, const float* clearance_out) {
+  if (!ctx || !set || !clearance_out || !(margin > 0.0f) || n <= 0 || n > state.n_pad) return DSIM_E_ARG;
+  if (ctx->n_types > 1 && !type_id) return DSIM_E_ARG;
+  if ((double)ctx_r_max(ctx) + (double)extra + (double)margin > (double)set->grid.reach) return DSIM_E_ARG;
+  return DSIM_OK;
+}
+
+static inline unsigned obs_blocks(long long tiles) { return (unsigned)(tiles < OBS_MAX_BLOCKS ? tiles : OBS_MAX_BLOCKS); }
+
+// one watch kernel over the fleet's tiles: the instance that stages the set in LDS when it fits, else the one that reads it through L2
+template <class... Args>
+static int obs_launch(void (*k_lds)(Args...), void (*k_l2)(Args...), const dsim_obstacles* set, long long tiles, void* stream,
+                      const Args&... args) {
+  const hipStream_t st_ = (hipStream_t)stream;
+  if (set->n_tri <= OBS_LDS_TRI)
+    hipLaunchKernelGGL(k_lds, dim3(obs_blocks(tiles)), dim3(256), (size_t)set->n_tri * 64, st_, args...);
+  else
+    hipLaunchKernelGGL(k_l2, dim3(obs_blocks(tiles)), dim3(256), 0, st_, args...);
+  return (int)hipGetLastError();
 }
 
 extern "C" {
@@ -245,21 +302,12 @@ int dsim_obstacles_destroy(dsim_ctx* ctx, dsim_obstacles* set) {
 int dsim_obstacle_clearance(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, const dsim_obstacles* set,
                             const float* offset, const uint8_t* type_id, float margin,
                             float* clearance_out, int32_t* nearest_out, uint64_t* contacts_out) {
-  if (!ctx || !set || !clearance_out || !(margin > 0.0f) || n <= 0 || n > state.n_pad) return DSIM_E_ARG;
-  if (ctx->n_types > 1 && !type_id) return DSIM_E_ARG;
-  float r_max = 0.0f;
-  for (int t = 0; t < ctx->n_types; ++t) r_max = fmaxf(r_max, (float)ctx->h_types[t].collision_sphere);
-  if ((double)r_max + (double)margin > (double)set->grid.reach) return DSIM_E_ARG;
-  ObsK a;
-  const int rc = obs_kargs(ctx, n, state, set, offset, type_id, margin, clearance_out, nearest_out, contacts_out, &a);
+  int rc = obs_refuse(ctx, n, state, set, type_id, margin, 0.0f, clearance_out);
   if (rc) return rc;
-  const unsigned blocks = (unsigned)(a.tiles < OBS_MAX_BLOCKS ? a.tiles : OBS_MAX_BLOCKS);
-  const hipStream_t st_ = (hipStream_t)stream;
-  if (set->n_tri <= OBS_LDS_TRI)
-    hipLaunchKernelGGL((k_obstacle_clearance<true>), dim3(blocks), dim3(256), (size_t)set->n_tri * 64, st_, a);
-  else
-    hipLaunchKernelGGL((k_obstacle_clearance<false>), dim3(blocks), dim3(256), 0, st_, a);
-  return (int)hipGetLastError();
+  ObsK a;
+  rc = obs_kargs(ctx, n, state, set, offset, type_id, margin, clearance_out, nearest_out, contacts_out, &a);
+  if (rc) return rc;
+  return obs_launch(k_obstacle_clearance<true>, k_obstacle_clearance<false>, set, a.tiles, stream, a);
 }
 
 }  // extern "C"

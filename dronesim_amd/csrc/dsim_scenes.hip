@@ -1,8 +1,9 @@
 // Obstacle scenes (dsim_scenes_create, dsim_obstacle_clearance_scenes, dsim_depth_image_scenes): K scenes of up to G rigid
 // placements of ONE prototype set, and a scene per drone.  Distances and ray parameters do not change under a rotation and a shift,
 // so the prototype's grids, records and LDS staging serve every placement: only the query point, or the ray, goes into the
-// placement's frame.  Compiled as part of dsim_obstacles.hip, which includes this file: it shares the watch's cell walk
-// (obs_cell_walk), its arguments (ObsK, obs_kargs) and the camera's kernel (k_depth_image<.., PLACED>, cam_fill).
+// placement's frame.  Compiled as part of dsim_obstacles.hip, which includes this file: it shares the watch's tile frame and
+// cell walk (obs_lane .. obs_point_walk), its arguments and launcher (ObsK, obs_kargs, obs_refuse, obs_launch) and the camera's
+// kernel (k_depth_image<.., PLACED>, cam_fill).
 #pragma once
 
 #define SCN_MAX_G 32                     // one bit per placement in a lane's mask
@@ -15,9 +16,8 @@ struct ScnK {
   int G, n_bodies;
 };
 
-// k_obstacle_clearance with the set placed: one drone per lane, tiles of 256 grid-stride, the prototype's records staged in LDS
-// once per workgroup.  Scene ids differ per lane, so placement records are per-lane vector loads: a lane reads the first 16 bytes
-// of each of its scene's G slots, (c_task, r_cull), and the other 48 only of a slot whose sphere it is within reach of — the bound
+// k_obstacle_clearance with the set placed, in the same tile frame (dsim_obstacles.hip).  Scene ids differ per lane, so
+// placement records are per-lane vector loads: a lane reads the first 16 bytes of each of its scene's G slots, (c_task, r_cull), and the other 48 only of a slot whose sphere it is within reach of — the bound
 // is widened (1e-4 relative, 1e-5 m) well beyond the fp32 rounding of q - c and of an R that is orthonormal to 1e-5, so it decides
 // speed only.  Then q goes into the placement's frame, subtract first, then rotate: R^T q - R^T t cancels digits at offsets of
 // 128 m, R^T (q - t) does not.  There the grown-box test and the cell walk are the unplaced kernel's.  The minimum runs over the
@@ -29,15 +29,10 @@ __global__ __launch_bounds__(256) void k_obstacle_clearance_scenes(ObsK a, ScnK 
   for (long long tile = blockIdx.x; tile < a.tiles; tile += gridDim.x) {
     const long long i = tile * 256 + threadIdx.x;
     const bool live = i < a.n;
-    float qx = 0.0f, qy = 0.0f, qz = 0.0f, R = 0.0f;
+    ObsLane l = {};
     int sid = -1;
-    if (live) {
-      const long long o = kv_off(a.st, i);
-      qx = a.st.base[o]; qy = a.st.base[o + a.st.field_stride]; qz = a.st.base[o + 2 * a.st.field_stride];
-      if (a.offset) { qx -= a.offset[i]; qy -= a.offset[a.n_pad + i]; qz -= a.offset[2 * a.n_pad + i]; }
-      R = a.types[a.type_id ? min((int)a.type_id[i], a.n_types - 1) : 0].coll_sphere;
-      sid = s.scene_id[i];
-    }
+    if (live) { l = obs_lane(a, i); sid = s.scene_id[i]; }
+    const float qx = l.qx, qy = l.qy, qz = l.qz, R = l.R;
     // the placements within reach, one bit each (a NaN position fails every comparison; a scene outside [0, K) has none)
     unsigned near = 0u;
     const float4* pl = s.place;
@@ -50,12 +45,7 @@ __global__ __launch_bounds__(256) void k_obstacle_clearance_scenes(ObsK a, ScnK 
         near |= (b >= 0.0f && ux * ux + uy * uy + uz * uz <= b * b) ? (1u << g) : 0u;
       }
     }
-    if (LDS) {
-      if (!staged && __syncthreads_or(near != 0u ? 1 : 0)) {
-        obs_stage(s_rec, a.rec, a.n_tri);
-        staged = true;
-      }
-    }
+    obs_stage_once<LDS>(a, s_rec, staged, near != 0u);
     float best = INFINITY;
     int body = -1;
     while (near != 0u) {                   // (a wave with no such lane skips the loop: the per-wave reject)
@@ -68,22 +58,12 @@ __global__ __launch_bounds__(256) void k_obstacle_clearance_scenes(ObsK a, ScnK 
       if (lx >= a.lox && lx <= a.hix && ly >= a.loy && ly <= a.hiy && lz >= a.loz && lz <= a.hiz) {
         float b2 = best;
         int bd = -1;
-        obs_cell_walk<LDS>(a, s_rec, lx, ly, lz, bd, b2);
+        obs_point_walk<LDS>(a, s_rec, lx, ly, lz, bd, b2);
         if (bd >= 0) { best = b2; body = g * s.n_bodies + bd; }
       }
     }
     const float c_i = DSIM_SQRT(best) - R;
-    const bool in = body >= 0 && c_i < a.margin;
-    if (live) {
-      a.clearance[i] = in ? c_i : a.margin;
-      if (a.nearest) a.nearest[i] = in ? body : -1;
-    }
-    const unsigned long long hit = __ballot(in && c_i < 0.0f);
-    if (hit != 0ULL && (threadIdx.x & 63u) == 0u) {
-      const unsigned long long cnt = (unsigned long long)__popcll(hit);
-      atomicAdd(&a.counters[8 + DSIM_GROUND_SHARDS + DSIM_DRONE_SHARDS + (tile & (DSIM_OBST_SHARDS - 1))], cnt);
-      if (a.contacts_out) atomicAdd(a.contacts_out, cnt);
-    }
+    obs_lane_store(a, tile, i, live, body >= 0 && c_i < a.margin, c_i, body);
   }
 }
 
@@ -151,24 +131,16 @@ int dsim_scenes_destroy(dsim_ctx* ctx, dsim_scenes* scenes) {
 int dsim_obstacle_clearance_scenes(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, const dsim_scenes* scenes,
                                    const int32_t* scene_id, const float* offset, const uint8_t* type_id, float margin,
                                    float* clearance_out, int32_t* nearest_out, uint64_t* contacts_out) {
-  if (!ctx || !scenes || !scene_id || !clearance_out || !(margin > 0.0f) || n <= 0 || n > state.n_pad) return DSIM_E_ARG;
-  if (ctx->n_types > 1 && !type_id) return DSIM_E_ARG;
+  if (!scenes || !scene_id) return DSIM_E_ARG;
   const dsim_obstacles* set = scenes->proto;
-  float r_max = 0.0f;
-  for (int t = 0; t < ctx->n_types; ++t) r_max = fmaxf(r_max, (float)ctx->h_types[t].collision_sphere);
-  if ((double)r_max + (double)margin > (double)set->grid.reach) return DSIM_E_ARG;
+  int rc = obs_refuse(ctx, n, state, set, type_id, margin, 0.0f, clearance_out);
+  if (rc) return rc;
   ObsK a;
-  const int rc = obs_kargs(ctx, n, state, set, offset, type_id, margin, clearance_out, nearest_out, contacts_out, &a);
+  rc = obs_kargs(ctx, n, state, set, offset, type_id, margin, clearance_out, nearest_out, contacts_out, &a);
   if (rc) return rc;
   ScnK s;
   s.place = scenes->place; s.scene_id = scene_id; s.K = scenes->K; s.G = scenes->G; s.n_bodies = set->n_bodies;
-  const unsigned blocks = (unsigned)(a.tiles < OBS_MAX_BLOCKS ? a.tiles : OBS_MAX_BLOCKS);
-  const hipStream_t st_ = (hipStream_t)stream;
-  if (set->n_tri <= OBS_LDS_TRI)
-    hipLaunchKernelGGL((k_obstacle_clearance_scenes<true>), dim3(blocks), dim3(256), (size_t)set->n_tri * 64, st_, a, s);
-  else
-    hipLaunchKernelGGL((k_obstacle_clearance_scenes<false>), dim3(blocks), dim3(256), 0, st_, a, s);
-  return (int)hipGetLastError();
+  return obs_launch(k_obstacle_clearance_scenes<true>, k_obstacle_clearance_scenes<false>, set, a.tiles, stream, a, s);
 }
 
 int dsim_depth_image_scenes(dsim_ctx* ctx, void* stream, dsim_view state, const dsim_scenes* scenes, const int32_t* scene_id,

@@ -1,6 +1,6 @@
 // Swept static-obstacle watch (dsim_obstacle_sweep): per-drone clearance between the vehicle's bounding sphere, swept along the chord
 // from the position the previous call saw to the current one, and the set's triangles (include/dronesim_amd.h).  Compiled as part
-// of dsim_obstacles.hip, which includes it: it shares the set's private record, tri_dist2 and the LDS threshold.
+// of dsim_obstacles.hip, which includes it: it shares the set's private record, tri_dist2, the watches' tile frame and their launcher.
 
 struct SweepK {
   ObsK o;                        // as the point watch's; contacts are counted on its shards (DSIM_Q_OBSTACLE_CONTACTS)
@@ -70,9 +70,8 @@ __global__ __launch_bounds__(256) void k_sweep_prime(SweepK w) {
   }
 }
 
-// As k_obstacle_clearance: one drone per lane, tiles of 256 grid-stride, the records from LDS when the whole set fits, one ballot
-// and one atomic per wave and counter.  A lane's chord q0 -> q1 is cut into K equal pieces no longer than 2 half; each piece is
-// looked up in the cell of its own midpoint, and a piece whose midpoint lies outside the grown box reads no list — a wave none
+// The swept watch, in the tile frame of dsim_obstacles.hip (obs_stage_once, obs_cell_walk, obs_lane_store).  A lane's chord q0 -> q1
+// is cut into K equal pieces no longer than 2 half; each piece is looked up in the cell of its own midpoint, and a piece whose midpoint lies outside the grown box reads no list — a wave none
 // of whose lanes has such a piece skips the walk (the per-wave reject).  The workgroup stages the records when a chord's
 // bounding box meets the grown box (a superset of "some midpoint inside": staging more often costs time, never results).
 // An unswept lane (K > 32, or a non-finite prev or position) is the point q1: its chord collapses to q1 and only tri_dist2 at
@@ -85,6 +84,8 @@ __global__ __launch_bounds__(256) void k_obstacle_sweep(SweepK w) {
   for (long long tile = blockIdx.x; tile < a.tiles; tile += gridDim.x) {
     const long long i = tile * 256 + threadIdx.x;
     const bool live = i < a.n;
+    // The lane's own load, not obs_lane: prev is read, and written, between the position and the offset, and the far case's time
+    // follows the order of these loads (measured: profiles/r13_obstacle_watches_refactor.txt).
     float q1x = 0.0f, q1y = 0.0f, q1z = 0.0f, q0x = 0.0f, q0y = 0.0f, q0z = 0.0f, R = 0.0f;
     if (live) {
       const long long o = kv_off(a.st, i);
@@ -109,12 +110,7 @@ __global__ __launch_bounds__(256) void k_obstacle_sweep(SweepK w) {
     // (a NaN position fails every comparison: no staging for it, no piece in the box, clearance = margin)
     const bool near_box = part && fminf(q0x, q1x) <= a.hix && fmaxf(q0x, q1x) >= a.lox && fminf(q0y, q1y) <= a.hiy &&
                           fmaxf(q0y, q1y) >= a.loy && fminf(q0z, q1z) <= a.hiz && fmaxf(q0z, q1z) >= a.loz;
-    if (LDS) {
-      if (!staged && __syncthreads_or(near_box ? 1 : 0)) {
-        obs_stage(s_rec, a.rec, a.n_tri);
-        staged = true;
-      }
-    }
+    obs_stage_once<LDS>(a, s_rec, staged, near_box);
     float best = INFINITY;
     int body = -1;
     bool inbox = false;
@@ -127,40 +123,20 @@ __global__ __launch_bounds__(256) void k_obstacle_sweep(SweepK w) {
         inbox = true;
         const float ax = q0x + dx * t0, ay = q0y + dy * t0, az = q0z + dz * t0;
         const float bx = last ? q1x : q0x + dx * t1, by = last ? q1y : q0y + dy * t1, bz = last ? q1z : q0z + dz * t1;
-        const int cx = min(max((int)floorf((mx - a.ox) * a.inv_cell), 0), a.nx - 1);
-        const int cy = min(max((int)floorf((my - a.oy) * a.inv_cell), 0), a.ny - 1);
-        const int cz = min(max((int)floorf((mz - a.oz) * a.inv_cell), 0), a.nz - 1);
-        const int c = (cz * a.ny + cy) * a.nx + cx;
-        const int end = a.cell_start[c + 1];
-        for (int k = a.cell_start[c]; k < end; ++k) {
-          const int t = a.cell_tri[k];
-          const float4* r = (LDS ? s_rec : a.rec) + 4 * t;
-          const float4 r0 = r[0], r1 = r[1], r2 = r[2], r3 = r[3];
-          const float d_a = tri_dist2(r0, r1, r2, r3, ax, ay, az);
-          const float d_s = seg_tri_dist2(r0, r1, r2, r3, ax, ay, az, bx, by, bz, d_a);
-          const float d2 = swept ? d_s : d_a;
-          const bool better = d2 < best;
-          best = better ? d2 : best;
-          body = better ? __float_as_int(r3.w) : body;
-        }
+        // the list of the midpoint's cell; per triangle the piece's distance, or the point A's for an unswept lane
+        obs_cell_walk<LDS>(a, s_rec, mx, my, mz,
+                           [=](const float4 r0, const float4 r1, const float4 r2, const float4 r3) {
+                             const float d_a = tri_dist2(r0, r1, r2, r3, ax, ay, az);
+                             const float d_s = seg_tri_dist2(r0, r1, r2, r3, ax, ay, az, bx, by, bz, d_a);
+                             return swept ? d_s : d_a;
+                           },
+                           body, best);
       }
     }
     const float c_i = DSIM_SQRT(best) - Rs;
-    const bool in = inbox && c_i < a.margin;
-    if (live) {
-      a.clearance[i] = in ? c_i : a.margin;
-      if (a.nearest) a.nearest[i] = in ? body : -1;
-    }
-    const unsigned long long hit = __ballot(in && c_i < 0.0f);
+    obs_lane_store(a, tile, i, live, inbox && c_i < a.margin, c_i, body);
     const unsigned long long pts = __ballot(part && !swept);
-    if ((threadIdx.x & 63u) == 0u) {
-      if (hit != 0ULL) {
-        const unsigned long long cnt = (unsigned long long)__popcll(hit);
-        atomicAdd(&a.counters[8 + DSIM_GROUND_SHARDS + DSIM_DRONE_SHARDS + (tile & (DSIM_OBST_SHARDS - 1))], cnt);
-        if (a.contacts_out) atomicAdd(a.contacts_out, cnt);
-      }
-      if (pts != 0ULL && w.unswept_out) atomicAdd(w.unswept_out, (unsigned long long)__popcll(pts));
-    }
+    if (pts != 0ULL && (threadIdx.x & 63u) == 0u && w.unswept_out) atomicAdd(w.unswept_out, (unsigned long long)__popcll(pts));
   }
 }
 
@@ -173,14 +149,12 @@ extern "C" int dsim_obstacle_sweep(dsim_ctx* ctx, void* stream, int64_t n, dsim_
   SweepK w;
   memset(&w, 0, sizeof(w));
   if (!prime) {
-    if (ctx->n_types > 1 && !args->type_id) return DSIM_E_ARG;
-    if (!args->clearance_out || !(args->margin > 0.0f) || !isfinite(args->margin) || !(args->sag >= 0.0f) || !isfinite(args->sag))
-      return DSIM_E_ARG;
-    float r_max = 0.0f;
-    for (int t = 0; t < ctx->n_types; ++t) r_max = fmaxf(r_max, (float)ctx->h_types[t].collision_sphere);
+    if (!isfinite(args->margin) || !(args->sag >= 0.0f) || !isfinite(args->sag)) return DSIM_E_ARG;
+    const int rc = obs_refuse(ctx, n, state, set, args->type_id, args->margin, args->sag, args->clearance_out);
+    if (rc) return rc;
     // a piece reaches `half` from its midpoint at most, so whatever is within R + sag + margin of it is within reach of the midpoint
     const double reach = (double)set->grid.reach;
-    const double half = reach - ((double)r_max + (double)args->sag + (double)args->margin);
+    const double half = reach - ((double)ctx_r_max(ctx) + (double)args->sag + (double)args->margin);
     if (!(half >= reach / 1024.0)) return DSIM_E_ARG;
     // 2^-10 shorter than allowed: covers the rounding of the length, of the quotient and of the midpoints (the lists carry a
     // hundredth of a cell on top, dsim_obstacle_grid.h)
@@ -191,13 +165,7 @@ extern "C" int dsim_obstacle_sweep(dsim_ctx* ctx, void* stream, int64_t n, dsim_
   if (rc) return rc;
   w.sag = args->sag; w.prev = args->prev; w.keep_prev = (fl & DSIM_SWEEP_KEEP_PREV) ? 1 : 0;
   w.unswept_out = (unsigned long long*)args->unswept_out;
-  const unsigned blocks = (unsigned)(w.o.tiles < OBS_MAX_BLOCKS ? w.o.tiles : OBS_MAX_BLOCKS);
-  const hipStream_t st_ = (hipStream_t)stream;
-  if (prime)
-    hipLaunchKernelGGL(k_sweep_prime, dim3(blocks), dim3(256), 0, st_, w);
-  else if (set->n_tri <= OBS_LDS_TRI)
-    hipLaunchKernelGGL((k_obstacle_sweep<true>), dim3(blocks), dim3(256), (size_t)set->n_tri * 64, st_, w);
-  else
-    hipLaunchKernelGGL((k_obstacle_sweep<false>), dim3(blocks), dim3(256), 0, st_, w);
+  if (!prime) return obs_launch(k_obstacle_sweep<true>, k_obstacle_sweep<false>, set, w.o.tiles, stream, w);
+  hipLaunchKernelGGL(k_sweep_prime, dim3(obs_blocks(w.o.tiles)), dim3(256), 0, (hipStream_t)stream, w);
   return (int)hipGetLastError();
 }

@@ -268,6 +268,70 @@ def test_soup_four_bodies_half_the_fleet_outside(gpu):
     ctx.close()
 
 
+# ---- 3b. more tiles than workgroups: the second trip of the tile loop -------------------------------------------------------------
+# 2 050 tiles on the launchers' 2 048 workgroups: workgroup 0 walks tiles 0 and 2 048, workgroup 1 tiles 1 and 2 049 (37 live lanes).
+# Every drone stands far from the set but three groups about it: tile 1, tile 2 048 and tile 2 049.  So workgroup 0 stages the records
+# at its second tile, behind a tile with nobody in the box, and workgroup 1 stages at its first and re-uses them at a ragged second.
+MT_N = 2049 * 256 + 37
+MT_NEAR = np.concatenate([np.arange(256, 512), np.arange(524288, 524544), np.arange(524544, MT_N)])
+MT_FAR = np.setdiff1d(np.arange(MT_N), MT_NEAR)
+
+
+def many_tiles_far(rng, n=MT_N):
+    """Positions about (60, 0, 1) m in the set's frame, a metre of jitter."""
+    return f32(np.array([60.0, 0.0, 1.0]) + rng.uniform(-1.0, 1.0, (n, 3)))
+
+
+def box_distance(p, lo, hi):
+    """Distance from every point to the box [lo, hi], fp64."""
+    p = np.asarray(p, dtype=np.float64)
+    return np.linalg.norm(np.maximum(np.maximum(lo - p, p - hi), 0.0), axis=1)
+
+
+def check_many_tiles(clr, near, ref, margin, check_fn, what):
+    """The near drones against their reference with the file's bars, every other drone exactly (float32(margin), -1)."""
+    ix = torch.from_numpy(MT_NEAR).to(clr.device)
+    check_fn(clr[ix], near[ix], ref, margin, what)
+    c_, n_ = clr[:MT_N].cpu().numpy(), near[:MT_N].cpu().numpy()
+    assert np.all(c_[MT_FAR] == np.float32(margin)) and np.all(n_[MT_FAR] == -1)
+
+
+@pytest.mark.parametrize("world", ["gate", "soup"])
+def test_many_tiles_per_workgroup(gpu, world):
+    nat, fleet = gpu
+    from dronesim_amd.obstacles import watch_reach
+    k = len(MT_NEAR)
+    assert k == 549 and (MT_N + 255) // 256 == 2050
+    if world == "gate":                                           # 108 triangles: the records in LDS
+        t, margin = params.builtin_type("robobee"), 1.0
+        s, rad, p_near, _ = _gate_world(k, margin, [t], np.zeros(k, dtype=int), False, 71)
+    else:                                                         # 3 000 triangles: the records through L2
+        t, margin, s = params.builtin_type("hexa_6DOF"), 0.6, soup()
+        rad = np.full(k, np.float32(t.collision_sphere))
+        decide = lambda p, o: (brute(p, s.triangles, s.body, rad[: len(p)], margin, o)[4], margin)
+        p_near, _, frac = settle(np.random.default_rng(73), lambda rng, m: (f32(rng.uniform(-10.0, 10.0, (m, 3))), None), k, decide)
+        assert frac <= 0.01, frac
+    assert (s.n_tri <= 512) == (world == "gate")
+    ref = brute(p_near, s.triangles, s.body, rad, margin)
+    pos = many_tiles_far(np.random.default_rng(72))
+    pos[MT_NEAR] = p_near
+    ctx = fleet.Context([t])
+    dev = s.to_device(ctx, watch_reach(ctx.types, margin))
+    tri = s.triangles.reshape(-1, 3).astype(np.float64)
+    assert box_distance(pos[MT_FAR], tri.min(0), tri.max(0)).min() > dev.reach
+    for lo_, hi_ in ((256, 512), (524288, 524544), (524544, MT_N)):      # each of the three tiles has drones in reach
+        assert (ref[1][(MT_NEAR >= lo_) & (MT_NEAR < hi_)] >= 0).any(), (lo_, hi_)
+    assert ref[3] > 0
+    st = load(fleet, ctx, pos)
+    cnt = torch.zeros((1,), dtype=torch.int64, device=ctx.device)
+    before = ctx.query(nat.QUERY_OBSTACLE_CONTACTS)
+    clr, near = run(ctx, st, dev, margin, counter=cnt)
+    check_many_tiles(clr, near, ref, margin, check, f"many tiles, {world}")
+    assert int(cnt.item()) == ref[3] == ctx.query(nat.QUERY_OBSTACLE_CONTACTS) - before
+    dev.close()
+    ctx.close()
+
+
 # ---- 4. refusals -----------------------------------------------------------------------------------------------------------------
 def test_refusals_leave_the_outputs_untouched(gpu):
     nat, fleet = gpu

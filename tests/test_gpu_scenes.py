@@ -13,7 +13,7 @@ import torch
 from dronesim_amd import params
 from tests import scenes_ref as sr
 from tests.obstacle_ref import brute
-from tests.test_gpu_obstacles import _gate_world, load, soa3
+from tests.test_gpu_obstacles import MT_FAR, MT_N, MT_NEAR, _gate_world, check_many_tiles, load, many_tiles_far, soa3
 from tests.util import f32
 
 pytestmark = pytest.mark.gpu
@@ -155,6 +155,45 @@ def test_soup_prototype_instance_major_bodies(gpu):
     clr, near = run(ctx, st, dev, ids_tensor(d["scene_id"], st.n_pad, ctx.device), margin)
     check(clr[:n], near[:n], ref, margin, "soup")
     assert ctx.query(nat.QUERY_OBSTACLE_CONTACTS) == ref["contacts"]
+    dev.close()
+    ctx.close()
+
+
+# ---- 4b. more tiles than workgroups (test_gpu_obstacles.py, 3b) ---------------------------------------------------------------------
+def test_many_tiles_per_workgroup(gpu):
+    """K = 4 scenes of G = 2 gates within +-2 m, scene_id = i mod K for every drone; the far drones stand out of reach of every
+    placement's bounding sphere, so nobody of their tiles has a bit in its mask."""
+    nat, fleet = gpu
+    from dronesim_amd.obstacles import ObstacleScenes, watch_reach
+    K, G, margin, k = 4, 2, 0.5, len(MT_NEAR)
+    rng = np.random.default_rng(71)
+    scenes = ObstacleScenes(sr.gate(), rng.uniform(-2.0, 2.0, (K, G, 3)), rng.uniform([-0.5, -0.5, -np.pi], [0.5, 0.5, np.pi], (K, G, 3)))
+    sid = np.arange(MT_N) % K
+    sid_near, rad = sid[MT_NEAR], sr._radius("robobee", k)
+    draw = lambda rg, idx: sr._drones_about(rg, scenes, sid_near, idx, False)
+    decide = lambda p, o: (sr.brute_scenes(p, scenes, sid_near, rad, margin, o)["raw"], margin)
+    p_near, _, frac = sr.settle(rng, draw, k, decide)
+    assert frac <= 0.01, frac
+    ref = sr.brute_scenes(p_near, scenes, sid_near, rad, margin)
+    pos = many_tiles_far(np.random.default_rng(72))
+    pos[MT_NEAR] = p_near
+    ctx = fleet.Context([params.builtin_type("robobee")])
+    dev = scenes.to_device(ctx, watch_reach(ctx.types, margin))
+    tri = scenes.prototype.triangles.reshape(-1, 3).astype(np.float64)
+    centre, half_diag = 0.5 * (tri.min(0) + tri.max(0)), 0.5 * np.linalg.norm(tri.max(0) - tri.min(0))
+    for kk in range(K):
+        for g in range(G):
+            R, t = sr.placement64(scenes, kk, g)
+            assert (np.linalg.norm(pos[MT_FAR] - (R @ centre + t), axis=1) - half_diag).min() > dev.reach
+    for lo_, hi_ in ((256, 512), (524288, 524544), (524544, MT_N)):      # each of the three tiles has drones in reach
+        assert (ref["near"][(MT_NEAR >= lo_) & (MT_NEAR < hi_)] >= 0).any(), (lo_, hi_)
+    assert ref["contacts"] > 0 and sr.tie_fraction(ref) <= 0.01
+    st = load(fleet, ctx, pos)
+    cnt = torch.zeros((1,), dtype=torch.int64, device=ctx.device)
+    before = ctx.query(nat.QUERY_OBSTACLE_CONTACTS)
+    clr, near = run(ctx, st, dev, ids_tensor(sid, st.n_pad, ctx.device), margin, counter=cnt)
+    check_many_tiles(clr, near, ref, margin, check, "many tiles")
+    assert int(cnt.item()) == ref["contacts"] == ctx.query(nat.QUERY_OBSTACLE_CONTACTS) - before
     dev.close()
     ctx.close()
 

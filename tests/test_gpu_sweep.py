@@ -19,7 +19,8 @@ import torch
 from dronesim_amd import params
 from tests.obstacle_ref import brute
 from tests.sweep_ref import chords, pierces, seg_seg, sweep_brute
-from tests.test_gpu_obstacles import ATOL, GOLDEN, GUARD, _mixed_types, _positions, check, gate, load, soa3, soup
+from tests.test_gpu_obstacles import (ATOL, GOLDEN, GUARD, MT_FAR, MT_N, MT_NEAR, _mixed_types, _positions, box_distance, check,
+                                      check_many_tiles, gate, load, many_tiles_far, soa3, soup)
 from tests.util import f32
 
 pytestmark = pytest.mark.gpu
@@ -277,7 +278,45 @@ def test_soup_results_do_not_depend_on_the_piece_count(gpu):
     ctx.close()
 
 
-# ---- 5. unswept drones are point samples ------------------------------------------------------------------------------------------------
+# ---- 4b. more tiles than workgroups (test_gpu_obstacles.py, 3b): chords of 0.1 m on every drone -------------------------------------
+def test_many_tiles_per_workgroup(gpu):
+    nat, fleet = gpu
+    from dronesim_amd.obstacles import sweep_reach
+    t = params.builtin_type("robobee")
+    margin, chord, k = 1.0, 0.1, len(MT_NEAR)
+    s = gate()
+    rad = np.full(k, np.float32(t.collision_sphere))
+    decide = lambda a, p, o: (sweep_brute(a, p, s.triangles, s.body, rad[: len(p)], margin, 0.0, o)[4], margin)
+    a_near, p_near, _, frac = settle_chords(np.random.default_rng(71), draw_chords(GATE_BOX, chord, chord), k, decide)
+    assert frac <= 0.01, frac
+    ref = sweep_brute(a_near, p_near, s.triangles, s.body, rad, margin)
+    rng = np.random.default_rng(72)
+    mid = many_tiles_far(rng).astype(np.float64)
+    q0, q1 = chords(rng, MT_N, [0.0] * 3, [0.0] * 3, chord, chord)
+    prev, pos = f32(mid + q0), f32(mid + q1)
+    prev[MT_NEAR], pos[MT_NEAR] = a_near, p_near
+    ctx = fleet.Context([t])
+    dev = s.to_device(ctx, sweep_reach(ctx.types, margin, 0.0, chord))
+    tri = s.triangles.reshape(-1, 3).astype(np.float64)
+    longest = np.linalg.norm(pos - prev, axis=1).max()
+    assert longest < chord + 1e-4                                  # (the ends are rounded to fp32 at 60 m)
+    assert box_distance(pos[MT_FAR], tri.min(0), tri.max(0)).min() > dev.reach + longest
+    for lo_, hi_ in ((256, 512), (524288, 524544), (524544, MT_N)):      # each of the three tiles has chords in reach
+        assert (ref[1][(MT_NEAR >= lo_) & (MT_NEAR < hi_)] >= 0).any(), (lo_, hi_)
+    assert ref[3] > 0
+    st = load(fleet, ctx, pos)
+    d_prev = soa3(prev, st.n_pad, ctx.device)
+    cnt, uns = counters(ctx)
+    before = ctx.query(nat.QUERY_OBSTACLE_CONTACTS)
+    clr, near = sweep_run(ctx, st, dev, margin, 0.0, d_prev, counter=cnt, unswept=uns)
+    check_many_tiles(clr, near, ref, margin, check, "swept, many tiles")
+    assert int(cnt.item()) == ref[3] == ctx.query(nat.QUERY_OBSTACLE_CONTACTS) - before and int(uns.item()) == 0
+    assert np.array_equal(d_prev[:, :MT_N].cpu().numpy().T, pos.astype(np.float32))      # prev moved on in every tile
+    dev.close()
+    ctx.close()
+
+
+# ---- 5. unswept drones are point samples------------------------------------------------------------------------------------------------
 def test_unswept_drones_equal_the_point_query_bit_for_bit(gpu):
     nat, fleet = gpu
     from dronesim_amd import obstacles as obs

@@ -6,7 +6,7 @@ fleet stands 100 m away: every drone is culled) and "near" (the fleet about the 
 the gate, unplaced against G = 1 identity and G = 3.  Device events around batches of --iters calls behind a warm-up, the variants
 interleaved round by round; prints one JSON line per case with the median and the range of each and of the paired ratios.
 
-    python tools/bench_scenes.py [--drones 65536 4194304] [--cameras 4096] [--iters 50] [--warmup 20] [--pairs 9]
+    python tools/bench_scenes.py [--drones 65536 4194304] [--cameras 4096] [--iters 50] [--warmup 20] [--pairs 9] [--lib PATH]
 
 The bytes a far drone must move: A reads 12 (position) and writes 8; the placed watch reads 4 (scene id) + 16 G (cull words) more.
 """
@@ -29,8 +29,12 @@ def main():
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--pairs", type=int, default=9)
+    ap.add_argument("--lib", default=None, help="another build of the library (an A/B against the one in the tree)")
     a = ap.parse_args()
     import torch
+    from dronesim_amd import _native as nat
+    if a.lib:
+        nat.load(a.lib)
     from dronesim_amd import fleet, params
     from dronesim_amd import obstacles as obs
     from dronesim_amd.camera import DepthCamera

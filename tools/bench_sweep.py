@@ -4,7 +4,7 @@ the gate) and "near" (the fleet inside the grown box), chords of --chord metres.
 behind a warm-up, A and B interleaved in pairs; prints one JSON line per case with the median and the spread of both and of the
 paired ratio.  B runs with KEEP_PREV, so every call sweeps the same chords (the writes of prev are measured on their own: "B_write").
 
-    python tools/bench_sweep.py [--drones 65536 4194304] [--chord 0.1] [--iters 50] [--warmup 20] [--pairs 9]
+    python tools/bench_sweep.py [--drones 65536 4194304] [--chord 0.1] [--iters 50] [--warmup 20] [--pairs 9] [--lib PATH]
 
 The bytes a call must move, per drone: A reads 3 floats and writes 2 (clearance, nearest); B reads 6 (position, prev) and writes 2,
 and 3 more without KEEP_PREV.
@@ -28,8 +28,12 @@ def main():
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--pairs", type=int, default=9)
+    ap.add_argument("--lib", default=None, help="another build of the library (an A/B against the one in the tree)")
     a = ap.parse_args()
     import torch
+    from dronesim_amd import _native as nat
+    if a.lib:
+        nat.load(a.lib)
     from dronesim_amd import fleet, params
     from dronesim_amd import obstacles as obs
     if not torch.cuda.is_available():
