@@ -30,6 +30,7 @@ EXPORTS = (
     "dsim_scenes_create", "dsim_scenes_destroy", "dsim_obstacle_clearance_scenes", "dsim_depth_image_scenes",
     "dsim_clearance_sweep", "dsim_clearance_sweep_workspace",
     "dsim_range_scan",
+    "dsim_gate_passage",
 )
 
 ABI_VERSION = 11
@@ -187,6 +188,45 @@ class SweepArgs(ctypes.Structure):
         ("clearance_out", ctypes.c_void_p),
         ("nearest_out", ctypes.c_void_p),
         ("contacts_out", ctypes.c_void_p),
+        ("unswept_out", ctypes.c_void_p),
+    ]
+
+
+APERTURE_RECT, APERTURE_ELLIPSE = 0, 1      # dsim_aperture.shape
+GATE_WRAP = 4                                # dsim_gate_args.flags, beside SWEEP_KEEP_PREV and SWEEP_PRIME
+
+
+class ApertureC(ctypes.Structure):
+    """dsim_aperture (dsim_gate_passage)."""
+    _fields_ = [
+        ("center", ctypes.c_float * 3),
+        ("normal", ctypes.c_float * 3),
+        ("u", ctypes.c_float * 3),
+        ("half", ctypes.c_float * 2),
+        ("outer", ctypes.c_float * 2),
+        ("shape", ctypes.c_int32),
+    ]
+
+
+class GateArgs(ctypes.Structure):
+    """dsim_gate_args (dsim_gate_passage)."""
+    _fields_ = [
+        ("aperture", ApertureC),
+        ("travel", ctypes.c_float),
+        ("flags", ctypes.c_int32),
+        ("offset", ctypes.c_void_p),
+        ("prev", ctypes.c_void_p),
+        ("due", ctypes.c_void_p),
+        ("laps", ctypes.c_void_p),
+        ("clock", ctypes.c_void_p),
+        ("pass_time", ctypes.c_void_p),
+        ("fwd_out", ctypes.c_void_p),
+        ("back_out", ctypes.c_void_p),
+        ("miss_out", ctypes.c_void_p),
+        ("passes_out", ctypes.c_void_p),
+        ("wrong_way_out", ctypes.c_void_p),
+        ("out_of_order_out", ctypes.c_void_p),
+        ("misses_out", ctypes.c_void_p),
         ("unswept_out", ctypes.c_void_p),
     ]
 
@@ -377,6 +417,7 @@ def load(path: str = None) -> ctypes.CDLL:
     lib.dsim_obstacle_clearance_scenes.argtypes = [vp, vp, i64, View, vp, vp, vp, vp, ctypes.c_float, vp, vp, vp]
     lib.dsim_depth_image_scenes.argtypes = [vp, vp, View, vp, vp, ctypes.POINTER(CameraParams), i64, vp, vp, vp, vp, vp]
     lib.dsim_range_scan.argtypes = [vp, vp, i64, View, vp, ctypes.POINTER(ScanArgs)]
+    lib.dsim_gate_passage.argtypes = [vp, vp, i64, View, vp, vp, ctypes.POINTER(GateArgs)]
     lib.dsim_trajgen_workspace.restype = ctypes.c_int64
     lib.dsim_trajgen_workspace.argtypes = [i64, i32]
     lib.dsim_trajgen.argtypes = [vp, vp, ctypes.POINTER(TrajBank), ctypes.POINTER(TrajGenArgs)]

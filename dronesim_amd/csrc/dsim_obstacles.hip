@@ -35,6 +35,7 @@ struct dsim_scenes {
   float4* place;                 // [K][G][4]
   long long K;
   int G;
+  float box_c[3];                // the centre of the prototype's box in its own frame (what c_task is the placed image of)
 };
 
 struct ObsK {
@@ -323,3 +324,6 @@ int dsim_obstacle_clearance(dsim_ctx* ctx, void* stream, int64_t n, dsim_view st
 
 // the range scanner: per-drone beam fans against the set, the scenes, the plane and the drones (it shares the camera's walk and records)
 #include "dsim_scan.hip"
+
+// the gate passage watch: the chord between two samples against one aperture per placement (it shares the tile frame and the scenes)
+#include "dsim_passage.hip"

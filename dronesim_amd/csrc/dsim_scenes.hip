@@ -110,6 +110,7 @@ int dsim_scenes_create(dsim_ctx* ctx, const dsim_obstacles* proto, const float* 
   dsim_scenes* sc = new (std::nothrow) dsim_scenes();
   if (!sc) return (int)hipErrorOutOfMemory;
   sc->proto = proto; sc->place = nullptr; sc->K = K; sc->G = G;
+  for (int k = 0; k < 3; ++k) sc->box_c[k] = (float)c[k];
   hipError_t e = hipSetDevice(ctx->device);
   if (e == hipSuccess) e = hipMalloc((void**)&sc->place, rec.size() * sizeof(float));
   if (e == hipSuccess) e = hipMemcpy(sc->place, rec.data(), rec.size() * sizeof(float), hipMemcpyHostToDevice);

@@ -152,6 +152,11 @@ class CtrlAviary(PlacedFleetArrays, FleetObservation, StepWatches):
         range_clamp: bool = False,
         range_see_drones: bool = False,
         range_drone_range: Optional[float] = None,
+        gate_watch=None,
+        gate_scenes=None,
+        gate_start: int = 0,
+        gate_laps: bool = False,
+        gate_travel: Optional[float] = None,
     ):
         if gui or record or obstacles:
             raise NotImplementedError("gui/record/obstacles are rendering features outside the hot path")
@@ -164,7 +169,8 @@ class CtrlAviary(PlacedFleetArrays, FleetObservation, StepWatches):
                             obstacle_scene_id=obstacle_scene_id, drone_sweep=drone_sweep, drone_sweep_sag=drone_sweep_sag,
                             drone_sweep_travel=drone_sweep_travel, range_scan=range_scan, range_scene=range_scene,
                             range_min=range_min, range_max=range_max, range_ground=range_ground, range_clamp=range_clamp,
-                            range_see_drones=range_see_drones, range_drone_range=range_drone_range)
+                            range_see_drones=range_see_drones, range_drone_range=range_drone_range, gate_watch=gate_watch,
+                            gate_scenes=gate_scenes, gate_start=gate_start, gate_laps=gate_laps, gate_travel=gate_travel)
         # the add-on terms of the PYB_* modes (dead code in the reference fork, intended formulas); Physics.DYN: the
         # reference's own explicit model, BaseAviary._dynamics (BaseAviary.py:1767-1828; DSIM_OPT_DYN)
         self._phys_options = {Physics.PYB: 0, Physics.PYB_DW: 0, Physics.PYB_GND: nat.OPT_GROUND,

@@ -23,6 +23,7 @@ class StepWatches:
     _vision = None                # the depth camera of vision_attributes=True (set by _watch_setup)
     _scan = None                  # the range scanner of range_scan= (set by _watch_setup)
     _scan_args = None
+    _gate = None                  # the gate passage watch's device scenes (set by _watch_setup)
 
     # ------------------------------------------------------------------ construction
     def _watch_options(self, *, num_drones, freq, aggregate_phy_steps, dist, drone_watch, drone_watch_margin, obstacle_watch,
@@ -30,7 +31,8 @@ class StepWatches:
                        vision_drones, vision_res, vision_ground, vision_see_drones, vision_drone_range, obstacle_scene_id=None,
                        drone_sweep=False, drone_sweep_sag=0.0, drone_sweep_travel=None, range_scan=None, range_scene=None,
                        range_min=0.0, range_max=10.0, range_ground=True, range_clamp=False, range_see_drones=False,
-                       range_drone_range=None) -> None:
+                       range_drone_range=None, gate_watch=None, gate_scenes=None, gate_start=0, gate_laps=False,
+                       gate_travel=None) -> None:
         """The services' keywords of ``CtrlAviary.__init__``: checked and stashed (the set-up follows in _watch_setup, when the
         context and the storage order exist)."""
         # The reference's Bullet world lets the vehicles' collision shapes act on each other; here every drone is integrated
@@ -75,11 +77,37 @@ class StepWatches:
         # [0, K) meaning no obstacles.  `nearest` and seg then hold the instance-major body index g n_bodies + body.  Two deliberate
         # cuts: the swept watch and the other drones in the images are not implemented on scenes (the unplaced forms are).
         from ..obstacles import ObstacleScenes
-        placed = [x for x in (obstacle_watch, vision_scene, range_scene) if isinstance(x, ObstacleScenes)]
+        # gate_watch=Aperture: every launch is followed, on the env's stream, by one dsim_gate_passage: the chord from the position
+        # the previous query saw (reset() primes it) to the state the launch left, against the aperture at every placement of each
+        # drone's scene.  gate_scenes: the ObstacleScenes whose placements are the gates (None: the ObstacleScenes of obstacle_watch,
+        # and its device object); obstacle_scene_id and obstacle_offsets are shared either way.  A plain world common to all drones
+        # is a scenes object of K = 1 with every id 0.  gate_start: the slot due first (every drone; a course that starts AT gate 0
+        # has s0 = 0 there, which is no forward crossing, so it starts at 1).  gate_laps: at the end of a scene's gates the course
+        # starts again and gate_laps counts.  gate_travel [m]: the longest chord that is a passage (None: 10 m/s x one Env.step); a
+        # longer one is a reset and is counted by gate_unswept().  On a sharded fleet it works per rank: nothing of the other
+        # ranks' drones is needed.  Off by default: nothing is allocated or launched.
+        from ..obstacles import Aperture
+        if gate_watch is None:
+            if gate_scenes is not None or gate_start != 0 or gate_laps or gate_travel is not None:
+                raise ValueError("gate_scenes / gate_start / gate_laps / gate_travel without gate_watch=Aperture")
+        else:
+            if not isinstance(gate_watch, Aperture):
+                raise ValueError("gate_watch takes an obstacles.Aperture")
+            world = gate_scenes if gate_scenes is not None else obstacle_watch
+            if not isinstance(world, ObstacleScenes):
+                raise ValueError("gate_watch needs the gates' placements: gate_scenes=ObstacleScenes, or obstacle_watch=ObstacleScenes "
+                                 "to share")
+            if not 0 <= int(gate_start) <= world.G:
+                raise ValueError(f"gate_start must be a slot in 0 .. {world.G}")
+        self._gate_ap, self._gate_scenes, self._gate_start, self._gate_wrap = gate_watch, gate_scenes, int(gate_start), bool(gate_laps)
+        self._gate_travel = 10.0 * int(aggregate_phy_steps) / float(freq) if gate_travel is None else float(gate_travel)
+        if gate_watch is not None and (not np.isfinite(self._gate_travel) or not self._gate_travel >= 1e-3):
+            raise ValueError("gate_travel must be at least a millimetre")
+        placed = [x for x in (obstacle_watch, vision_scene, range_scene, gate_scenes) if isinstance(x, ObstacleScenes)]
         if placed and obstacle_scene_id is None:
             raise ValueError("obstacle_scene_id [N] is required with an ObstacleScenes")
         if not placed and obstacle_scene_id is not None:
-            raise ValueError("obstacle_scene_id without an ObstacleScenes (obstacle_watch=, vision_scene= or range_scene=)")
+            raise ValueError("obstacle_scene_id without an ObstacleScenes (obstacle_watch=, vision_scene=, range_scene= or gate_scenes=)")
         if placed:
             ids = np.asarray(obstacle_scene_id)
             if ids.shape != (num_drones,) or not np.issubdtype(ids.dtype, np.integer):
@@ -189,12 +217,13 @@ class StepWatches:
         self._obstacle_setup(offsets)
         self._vision_setup(offsets)
         self._scan_setup(offsets)
+        self._gate_setup(offsets)
 
     def _obstacle_setup(self, offsets) -> None:
         """obstacle_watch: the device set for reach = R_max + margin, the offsets in storage order and the tensors every
         per-step query writes (fixed addresses: a captured sequence holds them)."""
         if self._obst_set is None:
-            if offsets is not None and self._vision_args is None and self._scan_args is None:
+            if offsets is not None and self._vision_args is None and self._scan_args is None and self._gate_ap is None:
                 raise ValueError("obstacle_offsets without obstacle_watch")
             return
         from .. import obstacles as obs
@@ -258,6 +287,55 @@ class StepWatches:
                                   offsets=offsets, type_id=self._type_id, drones=see_drones, drone_range=drone_range,
                                   scene_id=self._scene_ids if isinstance(world, (ObstacleScenes, DeviceScenes)) else None)
 
+    def _gate_setup(self, offsets) -> None:
+        """gate_watch=Aperture: the device scenes (the obstacle watch's when the gates are its placements), ids and offsets in
+        storage order, and the tensors every query reads and writes (fixed addresses: a captured sequence holds them)."""
+        if self._gate_ap is None:
+            return
+        from .. import obstacles as obs
+        dev, n_pad = self.ctx.device, self.state.n_pad
+        self._gate_shared = self._obst is not None and self._obst_placed and (self._gate_scenes is None
+                                                                             or self._gate_scenes is self._obst_set)
+        if self._gate_shared:
+            self._gate, self._gate_ids, self._gate_off = self._obst, self._obst_ids, self._obst_off
+        else:
+            # (the watch looks at placements only: the prototype's grid is made for the least reach the point watch would take)
+            self._gate = self._gate_scenes.to_device(self.ctx, obs.watch_reach(self.ctx.types, 1.0))
+            self._gate_ids = obs.scene_ids_tensor(self._scene_ids, self.NUM_DRONES, n_pad, dev, self.order)
+            self._gate_off = None
+            if offsets is not None:
+                offsets = np.asarray(offsets, dtype=np.float64)
+                if offsets.shape != (self.NUM_DRONES, 3):
+                    raise ValueError(f"obstacle_offsets must be [{self.NUM_DRONES}, 3]")
+                self._gate_off = self._soa3(offsets)
+        i32 = lambda: torch.zeros((n_pad,), dtype=torch.int32, device=dev)
+        self._gate_prev = torch.zeros((3, n_pad), dtype=torch.float32, device=dev)
+        self._gate_due, self._gate_lap = i32(), i32()
+        self._gate_time = torch.full((self._gate.G, n_pad), float("nan"), dtype=torch.float64, device=dev)
+        self._gate_fwd, self._gate_back, self._gate_miss = i32(), i32(), i32()
+        self._gate_clock = torch.zeros((1,), dtype=torch.int64, device=dev)      # queries so far: the whole part of a passage time
+        self._gate_counts = torch.zeros((5,), dtype=torch.int64, device=dev)     # passes, wrong way, out of order, misses, unswept
+        self._gate_sampled = False
+        self._watch_placed()
+
+    def _watch_gates(self, scratch: bool = False) -> None:
+        """One dsim_gate_passage on the state the launch just left, on the env's stream (also under capture), then the clock moves
+        on by one query.  ``scratch``: the eager call before a capture — a look ahead: prev and the course stay, events and counts go to copies."""
+        from .. import obstacles as obs
+        c = self._gate_counts
+        if scratch:
+            c = torch.zeros_like(c)
+            obs.gate_passage(self.ctx, self.state, self._gate, self._gate_ids, self._gate_ap, self._gate_travel, self._gate_prev,
+                             self._gate_due, self._gate_lap, self._gate_clock, self._gate_time,
+                             torch.zeros_like(self._gate_fwd), None, None, self._gate_off, c[0:1], c[1:2], c[2:3], c[3:4], c[4:5],
+                             wrap=self._gate_wrap, keep_prev=True)
+            return
+        obs.gate_passage(self.ctx, self.state, self._gate, self._gate_ids, self._gate_ap, self._gate_travel, self._gate_prev,
+                         self._gate_due, self._gate_lap, self._gate_clock, self._gate_time, self._gate_fwd, self._gate_back,
+                         self._gate_miss, self._gate_off, c[0:1], c[1:2], c[2:3], c[3:4], c[4:5], wrap=self._gate_wrap)
+        nat.check(self.ctx.lib.dsim_counter_add(self.ctx.handle, self.ctx.stream_ptr(), self._gate_clock.data_ptr(), 1))
+        self._gate_sampled = True
+
     def _watch_reset(self) -> None:
         """_housekeeping: the step counter is back at zero, and so is the last one the camera's cadence saw."""
         self._vision_seen = 0
@@ -269,12 +347,25 @@ class StepWatches:
             obs.prime(self.ctx, self.state, self._obst, self._obst_prev)
         if self._drone_prev is not None:
             self._drone_grid().clearance_prime(self._drone_prev)
+        if self._gate is not None:
+            # every course starts again: the chords from here, gate_start due, no lap, no passage time, the clock at zero
+            from .. import obstacles as obs
+            obs.gate_prime(self.ctx, self.state, self._gate_prev)
+            self._gate_due.fill_(self._gate_start)
+            self._gate_lap.zero_()
+            self._gate_time.fill_(float("nan"))
+            self._gate_clock.zero_()
+            for t in (self._gate_fwd, self._gate_back, self._gate_miss):
+                t.zero_()
+            self._gate_sampled = False
 
     def _watch_close(self) -> None:
         if self._vision is not None:
             self._vision.close()
         if self._scan is not None:
             self._scan.close()
+        if self._gate is not None and not self._gate_shared:
+            self._gate.close()
         if self._obst is not None:
             self._obst.close()
 
@@ -299,6 +390,8 @@ class StepWatches:
                 self._vision_capture()
         if self._scan is not None:
             self._scan_now()
+        if self._gate is not None:
+            self._watch_gates()
 
     def _drone_grid(self):
         from ..downwash import Downwash
@@ -386,6 +479,8 @@ class StepWatches:
             sampled = self._scan_sampled
             self._scan_now()
             self._scan_sampled = sampled
+        if self._gate is not None:
+            self._watch_gates(scratch=True)   # (eager: the watch's kernel is loaded before the capture starts; prev and the course stay)
 
     def _captured_step(self) -> None:
         """Behind every captured step, as in eager mode: the obstacle watch's query, the camera at its cadence of 1, the scan."""
@@ -395,6 +490,8 @@ class StepWatches:
             self._vision_capture()
         if self._scan is not None:
             self._scan_now()
+        if self._gate is not None:
+            self._watch_gates()
 
     def _capture_keepalive(self):
         """After the capture: what the graph must keep alive.  The captured captures hold the camera's addresses, among them the
@@ -407,6 +504,8 @@ class StepWatches:
         self._vision_seen = self.step_counter
         if self._scan is not None:
             self._scan_sampled = True
+        if self._gate is not None:
+            self._gate_sampled = True
 
     # ------------------------------------------------------------------ public surface
     @property
@@ -429,6 +528,68 @@ class StepWatches:
             self._downwash.invalidate_prebin()
         self._scan.scan()
         return self._scan.ranges, self._scan.hits
+
+    # ---- the gate passage watch
+    def _gate_need(self, what: str) -> None:
+        if self._gate is None:
+            raise ValueError(f"{what} needs an env made with gate_watch=Aperture")
+
+    def _gate_to_caller(self, t, dim: int = 0):
+        t = t[: self.NUM_DRONES] if dim == 0 else t[:, : self.NUM_DRONES]
+        return self.order.to_caller(t, dim) if self.order is not None else t
+
+    @property
+    def gate_due(self):
+        """[N] int32: the slot of its scene every drone has to pass next (the scene's count: finished), the caller's numbering."""
+        self._gate_need("gate_due")
+        return self._gate_to_caller(self._gate_due)
+
+    @property
+    def gate_laps(self):
+        """[N] int32: how often every drone completed its scene's gates (``gate_laps=True``; else 0)."""
+        self._gate_need("gate_laps")
+        return self._gate_to_caller(self._gate_lap)
+
+    @property
+    def gate_pass_time(self):
+        """[G, N] float64: when every drone last passed slot g IN ORDER, in queries (launches) since reset() — the number of the
+        query's chord plus the fraction tau of it at which the plane was crossed; NaN: not passed."""
+        self._gate_need("gate_pass_time")
+        return self._gate_to_caller(self._gate_time, 1)
+
+    @property
+    def last_gate_events(self):
+        """(fwd, back, miss) [N] int32 behind the last step, one bit per slot: crossed forward inside the aperture, backward inside
+        it, forward outside it but inside the outer rectangle.  None before the first step."""
+        self._gate_need("last_gate_events")
+        if not self._gate_sampled:
+            return None
+        return tuple(self._gate_to_caller(t) for t in (self._gate_fwd, self._gate_back, self._gate_miss))
+
+    def _gate_count(self, k: int, what: str) -> int:
+        self._gate_need(what)
+        return int(self._gate_counts[k].item())
+
+    def gate_passes(self) -> int:
+        """Gates passed in order so far, over the fleet (cumulative, also across reset(); synchronises the stream)."""
+        return self._gate_count(0, "gate_passes()")
+
+    def gate_wrong_way(self) -> int:
+        """Backward crossings inside an aperture so far (cumulative; synchronises the stream)."""
+        return self._gate_count(1, "gate_wrong_way()")
+
+    def gate_out_of_order(self) -> int:
+        """Forward crossings inside an aperture that did not advance a course: a gate that was not due (cumulative)."""
+        return self._gate_count(2, "gate_out_of_order()")
+
+    def gate_misses(self) -> int:
+        """Drones x queries whose due gate was crossed forward outside its aperture but inside the outer rectangle (cumulative)."""
+        return self._gate_count(3, "gate_misses()")
+
+    def gate_unswept(self) -> int:
+        """Drones x queries without a usable chord: longer than gate_travel, or a non-finite position on either end (cumulative).
+        Such a chord is no passage, whatever it crossed."""
+        return self._gate_count(4, "gate_unswept()")
 
     def drone_clearance(self, margin: float = 1.0):
         """Per-drone clearance of the CURRENT state between the vehicles' bounding spheres (dsim_clearance; no counterpart in

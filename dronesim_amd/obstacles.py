@@ -415,3 +415,81 @@ def prime(ctx, state, dev: DeviceObstacles, prev) -> None:
     """``prev`` := the current positions (DSIM_SWEEP_PRIME): the next :func:`sweep` starts its chords here."""
     a = nat.SweepArgs(None, None, 0.0, 0.0, prev.data_ptr(), nat.SWEEP_PRIME, None, None, None, None)
     nat.check(ctx.lib.dsim_obstacle_sweep(ctx.handle, ctx.stream_ptr(), state.n, state.view(), dev.handle, ctypes.byref(a)))
+
+
+# ---- the gate passage watch (dsim_gate_passage) ----------------------------------------------------------------------------------------
+class Aperture:
+    """One planar opening in the frame of an :class:`ObstacleScenes`' prototype: what a gate is flown THROUGH.  ``center`` [3];
+    ``normal`` [3], the forward direction, and ``u`` [3], an in-plane axis — both of unit length to 1e-5 and perpendicular to
+    1e-5 (they are used as given, never normalised: v = normal x u); ``half`` (a, b) > 0, the half-extents along u and v;
+    ``shape`` "rect" or "ellipse" (the ellipse inscribed in the rectangle); ``outer`` (a_out >= a, b_out >= b) or None: a
+    rectangle around the opening — a forward crossing inside it but outside the aperture is a miss, the vehicle went over or
+    round the opening."""
+
+    SHAPES = {"rect": nat.APERTURE_RECT, "ellipse": nat.APERTURE_ELLIPSE}
+
+    def __init__(self, center, normal, u, half, shape="rect", outer=None):
+        vec = lambda x, k, what: self._vec(x, k, what)
+        self.center, self.normal, self.u = vec(center, 3, "center"), vec(normal, 3, "normal"), vec(u, 3, "u")
+        self.half = vec(half, 2, "half")
+        self.outer = vec(outer, 2, "outer") if outer is not None else None
+        if shape not in self.SHAPES:
+            raise ValueError(f"shape must be 'rect' or 'ellipse', got {shape!r}")
+        self.shape = shape
+        n, uu = self.normal.astype(np.float64), self.u.astype(np.float64)
+        if abs(np.linalg.norm(n) - 1.0) > 1e-5 or abs(np.linalg.norm(uu) - 1.0) > 1e-5:
+            raise ValueError("normal and u must be of unit length (to 1e-5)")
+        if abs(float(n @ uu)) > 1e-5:
+            raise ValueError("u must be perpendicular to normal (to 1e-5)")
+        if not (self.half > 0).all():
+            raise ValueError("half-extents must be positive")
+        if self.outer is not None and not (self.outer >= self.half).all():
+            raise ValueError("the outer rectangle must not be smaller than the aperture")
+
+    @staticmethod
+    def _vec(x, k, what):
+        v = np.asarray(x, dtype=np.float32).reshape(-1)
+        if v.shape != (k,) or not np.isfinite(v).all():
+            raise ValueError(f"{what} must be {k} finite numbers")
+        return v
+
+    @property
+    def v(self) -> np.ndarray:
+        """normal x u, fp64 on the float32 numbers the device is given."""
+        return np.cross(self.normal.astype(np.float64), self.u.astype(np.float64))
+
+    def to_c(self) -> "nat.ApertureC":
+        c = nat.ApertureC()
+        c.center[:], c.normal[:], c.u[:], c.half[:] = self.center.tolist(), self.normal.tolist(), self.u.tolist(), self.half.tolist()
+        c.outer[:] = self.outer.tolist() if self.outer is not None else [0.0, 0.0]
+        c.shape = self.SHAPES[self.shape]
+        return c
+
+
+def gate_passage(ctx, state, dev_scenes: DeviceScenes, scene_id, aperture: Aperture, travel: float, prev, due, laps=None, clock=None,
+                 pass_time=None, fwd=None, back=None, miss=None, offset=None, passes_out=None, wrong_way_out=None,
+                 out_of_order_out=None, misses_out=None, unswept_out=None, wrap: bool = False, keep_prev: bool = False) -> None:
+    """dsim_gate_passage on the current stream: the chord from ``prev`` ([3, n_pad] float32, world frame, updated unless
+    ``keep_prev``) to the current positions against the aperture at every placement of each drone's scene.  ``due`` ([n_pad]
+    int32) and, with ``wrap``, ``laps`` ([n_pad] int32) are the course state, in-out; ``pass_time`` ([G, n_pad] float64) receives
+    ``clock`` (int64 [1] device counter, the caller advances it) + tau for every gate passed; ``fwd`` / ``back`` / ``miss``
+    ([n_pad] int32, one bit per slot) the events of this query; the ``*_out`` are int64 [1] device counters.  All but ``prev``
+    and ``due`` may be None."""
+    if not isinstance(aperture, Aperture):
+        raise TypeError("aperture takes an obstacles.Aperture")
+    if scene_id is None:
+        raise ValueError("scene_id is required")
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    flags = (nat.SWEEP_KEEP_PREV if keep_prev else 0) | (nat.GATE_WRAP if wrap else 0)
+    a = nat.GateArgs(aperture.to_c(), float(travel), flags, ptr(offset), prev.data_ptr(), due.data_ptr(), ptr(laps), ptr(clock),
+                     ptr(pass_time), ptr(fwd), ptr(back), ptr(miss), ptr(passes_out), ptr(wrong_way_out), ptr(out_of_order_out),
+                     ptr(misses_out), ptr(unswept_out))
+    nat.check(ctx.lib.dsim_gate_passage(ctx.handle, ctx.stream_ptr(), state.n, state.view(), dev_scenes.handle, scene_id.data_ptr(),
+                                        ctypes.byref(a)))
+
+
+def gate_prime(ctx, state, prev) -> None:
+    """``prev`` := the current positions (DSIM_SWEEP_PRIME): the next :func:`gate_passage` starts its chords here."""
+    a = nat.GateArgs()
+    a.prev, a.flags = prev.data_ptr(), nat.SWEEP_PRIME
+    nat.check(ctx.lib.dsim_gate_passage(ctx.handle, ctx.stream_ptr(), state.n, state.view(), None, None, ctypes.byref(a)))

@@ -15,7 +15,10 @@ scene of three placements per drone), yawed so that its normal lies along the xy
 flight is watched (obstacle_watch=scenes) and the run prints obstacle_contacts() and the least clearance per gate slot.  With
 --vision every drone also carries a camera that sees its own gates, and one depth frame is saved (--out).  With --scan N every
 drone carries a ring of N range beams (scanner.RangeScanner through the env's range_scan=) against its own gates, scanned behind
-every step, and the fleet's least range per gate slot is printed beside the clearances.
+every step, and the fleet's least range per gate slot is printed beside the clearances.  --gates also turns the gate passage watch
+on (gate_watch=Aperture: the rectangle |y| <= 0.30, |z| <= 0.20 m on the gate's plane x = 0, inside the mesh's opening): the run
+prints how many drones flew through 0 / 1 / 2 / 3 of their gates in order, the misses and wrong-way crossings, and the fleet's
+median passage time per slot.  Every drone starts AT its gate 0, on the plane, which is no forward crossing: gate 1 is due first.
 """
 import argparse
 import os
@@ -90,7 +93,10 @@ def main(argv=None):
         ctx0 = Context([builtin_type("robobee")])
         scenes = gate_scenes(ctx0, TrajectoryBank(ctx0, gates, max_vel=0.7, gamma=1e6, times=A.times), gates, AGGR / FREQ)
         ctx0.close()
-        watch = dict(obstacle_watch=scenes, obstacle_scene_id=np.arange(n), obstacle_offsets=off, obstacle_margin=A.margin)
+        from dronesim_amd.obstacles import Aperture
+        opening = Aperture((0, 0, 0), (1, 0, 0), (0, 1, 0), (0.30, 0.20), "rect", outer=(0.56, 0.40))
+        watch = dict(obstacle_watch=scenes, obstacle_scene_id=np.arange(n), obstacle_offsets=off, obstacle_margin=A.margin,
+                     gate_watch=opening, gate_start=1)        # (gate_scenes=None: the watch's scenes and their device object)
         if A.vision:
             watch["vision_attributes"] = True
         if A.scan:
@@ -137,6 +143,13 @@ def main(argv=None):
                     + (f", least range of {A.scan} beams {least_range[j]:.3f} m" if A.scan else "") for j in range(3)]
         print(f"obstacle_contacts() = {env.obstacle_contacts()} drone x steps with the bounding sphere on a gate; least clearance per "
               f"gate slot: " + "; ".join(per_slot))
+        due, when = env.gate_due.cpu().numpy(), env.gate_pass_time.cpu().numpy() * dt_ctrl       # (one query per control step)
+        passed = np.bincount(np.clip(due - 1, 0, 3), minlength=4)
+        med = ["-" if np.isnan(when[j]).all() else f"{np.nanmedian(when[j]):.2f} s" for j in range(3)]
+        print(f"gates passed in order (gate 0 is the start): " + ", ".join(f"{passed[k]} drones passed {k}" for k in range(3))
+              + f"; gate_passes() = {env.gate_passes()}, gate_misses() = {env.gate_misses()}, gate_wrong_way() = "
+              f"{env.gate_wrong_way()}, gate_out_of_order() = {env.gate_out_of_order()}, gate_unswept() = {env.gate_unswept()}; "
+              f"median passage time per slot: " + ", ".join(f"gate {j}: {med[j]}" for j in range(3)))
     if A.vision:
         np.save(A.out, (frame if frame is not None else env.dep).cpu().numpy())
         print(f"depth frame [{n}, 48, 64] saved to {A.out}" + ("" if frame is not None else " (no gate came into view)"))

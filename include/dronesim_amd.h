@@ -51,7 +51,8 @@ extern "C" {
                               DSIM_TRAJGEN_* (DSIM_TRAJGEN_BAD_CONDITION among them); the swept obstacle watch, dsim_obstacle_sweep, dsim_sweep_args, DSIM_SWEEP_*; obstacle
                               scenes, dsim_scenes_create / _destroy, dsim_obstacle_clearance_scenes, dsim_depth_image_scenes; the
                               swept drone-drone watch, dsim_clearance_sweep, dsim_clearance_sweep_workspace,
-                              dsim_clearance_sweep_args; the range scanner, dsim_range_scan, dsim_scan_args, DSIM_SCAN_* */
+                              dsim_clearance_sweep_args; the range scanner, dsim_range_scan, dsim_scan_args, DSIM_SCAN_*; the
+                              gate passage watch, dsim_gate_passage, dsim_gate_args, dsim_aperture, DSIM_APERTURE_*, DSIM_GATE_WRAP */
 #define DSIM_MAX_ACT 6     /* actuators per vehicle (quad 4, morphing hexa 6) */
 #define DSIM_MAX_TYPES 8
 
@@ -1090,6 +1091,87 @@ typedef struct dsim_scan_args {
 } dsim_scan_args;
 int dsim_range_scan(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, const dsim_obstacles* set,
                     const dsim_scan_args* args);
+
+/* Gate passage watch: which drones flew THROUGH the gates of their scene, in order.  The clearance watches say how close a
+ * vehicle came to a gate's frame; a drone that flies round its gate, goes through backwards or never reaches it has a perfect
+ * clearance.  Passage is a question about the chord between two states, so the watch keeps its own `prev` under the rules of
+ * dsim_obstacle_sweep.  Stream-ordered, allocates nothing, never synchronises; may be captured.
+ *
+ * The aperture: one planar opening in the PROTOTYPE's frame, the same for every placement.  Centre c, unit normal n (the forward
+ * direction), unit in-plane axis u perpendicular to n, v = n x u, half-extents half[0] along u and half[1] along v, a rectangle
+ * or the ellipse inscribed in it.  outer[0] >= half[0], outer[1] >= half[1]: an optional rectangle around the opening (the
+ * gate's frame seen from the front); (0, 0): none.  The gate index of a placement is its slot g in the scene.
+ *
+ * For drone i < n with s = scene_id[i] in [0, K), q0 = prev_i - offset_i, q1 = p_i - offset_i, and every slot g < count[s],
+ * with l = R_g^T (q - t_g) (subtract first, then rotate, as the placed clearance watch does):
+ *     s0 = n.(l0 - c), s1 = n.(l1 - c)          forward crossing: s0 < 0 && s1 >= 0; backward: s0 >= 0 && s1 < 0 (half-open: a
+ *                                               state exactly on the plane is counted once across two consecutive chords)
+ *     tau = s0 / (s0 - s1), x = l0 + tau (l1 - l0), y = u.(x - c), z = v.(x - c)
+ *     inside: |y| <= half[0] && |z| <= half[1]  (rectangle),  (y / half[0])^2 + (z / half[1])^2 <= 1  (ellipse)
+ *     fwd_out[i]  bit g: a forward crossing inside the aperture;  back_out[i] bit g: a backward crossing inside it
+ *     miss_out[i] bit g: a forward crossing outside the aperture but with |y| <= outer[0] && |z| <= outer[1]: the vehicle went
+ *                        over or round the opening (never set without an outer rectangle)
+ * Progress: while due_i < count[s] and the due gate has its fwd bit at a tau greater than the last accepted one of this chord,
+ * pass_time[due_i][i] := *clock + tau and due_i advances; one chord through three gates standing in order advances by three, the
+ * same chord through them in the wrong order by one.  At due_i == count[s] the drone has finished and advances no more; with
+ * DSIM_GATE_WRAP due_i returns to 0 instead and laps_i increments.  A due_i outside [0, count[s]) on entry makes no progress.
+ * due and laps are in-out, owned by the caller at fixed addresses (a captured and replayed call carries them); due_i is written
+ * only when it advanced, laps_i only when it wrapped, pass_time only for the gates passed.
+ *
+ * The passage time is a double: *clock (a device counter the caller advances between queries, dsim_counter_add; NULL: 0) as the
+ * whole part, exact up to 2^53, plus tau in [0, 1] of the chord: the unit is one query, the resolution a float of the chord.
+ * It is read from device memory when the kernel runs, so a replayed capture, whose arguments are frozen, stamps the right time.
+ *
+ * Fleet counters (device uint64, nullable; one atomic per wave and counter at most):
+ *     passes_out        advances of due, summed          wrong_way_out     bits set in back_out, summed
+ *     out_of_order_out  bits set in fwd_out that did not advance due (a gate that is not due, or a finished course)
+ *     misses_out        drones whose due gate — the one due when the query ends — has its miss bit
+ *     unswept_out       drones without a usable chord
+ * UNSWEPT, as in dsim_obstacle_sweep: a non-finite component of prev_i or p_i, or a chord longer than `travel`.  Such a drone has
+ * no event (its masks are 0), makes no progress and is counted once: a teleport across a gate is a reset, not a passage.
+ * A scene_id[i] outside [0, K) leaves everything of that drone untouched — masks, due, laps, pass_time, the counters — but prev;
+ * so do the slots at or above the count.  Then, unless DSIM_SWEEP_KEEP_PREV is set, prev_i := p_i bit for bit for every i < n.
+ * DSIM_SWEEP_KEEP_PREV is a look ahead (on-demand queries, the eager call before a capture): prev, due, laps and pass_time stay as
+ * they were; the masks and the counters are those of the query it would have been.
+ * DSIM_SWEEP_PRIME: prev_i := p_i for i < n and nothing else; scenes, scene_id and every other field are not looked at.
+ *
+ * A lane reads the first 16 bytes of each of its scene's G slots and the other 48 only of a slot the chord can reach
+ * (|q1 - c_task| <= r_ap + |q1 - q0| is necessary for a crossing point inside the outer rectangle; it decides speed only).
+ * DSIM_E_ARG, nothing enqueued: a null ctx / args / prev, n <= 0 or > n_pad, an unknown flag or KEEP_PREV together with PRIME;
+ * and unless PRIME: a null scenes / scene_id / due, WRAP without laps, travel <= 0 or not finite, an unknown shape, n or u not of
+ * unit length or u not perpendicular to n (each to 1e-5), a half-extent <= 0, an outer rectangle smaller than the aperture in
+ * either extent (or only one of its extents given), any non-finite entry of the aperture. */
+enum { DSIM_APERTURE_RECT = 0, DSIM_APERTURE_ELLIPSE = 1 };
+enum { DSIM_GATE_WRAP = 4 };      /* beside DSIM_SWEEP_KEEP_PREV = 1 and DSIM_SWEEP_PRIME = 2 in dsim_gate_args.flags */
+typedef struct dsim_aperture {
+  float   center[3];
+  float   normal[3];      /* unit: the forward direction                                            */
+  float   u[3];           /* unit, perpendicular to normal; v = normal x u                          */
+  float   half[2];        /* > 0: half-extents along u and v                                        */
+  float   outer[2];       /* (0, 0): none; else outer[k] >= half[k]                                 */
+  int32_t shape;          /* DSIM_APERTURE_RECT | DSIM_APERTURE_ELLIPSE                             */
+} dsim_aperture;
+typedef struct dsim_gate_args {
+  dsim_aperture   aperture;
+  float           travel;        /* > 0 [m]: a longer chord is unswept                                 */
+  int32_t         flags;         /* DSIM_SWEEP_KEEP_PREV | DSIM_SWEEP_PRIME | DSIM_GATE_WRAP           */
+  const float*    offset;        /* SoA [3][n_pad] or NULL, as dsim_obstacle_clearance                 */
+  float*          prev;          /* SoA [3][n_pad], WORLD frame, in-out; required                      */
+  int32_t*        due;           /* [n_pad], in-out; required unless PRIME                             */
+  int32_t*        laps;          /* [n_pad], in-out; required with DSIM_GATE_WRAP, else not looked at  */
+  const uint64_t* clock;         /* device counter, nullable (0)                                       */
+  double*         pass_time;     /* [G][n_pad] slot-major (G of the scenes), nullable                  */
+  uint32_t*       fwd_out;       /* [n_pad], nullable                                                  */
+  uint32_t*       back_out;      /* [n_pad], nullable                                                  */
+  uint32_t*       miss_out;      /* [n_pad], nullable                                                  */
+  uint64_t*       passes_out;    /* device counters, each nullable                                     */
+  uint64_t*       wrong_way_out;
+  uint64_t*       out_of_order_out;
+  uint64_t*       misses_out;
+  uint64_t*       unswept_out;
+} dsim_gate_args;
+int dsim_gate_passage(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, const dsim_scenes* scenes,
+                      const int32_t* scene_id, const dsim_gate_args* args);
 
 /* The rotor-noise normals the step kernels draw (diagnostics / distribution studies; no counterpart in the reference, whose
  * draws come from numpy's global generator): for drones [0, n) and the physics sub-steps [0, substeps) of Env.step number
