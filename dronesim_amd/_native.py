@@ -31,6 +31,7 @@ EXPORTS = (
     "dsim_clearance_sweep", "dsim_clearance_sweep_workspace",
     "dsim_range_scan",
     "dsim_gate_passage",
+    "dsim_knn", "dsim_knn_workspace",
 )
 
 ABI_VERSION = 11
@@ -246,6 +247,24 @@ class ClearanceSweepArgs(ctypes.Structure):
     ]
 
 
+KNN_MAX_K = 16            # dsim_knn_args.k: 1 .. 16
+
+
+class KnnArgs(ctypes.Structure):
+    """dsim_knn_args (dsim_knn): the k nearest drones within a radius, sorted, with their relative state."""
+    _fields_ = [
+        ("grid", ctypes.c_void_p),          # const dsim_downwash_args*
+        ("radius", ctypes.c_float),
+        ("k", ctypes.c_int32),
+        ("flags", ctypes.c_int32),
+        ("index_out", ctypes.c_void_p),
+        ("dist_out", ctypes.c_void_p),
+        ("rel_pos_out", ctypes.c_void_p),
+        ("rel_vel_out", ctypes.c_void_p),
+        ("count_out", ctypes.c_void_p),
+    ]
+
+
 class View(ctypes.Structure):
     _fields_ = [
         ("base", ctypes.c_void_p),
@@ -418,6 +437,9 @@ def load(path: str = None) -> ctypes.CDLL:
     lib.dsim_depth_image_scenes.argtypes = [vp, vp, View, vp, vp, ctypes.POINTER(CameraParams), i64, vp, vp, vp, vp, vp]
     lib.dsim_range_scan.argtypes = [vp, vp, i64, View, vp, ctypes.POINTER(ScanArgs)]
     lib.dsim_gate_passage.argtypes = [vp, vp, i64, View, vp, vp, ctypes.POINTER(GateArgs)]
+    lib.dsim_knn_workspace.restype = ctypes.c_int64
+    lib.dsim_knn_workspace.argtypes = [i64, i32, i32]
+    lib.dsim_knn.argtypes = [vp, vp, i64, View, ctypes.POINTER(KnnArgs)]
     lib.dsim_trajgen_workspace.restype = ctypes.c_int64
     lib.dsim_trajgen_workspace.argtypes = [i64, i32]
     lib.dsim_trajgen.argtypes = [vp, vp, ctypes.POINTER(TrajBank), ctypes.POINTER(TrajGenArgs)]

@@ -1742,3 +1742,5 @@ int dsim_sphere_grid_build(dsim_ctx* ctx, hipStream_t st_, int64_t n, const dsim
 
 // the swept drone-drone contact watch (dsim_clearance_sweep): part of this translation unit, it shares DwK, ClrK, grid_build, sort_ws and WsWalk
 #include "dsim_clearance_sweep.hip"
+// the nearest-neighbour observation (dsim_knn): part of this translation unit, it shares DwK, grid_build and the adjacency's sorted entry
+#include "dsim_knn.hip"

@@ -20,7 +20,7 @@ from __future__ import annotations
 import ctypes
 import math
 import os
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -30,6 +30,17 @@ CUTOFF = 10.0     # BaseAviary.py:1752: "Ignore drones more than 10 meters away"
 KEEP_RUN_AHEAD = 8    # kept candidate lists: list-served queries the host may be ahead of the device (Downwash._keep_next)
 CLEARANCE_CELLS_PER_DRONE = 4     # Downwash.clearance: its grid has at most this many cells per drone of the world (clearance_grid) ...
 CLEARANCE_MAX_CELLS = 1 << 22     # ... and never more than this (as Downwash._grid_box)
+
+
+class Neighbors(NamedTuple):
+    """The nearest-neighbour observation (Downwash.nearest, dsim_knn): slot t of drone i is its (t + 1)-th closest drone within
+    the radius.  A member that was not asked for is None."""
+
+    index: torch.Tensor                # [k, n] int32: world index, -1 in unused slots
+    dist: Optional[torch.Tensor]       # [k, n] float32 metres, +inf in unused slots
+    rel_pos: Optional[torch.Tensor]    # [k, 3, n] float32 p_j - p_i, 0 in unused slots
+    rel_vel: Optional[torch.Tensor]    # [k, 3, n] float32 v_j - v_i, 0 in unused slots
+    count: Optional[torch.Tensor]      # [n] int32: drones within the radius, exact whatever k
 
 
 def clearance_grid(lo, hi, r_max: float, margin: float, m: int):
@@ -722,6 +733,75 @@ class Downwash:
                                      rad.data_ptr() if rad is not None else None, margin, clr.data_ptr(), near.data_ptr(),
                                      pairs_out.data_ptr() if pairs_out is not None else None))
         return clr[: st.n], near[: st.n]
+
+    def nearest(self, radius: float, k: int, out: Optional["Neighbors"] = None, world_pos: Optional[torch.Tensor] = None,
+                local_offset: Optional[int] = None, box=None, rel_pos: bool = True, rel_vel: bool = True, count: bool = True):
+        """Nearest-neighbour observation (dsim_knn): per local drone the ``k`` (1 .. 16) closest drones within ``radius``,
+        ascending by distance (an exact tie in the fp32 squared distance goes to the lower index), as a ``Neighbors`` record
+        (index [k, n] int32 world indices, -1 unused; dist [k, n] metres, +inf unused; rel_pos [k, 3, n] = p_j - p_i and
+        rel_vel [k, 3, n] = v_j - v_i, 0 unused; count [n] int32 = the drones within the radius, exact whatever k).  An output
+        that was not asked for (``rel_pos`` / ``rel_vel`` / ``count`` = False) is None.  ``out``: a ``Neighbors`` record of
+        pre-allocated tensors over the padded fleet (index [k, n_pad] int32, dist [k, n_pad], rel_pos / rel_vel [k, 3, n_pad]
+        float32, count [n_pad] int32; contiguous; every member but index may be None): the call writes them at their fixed
+        addresses and returns views of their first n drones, and the three flags are not looked at.  ``world_pos`` [3, m]: the
+        positions of every drone of the world, this block's drones at ``local_offset``; the relative velocity is gathered from
+        this block's state, so it cannot be had with ``world_pos`` (pass rel_vel=False).  The grid is chosen as clearance()
+        chooses its own: cells of the radius (a thousandth more) or larger over the fleet's bounding box, re-measured every
+        ``box_refresh`` calls (one host sync), or over ``box`` = (xmin, ymin, xmax, ymax); drones outside the box are clamped to
+        its border cells, which costs search efficiency, never a neighbour."""
+        st, lib = self.state, self.ctx.lib
+        radius, k = float(radius), int(k)
+        if not 1 <= k <= nat.KNN_MAX_K:
+            raise ValueError(f"nearest: k must be in 1 .. {nat.KNN_MAX_K}")
+        if not (math.isfinite(radius) and radius > 0.0):
+            raise ValueError("nearest: the radius must be finite and positive")
+        if world_pos is None and self.dist is not None and self.dist.is_initialized() and self.dist.get_world_size() > 1:
+            raise NotImplementedError("nearest on a sharded fleet: pass the gathered world_pos (the velocities of the other ranks' "
+                                      "drones do not travel)")
+        if out is not None:
+            rel_pos, rel_vel, count = out.rel_pos is not None, out.rel_vel is not None, out.count is not None
+        if world_pos is not None:
+            if rel_vel:
+                raise ValueError("nearest: rel_vel with world_pos — the relative velocity is gathered from this block's state; "
+                                 "pass rel_vel=False")
+            world_pos = world_pos.to(torch.float32).contiguous()
+        dev, n_pad = self.ctx.device, st.n_pad
+        if out is None:
+            new = lambda *shape, dtype=torch.float32: torch.empty(shape, dtype=dtype, device=dev)
+            out = Neighbors(new(k, n_pad, dtype=torch.int32), new(k, n_pad), new(k, 3, n_pad) if rel_pos else None,
+                            new(k, 3, n_pad) if rel_vel else None, new(n_pad, dtype=torch.int32) if count else None)
+        else:
+            want = (("index", (k, n_pad), torch.int32), ("dist", (k, n_pad), torch.float32), ("rel_pos", (k, 3, n_pad), torch.float32),
+                    ("rel_vel", (k, 3, n_pad), torch.float32), ("count", (n_pad,), torch.int32))
+            for (name, shape, dtype), t in zip(want, out):
+                if t is None and name != "index":
+                    continue
+                if t is None or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous():
+                    raise ValueError(f"nearest: out.{name} must be a contiguous {dtype} {list(shape)}")
+        m = st.n if world_pos is None else int(world_pos.shape[1])
+        key = ("knn", radius, None if world_pos is None else m, None if box is None else tuple(float(v) for v in box))
+        if self._box is None or (box is None and self._box_age >= self._box_refresh) or getattr(self, "_clr_key", None) != key:
+            if box is not None:
+                lo, hi = key[3][:2], key[3][2:]
+            else:
+                src = st.raw_fields(0, 2) if world_pos is None else world_pos[:2]
+                src = torch.nan_to_num(src, nan=0.0, posinf=0.0, neginf=0.0)      # (a lost drone does not stretch the box)
+                lo, hi = src.min(dim=1).values.cpu(), src.max(dim=1).values.cpu()
+            self.cell, *grid = clearance_grid(lo, hi, 0.0, radius, m)
+            self._box, self._box_age, self._clr_key = tuple(grid), 0, key
+        elif self._box_age >= self._box_refresh:
+            self._box_age = 0                      # a pinned box stands (_grid_box would measure one of its own)
+        self._auto_cell = False
+        self._prebin_version = None
+        a = self._grid_args(world_pos, local_offset)
+        self._workspace(a, lib.dsim_knn_workspace(a.m, a.nx, a.ny))
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        q = nat.KnnArgs(ctypes.addressof(a), radius, k, 0, ptr(out.index), ptr(out.dist), ptr(out.rel_pos), ptr(out.rel_vel),
+                        ptr(out.count))
+        self._knn_args = (a, q, out)               # (the kernels read and write these asynchronously on the stream)
+        nat.check(lib.dsim_knn(self.ctx.handle, self.ctx.stream_ptr(), st.n, st.view(), ctypes.byref(q)))
+        cut = lambda t: t[..., : st.n] if t is not None else None
+        return Neighbors(*(cut(t) for t in out))
 
     def _single_rank_only(self, what: str) -> None:
         if self.halo is not None or (self.dist is not None and self.dist.is_initialized() and self.dist.get_world_size() > 1):

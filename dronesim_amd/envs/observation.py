@@ -2,7 +2,8 @@
 ``_computeObs`` in the reference's dict form for small fleets and as device tensors for large ones (CtrlAviary.py:225-232),
 and the neighbour lists that stand in for the reference's dense adjacency rows (BaseAviary.py:901-921).  A mix-in of
 ``CtrlAviary``: it uses the env's attributes as they are.  (The contact watches are no observation: drone_clearance() lives in
-watches.py.)"""
+watches.py.  So does the nearest-neighbour observation, last_neighbors / nearest_neighbors(), the k closest drones sorted and with
+their relative state, because it runs behind every launch as the watches do; neighbors() below stays the grid-order list.)"""
 from __future__ import annotations
 
 from typing import NamedTuple, Optional

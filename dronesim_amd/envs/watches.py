@@ -1,5 +1,6 @@
 """The services that follow every step of the fleet env on its stream: the drone-drone contact watch (``drone_watch``), the
-static-obstacle watch (``obstacle_watch``), the depth camera (``vision_attributes``) and the range scanner (``range_scan``).  Their keywords, set-up, state and public
+static-obstacle watch (``obstacle_watch``), the depth camera (``vision_attributes``), the range scanner (``range_scan``), the gate
+passage watch (``gate_watch``) and the nearest-neighbour observation (``neighbor_obs``).  Their keywords, set-up, state and public
 calls, the one epilogue of a launch (``_stepped``) and the four hooks a captured sequence goes through (``_capture_prepare``,
 ``_captured_step``, ``_capture_keepalive``, ``_replayed``).  A mix-in of ``CtrlAviary``: it uses the env's attributes as they are."""
 from __future__ import annotations
@@ -24,6 +25,10 @@ class StepWatches:
     _scan = None                  # the range scanner of range_scan= (set by _watch_setup)
     _scan_args = None
     _gate = None                  # the gate passage watch's device scenes (set by _watch_setup)
+    _knn_k = 0                    # the nearest-neighbour observation behind every step: how many neighbours (set by _watch_options)
+    _knn_sharded = False          # ... refused on demand too when the fleet is sharded
+    _knn = None                   # ... its grid, built on first use
+    last_neighbors = None         # ... and what it saw behind the last step
 
     # ------------------------------------------------------------------ construction
     def _watch_options(self, *, num_drones, freq, aggregate_phy_steps, dist, drone_watch, drone_watch_margin, obstacle_watch,
@@ -32,7 +37,8 @@ class StepWatches:
                        drone_sweep=False, drone_sweep_sag=0.0, drone_sweep_travel=None, range_scan=None, range_scene=None,
                        range_min=0.0, range_max=10.0, range_ground=True, range_clamp=False, range_see_drones=False,
                        range_drone_range=None, gate_watch=None, gate_scenes=None, gate_start=0, gate_laps=False,
-                       gate_travel=None) -> None:
+                       gate_travel=None, neighbor_obs=None, neighbor_radius=None, neighbor_vel=None,
+                       neighbourhood_radius=np.inf) -> None:
         """The services' keywords of ``CtrlAviary.__init__``: checked and stashed (the set-up follows in _watch_setup, when the
         context and the storage order exist)."""
         # The reference's Bullet world lets the vehicles' collision shapes act on each other; here every drone is integrated
@@ -64,6 +70,31 @@ class StepWatches:
         if drone_sweep and (not np.isfinite(self._drone_travel) or not self._drone_travel >= 1e-3):
             raise ValueError("drone_sweep_travel must be at least a millimetre")
         self._drone_prev = self._drone_unswept = None
+        # The reference puts the dense N x N adjacency row into every observation; neighbors() is its sparse stand-in, cut in grid
+        # order and without distances.  neighbor_obs=k (1 .. 16): every launch is followed, on the env's stream, by one dsim_knn on
+        # the state it left: last_neighbors holds, per drone, its k closest drones within neighbor_radius (None:
+        # neighbourhood_radius, which must then be finite) in ascending order of distance — (index, dist, rel_pos, rel_vel, count)
+        # in the caller's numbering, None before the first step; neighbor_vel=False leaves rel_vel out.  nearest_neighbors() asks
+        # on demand.  (Without a storage order the record's tensors are the query's own, at fixed addresses: the next launch writes
+        # them again, so clone what must outlive a step.)  Two limits: a sharded fleet (the velocities of the other ranks' drones do not travel) and graph capture
+        # (the grid's box is re-measured on the host).  Off by default: nothing is allocated or launched.
+        if neighbor_obs is None:
+            if neighbor_radius is not None or neighbor_vel is not None:
+                raise ValueError("neighbor_radius / neighbor_vel without neighbor_obs=k")
+        else:
+            if isinstance(neighbor_obs, bool) or int(neighbor_obs) != neighbor_obs or not 1 <= int(neighbor_obs) <= nat.KNN_MAX_K:
+                raise ValueError(f"neighbor_obs must be a whole number of neighbours in 1 .. {nat.KNN_MAX_K}")
+            r = float(neighbourhood_radius if neighbor_radius is None else neighbor_radius)
+            if not (np.isfinite(r) and r > 0.0):
+                raise ValueError("neighbor_radius must be finite and positive (None: a finite neighbourhood_radius)")
+            if dist is not None and dist.is_initialized() and dist.get_world_size() > 1:
+                raise NotImplementedError("neighbor_obs on a sharded fleet: the velocities of the other ranks' drones do not travel "
+                                          "(Downwash.nearest takes world_pos, without rel_vel)")
+        self._knn_k = 0 if neighbor_obs is None else int(neighbor_obs)
+        self._knn_radius = float(neighbourhood_radius if neighbor_radius is None else neighbor_radius)
+        self._knn_vel = True if neighbor_vel is None else bool(neighbor_vel)
+        self._knn_sharded = dist is not None and dist.is_initialized() and dist.get_world_size() > 1
+        self._knn_out = None
         # The reference's Bullet world also holds static bodies (p.loadURDF of a gate); here they act on nothing.
         # obstacle_watch=ObstacleSet: every step / step_fused / adaptor step is followed, on the env's stream, by one
         # dsim_obstacle_clearance on the state it left (once per LAUNCH: a step_fused with n_steps > 1 is sampled once, at its end);
@@ -214,6 +245,14 @@ class StepWatches:
             self._drone_prev = torch.zeros((3, n_pad), dtype=torch.float32, device=dev)
             self._drone_unswept = torch.zeros((1,), dtype=torch.int64, device=dev)
             self._drone_grid().clearance_prime(self._drone_prev)     # (the first _housekeeping ran before this tensor existed)
+        if self._knn_k:
+            # what the query behind every launch writes (storage order, fixed addresses)
+            from ..downwash import Neighbors
+            dev, n_pad, k = self.ctx.device, self.state.n_pad, self._knn_k
+            f32 = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)
+            self._knn_out = Neighbors(torch.full((k, n_pad), -1, dtype=torch.int32, device=dev), f32(k, n_pad), f32(k, 3, n_pad),
+                                      f32(k, 3, n_pad) if self._knn_vel else None,
+                                      torch.zeros((n_pad,), dtype=torch.int32, device=dev))
         self._obstacle_setup(offsets)
         self._vision_setup(offsets)
         self._scan_setup(offsets)
@@ -378,6 +417,8 @@ class StepWatches:
         self._env_steps += n_steps
         if self._drone_watch:
             self.last_clearance = self._drone_query(self._drone_watch_margin, None, self._drone_sweep)
+        if self._knn_k:
+            self.last_neighbors = self._neighbor_query(self._knn_k, self._knn_radius, self._knn_vel, self._knn_out)
         if self._obst is not None:
             self._watch_obstacles()
         if self._vision is not None:
@@ -413,6 +454,21 @@ class StepWatches:
         if self.order is not None:
             clr, near = self.order.to_caller(clr, 0), self.order.indices_to_caller(near, 0)
         return clr, near
+
+    def _neighbor_query(self, k: int, radius: float, vel: bool, out):
+        """One dsim_knn on the current state, on the env's stream and a grid of its own, in the caller's numbering on both axes:
+        the drone axis of every member, and the indices the lists hold."""
+        from ..downwash import Downwash, Neighbors
+        if self._knn is None:
+            self._knn = Downwash(self.ctx, self.state, self._type_id, None)
+        if self._downwash is not None:
+            self._downwash.invalidate_prebin()            # the query's binning re-uses the ctx's grid bookkeeping
+        nb = self._knn.nearest(radius, k, out=out, rel_vel=vel)
+        if self.order is None:
+            return nb
+        to = self.order.to_caller
+        return Neighbors(self.order.indices_to_caller(nb.index, 1), to(nb.dist, 1), to(nb.rel_pos, 2),
+                         to(nb.rel_vel, 2) if nb.rel_vel is not None else None, to(nb.count, 0))
 
     def _watch_obstacles(self) -> None:
         """One dsim_obstacle_clearance on the state the step just left, on the env's stream (also under capture); with
@@ -453,8 +509,11 @@ class StepWatches:
         if self._drone_watch:
             raise NotImplementedError("graph capture with drone_watch: the watch re-measures its grid's box on the host from "
                                       "time to time, which a captured sequence cannot")
+        if self._knn_k:
+            raise NotImplementedError("graph capture with neighbor_obs: the query re-measures its grid's box on the host from "
+                                      "time to time, which a captured sequence cannot")
         if self._obst is not None:
-            self.obstacle_clearance()     # (eager, not an Env.step: the watch's kernel is loaded before the capture starts)
+            self.obstacle_clearance()    # (eager, not an Env.step: the watch's kernel is loaded before the capture starts)
             if self._obst_sweep:          # (and the swept one's: prev stays, the contacts it counts go where on-demand ones go)
                 from .. import obstacles as obs
                 obs.sweep(self.ctx, self.state, self._obst, self._obst_margin, self._obst_sag, self._obst_prev,
@@ -599,6 +658,25 @@ class StepWatches:
         if self._clr_on_demand is None:
             self._clr_on_demand = torch.zeros((1,), dtype=torch.int64, device=self.ctx.device)
         return self._drone_query(float(margin), self._clr_on_demand)
+
+    def nearest_neighbors(self, k: Optional[int] = None, radius: Optional[float] = None):
+        """The nearest-neighbour observation of the CURRENT state (dsim_knn), asked now on the env's stream: a ``Neighbors``
+        record (index [k, N] int32, dist [k, N], rel_pos [k, 3, N], rel_vel [k, 3, N], count [N] int32) in the caller's
+        numbering — slot t of drone i is its (t + 1)-th closest drone within ``radius``; unused slots hold -1 / +inf / 0, and
+        count is exact whatever k.  ``k`` and ``radius`` default to the env's neighbor_obs and neighbor_radius, the radius
+        further to a finite neighbourhood_radius.  env.last_neighbors is left as it is.  Single rank only."""
+        if self._knn_sharded:
+            raise NotImplementedError("nearest_neighbors() on a sharded fleet: the velocities of the other ranks' drones do not travel")
+        if k is None:
+            if not self._knn_k:
+                raise ValueError("nearest_neighbors(): pass k, or make the env with neighbor_obs=k")
+            k = self._knn_k
+        if radius is None:
+            radius = self._knn_radius if self._knn_k else float(self.NEIGHBOURHOOD_RADIUS)
+        if not (np.isfinite(radius) and float(radius) > 0.0):
+            raise ValueError("nearest_neighbors(): the radius must be finite and positive (pass radius, or make the env with "
+                             "neighbor_radius or a finite neighbourhood_radius)")
+        return self._neighbor_query(int(k), float(radius), True, None)
 
     def drone_contacts(self) -> int:
         """Pairs of drones x Env.steps so far whose bounding spheres (DroneType.collision_sphere) overlapped behind a step

@@ -52,7 +52,8 @@ extern "C" {
                               scenes, dsim_scenes_create / _destroy, dsim_obstacle_clearance_scenes, dsim_depth_image_scenes; the
                               swept drone-drone watch, dsim_clearance_sweep, dsim_clearance_sweep_workspace,
                               dsim_clearance_sweep_args; the range scanner, dsim_range_scan, dsim_scan_args, DSIM_SCAN_*; the
-                              gate passage watch, dsim_gate_passage, dsim_gate_args, dsim_aperture, DSIM_APERTURE_*, DSIM_GATE_WRAP */
+                              gate passage watch, dsim_gate_passage, dsim_gate_args, dsim_aperture, DSIM_APERTURE_*, DSIM_GATE_WRAP; the
+                              nearest-neighbour observation, dsim_knn, dsim_knn_workspace, dsim_knn_args */
 #define DSIM_MAX_ACT 6     /* actuators per vehicle (quad 4, morphing hexa 6) */
 #define DSIM_MAX_TYPES 8
 
@@ -759,6 +760,43 @@ int64_t dsim_clearance_workspace(int64_t m, int32_t nx, int32_t ny);
 int dsim_clearance(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, const dsim_downwash_args* grid,
                    const float* radius_all, float margin,
                    float* clearance_out, int32_t* nearest_out, uint64_t* pairs_out);
+
+/* Nearest-neighbour observation: per local drone the k closest drones within `radius`, sorted, with their relative state.  The
+ * reference puts the dense N x N row of _getAdjacencyMatrix into every observation; dsim_adjacency's list is cut in grid order and
+ * carries no distance.  This is what a decentralised controller asks: who is nearest, where, and how it moves relative to me.
+ * For local drone i the neighbours are the world entries j != i with d_ij = |p_j - p_i| < radius (3-D, strict, as the adjacency):
+ *     count_out[i]        = their number, exact whatever k (as dsim_adjacency's)
+ *     slots t = 0 .. min(k, count) - 1: the neighbours of least distance, ascending by the key (d^2, j) — d^2 as fp32 computes it
+ *                           from the fp32 differences, an exact tie going to the lower world index —
+ *     index_out[t][i]     = j, an index into the world (pos_all, or this fleet);     -1 in unused slots
+ *     dist_out[t][i]      = d_ij [m];                                               +inf in unused slots
+ *     rel_pos_out[t][:][i] = p_j - p_i;                                              0 in unused slots
+ *     rel_vel_out[t][:][i] = v_j - v_i (DSIM_F_VEL, world frame);                    0 in unused slots
+ * Deterministic from run to run.  A local drone whose position is not finite gets count 0 and empty slots; a candidate whose
+ * position is not finite is nobody's neighbour (the comparison fails).  Entries i >= n are not written.  Stream-ordered, allocates
+ * nothing, never synchronises; all outputs are written with plain vector stores.
+ * The drones are binned per call on the counting-sort grid of `grid`, as dsim_adjacency bins them (pos_all / local_offset /
+ * workspace as there; type_id is ignored).  grid->cell must be >= radius: every pair closer than the radius is then less than one
+ * cell apart in x and in y, so its drones lie in the same or adjacent cells — also when one of them is clamped into a border cell
+ * from outside the box, because clamping never moves two cell indices further apart.  Workspace: at least
+ * dsim_knn_workspace(m, nx, ny) int32 entries.  The relative velocity is gathered from the state block by world index, so it needs
+ * the world to be this fleet: rel_vel_out must be NULL with grid->pos_all.
+ * DSIM_E_ARG, nothing enqueued: a null ctx, args, grid or index_out; k outside 1 .. 16; a radius that is not finite or not > 0; an
+ * unknown flag; grid->cell < radius; a workspace that is too short; rel_vel_out together with grid->pos_all; and what dsim_adjacency
+ * refuses of the grid and of n.  A halo plan: DSIM_E_UNSUPPORTED. */
+typedef struct dsim_knn_args {
+  const dsim_downwash_args* grid;  /* xy grid, counting-sort form, as for dsim_adjacency; cell >= radius; a halo plan: DSIM_E_UNSUPPORTED */
+  float radius;                    /* > 0, finite: only drones with |p_j - p_i| < radius are neighbours */
+  int32_t k;                       /* 1 .. 16 */
+  int32_t flags;                   /* 0 (unknown bits: DSIM_E_ARG) */
+  int32_t* index_out;              /* [k][n_pad] world index, -1 in unused slots; required */
+  float*   dist_out;               /* [k][n_pad] metres, +inf in unused slots; nullable */
+  float*   rel_pos_out;            /* [k][3][n_pad] p_j - p_i, 0 in unused slots; nullable */
+  float*   rel_vel_out;            /* [k][3][n_pad] v_j - v_i, 0 in unused slots; nullable; must be NULL with grid->pos_all */
+  int32_t* count_out;              /* [n_pad] number of drones within radius; nullable */
+} dsim_knn_args;
+int64_t dsim_knn_workspace(int64_t m, int32_t nx, int32_t ny);
+int dsim_knn(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, const dsim_knn_args* args);
 
 /* Static-obstacle watch: per-drone clearance to world triangle meshes.  The third thing a Bullet world does to a vehicle besides
  * the ground plane and the other vehicles is collide it with the static bodies loaded into the world (p.loadURDF of a gate, a
