@@ -32,6 +32,7 @@ EXPORTS = (
     "dsim_range_scan",
     "dsim_gate_passage",
     "dsim_knn", "dsim_knn_workspace",
+    "dsim_obstacle_witness", "dsim_obstacle_witness_scenes",
 )
 
 ABI_VERSION = 11
@@ -190,6 +191,24 @@ class SweepArgs(ctypes.Structure):
         ("nearest_out", ctypes.c_void_p),
         ("contacts_out", ctypes.c_void_p),
         ("unswept_out", ctypes.c_void_p),
+    ]
+
+
+WITNESS_BODY_FRAME = 1                  # dsim_witness_args.flags
+
+
+class WitnessArgs(ctypes.Structure):
+    """dsim_witness_args (dsim_obstacle_witness, dsim_obstacle_witness_scenes)."""
+    _fields_ = [
+        ("offset", ctypes.c_void_p),
+        ("type_id", ctypes.c_void_p),
+        ("margin", ctypes.c_float),
+        ("flags", ctypes.c_int32),
+        ("clearance_out", ctypes.c_void_p),
+        ("nearest_out", ctypes.c_void_p),
+        ("rel_out", ctypes.c_void_p),
+        ("triangle_out", ctypes.c_void_p),
+        ("contacts_out", ctypes.c_void_p),
     ]
 
 
@@ -435,6 +454,8 @@ def load(path: str = None) -> ctypes.CDLL:
     lib.dsim_scenes_destroy.argtypes = [vp, vp]
     lib.dsim_obstacle_clearance_scenes.argtypes = [vp, vp, i64, View, vp, vp, vp, vp, ctypes.c_float, vp, vp, vp]
     lib.dsim_depth_image_scenes.argtypes = [vp, vp, View, vp, vp, ctypes.POINTER(CameraParams), i64, vp, vp, vp, vp, vp]
+    lib.dsim_obstacle_witness.argtypes = [vp, vp, i64, View, vp, ctypes.POINTER(WitnessArgs)]
+    lib.dsim_obstacle_witness_scenes.argtypes = [vp, vp, i64, View, vp, vp, ctypes.POINTER(WitnessArgs)]
     lib.dsim_range_scan.argtypes = [vp, vp, i64, View, vp, ctypes.POINTER(ScanArgs)]
     lib.dsim_gate_passage.argtypes = [vp, vp, i64, View, vp, vp, ctypes.POINTER(GateArgs)]
     lib.dsim_knn_workspace.restype = ctypes.c_int64

@@ -327,3 +327,6 @@ int dsim_obstacle_clearance(dsim_ctx* ctx, void* stream, int64_t n, dsim_view st
 
 // the gate passage watch: the chord between two samples against one aperture per placement (it shares the tile frame and the scenes)
 #include "dsim_passage.hip"
+
+// the obstacle witness: the point watch with the vector to the closest point (it shares the tile frame, tri_dist2 and the scenes)
+#include "dsim_witness.hip"

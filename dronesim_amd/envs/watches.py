@@ -21,6 +21,8 @@ class StepWatches:
     _obst = None                  # the static-obstacle watch's device set (set by _watch_setup)
     _obst_sweep = False           # ... queried along the chord between two samples (obstacle_sweep=True)
     _obst_placed = False          # ... an ObstacleScenes: per-drone placements of one prototype (obstacle_scene_id)
+    _obst_wit = None              # ... with the witness query in the point query's place: "world" or "body" (obstacle_witness=)
+    _obst_rel = None              # ... and the vector it writes behind every launch (set by _obstacle_setup)
     _vision = None                # the depth camera of vision_attributes=True (set by _watch_setup)
     _scan = None                  # the range scanner of range_scan= (set by _watch_setup)
     _scan_args = None
@@ -38,7 +40,7 @@ class StepWatches:
                        range_min=0.0, range_max=10.0, range_ground=True, range_clamp=False, range_see_drones=False,
                        range_drone_range=None, gate_watch=None, gate_scenes=None, gate_start=0, gate_laps=False,
                        gate_travel=None, neighbor_obs=None, neighbor_radius=None, neighbor_vel=None,
-                       neighbourhood_radius=np.inf) -> None:
+                       neighbourhood_radius=np.inf, obstacle_witness=None) -> None:
         """The services' keywords of ``CtrlAviary.__init__``: checked and stashed (the set-up follows in _watch_setup, when the
         context and the storage order exist)."""
         # The reference's Bullet world lets the vehicles' collision shapes act on each other; here every drone is integrated
@@ -166,6 +168,21 @@ class StepWatches:
             raise ValueError("obstacle_sweep_sag must be >= 0")
         if obstacle_sweep and (not np.isfinite(self._obst_travel) or not self._obst_travel >= 1e-3):
             raise ValueError("obstacle_sweep_travel must be at least a millimetre")
+        # obstacle_witness="world" | "body": the query behind a launch is dsim_obstacle_witness (_scenes) instead of the point
+        # query — one launch, not two: the same clearance, nearest and counters, and beside them the vector from every drone's
+        # query point to the closest point of its world, in world axes or in the drone's body axes.  last_obstacle_witness holds
+        # it [3, N] in the caller's numbering (zeros for a drone with nothing within the margin; None before the first step),
+        # obstacle_witness() asks on demand.  On a sharded fleet it works per rank: nothing of the other ranks' drones is needed.
+        # Off by default: nothing new is allocated or launched.
+        if obstacle_witness is not None:
+            if obstacle_witness not in ("world", "body"):
+                raise ValueError(f"obstacle_witness must be None, 'world' or 'body', got {obstacle_witness!r}")
+            if obstacle_watch is None:
+                raise ValueError("obstacle_witness without obstacle_watch=ObstacleSet (or ObstacleScenes)")
+            if obstacle_sweep:
+                raise NotImplementedError("obstacle_witness with obstacle_sweep=True: the witness of a chord is another quantity "
+                                          "(the closest pair of a segment and the set, and where on the chord it lies)")
+        self._obst_wit = obstacle_witness
         # BaseAviary(vision_attributes=True) keeps self.rgb / self.dep / self.seg per drone at IMG_RES = [64, 48] and refreshes them
         # from _getDroneImages whenever step_counter % IMG_CAPTURE_FREQ == 0 (BaseAviary.py:236-261, 453-502, 794-853).  Here:
         # env.dep / env.seg ([n, H, W] device tensors; no rgb) of the static world `vision_scene` (default: the obstacle_watch
@@ -288,6 +305,8 @@ class StepWatches:
         self._obst_near = torch.empty((n_pad,), dtype=torch.int32, device=dev)
         self._obst_on_demand = torch.zeros((1,), dtype=torch.int64, device=dev)    # what on-demand queries counted
         self._obst_sampled = False
+        # the witness behind every launch (storage order, fixed address: a captured sequence holds it)
+        self._obst_rel = torch.zeros((3, n_pad), dtype=torch.float32, device=dev) if self._obst_wit is not None else None
         if self._obst_sweep:
             # where the previous query saw every drone (storage order, fixed address: a captured sequence holds it), and how many
             # drone x queries were point samples because they had no usable chord
@@ -479,13 +498,20 @@ class StepWatches:
                       self._obst_near, self._obst_off, self._type_id, None, self._obst_unswept)
             self._obst_sampled = True
             return
-        self._obst_query(self._obst_margin, self._obst_clr, self._obst_near, None)
+        self._obst_query(self._obst_margin, self._obst_clr, self._obst_near, None, self._obst_rel, self._obst_wit)
         self._obst_sampled = True
 
-    def _obst_query(self, margin, clr, near, contacts_out) -> None:
-        """The point query of the watch's world: dsim_obstacle_clearance, or dsim_obstacle_clearance_scenes on scenes."""
+    def _obst_query(self, margin, clr, near, contacts_out, rel=None, frame=None) -> None:
+        """The point query of the watch's world: dsim_obstacle_clearance, or dsim_obstacle_clearance_scenes on scenes; with
+        ``rel`` the witness query in its place (dsim_obstacle_witness / _scenes: the same answers and the vector beside them)."""
         from .. import obstacles as obs
-        if self._obst_placed:
+        if rel is not None and self._obst_placed:
+            obs.witness_scenes(self.ctx, self.state, self._obst, self._obst_ids, margin, clr, near, rel, None, self._obst_off,
+                               self._type_id, contacts_out, body_frame=frame == "body")
+        elif rel is not None:
+            obs.witness(self.ctx, self.state, self._obst, margin, clr, near, rel, None, self._obst_off, self._type_id, contacts_out,
+                        body_frame=frame == "body")
+        elif self._obst_placed:
             obs.query_scenes(self.ctx, self.state, self._obst, self._obst_ids, margin, clr, near, self._obst_off, self._type_id,
                              contacts_out)
         else:
@@ -513,7 +539,11 @@ class StepWatches:
             raise NotImplementedError("graph capture with neighbor_obs: the query re-measures its grid's box on the host from "
                                       "time to time, which a captured sequence cannot")
         if self._obst is not None:
-            self.obstacle_clearance()    # (eager, not an Env.step: the watch's kernel is loaded before the capture starts)
+            # (eager, not an Env.step: the watch's kernel is loaded before the capture starts)
+            if self._obst_wit is not None:
+                self.obstacle_witness()
+            else:
+                self.obstacle_clearance()
             if self._obst_sweep:          # (and the swept one's: prev stays, the contacts it counts go where on-demand ones go)
                 from .. import obstacles as obs
                 obs.sweep(self.ctx, self.state, self._obst, self._obst_margin, self._obst_sag, self._obst_prev,
@@ -746,6 +776,38 @@ class StepWatches:
         near = torch.empty((self.state.n_pad,), dtype=torch.int32, device=self.ctx.device)
         self._obst_query(margin, clr, near, self._obst_on_demand)
         return self._obst_to_caller(clr, near)
+
+    @property
+    def last_obstacle_witness(self):
+        """[3, N] float32 behind the last step of an ``obstacle_witness`` env, in the caller's numbering: the vector from every
+        drone's query point p_i - offset_i to the closest point of its world, in world axes ("world") or the drone's body axes
+        ("body"); zeros where last_obstacle_clearance says (margin, -1).  The unit direction is rel / (clearance + R_i), the
+        caller's to guard where the distance vanishes.  None before the first step."""
+        if self._obst_rel is None or not self._obst_sampled:
+            return None
+        return self._rel_to_caller(self._obst_rel)
+
+    def _rel_to_caller(self, rel):
+        rel = rel[:, : self.NUM_DRONES]
+        return self.order.to_caller(rel, 1) if self.order is not None else rel
+
+    def obstacle_witness(self, margin: Optional[float] = None, frame: Optional[str] = None):
+        """(clearance [N] float32, nearest [N] int32, rel [3, N] float32) of the CURRENT state, in the caller's numbering
+        (dsim_obstacle_witness / _scenes): what obstacle_clearance() returns and the vector to the closest point of the
+        ``obstacle_watch`` world.  ``frame``: "world" or "body" (default: the env's obstacle_witness, else "world").  Not counted as
+        an Env.step: the contacts it sees go where obstacle_clearance()'s go."""
+        if self._obst is None:
+            raise ValueError("obstacle_witness() needs an env made with obstacle_watch=ObstacleSet")
+        frame = (self._obst_wit or "world") if frame is None else frame
+        if frame not in ("world", "body"):
+            raise ValueError(f"frame must be 'world' or 'body', got {frame!r}")
+        margin = self._obst_margin if margin is None else float(margin)
+        dev, n_pad = self.ctx.device, self.state.n_pad
+        clr = torch.empty((n_pad,), dtype=torch.float32, device=dev)
+        near = torch.empty((n_pad,), dtype=torch.int32, device=dev)
+        rel = torch.zeros((3, n_pad), dtype=torch.float32, device=dev)
+        self._obst_query(margin, clr, near, self._obst_on_demand, rel, frame)
+        return self._obst_to_caller(clr, near) + (self._rel_to_caller(rel),)
 
     def drone_images(self):
         """(dep, seg) of the CURRENT state, captured now on the env's stream into env.dep / env.seg (BaseAviary._getDroneImages

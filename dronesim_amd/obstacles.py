@@ -367,6 +367,36 @@ def query_scenes(ctx, state, dev_scenes: DeviceScenes, scene_id, margin: float, 
         contacts_out.data_ptr() if contacts_out is not None else None))
 
 
+# ---- the obstacle witness (dsim_obstacle_witness) -----------------------------------------------------------------------------------
+def _witness_args(margin, clearance, nearest, rel, triangle, offset, type_id, contacts_out, body_frame) -> "nat.WitnessArgs":
+    if rel is None:
+        raise ValueError("rel ([3, n_pad] float32) is required")
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    return nat.WitnessArgs(ptr(offset), ptr(type_id), float(margin), nat.WITNESS_BODY_FRAME if body_frame else 0, clearance.data_ptr(),
+                           ptr(nearest), rel.data_ptr(), ptr(triangle), ptr(contacts_out))
+
+
+def witness(ctx, state, dev: DeviceObstacles, margin: float, clearance, nearest, rel, triangle=None, offset=None, type_id=None,
+            contacts_out=None, body_frame: bool = False) -> None:
+    """dsim_obstacle_witness on the current stream: what :func:`query` writes into ``clearance`` / ``nearest`` ([n_pad] float32 /
+    int32) and, into ``rel`` ([3, n_pad] float32), the vector from every drone's query point to the closest point of the set —
+    world axes, or the drone's body axes with ``body_frame`` — and into ``triangle`` ([n_pad] int32, may be None) the triangle
+    that holds it.  Zeros and -1 where ``nearest`` is -1.  The unit direction is rel / (clearance + R_i): not normalised here."""
+    a = _witness_args(margin, clearance, nearest, rel, triangle, offset, type_id, contacts_out, body_frame)
+    nat.check(ctx.lib.dsim_obstacle_witness(ctx.handle, ctx.stream_ptr(), state.n, state.view(), dev.handle, ctypes.byref(a)))
+
+
+def witness_scenes(ctx, state, dev_scenes: DeviceScenes, scene_id, margin: float, clearance, nearest, rel, triangle=None, offset=None,
+                   type_id=None, contacts_out=None, body_frame: bool = False) -> None:
+    """dsim_obstacle_witness_scenes on the current stream: :func:`witness` against the placements of each drone's scene
+    (``scene_id`` as in :func:`query_scenes`); ``triangle`` is instance-major, g n_tri + t, as ``nearest`` is g n_bodies + body."""
+    if scene_id is None:
+        raise ValueError("scene_id is required")
+    a = _witness_args(margin, clearance, nearest, rel, triangle, offset, type_id, contacts_out, body_frame)
+    nat.check(ctx.lib.dsim_obstacle_witness_scenes(ctx.handle, ctx.stream_ptr(), state.n, state.view(), dev_scenes.handle,
+                                                   scene_id.data_ptr(), ctypes.byref(a)))
+
+
 def scene_ids_tensor(scene_id, n: int, n_pad: int, device, order=None):
     """``scene_id`` [n] ints in the caller's numbering as the int32 device tensor [n_pad] in storage order the calls take (-1, no
     obstacles, behind n)."""

@@ -53,7 +53,8 @@ extern "C" {
                               swept drone-drone watch, dsim_clearance_sweep, dsim_clearance_sweep_workspace,
                               dsim_clearance_sweep_args; the range scanner, dsim_range_scan, dsim_scan_args, DSIM_SCAN_*; the
                               gate passage watch, dsim_gate_passage, dsim_gate_args, dsim_aperture, DSIM_APERTURE_*, DSIM_GATE_WRAP; the
-                              nearest-neighbour observation, dsim_knn, dsim_knn_workspace, dsim_knn_args */
+                              nearest-neighbour observation, dsim_knn, dsim_knn_workspace, dsim_knn_args; the obstacle witness,
+                              dsim_obstacle_witness, dsim_obstacle_witness_scenes, dsim_witness_args, DSIM_WITNESS_BODY_FRAME */
 #define DSIM_MAX_ACT 6     /* actuators per vehicle (quad 4, morphing hexa 6) */
 #define DSIM_MAX_TYPES 8
 
@@ -1079,6 +1080,45 @@ int dsim_obstacle_clearance_scenes(dsim_ctx* ctx, void* stream, int64_t n, dsim_
 int dsim_depth_image_scenes(dsim_ctx* ctx, void* stream, dsim_view state, const dsim_scenes* scenes, const int32_t* scene_id,
                             const dsim_camera_params* params, int64_t n_cam, const int32_t* cam_index,
                             const float* offset, const uint8_t* type_id, float* depth_out, int32_t* seg_out);
+
+/* The obstacle witness: the point watch's answer and WHERE the closest point lies.  A watch gives one scalar per drone and no
+ * direction; a potential field, a velocity obstacle, a control-barrier filter (h = clearance, grad h = the unit vector away from
+ * the closest point) and an obstacle observation need the vector.  With q_i = p_i - offset_i, R_i and margin as in
+ * dsim_obstacle_clearance, w* the point of the set (dsim_obstacle_witness) or of the placements of scene scene_id[i]
+ * (dsim_obstacle_witness_scenes) closest to q_i and d = |q_i - w*|:
+ *     clearance_out[i], nearest_out[i], the counters   what dsim_obstacle_clearance / _scenes write on the same inputs, bit for bit
+ *     rel_out[k][i]    = (w* - q_i)_k                  SoA [3][n_pad] (device), required.  A relative vector: offsets of 128 m cost it
+ *                                                      no digits.  World axes; with DSIM_WITNESS_BODY_FRAME the drone's body axes,
+ *                                                      R(quat_i)^T (w* - q_i), the quaternion (fields 3 .. 6 of `state`, x y z w,
+ *                                                      any positive length) read for the drones that have a witness only
+ *     triangle_out[i]  = the triangle that holds w*    [n_pad], nullable; on scenes instance-major, g n_tri + t, as the body is
+ *                                                      g n_bodies + body.  (Of the triangles that share an edge or a vertex with
+ *                                                      w* on it: the one the walk met first.)
+ * A drone for which the point watch answers (margin, -1) — out of reach, R_i = 0, a NaN position, a scene id outside [0, K) — gets
+ * rel = 0 exactly and triangle = -1.  |rel| = d = clearance + R_i up to rounding, and the unit direction is rel / (clearance + R_i):
+ * the library does not normalise, d -> 0 is the caller's to guard.  In the face region of a triangle w* = q - (n . (q - a)) n,
+ * in the edge and vertex regions a + v ab + w ac with the barycentric (v, w) whose distance the search minimised.  The position of
+ * a closest point is worse conditioned than its distance: where two triangles of a flat face lie within E of each other in
+ * distance, the witness may sit on either, up to sqrt(2 d E) apart.
+ * Stream-ordered, allocates nothing, never synchronises (may be captured).  DSIM_E_ARG, nothing enqueued: everything
+ * dsim_obstacle_clearance (_scenes) refuses, a null args or rel_out, an unknown flag; DSIM_E_LAYOUT: DSIM_WITNESS_BODY_FRAME on a
+ * view of fewer than 7 fields. */
+enum { DSIM_WITNESS_BODY_FRAME = 1 };   /* rel_out in the drone's body axes */
+typedef struct dsim_witness_args {
+  const float*   offset;        /* SoA [3][n_pad] or NULL, as dsim_obstacle_clearance                      */
+  const uint8_t* type_id;       /* [n_pad]; required with more than one type                               */
+  float          margin;        /* > 0                                                                      */
+  int32_t        flags;         /* DSIM_WITNESS_BODY_FRAME                                                  */
+  float*         clearance_out; /* [n_pad]; required                                                        */
+  int32_t*       nearest_out;   /* [n_pad], nullable                                                        */
+  float*         rel_out;       /* SoA [3][n_pad]; required                                                 */
+  int32_t*       triangle_out;  /* [n_pad], nullable                                                        */
+  uint64_t*      contacts_out;  /* device counter, nullable                                                 */
+} dsim_witness_args;
+int dsim_obstacle_witness(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, const dsim_obstacles* set,
+                          const dsim_witness_args* args);
+int dsim_obstacle_witness_scenes(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, const dsim_scenes* scenes,
+                                 const int32_t* scene_id, const dsim_witness_args* args);
 
 /* Range scanner: a fan of range beams per drone, for EVERY drone — the sensor real vehicles carry (a ToF ring, a downward altimeter,
  * a small lidar fan).  A watch gives one scalar per drone and no direction; the camera gives direction at thousands of rays per
