@@ -19,14 +19,6 @@ struct CamDr {
   float range;
 };
 
-// Obstacle scenes (dsim_depth_image_scenes): the placement table of dsim_scenes and the scene of every drone.
-struct CamPl {
-  const float4* place;             // [K][G][4] (dsim_obstacles.hip: struct dsim_scenes)
-  const int* scene_id;             // [n_pad], storage order
-  long long K;
-  int G, n_bodies;
-};
-
 // The set's ray grid as a kernel reads it (dsim_camera_walk.inc; zeroed: no set).  Its box is [o, hi].
 struct RayGridK {
   const float4* rec;
@@ -58,7 +50,7 @@ struct CamK {
 #endif
   union {
     CamDr dr;                             // DRONES instances only
-    CamPl pl;                             // PLACED instances only (never both: scenes with drones are refused)
+    ScnK pl;                              // PLACED instances only (never both: scenes with drones are refused); dsim_obstacles.hip
   };
 };
 

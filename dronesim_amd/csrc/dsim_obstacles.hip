@@ -1,6 +1,9 @@
 // Static-obstacle watch (dsim_obstacle_clearance): per-drone clearance between the vehicle's bounding sphere and a static soup
 // of triangles, on a uniform 3-D grid of per-cell triangle lists (include/dronesim_amd.h).  Point against triangle soup; the
-// drone-drone watch (dsim_downwash.hip, k_clearance_query) is point against points.
+// drone-drone watch (dsim_downwash.hip, k_clearance_query) is point against points.  What the files this one includes share is
+// stated here once: the region decision of a point against a triangle (tri_region: tri_dist2 for every watch, tri_closest for the
+// witness), the tile frame with the one cell walk (obs_cell_walk: the body or the record index of the winner), the scenes' table
+// as a kernel reads it (ScnK, scn_kargs), and the point kernel, which with the witness's arguments behind its own is the witness.
 #include <hip/hip_runtime.h>
 
 #include <new>
@@ -38,6 +41,19 @@ struct dsim_scenes {
   float box_c[3];                // the centre of the prototype's box in its own frame (what c_task is the placed image of)
 };
 
+// ... and as every placed kernel reads them (the point watch and the witness, the camera, the scanner), with the scene of every drone
+struct ScnK {
+  const float4* place;           // [K][G][4]
+  const int* scene_id;           // [n_pad], storage order
+  long long K;
+  int G, n_bodies;
+};
+static int scn_kargs(const dsim_scenes* scenes, const int32_t* scene_id, ScnK* s) {
+  if (!scenes || !scene_id) return DSIM_E_ARG;
+  s->place = scenes->place; s->scene_id = scene_id; s->K = scenes->K; s->G = scenes->G; s->n_bodies = scenes->proto->n_bodies;
+  return DSIM_OK;
+}
+
 struct ObsK {
   KView st;
   long long n, n_pad, tiles;
@@ -66,13 +82,17 @@ __device__ __forceinline__ void obs_stage(float4* s_rec, const float4* rec, int 
   __syncthreads();
 }
 
-// Squared distance from q to one triangle record (Ericson, Real-Time Collision Detection 5.1.5, without branches: every lane of a
-// wave meets another region).  The vertex and edge regions give barycentric (v, w) of the closest point and the distance to it;
-// in the face region the distance is |n . ap| with the record's unit normal, which does not lose digits in the quotient
-// vb / (va + vb + vc) of a thin triangle.  A point that fp32 rounding puts on the wrong side of a region border gets the
-// neighbouring region's formula, which agrees with its own to second order in the distance from the border.
-__device__ __forceinline__ float tri_dist2(const float4 r0, const float4 r1, const float4 r2, const float4 r3, float qx, float qy,
-                                           float qz) {
+// The region of q against one triangle record (Ericson, Real-Time Collision Detection 5.1.5, without branches: every lane of a
+// wave meets another region), decided in ONE place for the squared distance, which it returns, and for the closest point, which
+// it gives with CLOSEST as the vector from q to it (`to`, else null): the witness is right because it reads the decision the
+// distance was taken on.  The vertex and edge regions give barycentric (v, w) of the closest point a + v ab + w ac, and
+// e = p - v ab - w ac points from it to q; in the face region the distance is |h| = |n . p| with the record's unit normal, which
+// does not lose digits in the quotient vb / (va + vb + vc) of a thin triangle, and the point is q - h n.  A point that fp32
+// rounding puts on the wrong side of a region border gets the neighbouring region's formula, which agrees with its own to second
+// order in the distance from the border.
+template <bool CLOSEST>
+__device__ __forceinline__ float tri_region(const float4 r0, const float4 r1, const float4 r2, const float4 r3, float qx, float qy,
+                                            float qz, float3* to) {
   const float ax = r0.x, ay = r0.y, az = r0.z, abx = r0.w, aby = r1.x, abz = r1.y, acx = r1.z, acy = r1.w, acz = r2.x;
   const float nx = r2.y, ny = r2.z, nz = r2.w, e00 = r3.x, e01 = r3.y, e11 = r3.z;
   const float px = qx - ax, py = qy - ay, pz = qz - az;
@@ -100,7 +120,18 @@ __device__ __forceinline__ float tri_dist2(const float4 r0, const float4 r1, con
   const float w = mode == 3 ? 1.0f : (mode == 4 || mode == 5 ? t : 0.0f);
   const float ex = px - v * abx - w * acx, ey = py - v * aby - w * acy, ez = pz - v * abz - w * acz;
   const float h = nx * px + ny * py + nz * pz;
+  if constexpr (CLOSEST) {
+    to->x = mode == 6 ? -(h * nx) : -ex;
+    to->y = mode == 6 ? -(h * ny) : -ey;
+    to->z = mode == 6 ? -(h * nz) : -ez;
+  }
   return mode == 6 ? h * h : ex * ex + ey * ey + ez * ez;
+}
+
+// Squared distance from q to one triangle record.
+__device__ __forceinline__ float tri_dist2(const float4 r0, const float4 r1, const float4 r2, const float4 r3, float qx, float qy,
+                                           float qz) {
+  return tri_region<false>(r0, r1, r2, r3, qx, qy, qz, nullptr);
 }
 
 // ---- the tile frame of the three watch kernels (k_obstacle_clearance, k_obstacle_clearance_scenes, k_obstacle_sweep) ----------------
@@ -149,8 +180,10 @@ __device__ __forceinline__ void obs_lane_store(const ObsK& a, long long tile, lo
 }
 
 // The cell of q and the walk of its list (the set's frame, or a placement's): the least dist2(r0, r1, r2, r3) below `best` over
-// the list's records and the body of the triangle that attains it.  The records come from LDS when the whole set was staged.
-template <bool LDS, class Dist2>
+// the list's records and the body of the triangle that attains it — with INDEX its record index instead (the witness, which
+// reads that one record again behind the walk; the watches never carry an index).  The records come from LDS when the whole set
+// was staged.
+template <bool LDS, bool INDEX = false, class Dist2>
 __device__ __forceinline__ void obs_cell_walk(const ObsK& a, const float4* s_rec, float qx, float qy, float qz, Dist2 dist2, int& body,
                                               float& best) {
   const int cx = min(max((int)floorf((qx - a.ox) * a.inv_cell), 0), a.nx - 1);
@@ -165,23 +198,35 @@ __device__ __forceinline__ void obs_cell_walk(const ObsK& a, const float4* s_rec
     const float d2 = dist2(r0, r1, r2, r3);
     const bool better = d2 < best;
     best = better ? d2 : best;
-    body = better ? __float_as_int(r3.w) : body;
+    body = better ? (INDEX ? t : __float_as_int(r3.w)) : body;
   }
 }
 
-// ... for the point q itself (both point kernels)
-template <bool LDS>
+// ... for the point q itself (both point kernels, with and without the witness)
+template <bool LDS, bool INDEX>
 __device__ __forceinline__ void obs_point_walk(const ObsK& a, const float4* s_rec, float qx, float qy, float qz, int& body, float& best) {
-  obs_cell_walk<LDS>(a, s_rec, qx, qy, qz,
-                     [=](const float4 r0, const float4 r1, const float4 r2, const float4 r3) { return tri_dist2(r0, r1, r2, r3, qx, qy, qz); },
-                     body, best);
+  obs_cell_walk<LDS, INDEX>(a, s_rec, qx, qy, qz,
+                            [=](const float4 r0, const float4 r1, const float4 r2, const float4 r3) { return tri_dist2(r0, r1, r2, r3, qx, qy, qz); },
+                            body, best);
 }
+
+// The witness's tail of both point kernels (dsim_witness.hip, which this file includes behind them: its entry points launch them).
+struct WitK;
+template <bool LDS>
+__device__ __forceinline__ int wit_point(const ObsK& a, const float4* s_rec, int tri, float lx, float ly, float lz, float& wx, float& wy,
+                                         float& wz);
+__device__ __forceinline__ void wit_lane_store(const ObsK& a, const WitK& w, long long i, bool live, bool in, float wx, float wy, float wz,
+                                               int tri);
 
 // The point watch.  A tile none of whose drones lies in the grown box reads its positions (and offsets) and writes (margin, -1);
 // of a tile that has some, the waves that have none do the same.  The others look up their cell and walk its list: the records
 // come from LDS when the whole set fits, else through L2 — the set is read-only and small next to the fleet.
-template <bool LDS>
-__global__ __launch_bounds__(256) void k_obstacle_clearance(ObsK a) {
+// Instantiated with Wit = WitK, the witness's arguments behind the watch's, it is the witness (dsim_witness.hip; the watch itself
+// has an empty Wit and its own argument only): the same frame, decisions and walk order, the walk keeping the winner's record
+// index, on which the lanes within the margin evaluate tri_closest once.
+template <bool LDS, class... Wit>
+__global__ __launch_bounds__(256) void k_obstacle_clearance(ObsK a, Wit... w) {
+  constexpr bool WIT = sizeof...(Wit) != 0;
   extern __shared__ float4 s_rec[];
   bool staged = false;
   for (long long tile = blockIdx.x; tile < a.tiles; tile += gridDim.x) {
@@ -194,10 +239,19 @@ __global__ __launch_bounds__(256) void k_obstacle_clearance(ObsK a) {
     const bool inbox = live && R > 0.0f && qx >= a.lox && qx <= a.hix && qy >= a.loy && qy <= a.hiy && qz >= a.loz && qz <= a.hiz;
     obs_stage_once<LDS>(a, s_rec, staged, inbox);
     float best = INFINITY;
-    int body = -1;
-    if (inbox) obs_point_walk<LDS>(a, s_rec, qx, qy, qz, body, best);   // (a wave with no such lane skips it: the per-wave reject)
+    int win = -1;                        // the winner's body; with WIT its record index
+    if (inbox) obs_point_walk<LDS, WIT>(a, s_rec, qx, qy, qz, win, best);   // (a wave with no such lane skips it: the per-wave reject)
     const float c_i = DSIM_SQRT(best) - R;
-    obs_lane_store(a, tile, i, live, inbox && c_i < a.margin, c_i, body);
+    const bool in = (WIT ? win >= 0 : inbox) && c_i < a.margin;           // (the same lanes: c_i < margin needs a winner)
+    if constexpr (WIT) {
+      float wx = 0.0f, wy = 0.0f, wz = 0.0f;
+      int body = -1;
+      if (in) body = wit_point<LDS>(a, s_rec, win, qx, qy, qz, wx, wy, wz);
+      obs_lane_store(a, tile, i, live, in, c_i, body);
+      wit_lane_store(a, w..., i, live, in, wx, wy, wz, win);
+    } else {
+      obs_lane_store(a, tile, i, live, in, c_i, win);
+    }
   }
 }
 
@@ -328,5 +382,6 @@ int dsim_obstacle_clearance(dsim_ctx* ctx, void* stream, int64_t n, dsim_view st
 // the gate passage watch: the chord between two samples against one aperture per placement (it shares the tile frame and the scenes)
 #include "dsim_passage.hip"
 
-// the obstacle witness: the point watch with the vector to the closest point (it shares the tile frame, tri_dist2 and the scenes)
+// the obstacle witness: the point watch with the vector to the closest point (both point kernels above are its kernels too; the
+// file holds the tail they call, its arguments and its entry points)
 #include "dsim_witness.hip"

@@ -5,7 +5,7 @@
 // watches': one drone per lane, tiles of 256 walked grid-stride, the pose loaded coalesced once, the lane loops over the beams.
 // Compiled as part of dsim_obstacles.hip, which includes this file: it reads the set's and the scenes' private records and uses
 // what dsim_camera.hip states for both sensors: the ray grid's record, the triangle walk (dsim_camera_walk.inc), the walk of the
-// drones' grid (dsim_camera_drones.inc), the drone targets' host set-up (cam_drones_fill) and the argument records CamPl / CamDr.
+// drones' grid (dsim_camera_drones.inc), the drone targets' host set-up (cam_drones_fill) and the argument records ScnK / CamDr.
 #pragma once
 
 struct ScanK {
@@ -20,7 +20,7 @@ struct ScanK {
   int beams_per_block;                    // blockIdx.y takes the beams [y, y + 1) * beams_per_block (n_beams: one chunk)
   float* range;                           // [n_beams][n_pad]
   int* hit;                               // same shape, or null
-  CamPl pl;                               // PLACED instances (not a union with dr: a placed scan sees drones)
+  ScnK pl;                                // PLACED instances (not a union with dr: a placed scan sees drones)
   CamDr dr;                               // DRONES instances
 };
 
@@ -215,9 +215,7 @@ int dsim_range_scan(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, con
   if (tris) ray_grid_fill(tris, &a.rg);
   a.far = s.t_max; a.t_min = s.t_min; a.flags = s.flags; a.beams = s.beams; a.n_beams = s.n_beams;
   a.range = s.range_out; a.hit = s.hit_out;
-  if (s.scenes) {
-    a.pl.place = s.scenes->place; a.pl.scene_id = s.scene_id; a.pl.K = s.scenes->K; a.pl.G = s.scenes->G; a.pl.n_bodies = tris->n_bodies;
-  }
+  if (s.scenes && (rc = scn_kargs(s.scenes, s.scene_id, &a.pl)) != 0) return rc;
   const hipStream_t st_ = (hipStream_t)stream;
   if (s.drones && (rc = cam_drones_fill(ctx, st_, state, s.drones, &a.dr)) != 0) return rc;
   const bool placed = s.scenes != nullptr, dr = s.drones != nullptr, lds = tris && tris->n_tri <= OBS_LDS_TRI;

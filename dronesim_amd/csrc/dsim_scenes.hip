@@ -2,28 +2,34 @@
 // placements of ONE prototype set, and a scene per drone.  Distances and ray parameters do not change under a rotation and a shift,
 // so the prototype's grids, records and LDS staging serve every placement: only the query point, or the ray, goes into the
 // placement's frame.  Compiled as part of dsim_obstacles.hip, which includes this file: it shares the watch's tile frame and
-// cell walk (obs_lane .. obs_point_walk), its arguments and launcher (ObsK, obs_kargs, obs_refuse, obs_launch) and the camera's
-// kernel (k_depth_image<.., PLACED>, cam_fill).
+// cell walk (obs_lane .. obs_point_walk), its arguments and launcher (ObsK, obs_kargs, obs_refuse, obs_launch), the scenes' table
+// as the kernels read it (ScnK, scn_kargs: stated there once for the watch, the witness, the camera and the scanner) and the
+// camera's kernel (k_depth_image<.., PLACED>, cam_fill).  The placed point kernel here is also the placed witness's.
 #pragma once
 
 #define SCN_MAX_G 32                     // one bit per placement in a lane's mask
 #define SCN_MAX_SLOTS (1LL << 22)
 
-struct ScnK {
-  const float4* place;                   // [K][G][4] (struct dsim_scenes)
-  const int* scene_id;                   // [n_pad]
-  long long K;
-  int G, n_bodies;
-};
+// A query point in a placement's frame, from the slot's three columns of R, each followed by one component of t: subtract first,
+// then rotate.  R^T q - R^T t cancels digits at offsets of 128 m, R^T (q - t) does not.
+__device__ __forceinline__ float3 scn_local(const float4 c0, const float4 c1, const float4 c2, float qx, float qy, float qz) {
+  const float tx = qx - c0.w, ty = qy - c1.w, tz = qz - c2.w;
+  const float lx = c0.x * tx + c0.y * ty + c0.z * tz, ly = c1.x * tx + c1.y * ty + c1.z * tz, lz = c2.x * tx + c2.y * ty + c2.z * tz;
+  return make_float3(lx, ly, lz);
+}
 
 // k_obstacle_clearance with the set placed, in the same tile frame (dsim_obstacles.hip).  Scene ids differ per lane, so
 // placement records are per-lane vector loads: a lane reads the first 16 bytes of each of its scene's G slots, (c_task, r_cull), and the other 48 only of a slot whose sphere it is within reach of — the bound
 // is widened (1e-4 relative, 1e-5 m) well beyond the fp32 rounding of q - c and of an R that is orthonormal to 1e-5, so it decides
-// speed only.  Then q goes into the placement's frame, subtract first, then rotate: R^T q - R^T t cancels digits at offsets of
-// 128 m, R^T (q - t) does not.  There the grown-box test and the cell walk are the unplaced kernel's.  The minimum runs over the
-// placements in slot order with a strict <, and the body is g * n_bodies + the triangle's.
-template <bool LDS>
-__global__ __launch_bounds__(256) void k_obstacle_clearance_scenes(ObsK a, ScnK s) {
+// speed only.  Then q goes into the placement's frame (scn_local).  There the grown-box test and the cell walk are the unplaced
+// kernel's.  The minimum runs over the placements in slot order with a strict <, and the body is g * n_bodies + the triangle's.
+// Instantiated with Wit = WitK it is the witness, as k_obstacle_clearance is (dsim_witness.hip): the loop keeps the winner's slot
+// and record index; behind it the winner's three columns are read again (the lane read them in the loop: they come from cache), q
+// goes into that placement's frame by the loop's own scn_local, tri_closest gives the local vector and R takes it back:
+// rel = sum_k col_k l_k.  The triangle is instance-major, g n_tri + t, as the body is g n_bodies + body.
+template <bool LDS, class... Wit>
+__global__ __launch_bounds__(256) void k_obstacle_clearance_scenes(ObsK a, ScnK s, Wit... w) {
+  constexpr bool WIT = sizeof...(Wit) != 0;
   extern __shared__ float4 s_rec[];
   bool staged = false;
   for (long long tile = blockIdx.x; tile < a.tiles; tile += gridDim.x) {
@@ -39,31 +45,45 @@ __global__ __launch_bounds__(256) void k_obstacle_clearance_scenes(ObsK a, ScnK 
     if (live && R > 0.0f && sid >= 0 && (long long)sid < s.K) {
       pl += 4 * ((size_t)sid * (size_t)s.G);
       for (int g = 0; g < s.G; ++g) {
-        const float4 w = pl[4 * g];
-        const float ux = qx - w.x, uy = qy - w.y, uz = qz - w.z;
-        const float b = (w.w + R + a.margin) * 1.0001f + 1e-5f;                // (-inf for a slot at or above the count)
+        const float4 c = pl[4 * g];
+        const float ux = qx - c.x, uy = qy - c.y, uz = qz - c.z;
+        const float b = (c.w + R + a.margin) * 1.0001f + 1e-5f;                // (-inf for a slot at or above the count)
         near |= (b >= 0.0f && ux * ux + uy * uy + uz * uz <= b * b) ? (1u << g) : 0u;
       }
     }
     obs_stage_once<LDS>(a, s_rec, staged, near != 0u);
     float best = INFINITY;
-    int body = -1;
+    int win = -1, slot = 0;                // the winner's body, g * n_bodies + the triangle's; with WIT its record index and its slot
     while (near != 0u) {                   // (a wave with no such lane skips the loop: the per-wave reject)
       const int g = __ffs((int)near) - 1;
       near &= near - 1u;
-      const float4 c0 = pl[4 * g + 1], c1 = pl[4 * g + 2], c2 = pl[4 * g + 3];
-      const float tx = qx - c0.w, ty = qy - c1.w, tz = qz - c2.w;
-      const float lx = c0.x * tx + c0.y * ty + c0.z * tz, ly = c1.x * tx + c1.y * ty + c1.z * tz, lz = c2.x * tx + c2.y * ty + c2.z * tz;
+      const float3 p = scn_local(pl[4 * g + 1], pl[4 * g + 2], pl[4 * g + 3], qx, qy, qz);
       // (the grown box of the prototype, in its own frame: outside it no triangle is within reach)
-      if (lx >= a.lox && lx <= a.hix && ly >= a.loy && ly <= a.hiy && lz >= a.loz && lz <= a.hiz) {
+      if (p.x >= a.lox && p.x <= a.hix && p.y >= a.loy && p.y <= a.hiy && p.z >= a.loz && p.z <= a.hiz) {
         float b2 = best;
-        int bd = -1;
-        obs_point_walk<LDS>(a, s_rec, lx, ly, lz, bd, b2);
-        if (bd >= 0) { best = b2; body = g * s.n_bodies + bd; }
+        int w2 = -1;
+        obs_point_walk<LDS, WIT>(a, s_rec, p.x, p.y, p.z, w2, b2);
+        if (w2 >= 0) { best = b2; win = WIT ? w2 : g * s.n_bodies + w2; slot = g; }
       }
     }
     const float c_i = DSIM_SQRT(best) - R;
-    obs_lane_store(a, tile, i, live, body >= 0 && c_i < a.margin, c_i, body);
+    const bool in = win >= 0 && c_i < a.margin;
+    if constexpr (WIT) {
+      float wx = 0.0f, wy = 0.0f, wz = 0.0f;
+      int body = -1;
+      if (in) {
+        const float4 c0 = pl[4 * slot + 1], c1 = pl[4 * slot + 2], c2 = pl[4 * slot + 3];
+        const float3 p = scn_local(c0, c1, c2, qx, qy, qz);
+        float vx, vy, vz;
+        body = slot * s.n_bodies + wit_point<LDS>(a, s_rec, win, p.x, p.y, p.z, vx, vy, vz);
+        wx = c0.x * vx + c1.x * vy + c2.x * vz; wy = c0.y * vx + c1.y * vy + c2.y * vz; wz = c0.z * vx + c1.z * vy + c2.z * vz;
+        win += slot * a.n_tri;
+      }
+      obs_lane_store(a, tile, i, live, in, c_i, body);
+      wit_lane_store(a, w..., i, live, in, wx, wy, wz, win);
+    } else {
+      obs_lane_store(a, tile, i, live, in, c_i, win);
+    }
   }
 }
 
@@ -132,28 +152,30 @@ int dsim_scenes_destroy(dsim_ctx* ctx, dsim_scenes* scenes) {
 int dsim_obstacle_clearance_scenes(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, const dsim_scenes* scenes,
                                    const int32_t* scene_id, const float* offset, const uint8_t* type_id, float margin,
                                    float* clearance_out, int32_t* nearest_out, uint64_t* contacts_out) {
-  if (!scenes || !scene_id) return DSIM_E_ARG;
+  ScnK s;
+  int rc = scn_kargs(scenes, scene_id, &s);
+  if (rc) return rc;
   const dsim_obstacles* set = scenes->proto;
-  int rc = obs_refuse(ctx, n, state, set, type_id, margin, 0.0f, clearance_out);
+  rc = obs_refuse(ctx, n, state, set, type_id, margin, 0.0f, clearance_out);
   if (rc) return rc;
   ObsK a;
   rc = obs_kargs(ctx, n, state, set, offset, type_id, margin, clearance_out, nearest_out, contacts_out, &a);
   if (rc) return rc;
-  ScnK s;
-  s.place = scenes->place; s.scene_id = scene_id; s.K = scenes->K; s.G = scenes->G; s.n_bodies = set->n_bodies;
   return obs_launch(k_obstacle_clearance_scenes<true>, k_obstacle_clearance_scenes<false>, set, a.tiles, stream, a, s);
 }
 
 int dsim_depth_image_scenes(dsim_ctx* ctx, void* stream, dsim_view state, const dsim_scenes* scenes, const int32_t* scene_id,
                             const dsim_camera_params* params, int64_t n_cam, const int32_t* cam_index, const float* offset,
                             const uint8_t* type_id, float* depth_out, int32_t* seg_out) {
-  if (!scenes || !scene_id) return DSIM_E_ARG;
+  ScnK pl;
+  int rc = scn_kargs(scenes, scene_id, &pl);
+  if (rc) return rc;
   const dsim_obstacles* set = scenes->proto;
   CamK a;
   int64_t blocks;
-  const int rc = cam_fill(ctx, state, set, params, n_cam, cam_index, offset, type_id, depth_out, seg_out, &a, &blocks);
+  rc = cam_fill(ctx, state, set, params, n_cam, cam_index, offset, type_id, depth_out, seg_out, &a, &blocks);
   if (rc) return rc;
-  a.pl.place = scenes->place; a.pl.scene_id = scene_id; a.pl.K = scenes->K; a.pl.G = scenes->G; a.pl.n_bodies = set->n_bodies;
+  a.pl = pl;
   const hipStream_t st_ = (hipStream_t)stream;
   const bool lds = set->n_tri <= OBS_LDS_TRI;
   const size_t shm = lds ? (size_t)set->n_tri * 64 : 0;

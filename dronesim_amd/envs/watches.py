@@ -21,6 +21,7 @@ class StepWatches:
     _obst = None                  # the static-obstacle watch's device set (set by _watch_setup)
     _obst_sweep = False           # ... queried along the chord between two samples (obstacle_sweep=True)
     _obst_placed = False          # ... an ObstacleScenes: per-drone placements of one prototype (obstacle_scene_id)
+    _obst_ids = None              # ... and then the scene of every drone, in storage order (set by _obstacle_setup)
     _obst_wit = None              # ... with the witness query in the point query's place: "world" or "body" (obstacle_witness=)
     _obst_rel = None              # ... and the vector it writes behind every launch (set by _obstacle_setup)
     _vision = None                # the depth camera of vision_attributes=True (set by _watch_setup)
@@ -505,17 +506,8 @@ class StepWatches:
         """The point query of the watch's world: dsim_obstacle_clearance, or dsim_obstacle_clearance_scenes on scenes; with
         ``rel`` the witness query in its place (dsim_obstacle_witness / _scenes: the same answers and the vector beside them)."""
         from .. import obstacles as obs
-        if rel is not None and self._obst_placed:
-            obs.witness_scenes(self.ctx, self.state, self._obst, self._obst_ids, margin, clr, near, rel, None, self._obst_off,
-                               self._type_id, contacts_out, body_frame=frame == "body")
-        elif rel is not None:
-            obs.witness(self.ctx, self.state, self._obst, margin, clr, near, rel, None, self._obst_off, self._type_id, contacts_out,
-                        body_frame=frame == "body")
-        elif self._obst_placed:
-            obs.query_scenes(self.ctx, self.state, self._obst, self._obst_ids, margin, clr, near, self._obst_off, self._type_id,
-                             contacts_out)
-        else:
-            obs.query(self.ctx, self.state, self._obst, margin, clr, near, self._obst_off, self._type_id, contacts_out)
+        obs.point_query(self.ctx, self.state, self._obst, self._obst_ids, margin, clr, near, rel, self._obst_off, self._type_id,
+                        contacts_out, body_frame=frame == "body")
 
     def _scan_now(self):
         """One dsim_range_scan on the state the launch just left, on the env's stream (also under capture)."""
@@ -771,11 +763,19 @@ class StepWatches:
         (default: the env's obstacle_margin, which is also the largest the device set serves).  Not counted as an Env.step."""
         if self._obst is None:
             raise ValueError("obstacle_clearance() needs an env made with obstacle_watch=ObstacleSet")
+        return self._obst_now(margin)
+
+    def _obst_now(self, margin, frame=None):
+        """The on-demand point query of the current state into tensors of its own, in the caller's numbering; with ``frame`` the
+        witness query, and ``rel`` behind the two.  Its contacts are counted apart (_obst_on_demand)."""
         margin = self._obst_margin if margin is None else float(margin)
-        clr = torch.empty((self.state.n_pad,), dtype=torch.float32, device=self.ctx.device)
-        near = torch.empty((self.state.n_pad,), dtype=torch.int32, device=self.ctx.device)
-        self._obst_query(margin, clr, near, self._obst_on_demand)
-        return self._obst_to_caller(clr, near)
+        dev, n_pad = self.ctx.device, self.state.n_pad
+        clr = torch.empty((n_pad,), dtype=torch.float32, device=dev)
+        near = torch.empty((n_pad,), dtype=torch.int32, device=dev)
+        rel = torch.zeros((3, n_pad), dtype=torch.float32, device=dev) if frame is not None else None
+        self._obst_query(margin, clr, near, self._obst_on_demand, rel, frame)
+        out = self._obst_to_caller(clr, near)
+        return out if rel is None else out + (self._rel_to_caller(rel),)
 
     @property
     def last_obstacle_witness(self):
@@ -801,13 +801,7 @@ class StepWatches:
         frame = (self._obst_wit or "world") if frame is None else frame
         if frame not in ("world", "body"):
             raise ValueError(f"frame must be 'world' or 'body', got {frame!r}")
-        margin = self._obst_margin if margin is None else float(margin)
-        dev, n_pad = self.ctx.device, self.state.n_pad
-        clr = torch.empty((n_pad,), dtype=torch.float32, device=dev)
-        near = torch.empty((n_pad,), dtype=torch.int32, device=dev)
-        rel = torch.zeros((3, n_pad), dtype=torch.float32, device=dev)
-        self._obst_query(margin, clr, near, self._obst_on_demand, rel, frame)
-        return self._obst_to_caller(clr, near) + (self._rel_to_caller(rel),)
+        return self._obst_now(margin, frame)
 
     def drone_images(self):
         """(dep, seg) of the CURRENT state, captured now on the env's stream into env.dep / env.seg (BaseAviary._getDroneImages

@@ -397,6 +397,19 @@ def witness_scenes(ctx, state, dev_scenes: DeviceScenes, scene_id, margin: float
                                                    scene_id.data_ptr(), ctypes.byref(a)))
 
 
+def point_query(ctx, state, dev, scene_id, margin: float, clearance, nearest, rel=None, offset=None, type_id=None, contacts_out=None,
+                body_frame: bool = False) -> None:
+    """The point query of a device world, whichever it is: :func:`query` on a :class:`DeviceObstacles`, :func:`query_scenes` on a
+    :class:`DeviceScenes` (``scene_id`` is theirs and is not looked at otherwise); with ``rel`` the witness query in its place
+    (:func:`witness` / :func:`witness_scenes`: the same answers and the vector beside them, no ``triangle``)."""
+    ids = (scene_id,) if isinstance(dev, DeviceScenes) else ()
+    if rel is None:
+        (query_scenes if ids else query)(ctx, state, dev, *ids, margin, clearance, nearest, offset, type_id, contacts_out)
+    else:
+        (witness_scenes if ids else witness)(ctx, state, dev, *ids, margin, clearance, nearest, rel, None, offset, type_id,
+                                             contacts_out, body_frame=body_frame)
+
+
 def scene_ids_tensor(scene_id, n: int, n_pad: int, device, order=None):
     """``scene_id`` [n] ints in the caller's numbering as the int32 device tensor [n_pad] in storage order the calls take (-1, no
     obstacles, behind n)."""

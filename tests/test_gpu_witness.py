@@ -176,6 +176,38 @@ def test_soup_four_bodies_records_through_l2(gpu):
     ctx.close()
 
 
+@pytest.mark.parametrize("placed", [False, True])
+def test_soup_is_the_point_watch_bit_for_bit_records_through_l2(gpu, placed):
+    """Case 2's identity on the instances that read the records through L2 (the 3 000-triangle soup): case 4's inputs unplaced,
+    scenes_ref.case_soup (512 drones, K = 4, G = 2) placed.  The witness is the point watch's kernel with a tail, and this is
+    the check that the tail changes nothing in front of it."""
+    nat, fleet = gpu
+    from dronesim_amd import obstacles as obs
+    d = sr.case_soup() if placed else wr.case_soup()
+    world, margin, n = d["scenes"] if placed else d["set"], d["margin"], len(d["pos"])
+    assert (world.prototype if placed else world).n_tri > 512
+    ctx = fleet.Context([params.builtin_type("hexa_6DOF")])
+    dev = world.to_device(ctx, obs.watch_reach(ctx.types, margin))
+    st = load(fleet, ctx, d["pos"])
+    ids = ids_tensor(d["scene_id"], st.n_pad, ctx.device) if placed else None
+    want_clr = torch.full((st.n_pad,), -7.0, dtype=torch.float32, device=ctx.device)
+    want_near = torch.full((st.n_pad,), -7, dtype=torch.int32, device=ctx.device)
+    c0, c1 = (torch.zeros((1,), dtype=torch.int64, device=ctx.device) for _ in range(2))
+    if placed:
+        obs.query_scenes(ctx, st, dev, ids, margin, want_clr, want_near, None, None, c0)
+    else:
+        obs.query(ctx, st, dev, margin, want_clr, want_near, None, None, c0)
+    clr, near, rel, tri = run(ctx, st, dev, margin, counter=c1, ids=ids)
+    none = near[:n] < 0
+    print(f"soup through L2 placed={placed}: {int((~none).sum())} of {n} with a witness, {int(c1.item())} contacts")
+    assert same_bits(clr, want_clr) and torch.equal(near, want_near) and int(c1.item()) == int(c0.item())
+    assert int((~none).sum()) >= int((d["ref"]["near"] >= 0).sum()) // 2 > 0 and int(none.sum()) > 0
+    assert bool((rel[:, :n][:, none] == 0.0).all()) and bool((rel[:, :n][:, ~none] != 0.0).any(0).all())
+    assert bool((tri[:n][none] == -1).all()) and bool((tri[:n][~none] >= 0).all())
+    dev.close()
+    ctx.close()
+
+
 # ---- 5. scenes -----------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name,offsets,model", [("gates", False, "robobee"), ("gates", True, "robobee"), ("ragged", True, "robobee"),
                                                 ("soup", False, "hexa_6DOF")])
