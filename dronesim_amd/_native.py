@@ -33,6 +33,7 @@ EXPORTS = (
     "dsim_gate_passage",
     "dsim_knn", "dsim_knn_workspace",
     "dsim_obstacle_witness", "dsim_obstacle_witness_scenes",
+    "dsim_line_of_sight",
 )
 
 ABI_VERSION = 11
@@ -121,6 +122,26 @@ class ScanArgs(ctypes.Structure):
         ("drones", ctypes.c_void_p),
         ("range_out", ctypes.c_void_p),
         ("hit_out", ctypes.c_void_p),
+    ]
+
+
+SIGHT_GROUND = 1                 # dsim_sight_args.flags
+SIGHT_MAX_K = 32                 # dsim_sight_args.k: 1 .. 32
+
+
+class SightArgs(ctypes.Structure):
+    """dsim_sight_args (dsim_line_of_sight)."""
+    _fields_ = [
+        ("rel", ctypes.c_void_p),
+        ("index", ctypes.c_void_p),
+        ("k", ctypes.c_int32),
+        ("flags", ctypes.c_uint32),
+        ("offset", ctypes.c_void_p),
+        ("scenes", ctypes.c_void_p),
+        ("scene_id", ctypes.c_void_p),
+        ("visible_out", ctypes.c_void_p),
+        ("blocker_out", ctypes.c_void_p),
+        ("frac_out", ctypes.c_void_p),
     ]
 
 
@@ -457,6 +478,7 @@ def load(path: str = None) -> ctypes.CDLL:
     lib.dsim_obstacle_witness.argtypes = [vp, vp, i64, View, vp, ctypes.POINTER(WitnessArgs)]
     lib.dsim_obstacle_witness_scenes.argtypes = [vp, vp, i64, View, vp, vp, ctypes.POINTER(WitnessArgs)]
     lib.dsim_range_scan.argtypes = [vp, vp, i64, View, vp, ctypes.POINTER(ScanArgs)]
+    lib.dsim_line_of_sight.argtypes = [vp, vp, i64, View, vp, ctypes.POINTER(SightArgs)]
     lib.dsim_gate_passage.argtypes = [vp, vp, i64, View, vp, vp, ctypes.POINTER(GateArgs)]
     lib.dsim_knn_workspace.restype = ctypes.c_int64
     lib.dsim_knn_workspace.argtypes = [i64, i32, i32]

@@ -379,6 +379,10 @@ int dsim_obstacle_clearance(dsim_ctx* ctx, void* stream, int64_t n, dsim_view st
 // the range scanner: per-drone beam fans against the set, the scenes, the plane and the drones (it shares the camera's walk and records)
 #include "dsim_scan.hip"
 
+// line of sight: per-drone segments to the neighbours a knn record names, against the set, the scenes and the plane (it shares the
+// camera's walk and records and the scanner's spreading of a small fleet)
+#include "dsim_sight.hip"
+
 // the gate passage watch: the chord between two samples against one aperture per placement (it shares the tile frame and the scenes)
 #include "dsim_passage.hip"
 

@@ -1,6 +1,6 @@
 """The services that follow every step of the fleet env on its stream: the drone-drone contact watch (``drone_watch``), the
 static-obstacle watch (``obstacle_watch``), the depth camera (``vision_attributes``), the range scanner (``range_scan``), the gate
-passage watch (``gate_watch``) and the nearest-neighbour observation (``neighbor_obs``).  Their keywords, set-up, state and public
+passage watch (``gate_watch``), the nearest-neighbour observation (``neighbor_obs``) and its line of sight (``neighbor_sight``).  Their keywords, set-up, state and public
 calls, the one epilogue of a launch (``_stepped``) and the four hooks a captured sequence goes through (``_capture_prepare``,
 ``_captured_step``, ``_capture_keepalive``, ``_replayed``).  A mix-in of ``CtrlAviary``: it uses the env's attributes as they are."""
 from __future__ import annotations
@@ -32,6 +32,10 @@ class StepWatches:
     _knn_sharded = False          # ... refused on demand too when the fleet is sharded
     _knn = None                   # ... its grid, built on first use
     last_neighbors = None         # ... and what it saw behind the last step
+    _sight_on = False             # line of sight behind every step's neighbour query (neighbor_sight=True; set by _watch_options)
+    _sight = None                 # ... its LineOfSight (set by _watch_setup)
+    _sight_demand = None          # ... and those of the on-demand queries, by k
+    last_neighbor_sight = None    # ... and what it saw behind the last step
 
     # ------------------------------------------------------------------ construction
     def _watch_options(self, *, num_drones, freq, aggregate_phy_steps, dist, drone_watch, drone_watch_margin, obstacle_watch,
@@ -41,7 +45,8 @@ class StepWatches:
                        range_min=0.0, range_max=10.0, range_ground=True, range_clamp=False, range_see_drones=False,
                        range_drone_range=None, gate_watch=None, gate_scenes=None, gate_start=0, gate_laps=False,
                        gate_travel=None, neighbor_obs=None, neighbor_radius=None, neighbor_vel=None,
-                       neighbourhood_radius=np.inf, obstacle_witness=None) -> None:
+                       neighbourhood_radius=np.inf, obstacle_witness=None, neighbor_sight=False,
+                       neighbor_sight_scene=None) -> None:
         """The services' keywords of ``CtrlAviary.__init__``: checked and stashed (the set-up follows in _watch_setup, when the
         context and the storage order exist)."""
         # The reference's Bullet world lets the vehicles' collision shapes act on each other; here every drone is integrated
@@ -98,6 +103,23 @@ class StepWatches:
         self._knn_vel = True if neighbor_vel is None else bool(neighbor_vel)
         self._knn_sharded = dist is not None and dist.is_initialized() and dist.get_world_size() > 1
         self._knn_out = None
+        # neighbor_sight=True: every launch's dsim_knn is followed, on the env's stream, by one dsim_line_of_sight on the record it
+        # just wrote (rel_pos and index, in storage order): last_neighbor_sight holds, per drone and slot, whether the segment to
+        # that neighbour is clear of neighbor_sight_scene (default: the obstacle_watch world, whose device set is then shared; an
+        # ObstacleScenes goes by obstacle_scene_id), what hides it first and where — a Sight (visible, blocker, frac) [k, N] in the
+        # caller's numbering on the drone axis, None before the first step; unused slots read 0 / -1 / +inf.  neighbor_sight()
+        # asks on demand.  The world lies in the frame of obstacle_offsets, and the segment of drone i in ITS task frame, from
+        # p_i - offset_i to p_j - offset_i: two drones of different replicas (different offsets) may disagree on whether they see
+        # each other.  The other drones hide nobody.  A sharded fleet and graph capture are refused by neighbor_obs itself.  Off
+        # by default: nothing is allocated or launched.
+        if neighbor_sight and neighbor_obs is None:
+            raise ValueError("neighbor_sight=True without neighbor_obs=k")
+        if neighbor_sight_scene is not None and not neighbor_sight:
+            raise ValueError("neighbor_sight_scene without neighbor_sight=True")
+        if neighbor_sight and neighbor_sight_scene is None and obstacle_watch is None:
+            raise ValueError("neighbor_sight=True needs a world to look at: neighbor_sight_scene=ObstacleSet (or obstacle_watch)")
+        self._sight_on, self._sight_scene = bool(neighbor_sight), neighbor_sight_scene
+        self.last_neighbor_sight = None
         # The reference's Bullet world also holds static bodies (p.loadURDF of a gate); here they act on nothing.
         # obstacle_watch=ObstacleSet: every step / step_fused / adaptor step is followed, on the env's stream, by one
         # dsim_obstacle_clearance on the state it left (once per LAUNCH: a step_fused with n_steps > 1 is sampled once, at its end);
@@ -137,11 +159,12 @@ class StepWatches:
         self._gate_travel = 10.0 * int(aggregate_phy_steps) / float(freq) if gate_travel is None else float(gate_travel)
         if gate_watch is not None and (not np.isfinite(self._gate_travel) or not self._gate_travel >= 1e-3):
             raise ValueError("gate_travel must be at least a millimetre")
-        placed = [x for x in (obstacle_watch, vision_scene, range_scene, gate_scenes) if isinstance(x, ObstacleScenes)]
+        placed = [x for x in (obstacle_watch, vision_scene, range_scene, gate_scenes, neighbor_sight_scene) if isinstance(x, ObstacleScenes)]
         if placed and obstacle_scene_id is None:
             raise ValueError("obstacle_scene_id [N] is required with an ObstacleScenes")
         if not placed and obstacle_scene_id is not None:
-            raise ValueError("obstacle_scene_id without an ObstacleScenes (obstacle_watch=, vision_scene=, range_scene= or gate_scenes=)")
+            raise ValueError("obstacle_scene_id without an ObstacleScenes (obstacle_watch=, vision_scene=, range_scene=, gate_scenes= or "
+                             "neighbor_sight_scene=)")
         if placed:
             ids = np.asarray(obstacle_scene_id)
             if ids.shape != (num_drones,) or not np.issubdtype(ids.dtype, np.integer):
@@ -275,12 +298,13 @@ class StepWatches:
         self._vision_setup(offsets)
         self._scan_setup(offsets)
         self._gate_setup(offsets)
+        self._sight_setup(offsets)
 
     def _obstacle_setup(self, offsets) -> None:
         """obstacle_watch: the device set for reach = R_max + margin, the offsets in storage order and the tensors every
         per-step query writes (fixed addresses: a captured sequence holds them)."""
         if self._obst_set is None:
-            if offsets is not None and self._vision_args is None and self._scan_args is None and self._gate_ap is None:
+            if offsets is not None and self._vision_args is None and self._scan_args is None and self._gate_ap is None and not self._sight_on:
                 raise ValueError("obstacle_offsets without obstacle_watch")
             return
         from .. import obstacles as obs
@@ -345,6 +369,30 @@ class StepWatches:
         self._scan = RangeScanner(self.ctx, self.state, world, beams, t_min=t_min, t_max=t_max, ground=ground, clamp=clamp,
                                   offsets=offsets, type_id=self._type_id, drones=see_drones, drone_range=drone_range,
                                   scene_id=self._scene_ids if isinstance(world, (ObstacleScenes, DeviceScenes)) else None)
+
+    def _sight_setup(self, offsets) -> None:
+        """neighbor_sight=True: the LineOfSight and its device set (shared with the obstacle watch when both look at the same world)."""
+        if not self._sight_on:
+            return
+        scene = self._sight_scene
+        shared = self._obst is not None and (scene is None or scene is self._obst_set)
+        self._sight_offsets = offsets
+        self._sight = self._sight_make(self._obst if shared else scene, self._knn_k)
+        self._sight_demand = {}
+
+    def _sight_make(self, world, k: int):
+        from ..obstacles import DeviceScenes, ObstacleScenes
+        from ..sight import LineOfSight
+        return LineOfSight(self.ctx, self.state, world, k, offsets=self._sight_offsets,
+                           scene_id=self._scene_ids if isinstance(world, (ObstacleScenes, DeviceScenes)) else None)
+
+    def _sight_caller(self, s):
+        """A Sight in storage order in the caller's numbering on the drone axis."""
+        if self.order is None:
+            return s
+        from ..sight import Sight
+        to = self.order.to_caller
+        return Sight(*(to(t, 1) if t is not None else None for t in s))
 
     def _gate_setup(self, offsets) -> None:
         """gate_watch=Aperture: the device scenes (the obstacle watch's when the gates are its placements), ids and offsets in
@@ -423,6 +471,8 @@ class StepWatches:
             self._vision.close()
         if self._scan is not None:
             self._scan.close()
+        if self._sight is not None:
+            self._sight.close()
         if self._gate is not None and not self._gate_shared:
             self._gate.close()
         if self._obst is not None:
@@ -439,6 +489,9 @@ class StepWatches:
             self.last_clearance = self._drone_query(self._drone_watch_margin, None, self._drone_sweep)
         if self._knn_k:
             self.last_neighbors = self._neighbor_query(self._knn_k, self._knn_radius, self._knn_vel, self._knn_out)
+            if self._sight is not None:
+                # (on the record the query just wrote, in storage order: the vectors last_neighbors reports, bit for bit)
+                self.last_neighbor_sight = self._sight_caller(self._sight.query(self._knn_out.rel_pos, self._knn_out.index))
         if self._obst is not None:
             self._watch_obstacles()
         if self._vision is not None:
@@ -478,12 +531,19 @@ class StepWatches:
     def _neighbor_query(self, k: int, radius: float, vel: bool, out):
         """One dsim_knn on the current state, on the env's stream and a grid of its own, in the caller's numbering on both axes:
         the drone axis of every member, and the indices the lists hold."""
-        from ..downwash import Downwash, Neighbors
+        return self._neighbors_caller(self._neighbor_raw(k, radius, vel, out))
+
+    def _neighbor_raw(self, k: int, radius: float, vel: bool, out):
+        """... and the record as the query wrote it, in storage order on both axes."""
+        from ..downwash import Downwash
         if self._knn is None:
             self._knn = Downwash(self.ctx, self.state, self._type_id, None)
         if self._downwash is not None:
             self._downwash.invalidate_prebin()            # the query's binning re-uses the ctx's grid bookkeeping
-        nb = self._knn.nearest(radius, k, out=out, rel_vel=vel)
+        return self._knn.nearest(radius, k, out=out, rel_vel=vel)
+
+    def _neighbors_caller(self, nb):
+        from ..downwash import Neighbors
         if self.order is None:
             return nb
         to = self.order.to_caller
@@ -699,6 +759,23 @@ class StepWatches:
             raise ValueError("nearest_neighbors(): the radius must be finite and positive (pass radius, or make the env with "
                              "neighbor_radius or a finite neighbourhood_radius)")
         return self._neighbor_query(int(k), float(radius), True, None)
+
+    def neighbor_sight(self, k: Optional[int] = None, radius: Optional[float] = None):
+        """(Neighbors, Sight) of the CURRENT state, asked now on the env's stream: what nearest_neighbors(k, radius) returns, and
+        for every slot of it whether the segment to that neighbour is clear of the ``neighbor_sight`` world (dsim_line_of_sight on
+        that record: visible, blocker, frac [k, N]), both in the caller's numbering.  env.last_neighbors and
+        env.last_neighbor_sight are left as they are.  The Sight's tensors are those of the on-demand query of this k: the next
+        one writes them again."""
+        if self._sight is None:
+            raise ValueError("neighbor_sight() needs an env made with neighbor_sight=True")
+        k = self._knn_k if k is None else int(k)
+        radius = self._knn_radius if radius is None else float(radius)
+        if not (np.isfinite(radius) and radius > 0.0):
+            raise ValueError("neighbor_sight(): the radius must be finite and positive")
+        nb = self._neighbor_raw(k, radius, True, None)
+        if k not in self._sight_demand:
+            self._sight_demand[k] = self._sight_make(self._sight.set, k)
+        return self._neighbors_caller(nb), self._sight_caller(self._sight_demand[k].query_neighbors(nb))
 
     def drone_contacts(self) -> int:
         """Pairs of drones x Env.steps so far whose bounding spheres (DroneType.collision_sphere) overlapped behind a step

@@ -54,7 +54,8 @@ extern "C" {
                               dsim_clearance_sweep_args; the range scanner, dsim_range_scan, dsim_scan_args, DSIM_SCAN_*; the
                               gate passage watch, dsim_gate_passage, dsim_gate_args, dsim_aperture, DSIM_APERTURE_*, DSIM_GATE_WRAP; the
                               nearest-neighbour observation, dsim_knn, dsim_knn_workspace, dsim_knn_args; the obstacle witness,
-                              dsim_obstacle_witness, dsim_obstacle_witness_scenes, dsim_witness_args, DSIM_WITNESS_BODY_FRAME */
+                              dsim_obstacle_witness, dsim_obstacle_witness_scenes, dsim_witness_args, DSIM_WITNESS_BODY_FRAME; line
+                              of sight, dsim_line_of_sight, dsim_sight_args, DSIM_SIGHT_GROUND */
 #define DSIM_MAX_ACT 6     /* actuators per vehicle (quad 4, morphing hexa 6) */
 #define DSIM_MAX_TYPES 8
 
@@ -1169,6 +1170,51 @@ typedef struct dsim_scan_args {
 } dsim_scan_args;
 int dsim_range_scan(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, const dsim_obstacles* set,
                     const dsim_scan_args* args);
+
+/* Line of sight: which of a drone's neighbours its obstacles hide, per slot.  dsim_knn tells a drone who its neighbours are,
+ * through walls; the watches, the scanner and the camera know the walls, not the neighbours behind them.  dsim_line_of_sight casts,
+ * for every drone i < n and slot t < k, the SEGMENT
+ *     e + s d,  s in [0, 1],   e = p_i - offset_i (formed in float32 as dsim_range_scan forms it),   d = rel[t][:][i]
+ * against the world of the scanner: both faces of every triangle of `set`; with `scenes`, every placement of scene scene_id[i],
+ * the segment taken into the placement's frame (subtract first, then rotate; an id outside [0, K): no obstacles); with
+ * DSIM_SIGHT_GROUND the plane z = 0 of the task frame, analytic.  d is `rel` as given (world axes, the layout of dsim_knn's
+ * rel_pos_out) and is NOT recomputed from positions: a knn record is tested on exactly the vectors it reports, a gathered world of
+ * a sharded rank works at this level, and so does any target point (a goal: rel = goal - p).  The other drones hide nobody.
+ *
+ * A slot is CAST when its index is not negative (or `index` is NULL), e is finite, and d is finite, not zero, and of a squared
+ * length that is finite in float32 (shorter than about 1.8e19).  The hit test is the triangle walk's of the camera and the scanner
+ * with near = 0 and far = 1, both ends closed (a wall exactly at the neighbour hides it); the nearest hit wins:
+ *     visible_out[t][i] = 1 when the slot was cast and nothing lies in [0, 1];  0 when it is blocked, or was not cast
+ *     blocker_out[t][i] = the body of the FIRST hit (instance-major g n_bodies + body on scenes), DSIM_SEG_GROUND for the plane;
+ *                         -1 when clear or not cast.  Nullable.
+ *     frac_out[t][i]    = s of the first hit; +inf when clear or not cast.  Nullable.
+ * All three are slot-major [k][n_pad] (device, storage order like offset), so a slot is one coalesced row and belongs to one
+ * workgroup (a small fleet spreads chunks of the slots over the grid as the scanner spreads its beams): there is no packed mask
+ * on the device.  Lanes i >= n are not written.  The segment lies in drone i's task frame: with per-drone offsets, i may see j
+ * where j does not see i.
+ *
+ * No bound on the segments' length is asked of the caller: every lane measures the longest slot it will cast in one more pass over
+ * its rel rows, and that reach decides what it stages and walks (speed only).  Stream-ordered, allocates nothing, never
+ * synchronises; may be captured; all outputs are written with plain vector stores.  DSIM_E_ARG, nothing enqueued: a null ctx,
+ * args, rel or visible_out; n <= 0 or n > n_pad; k outside 1 .. 32; an unknown flag; scenes without scene_id or the reverse;
+ * scenes together with a non-NULL set; no world at all (no set, no scenes, no ground flag); a set (or the scenes' prototype)
+ * without rays enabled. */
+enum { DSIM_SIGHT_GROUND = 1u << 0 };  /* the plane z = 0 of the task frame blocks too, body DSIM_SEG_GROUND */
+typedef struct dsim_sight_args {
+  const float*   rel;          /* device [k][3][n_pad]: the segment of slot t of drone i is e_i + s rel[t][:][i], s in [0, 1]
+                                  (world axes; the layout of dsim_knn's rel_pos_out)                               */
+  const int32_t* index;        /* device [k][n_pad] or NULL: a slot with index < 0 is not cast (dsim_knn's index_out) */
+  int32_t        k;            /* 1 .. 32                                                                      */
+  uint32_t       flags;        /* DSIM_SIGHT_GROUND (unknown bits: DSIM_E_ARG)                                 */
+  const float*   offset;       /* SoA [3][n_pad] or NULL: e_i = p_i - offset_i, as the scanner                 */
+  const dsim_scenes* scenes;   /* nullable: the placed world; then `set` must be NULL (the prototype is its)   */
+  const int32_t* scene_id;     /* [n_pad] storage order; with `scenes`, and only with it                       */
+  int32_t*       visible_out;  /* [k][n_pad], required: 1 = cast and nothing in [0, 1]; 0 = blocked, or not cast */
+  int32_t*       blocker_out;  /* [k][n_pad] or NULL: what hides the neighbour first                           */
+  float*         frac_out;     /* [k][n_pad] or NULL: where along the segment                                  */
+} dsim_sight_args;
+int dsim_line_of_sight(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, const dsim_obstacles* set,
+                       const dsim_sight_args* args);
 
 /* Gate passage watch: which drones flew THROUGH the gates of their scene, in order.  The clearance watches say how close a
  * vehicle came to a gate's frame; a drone that flies round its gate, goes through backwards or never reaches it has a perfect
