@@ -34,6 +34,7 @@ EXPORTS = (
     "dsim_knn", "dsim_knn_workspace",
     "dsim_obstacle_witness", "dsim_obstacle_witness_scenes",
     "dsim_line_of_sight",
+    "dsim_scenes_motion_set", "dsim_scenes_move", "dsim_scenes_read",
 )
 
 ABI_VERSION = 11
@@ -272,6 +273,20 @@ class GateArgs(ctypes.Structure):
     ]
 
 
+class SceneMotionC(ctypes.Structure):
+    """dsim_scene_motion (dsim_scenes_motion_set): one placement's motion record, 64 bytes."""
+    _fields_ = [
+        ("vel", ctypes.c_float * 3),
+        ("amp", ctypes.c_float * 3),
+        ("omega", ctypes.c_float),
+        ("phase", ctypes.c_float),
+        ("axis", ctypes.c_float * 3),
+        ("rate", ctypes.c_float),
+        ("swing", ctypes.c_float),
+        ("pad_", ctypes.c_float * 3),
+    ]
+
+
 class ClearanceSweepArgs(ctypes.Structure):
     """dsim_clearance_sweep_args (dsim_clearance_sweep); flags as dsim_sweep_args'."""
     _fields_ = [
@@ -475,6 +490,9 @@ def load(path: str = None) -> ctypes.CDLL:
     lib.dsim_scenes_destroy.argtypes = [vp, vp]
     lib.dsim_obstacle_clearance_scenes.argtypes = [vp, vp, i64, View, vp, vp, vp, vp, ctypes.c_float, vp, vp, vp]
     lib.dsim_depth_image_scenes.argtypes = [vp, vp, View, vp, vp, ctypes.POINTER(CameraParams), i64, vp, vp, vp, vp, vp]
+    lib.dsim_scenes_motion_set.argtypes = [vp, vp, vp]
+    lib.dsim_scenes_move.argtypes = [vp, vp, vp, vp, ctypes.c_double, ctypes.c_double]
+    lib.dsim_scenes_read.argtypes = [vp, vp, vp, vp]
     lib.dsim_obstacle_witness.argtypes = [vp, vp, i64, View, vp, ctypes.POINTER(WitnessArgs)]
     lib.dsim_obstacle_witness_scenes.argtypes = [vp, vp, i64, View, vp, vp, ctypes.POINTER(WitnessArgs)]
     lib.dsim_range_scan.argtypes = [vp, vp, i64, View, vp, ctypes.POINTER(ScanArgs)]

@@ -39,6 +39,9 @@ struct dsim_scenes {
   long long K;
   int G;
   float box_c[3];                // the centre of the prototype's box in its own frame (what c_task is the placed image of)
+  // the motion (dsim_scenes_motion_set; dsim_scene_motion.hip): both null until one is attached
+  float4* motion = nullptr;      // [K][G][4]: the motion records, the `moving` flag and r_cull in their padding
+  float4* base = nullptr;        // [K][G][4]: the table as dsim_scenes_create wrote it
 };
 
 // ... and as every placed kernel reads them (the point watch and the witness, the camera, the scanner), with the scene of every drone
@@ -385,6 +388,9 @@ int dsim_obstacle_clearance(dsim_ctx* ctx, void* stream, int64_t n, dsim_view st
 
 // the gate passage watch: the chord between two samples against one aperture per placement (it shares the tile frame and the scenes)
 #include "dsim_passage.hip"
+
+// moving scenes: per-placement motion that rewrites the scenes' table in stream order (every placed kernel above reads it per launch)
+#include "dsim_scene_motion.hip"
 
 // the obstacle witness: the point watch with the vector to the closest point (both point kernels above are its kernels too; the
 // file holds the tail they call, its arguments and its entry points)

@@ -145,6 +145,8 @@ int dsim_scenes_destroy(dsim_ctx* ctx, dsim_scenes* scenes) {
   if (!scenes) return DSIM_OK;
   hipError_t e = hipSuccess;                          // (hipFree waits for the work that may still read the table)
   if (scenes->place) e = hipFree(scenes->place);
+  for (float4* p : {scenes->motion, scenes->base})    // (dsim_scenes_motion_set's buffers)
+    if (p) { const hipError_t f = hipFree(p); if (e == hipSuccess) e = f; }
   delete scenes;
   return (int)e;
 }

@@ -163,6 +163,7 @@ class CtrlAviary(PlacedFleetArrays, FleetObservation, StepWatches):
         obstacle_witness: Optional[str] = None,
         neighbor_sight: bool = False,
         neighbor_sight_scene=None,
+        obstacle_motion=None,
     ):
         if gui or record or obstacles:
             raise NotImplementedError("gui/record/obstacles are rendering features outside the hot path")
@@ -179,7 +180,8 @@ class CtrlAviary(PlacedFleetArrays, FleetObservation, StepWatches):
                             gate_scenes=gate_scenes, gate_start=gate_start, gate_laps=gate_laps, gate_travel=gate_travel,
                             neighbor_obs=neighbor_obs, neighbor_radius=neighbor_radius, neighbor_vel=neighbor_vel,
                             neighbourhood_radius=neighbourhood_radius, obstacle_witness=obstacle_witness,
-                            neighbor_sight=neighbor_sight, neighbor_sight_scene=neighbor_sight_scene)
+                            neighbor_sight=neighbor_sight, neighbor_sight_scene=neighbor_sight_scene,
+                            obstacle_motion=obstacle_motion)
         # the add-on terms of the PYB_* modes (dead code in the reference fork, intended formulas); Physics.DYN: the
         # reference's own explicit model, BaseAviary._dynamics (BaseAviary.py:1767-1828; DSIM_OPT_DYN)
         self._phys_options = {Physics.PYB: 0, Physics.PYB_DW: 0, Physics.PYB_GND: nat.OPT_GROUND,

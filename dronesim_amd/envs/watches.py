@@ -24,6 +24,8 @@ class StepWatches:
     _obst_ids = None              # ... and then the scene of every drone, in storage order (set by _obstacle_setup)
     _obst_wit = None              # ... with the witness query in the point query's place: "world" or "body" (obstacle_witness=)
     _obst_rel = None              # ... and the vector it writes behind every launch (set by _obstacle_setup)
+    _motion = None                # the SceneMotion of the watch's scenes (obstacle_motion=; attached by _obstacle_setup)
+    _scene_clock = None           # ... and the Env.steps since reset() its scene time counts, on the device
     _vision = None                # the depth camera of vision_attributes=True (set by _watch_setup)
     _scan = None                  # the range scanner of range_scan= (set by _watch_setup)
     _scan_args = None
@@ -46,7 +48,7 @@ class StepWatches:
                        range_drone_range=None, gate_watch=None, gate_scenes=None, gate_start=0, gate_laps=False,
                        gate_travel=None, neighbor_obs=None, neighbor_radius=None, neighbor_vel=None,
                        neighbourhood_radius=np.inf, obstacle_witness=None, neighbor_sight=False,
-                       neighbor_sight_scene=None) -> None:
+                       neighbor_sight_scene=None, obstacle_motion=None) -> None:
         """The services' keywords of ``CtrlAviary.__init__``: checked and stashed (the set-up follows in _watch_setup, when the
         context and the storage order exist)."""
         # The reference's Bullet world lets the vehicles' collision shapes act on each other; here every drone is integrated
@@ -177,6 +179,25 @@ class StepWatches:
                 raise NotImplementedError("vision_see_drones=True with an ObstacleScenes: the other drones in placed images are a "
                                           "follow-up (there is no placed dsim_depth_image_drones)")
         self._scene_ids = obstacle_scene_id
+        # obstacle_motion=SceneMotion (made for the ObstacleScenes of obstacle_watch): the watch's world moves.  The env owns a device
+        # clock of Env.steps since reset(); every launch first advances it, then one dsim_scenes_move puts the table to scene time
+        # clock x (one Env.step) on the env's stream, then the watches run: the world stands where it is at the time of the state
+        # they see.  reset() returns it to scene time 0.  The camera, the scanner and line of sight see the motion when they share
+        # the watch's device scenes (the default); with a vision_scene=, range_scene= or neighbor_sight_scene= of their own they
+        # look at a static copy.  A captured sequence captures both calls, and a replay reads the clock from the device.  On a
+        # sharded fleet every rank moves its own copy.  scene_time() and scene_placements() report it.  Off by default: nothing
+        # new is allocated or launched.
+        if obstacle_motion is not None:
+            from ..obstacles import SceneMotion
+            if not isinstance(obstacle_motion, SceneMotion):
+                raise ValueError("obstacle_motion takes an obstacles.SceneMotion")
+            if not isinstance(obstacle_watch, ObstacleScenes) or obstacle_motion.scenes is not obstacle_watch:
+                raise ValueError("obstacle_motion must be made for the ObstacleScenes given as obstacle_watch")
+            if gate_watch is not None and (gate_scenes is None or gate_scenes is obstacle_watch):
+                raise NotImplementedError("gate_watch on the scenes obstacle_motion moves: a passage through a moving opening needs "
+                                          "the chord's start in the pose of the PREVIOUS query, a change to k_gate_passage and a "
+                                          "follow-up (gate_scenes= of their own stay static and work)")
+        self._motion = obstacle_motion
         # obstacle_sweep=True: the query behind a launch is dsim_obstacle_sweep instead, the chord from the position the previous
         # query saw (reset() primes it) to the state the launch left, as a sphere of radius R + obstacle_sweep_sag swept along it:
         # with sag >= obstacles.sweep_sag(a_max, time between two queries) every sub-step state in between lies in the tested
@@ -332,6 +353,11 @@ class StepWatches:
         self._obst_sampled = False
         # the witness behind every launch (storage order, fixed address: a captured sequence holds it)
         self._obst_rel = torch.zeros((3, n_pad), dtype=torch.float32, device=dev) if self._obst_wit is not None else None
+        if self._motion is not None:
+            # the scene clock (fixed address: a captured sequence holds it) and the motion's device copy; the table to scene time 0
+            self._scene_clock = torch.zeros((1,), dtype=torch.int64, device=dev)
+            self._obst.set_motion(self._motion)
+            self._obst.move(self._scene_clock, self._scene_dt())
         if self._obst_sweep:
             # where the previous query saw every drone (storage order, fixed address: a captured sequence holds it), and how many
             # drone x queries were point samples because they had no usable chord
@@ -454,6 +480,10 @@ class StepWatches:
             obs.prime(self.ctx, self.state, self._obst, self._obst_prev)
         if self._drone_prev is not None:
             self._drone_grid().clearance_prime(self._drone_prev)
+        if self._scene_clock is not None:
+            # the world starts again: scene time 0
+            self._scene_clock.zero_()
+            self._obst.move(self._scene_clock, self._scene_dt())
         if self._gate is not None:
             # every course starts again: the chords from here, gate_start due, no lap, no passage time, the clock at zero
             from .. import obstacles as obs
@@ -485,6 +515,8 @@ class StepWatches:
         one dsim_clearance with drone_watch=True, one dsim_obstacle_clearance with obstacle_watch, the camera when it is due."""
         self.step_counter += self.AGGR_PHY_STEPS * n_steps
         self._env_steps += n_steps
+        if self._scene_clock is not None:
+            self._scene_move(n_steps)          # (first: every watch below sees the world at the time of the state it looks at)
         if self._drone_watch:
             self.last_clearance = self._drone_query(self._drone_watch_margin, None, self._drone_sweep)
         if self._knn_k:
@@ -506,6 +538,16 @@ class StepWatches:
             self._scan_now()
         if self._gate is not None:
             self._watch_gates()
+
+    def _scene_dt(self) -> float:
+        """One Env.step in seconds: the unit of the scene clock."""
+        return float(self.AGGR_PHY_STEPS) / float(self.SIM_FREQ)
+
+    def _scene_move(self, n_steps: int) -> None:
+        """The scene clock moves on by ``n_steps`` Env.steps, then the watch's table to that scene time, both on the env's stream
+        (also under capture: the kernel reads the clock from the device)."""
+        nat.check(self.ctx.lib.dsim_counter_add(self.ctx.handle, self.ctx.stream_ptr(), self._scene_clock.data_ptr(), int(n_steps)))
+        self._obst.move(self._scene_clock, self._scene_dt())
 
     def _drone_grid(self):
         from ..downwash import Downwash
@@ -590,6 +632,9 @@ class StepWatches:
         if self._knn_k:
             raise NotImplementedError("graph capture with neighbor_obs: the query re-measures its grid's box on the host from "
                                       "time to time, which a captured sequence cannot")
+        if self._scene_clock is not None:
+            # (eager: the move's kernel is loaded before the capture starts; the clock stays, so the table is rewritten as it stands)
+            self._obst.move(self._scene_clock, self._scene_dt())
         if self._obst is not None:
             # (eager, not an Env.step: the watch's kernel is loaded before the capture starts)
             if self._obst_wit is not None:
@@ -625,6 +670,8 @@ class StepWatches:
 
     def _captured_step(self) -> None:
         """Behind every captured step, as in eager mode: the obstacle watch's query, the camera at its cadence of 1, the scan."""
+        if self._scene_clock is not None:
+            self._scene_move(1)
         if self._obst is not None:
             self._watch_obstacles()
         if self._vision is not None:
@@ -669,6 +716,21 @@ class StepWatches:
             self._downwash.invalidate_prebin()
         self._scan.scan()
         return self._scan.ranges, self._scan.hits
+
+    # ---- moving scenes
+    def scene_time(self) -> float:
+        """Seconds of scene time since reset(): Env.steps so far x one Env.step, read from the device clock (synchronises the
+        stream).  The table behind the last launch stands at this time."""
+        if self._scene_clock is None:
+            raise ValueError("scene_time() needs an env made with obstacle_motion=SceneMotion")
+        return int(self._scene_clock.item()) * self._scene_dt()
+
+    def scene_placements(self) -> np.ndarray:
+        """float32 [K, G, 12]: the watch's placements as the device holds them now (DeviceScenes.read(): R row-major then t, NaN in
+        unused slots; waits for the stream)."""
+        if self._scene_clock is None:
+            raise ValueError("scene_placements() needs an env made with obstacle_motion=SceneMotion")
+        return self._obst.read()
 
     # ---- the gate passage watch
     def _gate_need(self, what: str) -> None:

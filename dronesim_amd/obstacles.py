@@ -250,6 +250,7 @@ class DeviceScenes:
         self.set = scenes.prototype.to_device(ctx, reach) if self._owns_set else prototype_dev
         self.reach = self.set.reach
         self._h = ctypes.c_void_p()
+        self.motion = None                 # the SceneMotion attached (set_motion)
         place, count = scenes.place, scenes.count
         nat.check(ctx.lib.dsim_scenes_create(ctx.handle, self.set.handle, place.ctypes.data, count.ctypes.data, self.K, self.G,
                                              ctypes.byref(self._h)))
@@ -262,6 +263,36 @@ class DeviceScenes:
         """The prototype's ray grid for the depth camera (DeviceObstacles.enable_rays)."""
         self.set.enable_rays()
         return self
+
+    def set_motion(self, motion: "SceneMotion" = None) -> "DeviceScenes":
+        """Attaches a :class:`SceneMotion` made for these scenes (dsim_scenes_motion_set: uploads, synchronises; not inside a graph
+        capture); the table stands at its base until :meth:`move`.  None detaches it and restores the base table."""
+        if motion is None:
+            nat.check(self.ctx.lib.dsim_scenes_motion_set(self.ctx.handle, self._h, None))
+            self.motion = None
+            return self
+        if not isinstance(motion, SceneMotion) or motion.scenes is not self.scenes:
+            raise ValueError("set_motion takes a SceneMotion made for the ObstacleScenes of this device object")
+        rec = motion.records()
+        nat.check(self.ctx.lib.dsim_scenes_motion_set(self.ctx.handle, self._h, rec.ctypes.data))
+        self.motion = motion
+        return self
+
+    def move(self, clock, dt: float, t_start: float = 0.0) -> None:
+        """dsim_scenes_move on the current stream: the table to scene time t_start + dt * clock.  ``clock``: a device int64 tensor
+        [1] read when the kernel runs (a captured call follows it), or None for 0.  Every query of these scenes on the same
+        stream is ordered behind it."""
+        if self.motion is None:
+            raise ValueError("move() needs a motion: set_motion(SceneMotion)")
+        nat.check(self.ctx.lib.dsim_scenes_move(self.ctx.handle, self.ctx.stream_ptr(), self._h,
+                                                clock.data_ptr() if clock is not None else None, float(dt), float(t_start)))
+
+    def read(self) -> np.ndarray:
+        """float32 [K, G, 12]: the table as the device holds it now (dsim_scenes_read: waits for the current stream), R row-major
+        then t, NaN in unused slots — the layout of ``ObstacleScenes.place``."""
+        out = np.empty((self.K, self.G, 12), dtype=np.float32)
+        nat.check(self.ctx.lib.dsim_scenes_read(self.ctx.handle, self.ctx.stream_ptr(), self._h, out.ctypes.data))
+        return out
 
     def close(self) -> None:
         if self._h:
@@ -320,6 +351,22 @@ class ObstacleScenes:
             raise ValueError("a placement is not finite in float32")
         self.place = np.ascontiguousarray(place)
 
+    @classmethod
+    def from_place(cls, prototype: ObstacleSet, place, count=None) -> "ObstacleScenes":
+        """Scenes from a table as the device takes and hands back (``place``, ``DeviceScenes.read()``, ``SceneMotion.place``):
+        float32 [K, G, 12], R row-major then t, taken verbatim.  ``position`` is t; ``rpy`` is NaN: the rotation is held as a
+        matrix only."""
+        place = np.ascontiguousarray(place, dtype=np.float32)
+        if place.ndim != 3 or place.shape[2] != 12:
+            raise ValueError("place must be [K, G, 12]")
+        K, G = place.shape[:2]
+        proxy = cls(prototype, np.zeros((K, G, 3)), np.zeros((K, G, 3)), count)        # (the checks of K, G and count)
+        if not np.isfinite(place[np.arange(G)[None, :] < proxy.count[:, None]]).all():
+            raise ValueError("non-finite placement")
+        proxy.place = place
+        proxy.position, proxy.rpy = place[..., 9:].astype(np.float64), np.full((K, G, 3), np.nan)
+        return proxy
+
     @property
     def K(self) -> int:
         return int(self.place.shape[0])
@@ -352,6 +399,86 @@ class ObstacleScenes:
         """The library's device scenes for queries with R_max + margin <= ``reach`` (allocates, uploads, synchronises: not inside
         a graph capture); ``prototype_dev``: a device set of the prototype to share instead of making one."""
         return DeviceScenes(ctx, self, reach, prototype_dev)
+
+
+class SceneMotion:
+    """Per-placement motion of an :class:`ObstacleScenes` (dsim_scene_motion; include/dronesim_amd.h states the law).  With
+    (R0, t0) the base pose of placement (k, g) — the float32 ``scenes.place`` — at scene time tau:
+
+        s = sin(omega tau + phase),  t = t0 + velocity tau + amplitude s,  theta = rate tau + swing s,  R = Rot(axis, theta) R0
+
+    a rotation about the placement's own origin.  Every argument broadcasts to [K, G] (``velocity``, ``amplitude``, ``axis``: to
+    [K, G, 3]) and is kept as the float32 the library is given; ``axis`` is a unit vector of the task frame (to 1e-5), or zero
+    with ``rate == swing == 0``.  A placement whose record is all zeros is static: it equals ``scenes.place`` at every tau, bit
+    for bit, and the device never rewrites it.  Entries of unused slots are not looked at.
+
+    Nothing here needs a device: :meth:`pose` and :meth:`place` are the fp64 restatement of what ``DeviceScenes.move`` writes."""
+
+    def __init__(self, scenes: ObstacleScenes, velocity=None, amplitude=None, omega=0.0, phase=0.0, axis=None, rate=0.0, swing=0.0):
+        if not isinstance(scenes, ObstacleScenes):
+            raise TypeError("SceneMotion takes the ObstacleScenes it moves")
+        K, G = scenes.K, scenes.G
+
+        def cast(x, shape, what):
+            try:
+                return np.ascontiguousarray(np.broadcast_to(np.asarray(0.0 if x is None else x, dtype=np.float32), shape))
+            except ValueError:
+                raise ValueError(f"{what} does not broadcast to {list(shape)}") from None
+
+        self.scenes = scenes
+        self.velocity, self.amplitude = cast(velocity, (K, G, 3), "velocity"), cast(amplitude, (K, G, 3), "amplitude")
+        self.axis = cast(axis, (K, G, 3), "axis")
+        self.omega, self.phase = cast(omega, (K, G), "omega"), cast(phase, (K, G), "phase")
+        self.rate, self.swing = cast(rate, (K, G), "rate"), cast(swing, (K, G), "swing")
+        used = self.used = np.arange(G)[None, :] < scenes.count[:, None]
+        rec = self.records()
+        if not np.isfinite(rec[used]).all():
+            raise ValueError("non-finite motion entry in a used slot")
+        norm = np.sqrt((self.axis.astype(np.float64) ** 2).sum(-1))
+        turning = (self.rate != 0.0) | (self.swing != 0.0)
+        bad = used & np.where(norm == 0.0, turning, ~(np.abs(norm - 1.0) <= 1e-5))
+        if bad.any():
+            raise ValueError("axis must be a unit vector (to 1e-5), or zero with rate == swing == 0")
+        # the slots the device rewrites: used, and any entry of the record non-zero
+        self.moving = used & (rec != 0.0).any(-1)
+
+    def records(self) -> np.ndarray:
+        """float32 [K, G, 16]: the dsim_scene_motion records as dsim_scenes_motion_set takes them (13 floats and the padding)."""
+        rec = np.zeros(self.omega.shape + (16,), dtype=np.float32)
+        rec[..., 0:3], rec[..., 3:6], rec[..., 6], rec[..., 7] = self.velocity, self.amplitude, self.omega, self.phase
+        rec[..., 8:11], rec[..., 11], rec[..., 12] = self.axis, self.rate, self.swing
+        return rec
+
+    def pose(self, tau: float):
+        """fp64 (R [K, G, 3, 3], t [K, G, 3]) at scene time ``tau``; NaN in unused slots.  For a static slot the base pose."""
+        tau = float(tau)
+        d = lambda x: x.astype(np.float64)
+        place = d(self.scenes.place)
+        R0, t0 = place[..., :9].reshape(place.shape[:2] + (3, 3)), place[..., 9:]
+        with np.errstate(invalid="ignore", over="ignore"):
+            s = np.sin(d(self.omega) * tau + d(self.phase))
+            t = t0 + d(self.velocity) * tau + d(self.amplitude) * s[..., None]
+            th = d(self.rate) * tau + d(self.swing) * s
+            ct, st = np.cos(th)[..., None, None], np.sin(th)[..., None, None]
+            k = d(self.axis)[..., :, None]                             # against every column v of R0
+            kxv = np.cross(np.broadcast_to(k, R0.shape), R0, axis=-2)
+            kv = (k * R0).sum(-2, keepdims=True)
+            R = R0 * ct + kxv * st + k * (kv * (1.0 - ct))
+        R, t = np.where(self.moving[..., None, None], R, R0), np.where(self.moving[..., None], t, t0)
+        return R, t
+
+    def place(self, tau: float) -> np.ndarray:
+        """float32 [K, G, 12] at scene time ``tau``, R row-major then t: what ``DeviceScenes.read()`` returns after a move to
+        ``tau`` (to the rounding of one float), NaN in unused slots.  Static slots are ``scenes.place``'s, bit for bit."""
+        R, t = self.pose(tau)
+        with np.errstate(over="ignore"):
+            out = np.concatenate([R.reshape(R.shape[:2] + (9,)), t], -1).astype(np.float32)
+        return np.ascontiguousarray(np.where(self.moving[..., None], out, self.scenes.place))
+
+    def snapshot(self, tau: float) -> ObstacleScenes:
+        """A plain static :class:`ObstacleScenes` whose ``place`` is :meth:`place` at ``tau`` (same prototype and counts; its
+        ``position`` is t(tau), its ``rpy`` NaN: the rotation is held as a matrix only)."""
+        return ObstacleScenes.from_place(self.scenes.prototype, self.place(tau), self.scenes.count)
 
 
 def query_scenes(ctx, state, dev_scenes: DeviceScenes, scene_id, margin: float, clearance, nearest, offset=None, type_id=None,

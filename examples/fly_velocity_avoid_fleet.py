@@ -3,9 +3,10 @@
 in its own scene, and adds to that goal velocity a repulsion away from the closest point of the world — env.last_obstacle_witness,
 the vector from the drone to that point (dsim_obstacle_witness_scenes in place of the point watch behind every step).  The flight
 is flown twice, without and with the term, and prints obstacle_contacts() of both.  Nothing leaves the device: the term is a few
-torch ops on [3, N].
+torch ops on [3, N].  With --moving the gates swing across the course (obstacle_motion=SceneMotion: a sideways oscillation of
+every gate, each at its own pace and phase, evaluated on the device before every step's watch); the repulsion is the same.
 
-    python examples/fly_velocity_avoid_fleet.py --num_drones 4096 --duration_sec 6
+    python examples/fly_velocity_avoid_fleet.py --num_drones 4096 --duration_sec 6 [--moving]
 """
 import argparse
 import os
@@ -18,7 +19,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from dronesim_amd.envs import VelocityAviary  # noqa: E402
-from dronesim_amd.obstacles import ObstacleScenes, ObstacleSet  # noqa: E402
+from dronesim_amd.obstacles import ObstacleScenes, ObstacleSet, SceneMotion  # noqa: E402
 
 GATE = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "gate_50_curved.urdf")
 
@@ -41,12 +42,19 @@ def fly(A, avoid: bool):
                     2.0 + rng.uniform(-0.6, 0.6, (K, G))], 2)
     rpy = np.stack([np.zeros((K, G)), np.zeros((K, G)), rng.uniform(-np.pi, np.pi, (K, G))], 2)
     scenes = ObstacleScenes(gate, pos, rpy)
+    moving = {}
+    if A.moving:
+        # every gate swings across the course: +-0.8 m along y, a period of 2 .. 4 s, its own phase
+        amp = np.zeros((K, G, 3))
+        amp[..., 1] = 0.8
+        moving = dict(obstacle_motion=SceneMotion(scenes, amplitude=amp, omega=rng.uniform(0.5 * np.pi, np.pi, (K, G)),
+                                                  phase=rng.uniform(-np.pi, np.pi, (K, G))))
     side = int(np.ceil(np.sqrt(n)))
     off = np.stack([(np.arange(n) % side) * 40.0, (np.arange(n) // side) * 40.0, np.zeros(n)], 1)      # a frame per drone
     xyz = off + np.array([0.0, 0.0, 2.0]) + rng.uniform(-0.5, 0.5, (n, 3))
     env = VelocityAviary([A.drone], n, initial_xyzs=xyz, aggregate_phy_steps=AGGR, freq=FREQ, dict_io=False, obstacle_watch=scenes,
                          obstacle_scene_id=np.arange(n) % K, obstacle_offsets=off, obstacle_margin=A.margin,
-                         obstacle_witness="world")
+                         obstacle_witness="world", **moving)
     dev = env.ctx.device
     radius = float(np.float32(env.ctx.types[0].collision_sphere))
     goal = torch.tensor([A.speed, 0.0, 0.0], device=dev)[:, None].expand(3, n)
@@ -63,7 +71,7 @@ def fly(A, avoid: bool):
         (clr, _), rel = env.last_obstacle_clearance, env.last_obstacle_witness
         closest = min(closest, float(clr.min().item()))
     contacts = env.obstacle_contacts()
-    print(f"{'with' if avoid else 'without'} the repulsion term: {n} drones x {steps} env steps in {time.time() - START:.2f} s wall; "
+    print(f"{'with' if avoid else 'without'} the repulsion term{', swinging gates' if A.moving else ''}: {n} drones x {steps} env steps in {time.time() - START:.2f} s wall; "
           f"obstacle_contacts() = {contacts} drone x steps, least clearance {closest:.3f} m")
     env.close()
     return contacts
@@ -77,6 +85,7 @@ def main(argv=None):
     ap.add_argument("--speed", type=float, default=2.0)
     ap.add_argument("--margin", type=float, default=1.0)
     ap.add_argument("--gain", type=float, default=1.5)
+    ap.add_argument("--moving", action="store_true", help="the gates swing across the course (obstacle_motion=SceneMotion)")
     A = ap.parse_args(argv)
     return fly(A, False), fly(A, True)
 

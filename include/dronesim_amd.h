@@ -55,7 +55,8 @@ extern "C" {
                               gate passage watch, dsim_gate_passage, dsim_gate_args, dsim_aperture, DSIM_APERTURE_*, DSIM_GATE_WRAP; the
                               nearest-neighbour observation, dsim_knn, dsim_knn_workspace, dsim_knn_args; the obstacle witness,
                               dsim_obstacle_witness, dsim_obstacle_witness_scenes, dsim_witness_args, DSIM_WITNESS_BODY_FRAME; line
-                              of sight, dsim_line_of_sight, dsim_sight_args, DSIM_SIGHT_GROUND */
+                              of sight, dsim_line_of_sight, dsim_sight_args, DSIM_SIGHT_GROUND; moving scenes,
+                              dsim_scenes_motion_set, dsim_scenes_move, dsim_scenes_read, dsim_scene_motion */
 #define DSIM_MAX_ACT 6     /* actuators per vehicle (quad 4, morphing hexa 6) */
 #define DSIM_MAX_TYPES 8
 
@@ -1081,6 +1082,50 @@ int dsim_obstacle_clearance_scenes(dsim_ctx* ctx, void* stream, int64_t n, dsim_
 int dsim_depth_image_scenes(dsim_ctx* ctx, void* stream, dsim_view state, const dsim_scenes* scenes, const int32_t* scene_id,
                             const dsim_camera_params* params, int64_t n_cam, const int32_t* cam_index,
                             const float* offset, const uint8_t* type_id, float* depth_out, int32_t* seg_out);
+
+/* Moving scenes: per-placement motion of a dsim_scenes, evaluated on the device in stream order.  Every placed call above and
+ * below (the watch, the witness, the camera, the scanner, line of sight, the gate passage watch) reads the scenes' table from
+ * device memory when its kernel runs, so dsim_scenes_move moves the world for all of them at once; none of them changes.
+ *
+ * The law.  Placement (k, g) has the base pose (R0, t0) dsim_scenes_create was given and one dsim_scene_motion record.  At scene
+ * time tau = t_start + dt * (*clock)  (clock: a device counter the caller advances, dsim_counter_add; NULL: 0 — it is read when
+ * the kernel runs, so a replayed capture, whose arguments are frozen, still puts the world where it belongs):
+ *     s      = sin(omega tau + phase)
+ *     t(tau) = t0 + vel tau + amp s
+ *     theta  = rate tau + swing s
+ *     R(tau) = Rot(axis, theta) R0,   Rot(k, theta) v = v cos(theta) + (k x v) sin(theta) + k (k . v) (1 - cos(theta))
+ * a rotation about the placement's own origin, applied to each column v of R0.  Everything is evaluated in double from the
+ * floats given and rounded to float once; a moving slot's record becomes c_task = R(tau) box_c + t(tau) (box_c: the centre of the
+ * prototype's box as dsim_scenes_create rounded it), its r_cull as it was, and R(tau), t(tau) in the layout dsim_scenes_create
+ * writes.  A record of all zeros is a static placement: its table entry is never rewritten.  Neither is a slot at or above its
+ * scene's count, whose record is not looked at.
+ *
+ * dsim_scenes_motion_set: motion_host [K][G] (host).  DSIM_E_ARG with nothing changed: a null ctx or scenes; a non-finite entry
+ * in a used slot; an axis that is neither of unit length to 1e-5 nor zero with rate == swing == 0.  The first call keeps device
+ * copies of the base table and of the records; a later call replaces the records and puts the base table back first; NULL
+ * detaches the motion, frees both and restores the base table bit for bit.  Allocates, copies and synchronises the device, as
+ * dsim_scenes_create does (not inside a capture).  dsim_scenes_destroy frees what is attached.
+ *
+ * dsim_scenes_move: stream-ordered; allocates nothing, never synchronises, may be captured.  One lane per slot.  DSIM_E_ARG,
+ * nothing enqueued: a null ctx or scenes, scenes without a motion, a non-finite dt or t_start.  Calls that read the scenes on
+ * the SAME stream are ordered behind it; ordering against work on other streams is the caller's business.
+ *
+ * dsim_scenes_read: waits for `stream`, then hands back the table as the device holds it: place_host_out [K][G][12] (host), R
+ * row-major then t per slot, exactly the floats of the table (the layout dsim_scenes_create takes, so a static scenes created
+ * from it holds the same R and t); NaN in the slots at or above their scene's count.  DSIM_E_ARG: a null ctx, scenes or out. */
+typedef struct dsim_scene_motion {
+  float vel[3];    /* [m/s]                                                    */
+  float amp[3];    /* [m]                                                      */
+  float omega;     /* [rad/s]                                                  */
+  float phase;     /* [rad]                                                    */
+  float axis[3];   /* unit, task frame; or zero with rate == swing == 0        */
+  float rate;      /* [rad/s]                                                  */
+  float swing;     /* [rad]                                                    */
+  float pad_[3];   /* to 64 bytes; not looked at                               */
+} dsim_scene_motion;
+int dsim_scenes_motion_set(dsim_ctx* ctx, dsim_scenes* scenes, const dsim_scene_motion* motion_host);
+int dsim_scenes_move(dsim_ctx* ctx, void* stream, dsim_scenes* scenes, const uint64_t* clock, double dt, double t_start);
+int dsim_scenes_read(dsim_ctx* ctx, void* stream, const dsim_scenes* scenes, float* place_host_out);
 
 /* The obstacle witness: the point watch's answer and WHERE the closest point lies.  A watch gives one scalar per drone and no
  * direction; a potential field, a velocity obstacle, a control-barrier filter (h = clearance, grad h = the unit vector away from
