@@ -35,6 +35,7 @@ EXPORTS = (
     "dsim_obstacle_witness", "dsim_obstacle_witness_scenes",
     "dsim_line_of_sight",
     "dsim_scenes_motion_set", "dsim_scenes_move", "dsim_scenes_read",
+    "dsim_scenes_move_twist", "dsim_obstacle_witness_scenes_vel",
 )
 
 ABI_VERSION = 11
@@ -493,8 +494,10 @@ def load(path: str = None) -> ctypes.CDLL:
     lib.dsim_scenes_motion_set.argtypes = [vp, vp, vp]
     lib.dsim_scenes_move.argtypes = [vp, vp, vp, vp, ctypes.c_double, ctypes.c_double]
     lib.dsim_scenes_read.argtypes = [vp, vp, vp, vp]
+    lib.dsim_scenes_move_twist.argtypes = [vp, vp, vp, vp, ctypes.c_double, ctypes.c_double, vp]
     lib.dsim_obstacle_witness.argtypes = [vp, vp, i64, View, vp, ctypes.POINTER(WitnessArgs)]
     lib.dsim_obstacle_witness_scenes.argtypes = [vp, vp, i64, View, vp, vp, ctypes.POINTER(WitnessArgs)]
+    lib.dsim_obstacle_witness_scenes_vel.argtypes = [vp, vp, i64, View, vp, vp, ctypes.POINTER(WitnessArgs), vp, vp]
     lib.dsim_range_scan.argtypes = [vp, vp, i64, View, vp, ctypes.POINTER(ScanArgs)]
     lib.dsim_line_of_sight.argtypes = [vp, vp, i64, View, vp, ctypes.POINTER(SightArgs)]
     lib.dsim_gate_passage.argtypes = [vp, vp, i64, View, vp, vp, ctypes.POINTER(GateArgs)]

@@ -1,4 +1,4 @@
-// Moving obstacle scenes (dsim_scenes_motion_set, dsim_scenes_move, dsim_scenes_read): per-placement motion of the scenes' table,
+// Moving obstacle scenes (dsim_scenes_motion_set, dsim_scenes_move, dsim_scenes_move_twist, dsim_scenes_read): per-placement motion of the scenes' table,
 // evaluated on the device in stream order.  Every placed kernel reads the [K][G] table of 64-byte records from device memory on
 // every launch (ScnK.place), so rewriting a record moves that placement for the watch, the witness, the camera, the scanner and
 // line of sight at once: none of them changes.  Compiled as part of dsim_obstacles.hip, which includes this file behind
@@ -8,6 +8,8 @@
 //     s = sin(omega tau + phase),  t = t0 + vel tau + amp s,  theta = rate tau + swing s,  R = Rot(axis, theta) R0  (Rodrigues)
 // in double from the floats of the record and of the base table, rounded to float once: a float phase at a clock of 2^33 would be
 // wrong by radians, and the result can be checked against an fp64 restatement to an ulp of float.
+// Its derivative, off the same sincos (dsim_scenes_move_twist: the placement's twist, for the velocity of a witness on it):
+//     t' = vel + amp omega cos(omega tau + phase),  theta' = rate + swing omega cos(omega tau + phase),  w = theta' axis
 #pragma once
 
 #define SCM_BLOCK 256
@@ -20,6 +22,7 @@ struct ScmK {
   const float4* motion;          // [slots][4]
   const float4* base;            // [slots][4]: the table as dsim_scenes_create wrote it
   float4* place;                 // [slots][4]: the live table
+  float4* twist;                 // [slots][2] or null: (t'.xyz, 0), (w.xyz, 0) of the moving slots (dsim_scenes_move_twist)
   const unsigned long long* clock;
   long long slots;
   double dt, t_start;
@@ -27,9 +30,10 @@ struct ScmK {
 };
 
 // The record of moving slot i at scene time tau, from its motion record (m3 is its last quarter, which the caller read for the
-// flag) and its base pose: o0 = (c_task, r_cull), o1 .. o3 = R's columns, each followed by a component of t.
+// flag) and its base pose: o0 = (c_task, r_cull), o1 .. o3 = R's columns, each followed by a component of t.  And its twist at
+// that time, w0 = (t', 0), w1 = (theta' axis, 0): the derivative of the law, a few multiplies on the first sincos's cosine.
 __device__ __forceinline__ void scm_record(const ScmK& a, long long i, double tau, const float4 m3, float4& o0, float4& o1, float4& o2,
-                                           float4& o3) {
+                                           float4& o3, float4& w0, float4& w1) {
   const float4 m0 = a.motion[4 * i], m1 = a.motion[4 * i + 1], m2 = a.motion[4 * i + 2];
   const float4 c0 = a.base[4 * i + 1], c1 = a.base[4 * i + 2], c2 = a.base[4 * i + 3];
   double s, c;
@@ -41,6 +45,12 @@ __device__ __forceinline__ void scm_record(const ScmK& a, long long i, double ta
   sincos((double)m2.w * tau + (double)m3.x * s, &st, &ct);
   // Rodrigues: Rot v = v cos + (k x v) sin + k (k . v) (1 - cos), column by column of R0 (column j is (cj.x, cj.y, cj.z))
   const double kx = m2.x, ky = m2.y, kz = m2.z, vc = 1.0 - ct;
+  if (a.twist) {                         // (the launch's: a plain move evaluates nothing of it)
+    const double oc = (double)m1.z * c, thd = (double)m2.w + (double)m3.x * oc;
+    w0 = make_float4((float)((double)m0.x + (double)m0.w * oc), (float)((double)m0.y + (double)m1.x * oc),
+                     (float)((double)m0.z + (double)m1.y * oc), 0.0f);
+    w1 = make_float4((float)(thd * kx), (float)(thd * ky), (float)(thd * kz), 0.0f);
+  }
   double r[3][3];
   const float4 col[3] = {c0, c1, c2};
 #pragma unroll
@@ -66,6 +76,9 @@ __device__ __forceinline__ void scm_record(const ScmK& a, long long i, double ta
 // 256 j + t of the block's 16 KiB, so each store instruction of a wave covers 1 KiB of contiguous table, where four 16-byte stores
 // per lane straight from its registers leave every instruction of a wave strided by 64 bytes.  Only the quarters of moving slots
 // are written.  Measured against that direct form and against a per-block choice between the two: DESIGN.md section 7.
+// With a twist table (dsim_scenes_move_twist) a moving lane also stores the two quarters of its twist, straight from its
+// registers: 32 contiguous bytes per lane, so the two store instructions of a wave cover 2 KiB between them.  Measured against
+// the same two quarters through an LDS transpose of their own (8 KiB more): within 3 % in every case.
 // LDS holds quarter q of lane t at float4 index 4 t + (q ^ (t & 3)): a lane's four writes and a wave's transposed reads both spread
 // over the 16-byte slots of a bank row.
 __global__ __launch_bounds__(SCM_BLOCK) void k_scenes_move(ScmK a) {
@@ -80,8 +93,9 @@ __global__ __launch_bounds__(SCM_BLOCK) void k_scenes_move(ScmK a) {
       const float4 m3 = a.motion[4 * i + 3];
       if (m3.y != 0.0f) {
         mv = true;
-        float4 o0, o1, o2, o3;
-        scm_record(a, i, tau, m3, o0, o1, o2, o3);
+        float4 o0, o1, o2, o3, w0 = {}, w1 = {};
+        scm_record(a, i, tau, m3, o0, o1, o2, o3, w0, w1);
+        if (a.twist) { a.twist[2 * i] = w0; a.twist[2 * i + 1] = w1; }
         s_out[4 * tid + x] = o0; s_out[4 * tid + (1 ^ x)] = o1; s_out[4 * tid + (2 ^ x)] = o2; s_out[4 * tid + (3 ^ x)] = o3;
       }
     }
@@ -100,6 +114,20 @@ static void scm_free(dsim_scenes* sc, hipError_t* e) {
   if (sc->motion) { const hipError_t f = hipFree(sc->motion); if (*e == hipSuccess) *e = f; }
   if (sc->base) { const hipError_t f = hipFree(sc->base); if (*e == hipSuccess) *e = f; }
   sc->motion = sc->base = nullptr;
+}
+
+// both moves: the one kernel, with the twist table or without
+static int scm_move(dsim_ctx* ctx, void* stream, dsim_scenes* scenes, const uint64_t* clock, double dt, double t_start, float* twist) {
+  if (!ctx || !scenes || !scenes->motion || !isfinite(dt) || !isfinite(t_start)) return DSIM_E_ARG;
+  ScmK a;
+  a.motion = scenes->motion; a.base = scenes->base; a.place = scenes->place; a.clock = (const unsigned long long*)clock;
+  a.twist = (float4*)twist;
+  a.slots = scenes->K * (long long)scenes->G; a.dt = dt; a.t_start = t_start;
+  a.bx = scenes->box_c[0]; a.by = scenes->box_c[1]; a.bz = scenes->box_c[2];
+  long long blocks = (a.slots + SCM_BLOCK - 1) / SCM_BLOCK;
+  if (blocks > SCM_MAX_BLOCKS) blocks = SCM_MAX_BLOCKS;
+  hipLaunchKernelGGL(k_scenes_move, dim3((unsigned)blocks), dim3(SCM_BLOCK), 0, (hipStream_t)stream, a);
+  return (int)hipGetLastError();
 }
 
 extern "C" {
@@ -159,15 +187,13 @@ int dsim_scenes_motion_set(dsim_ctx* ctx, dsim_scenes* scenes, const dsim_scene_
 }
 
 int dsim_scenes_move(dsim_ctx* ctx, void* stream, dsim_scenes* scenes, const uint64_t* clock, double dt, double t_start) {
-  if (!ctx || !scenes || !scenes->motion || !isfinite(dt) || !isfinite(t_start)) return DSIM_E_ARG;
-  ScmK a;
-  a.motion = scenes->motion; a.base = scenes->base; a.place = scenes->place; a.clock = (const unsigned long long*)clock;
-  a.slots = scenes->K * (long long)scenes->G; a.dt = dt; a.t_start = t_start;
-  a.bx = scenes->box_c[0]; a.by = scenes->box_c[1]; a.bz = scenes->box_c[2];
-  long long blocks = (a.slots + SCM_BLOCK - 1) / SCM_BLOCK;
-  if (blocks > SCM_MAX_BLOCKS) blocks = SCM_MAX_BLOCKS;
-  hipLaunchKernelGGL(k_scenes_move, dim3((unsigned)blocks), dim3(SCM_BLOCK), 0, (hipStream_t)stream, a);
-  return (int)hipGetLastError();
+  return scm_move(ctx, stream, scenes, clock, dt, t_start, nullptr);
+}
+
+int dsim_scenes_move_twist(dsim_ctx* ctx, void* stream, dsim_scenes* scenes, const uint64_t* clock, double dt, double t_start,
+                           float* twist_out) {
+  if (!twist_out) return DSIM_E_ARG;
+  return scm_move(ctx, stream, scenes, clock, dt, t_start, twist_out);
 }
 
 int dsim_scenes_read(dsim_ctx* ctx, void* stream, const dsim_scenes* scenes, float* place_host_out) {

@@ -27,9 +27,13 @@ __device__ __forceinline__ float3 scn_local(const float4 c0, const float4 c1, co
 // and record index; behind it the winner's three columns are read again (the lane read them in the loop: they come from cache), q
 // goes into that placement's frame by the loop's own scn_local, tri_closest gives the local vector and R takes it back:
 // rel = sum_k col_k l_k.  The triangle is instance-major, g n_tri + t, as the body is g n_bodies + body.
+// Instantiated with Wit = WitVelK it is the witness with a velocity (dsim_obstacle_witness_scenes_vel, dsim_witness.hip): the same
+// tail, and from the local point and the local vector it already holds the velocity of the witness as a point of the winner's
+// placement (wit_velocity: the placement's twist, read once, behind the walk, by the lanes that have a witness).
+struct WitVelK;
 template <bool LDS, class... Wit>
 __global__ __launch_bounds__(256) void k_obstacle_clearance_scenes(ObsK a, ScnK s, Wit... w) {
-  constexpr bool WIT = sizeof...(Wit) != 0;
+  constexpr bool WIT = sizeof...(Wit) != 0, VEL = (std::is_same<Wit, WitVelK>::value || ...);
   extern __shared__ float4 s_rec[];
   bool staged = false;
   for (long long tile = blockIdx.x; tile < a.tiles; tile += gridDim.x) {
@@ -69,7 +73,7 @@ __global__ __launch_bounds__(256) void k_obstacle_clearance_scenes(ObsK a, ScnK 
     const float c_i = DSIM_SQRT(best) - R;
     const bool in = win >= 0 && c_i < a.margin;
     if constexpr (WIT) {
-      float wx = 0.0f, wy = 0.0f, wz = 0.0f;
+      float wx = 0.0f, wy = 0.0f, wz = 0.0f, ux = 0.0f, uy = 0.0f, uz = 0.0f;
       int body = -1;
       if (in) {
         const float4 c0 = pl[4 * slot + 1], c1 = pl[4 * slot + 2], c2 = pl[4 * slot + 3];
@@ -78,9 +82,11 @@ __global__ __launch_bounds__(256) void k_obstacle_clearance_scenes(ObsK a, ScnK 
         body = slot * s.n_bodies + wit_point<LDS>(a, s_rec, win, p.x, p.y, p.z, vx, vy, vz);
         wx = c0.x * vx + c1.x * vy + c2.x * vz; wy = c0.y * vx + c1.y * vy + c2.y * vz; wz = c0.z * vx + c1.z * vy + c2.z * vz;
         win += slot * a.n_tri;
+        if constexpr (VEL) wit_velocity(w..., (size_t)sid * (size_t)s.G + (size_t)slot, c0, c1, c2, p, vx, vy, vz, ux, uy, uz);
       }
       obs_lane_store(a, tile, i, live, in, c_i, body);
-      wit_lane_store(a, w..., i, live, in, wx, wy, wz, win);
+      if constexpr (VEL) wit_lane_store(a, w..., i, live, in, wx, wy, wz, win, ux, uy, uz);
+      else wit_lane_store(a, w..., i, live, in, wx, wy, wz, win);
     } else {
       obs_lane_store(a, tile, i, live, in, c_i, win);
     }

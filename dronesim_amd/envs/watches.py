@@ -24,6 +24,8 @@ class StepWatches:
     _obst_ids = None              # ... and then the scene of every drone, in storage order (set by _obstacle_setup)
     _obst_wit = None              # ... with the witness query in the point query's place: "world" or "body" (obstacle_witness=)
     _obst_rel = None              # ... and the vector it writes behind every launch (set by _obstacle_setup)
+    _obst_vel = None              # ... and, with obstacle_witness_velocity=True, the velocity of that point behind every launch
+    _wit_vel = False
     _motion = None                # the SceneMotion of the watch's scenes (obstacle_motion=; attached by _obstacle_setup)
     _scene_clock = None           # ... and the Env.steps since reset() its scene time counts, on the device
     _vision = None                # the depth camera of vision_attributes=True (set by _watch_setup)
@@ -48,7 +50,7 @@ class StepWatches:
                        range_drone_range=None, gate_watch=None, gate_scenes=None, gate_start=0, gate_laps=False,
                        gate_travel=None, neighbor_obs=None, neighbor_radius=None, neighbor_vel=None,
                        neighbourhood_radius=np.inf, obstacle_witness=None, neighbor_sight=False,
-                       neighbor_sight_scene=None, obstacle_motion=None) -> None:
+                       neighbor_sight_scene=None, obstacle_motion=None, obstacle_witness_velocity=False) -> None:
         """The services' keywords of ``CtrlAviary.__init__``: checked and stashed (the set-up follows in _watch_setup, when the
         context and the storage order exist)."""
         # The reference's Bullet world lets the vehicles' collision shapes act on each other; here every drone is integrated
@@ -228,6 +230,19 @@ class StepWatches:
                 raise NotImplementedError("obstacle_witness with obstacle_sweep=True: the witness of a chord is another quantity "
                                           "(the closest pair of a segment and the set, and where on the chord it lies)")
         self._obst_wit = obstacle_witness
+        # obstacle_witness_velocity=True (with obstacle_witness and obstacle_motion): every launch moves the world with its twist
+        # (dsim_scenes_move_twist) and the query behind it is dsim_obstacle_witness_scenes_vel — still one watch launch: the same
+        # clearance, nearest, witness and counters, and beside them the velocity of every drone's closest obstacle point as a
+        # material point of the moving placement that holds it, in the witness's axes.  last_obstacle_witness_velocity holds it
+        # [3, N] in the caller's numbering (None before the first step), obstacle_witness_velocity() asks on demand,
+        # scene_twists() reports the table.  The obstacle's own velocity, not the relative one: h' = n . (v_drone - v_obstacle)
+        # is the caller's to form.  Off by default: nothing new is allocated or launched.
+        if obstacle_witness_velocity:
+            if obstacle_witness is None:
+                raise ValueError("obstacle_witness_velocity without obstacle_witness='world' or 'body'")
+            if obstacle_motion is None:
+                raise ValueError("obstacle_witness_velocity without obstacle_motion=SceneMotion: a static world's points stand still")
+        self._wit_vel = bool(obstacle_witness_velocity)
         # BaseAviary(vision_attributes=True) keeps self.rgb / self.dep / self.seg per drone at IMG_RES = [64, 48] and refreshes them
         # from _getDroneImages whenever step_counter % IMG_CAPTURE_FREQ == 0 (BaseAviary.py:236-261, 453-502, 794-853).  Here:
         # env.dep / env.seg ([n, H, W] device tensors; no rgb) of the static world `vision_scene` (default: the obstacle_watch
@@ -356,6 +371,10 @@ class StepWatches:
         if self._motion is not None:
             # the scene clock (fixed address: a captured sequence holds it) and the motion's device copy; the table to scene time 0
             self._scene_clock = torch.zeros((1,), dtype=torch.int64, device=dev)
+            if self._wit_vel:
+                # the twist table every move then writes, and the velocity behind every launch (storage order, fixed addresses)
+                self._obst.enable_twist()
+                self._obst_vel = torch.zeros((3, n_pad), dtype=torch.float32, device=dev)
             self._obst.set_motion(self._motion)
             self._obst.move(self._scene_clock, self._scene_dt())
         if self._obst_sweep:
@@ -601,15 +620,16 @@ class StepWatches:
                       self._obst_near, self._obst_off, self._type_id, None, self._obst_unswept)
             self._obst_sampled = True
             return
-        self._obst_query(self._obst_margin, self._obst_clr, self._obst_near, None, self._obst_rel, self._obst_wit)
+        self._obst_query(self._obst_margin, self._obst_clr, self._obst_near, None, self._obst_rel, self._obst_wit, self._obst_vel)
         self._obst_sampled = True
 
-    def _obst_query(self, margin, clr, near, contacts_out, rel=None, frame=None) -> None:
+    def _obst_query(self, margin, clr, near, contacts_out, rel=None, frame=None, vel=None) -> None:
         """The point query of the watch's world: dsim_obstacle_clearance, or dsim_obstacle_clearance_scenes on scenes; with
-        ``rel`` the witness query in its place (dsim_obstacle_witness / _scenes: the same answers and the vector beside them)."""
+        ``rel`` the witness query in its place (dsim_obstacle_witness / _scenes: the same answers and the vector beside them);
+        with ``vel`` too dsim_obstacle_witness_scenes_vel."""
         from .. import obstacles as obs
         obs.point_query(self.ctx, self.state, self._obst, self._obst_ids, margin, clr, near, rel, self._obst_off, self._type_id,
-                        contacts_out, body_frame=frame == "body")
+                        contacts_out, body_frame=frame == "body", vel=vel)
 
     def _scan_now(self):
         """One dsim_range_scan on the state the launch just left, on the env's stream (also under capture)."""
@@ -637,7 +657,9 @@ class StepWatches:
             self._obst.move(self._scene_clock, self._scene_dt())
         if self._obst is not None:
             # (eager, not an Env.step: the watch's kernel is loaded before the capture starts)
-            if self._obst_wit is not None:
+            if self._obst_vel is not None:
+                self.obstacle_witness_velocity()
+            elif self._obst_wit is not None:
                 self.obstacle_witness()
             else:
                 self.obstacle_clearance()
@@ -904,17 +926,21 @@ class StepWatches:
             raise ValueError("obstacle_clearance() needs an env made with obstacle_watch=ObstacleSet")
         return self._obst_now(margin)
 
-    def _obst_now(self, margin, frame=None):
+    def _obst_now(self, margin, frame=None, velocity=False):
         """The on-demand point query of the current state into tensors of its own, in the caller's numbering; with ``frame`` the
-        witness query, and ``rel`` behind the two.  Its contacts are counted apart (_obst_on_demand)."""
+        witness query, and ``rel`` behind the two; with ``velocity`` the witness's velocity behind the three.  Its contacts are
+        counted apart (_obst_on_demand)."""
         margin = self._obst_margin if margin is None else float(margin)
         dev, n_pad = self.ctx.device, self.state.n_pad
         clr = torch.empty((n_pad,), dtype=torch.float32, device=dev)
         near = torch.empty((n_pad,), dtype=torch.int32, device=dev)
         rel = torch.zeros((3, n_pad), dtype=torch.float32, device=dev) if frame is not None else None
-        self._obst_query(margin, clr, near, self._obst_on_demand, rel, frame)
+        vel = torch.zeros((3, n_pad), dtype=torch.float32, device=dev) if velocity else None
+        self._obst_query(margin, clr, near, self._obst_on_demand, rel, frame, vel)
         out = self._obst_to_caller(clr, near)
-        return out if rel is None else out + (self._rel_to_caller(rel),)
+        if rel is not None:
+            out = out + (self._rel_to_caller(rel),)
+        return out if vel is None else out + (self._rel_to_caller(vel),)
 
     @property
     def last_obstacle_witness(self):
@@ -941,6 +967,38 @@ class StepWatches:
         if frame not in ("world", "body"):
             raise ValueError(f"frame must be 'world' or 'body', got {frame!r}")
         return self._obst_now(margin, frame)
+
+    @property
+    def last_obstacle_witness_velocity(self):
+        """[3, N] float32 behind the last step of an ``obstacle_witness_velocity`` env, in the caller's numbering: the velocity of
+        the point last_obstacle_witness leads to, as a material point of the moving placement that holds it (t' + w x r at the
+        launch's scene time), in the witness's axes; zeros where there is no witness and on a static placement.  None before the
+        first step."""
+        if self._obst_vel is None or not self._obst_sampled:
+            return None
+        return self._rel_to_caller(self._obst_vel)
+
+    def obstacle_witness_velocity(self, margin: Optional[float] = None, frame: Optional[str] = None):
+        """(clearance [N] float32, nearest [N] int32, rel [3, N] float32, vel [3, N] float32) of the CURRENT state, in the caller's
+        numbering (dsim_obstacle_witness_scenes_vel): what obstacle_witness() returns and the velocity of the closest point,
+        from the twist table as the last launch left it.  Not counted as an Env.step: the contacts it sees go where
+        obstacle_clearance()'s go."""
+        if self._obst_vel is None:
+            raise ValueError("obstacle_witness_velocity() needs an env made with obstacle_witness_velocity=True")
+        frame = self._obst_wit if frame is None else frame
+        if frame not in ("world", "body"):
+            raise ValueError(f"frame must be 'world' or 'body', got {frame!r}")
+        return self._obst_now(margin, frame, velocity=True)
+
+    def scene_twists(self) -> np.ndarray:
+        """float32 [K, G, 6]: (t', w) of the watch's placements as the device holds them now, the last launch's scene time; zeros
+        in static slots, NaN in unused ones (waits for the stream)."""
+        if self._obst_vel is None:
+            raise ValueError("scene_twists() needs an env made with obstacle_witness_velocity=True")
+        tw = self._obst.twist.cpu().numpy()
+        out = np.concatenate([tw[..., 0:3], tw[..., 4:7]], -1)
+        out[~self._motion.used] = np.nan
+        return out
 
     def drone_images(self):
         """(dep, seg) of the CURRENT state, captured now on the env's stream into env.dep / env.seg (BaseAviary._getDroneImages

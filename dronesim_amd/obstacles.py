@@ -251,6 +251,7 @@ class DeviceScenes:
         self.reach = self.set.reach
         self._h = ctypes.c_void_p()
         self.motion = None                 # the SceneMotion attached (set_motion)
+        self.twist = None                  # float32 [K, G, 8] on the device: the placements' twists (enable_twist)
         place, count = scenes.place, scenes.count
         nat.check(ctx.lib.dsim_scenes_create(ctx.handle, self.set.handle, place.ctypes.data, count.ctypes.data, self.K, self.G,
                                              ctypes.byref(self._h)))
@@ -267,25 +268,37 @@ class DeviceScenes:
     def set_motion(self, motion: "SceneMotion" = None) -> "DeviceScenes":
         """Attaches a :class:`SceneMotion` made for these scenes (dsim_scenes_motion_set: uploads, synchronises; not inside a graph
         capture); the table stands at its base until :meth:`move`.  None detaches it and restores the base table."""
-        if motion is None:
-            nat.check(self.ctx.lib.dsim_scenes_motion_set(self.ctx.handle, self._h, None))
-            self.motion = None
-            return self
-        if not isinstance(motion, SceneMotion) or motion.scenes is not self.scenes:
+        if motion is not None and (not isinstance(motion, SceneMotion) or motion.scenes is not self.scenes):
             raise ValueError("set_motion takes a SceneMotion made for the ObstacleScenes of this device object")
-        rec = motion.records()
-        nat.check(self.ctx.lib.dsim_scenes_motion_set(self.ctx.handle, self._h, rec.ctypes.data))
+        rec = motion.records() if motion is not None else None
+        nat.check(self.ctx.lib.dsim_scenes_motion_set(self.ctx.handle, self._h, rec.ctypes.data if rec is not None else None))
         self.motion = motion
+        if self.twist is not None:             # (what the old motion moved and the new one leaves alone reads zero again)
+            self.twist.zero_()
+        return self
+
+    def enable_twist(self) -> "DeviceScenes":
+        """Allocates ``twist``, float32 [K, G, 8] of zeros on the context's device: from now on :meth:`move` also writes
+        (t'.xyz, 0, w.xyz, 0) of every moving placement into it (dsim_scenes_move_twist); static and unused slots stay zero.
+        :func:`witness_scenes_vel` reads it.  Not inside a graph capture."""
+        if self.twist is None:
+            import torch
+            self.twist = torch.zeros((self.K, self.G, 8), dtype=torch.float32, device=self.ctx.device)
         return self
 
     def move(self, clock, dt: float, t_start: float = 0.0) -> None:
         """dsim_scenes_move on the current stream: the table to scene time t_start + dt * clock.  ``clock``: a device int64 tensor
         [1] read when the kernel runs (a captured call follows it), or None for 0.  Every query of these scenes on the same
-        stream is ordered behind it."""
+        stream is ordered behind it.  After :meth:`enable_twist` it is dsim_scenes_move_twist: the same table, and ``twist``
+        at the same scene time."""
         if self.motion is None:
             raise ValueError("move() needs a motion: set_motion(SceneMotion)")
-        nat.check(self.ctx.lib.dsim_scenes_move(self.ctx.handle, self.ctx.stream_ptr(), self._h,
-                                                clock.data_ptr() if clock is not None else None, float(dt), float(t_start)))
+        clk = clock.data_ptr() if clock is not None else None
+        if self.twist is not None:
+            nat.check(self.ctx.lib.dsim_scenes_move_twist(self.ctx.handle, self.ctx.stream_ptr(), self._h, clk, float(dt),
+                                                          float(t_start), self.twist.data_ptr()))
+        else:
+            nat.check(self.ctx.lib.dsim_scenes_move(self.ctx.handle, self.ctx.stream_ptr(), self._h, clk, float(dt), float(t_start)))
 
     def read(self) -> np.ndarray:
         """float32 [K, G, 12]: the table as the device holds it now (dsim_scenes_read: waits for the current stream), R row-major
@@ -412,7 +425,8 @@ class SceneMotion:
     with ``rate == swing == 0``.  A placement whose record is all zeros is static: it equals ``scenes.place`` at every tau, bit
     for bit, and the device never rewrites it.  Entries of unused slots are not looked at.
 
-    Nothing here needs a device: :meth:`pose` and :meth:`place` are the fp64 restatement of what ``DeviceScenes.move`` writes."""
+    Nothing here needs a device: :meth:`pose` and :meth:`place` are the fp64 restatement of what ``DeviceScenes.move`` writes,
+    :meth:`twist` and :meth:`point_velocity` of its derivative (``DeviceScenes.enable_twist``)."""
 
     def __init__(self, scenes: ObstacleScenes, velocity=None, amplitude=None, omega=0.0, phase=0.0, axis=None, rate=0.0, swing=0.0):
         if not isinstance(scenes, ObstacleScenes):
@@ -466,6 +480,31 @@ class SceneMotion:
             R = R0 * ct + kxv * st + k * (kv * (1.0 - ct))
         R, t = np.where(self.moving[..., None, None], R, R0), np.where(self.moving[..., None], t, t0)
         return R, t
+
+    def twist(self, tau: float):
+        """fp64 (v [K, G, 3], w [K, G, 3]) at scene time ``tau``, the derivative of the law: v = velocity + amplitude omega
+        cos(omega tau + phase), w = (rate + swing omega cos(omega tau + phase)) axis — the axis is fixed in the task frame, so w
+        is the placement's angular velocity in task axes.  Exact zeros in static slots, NaN in unused ones."""
+        tau = float(tau)
+        d = lambda x: x.astype(np.float64)
+        with np.errstate(invalid="ignore", over="ignore"):
+            oc = d(self.omega) * np.cos(d(self.omega) * tau + d(self.phase))
+            v = d(self.velocity) + d(self.amplitude) * oc[..., None]
+            w = (d(self.rate) + d(self.swing) * oc)[..., None] * d(self.axis)
+        out = []
+        for x in (v, w):
+            x = np.where(self.moving[..., None], x, 0.0)
+            x[~self.used] = np.nan
+            out.append(x)
+        return out[0], out[1]
+
+    def point_velocity(self, tau: float, x) -> np.ndarray:
+        """fp64 [K, G, 3]: the velocity at scene time ``tau`` of the material point of each placement that stands at the
+        task-frame position ``x`` ([K, G, 3], or what broadcasts to it): t' + w x (x - t(tau)).  NaN in unused slots."""
+        v, w = self.twist(tau)
+        _, t = self.pose(tau)
+        r = np.broadcast_to(np.asarray(x, dtype=np.float64), t.shape) - t
+        return v + np.cross(w, r)
 
     def place(self, tau: float) -> np.ndarray:
         """float32 [K, G, 12] at scene time ``tau``, R row-major then t: what ``DeviceScenes.read()`` returns after a move to
@@ -524,13 +563,38 @@ def witness_scenes(ctx, state, dev_scenes: DeviceScenes, scene_id, margin: float
                                                    scene_id.data_ptr(), ctypes.byref(a)))
 
 
+def witness_scenes_vel(ctx, state, dev_scenes: DeviceScenes, scene_id, margin: float, clearance, nearest, rel, vel, triangle=None,
+                       offset=None, type_id=None, contacts_out=None, body_frame: bool = False) -> None:
+    """dsim_obstacle_witness_scenes_vel on the current stream: what :func:`witness_scenes` writes, bit for bit, and into ``vel``
+    ([3, n_pad] float32) the velocity of every drone's closest obstacle point as a material point of the placement that holds
+    it, t' + w x r from ``dev_scenes.twist`` as the last :meth:`DeviceScenes.move` left it — world axes, or the drone's body axes
+    with ``body_frame``; the obstacle's own velocity, not the relative one.  Zeros where ``nearest`` is -1 and on a static
+    placement."""
+    if scene_id is None:
+        raise ValueError("scene_id is required")
+    if vel is None:
+        raise ValueError("vel ([3, n_pad] float32) is required")
+    if dev_scenes.twist is None:
+        raise ValueError("witness_scenes_vel needs the scenes' twist table: DeviceScenes.enable_twist()")
+    a = _witness_args(margin, clearance, nearest, rel, triangle, offset, type_id, contacts_out, body_frame)
+    nat.check(ctx.lib.dsim_obstacle_witness_scenes_vel(ctx.handle, ctx.stream_ptr(), state.n, state.view(), dev_scenes.handle,
+                                                       scene_id.data_ptr(), ctypes.byref(a), dev_scenes.twist.data_ptr(),
+                                                       vel.data_ptr()))
+
+
 def point_query(ctx, state, dev, scene_id, margin: float, clearance, nearest, rel=None, offset=None, type_id=None, contacts_out=None,
-                body_frame: bool = False) -> None:
+                body_frame: bool = False, vel=None) -> None:
     """The point query of a device world, whichever it is: :func:`query` on a :class:`DeviceObstacles`, :func:`query_scenes` on a
     :class:`DeviceScenes` (``scene_id`` is theirs and is not looked at otherwise); with ``rel`` the witness query in its place
-    (:func:`witness` / :func:`witness_scenes`: the same answers and the vector beside them, no ``triangle``)."""
+    (:func:`witness` / :func:`witness_scenes`: the same answers and the vector beside them, no ``triangle``); with ``vel`` too,
+    on scenes, :func:`witness_scenes_vel`."""
     ids = (scene_id,) if isinstance(dev, DeviceScenes) else ()
-    if rel is None:
+    if vel is not None:
+        if not ids or rel is None:
+            raise ValueError("vel needs a DeviceScenes and rel")
+        witness_scenes_vel(ctx, state, dev, scene_id, margin, clearance, nearest, rel, vel, None, offset, type_id, contacts_out,
+                           body_frame=body_frame)
+    elif rel is None:
         (query_scenes if ids else query)(ctx, state, dev, *ids, margin, clearance, nearest, offset, type_id, contacts_out)
     else:
         (witness_scenes if ids else witness)(ctx, state, dev, *ids, margin, clearance, nearest, rel, None, offset, type_id,

@@ -5,8 +5,12 @@ the vector from the drone to that point (dsim_obstacle_witness_scenes in place o
 is flown twice, without and with the term, and prints obstacle_contacts() of both.  Nothing leaves the device: the term is a few
 torch ops on [3, N].  With --moving the gates swing across the course (obstacle_motion=SceneMotion: a sideways oscillation of
 every gate, each at its own pace and phase, evaluated on the device before every step's watch); the repulsion is the same.
+With --moving --lead a third flight adds env.last_obstacle_witness_velocity (obstacle_witness_velocity=True: the velocity of the
+closest point as a point of its moving gate, from dsim_obstacle_witness_scenes_vel), weighted by the repulsion's own falloff: the
+drone is carried along with the gate that closes on it, so the repulsion leads the gate instead of answering where it was.  The
+least clearance of each flight is printed; no figure is promised for it.
 
-    python examples/fly_velocity_avoid_fleet.py --num_drones 4096 --duration_sec 6 [--moving]
+    python examples/fly_velocity_avoid_fleet.py --num_drones 4096 --duration_sec 6 [--moving [--lead]]
 """
 import argparse
 import os
@@ -33,7 +37,14 @@ def repulsion(rel, clearance, radius, margin, gain):
     return gain * push * away
 
 
-def fly(A, avoid: bool):
+def lead_term(vel, clearance, margin):
+    """[3, N]: the closest point's own velocity, faded in as the repulsion is — 0 at the margin and beyond (where vel is 0 too),
+    whole where the repulsion has reached its cap."""
+    weight = ((1.0 / clearance.clamp(min=0.05) - 1.0 / margin) / 10.0).clamp(min=0.0, max=1.0)
+    return weight * vel
+
+
+def fly(A, avoid: bool, lead: bool = False):
     n, AGGR, FREQ, K, G = A.num_drones, 5, 240, 64, 6
     rng = np.random.default_rng(0)
     gate = ObstacleSet.from_urdf(GATE, (0, 0, 0), (0, 0, 0))
@@ -54,24 +65,29 @@ def fly(A, avoid: bool):
     xyz = off + np.array([0.0, 0.0, 2.0]) + rng.uniform(-0.5, 0.5, (n, 3))
     env = VelocityAviary([A.drone], n, initial_xyzs=xyz, aggregate_phy_steps=AGGR, freq=FREQ, dict_io=False, obstacle_watch=scenes,
                          obstacle_scene_id=np.arange(n) % K, obstacle_offsets=off, obstacle_margin=A.margin,
-                         obstacle_witness="world", **moving)
+                         obstacle_witness="world", obstacle_witness_velocity=lead, **moving)
     dev = env.ctx.device
     radius = float(np.float32(env.ctx.types[0].collision_sphere))
     goal = torch.tensor([A.speed, 0.0, 0.0], device=dev)[:, None].expand(3, n)
     limit = float(env.SPEED_LIMIT[0])
     clr, _, rel = env.obstacle_witness()
+    vel = torch.zeros_like(rel)
     steps = int(A.duration_sec * FREQ / AGGR)
     closest = float("inf")
     START = time.time()
     for _ in range(steps):
         wish = goal + repulsion(rel, clr, radius, A.margin, A.gain) if avoid else goal
+        if lead:
+            wish = wish + lead_term(vel, clr, A.margin)
         speed = wish.norm(dim=0)
         action = torch.cat([wish / speed.clamp(min=1e-6), (speed / limit).clamp(max=1.0)[None, :]], 0).T.contiguous()
         env.step(action)
         (clr, _), rel = env.last_obstacle_clearance, env.last_obstacle_witness
+        if lead:
+            vel = env.last_obstacle_witness_velocity
         closest = min(closest, float(clr.min().item()))
     contacts = env.obstacle_contacts()
-    print(f"{'with' if avoid else 'without'} the repulsion term{', swinging gates' if A.moving else ''}: {n} drones x {steps} env steps in {time.time() - START:.2f} s wall; "
+    print(f"{'with' if avoid else 'without'} the repulsion term{' and the lead term' if lead else ''}{', swinging gates' if A.moving else ''}: {n} drones x {steps} env steps in {time.time() - START:.2f} s wall; "
           f"obstacle_contacts() = {contacts} drone x steps, least clearance {closest:.3f} m")
     env.close()
     return contacts
@@ -86,8 +102,13 @@ def main(argv=None):
     ap.add_argument("--margin", type=float, default=1.0)
     ap.add_argument("--gain", type=float, default=1.5)
     ap.add_argument("--moving", action="store_true", help="the gates swing across the course (obstacle_motion=SceneMotion)")
+    ap.add_argument("--lead", action="store_true", help="with --moving: a third flight adds the closest point's own velocity "
+                                                        "(obstacle_witness_velocity=True), weighted by the repulsion's falloff")
     A = ap.parse_args(argv)
-    return fly(A, False), fly(A, True)
+    if A.lead and not A.moving:
+        ap.error("--lead needs --moving: a static world's points stand still")
+    out = fly(A, False), fly(A, True)
+    return out + (fly(A, True, True),) if A.lead else out
 
 
 if __name__ == "__main__":

@@ -56,7 +56,8 @@ extern "C" {
                               nearest-neighbour observation, dsim_knn, dsim_knn_workspace, dsim_knn_args; the obstacle witness,
                               dsim_obstacle_witness, dsim_obstacle_witness_scenes, dsim_witness_args, DSIM_WITNESS_BODY_FRAME; line
                               of sight, dsim_line_of_sight, dsim_sight_args, DSIM_SIGHT_GROUND; moving scenes,
-                              dsim_scenes_motion_set, dsim_scenes_move, dsim_scenes_read, dsim_scene_motion */
+                              dsim_scenes_motion_set, dsim_scenes_move, dsim_scenes_read, dsim_scene_motion; the velocity of the
+                              witness on moving scenes, dsim_scenes_move_twist, dsim_obstacle_witness_scenes_vel */
 #define DSIM_MAX_ACT 6     /* actuators per vehicle (quad 4, morphing hexa 6) */
 #define DSIM_MAX_TYPES 8
 
@@ -1112,7 +1113,18 @@ int dsim_depth_image_scenes(dsim_ctx* ctx, void* stream, dsim_view state, const 
  *
  * dsim_scenes_read: waits for `stream`, then hands back the table as the device holds it: place_host_out [K][G][12] (host), R
  * row-major then t per slot, exactly the floats of the table (the layout dsim_scenes_create takes, so a static scenes created
- * from it holds the same R and t); NaN in the slots at or above their scene's count.  DSIM_E_ARG: a null ctx, scenes or out. */
+ * from it holds the same R and t); NaN in the slots at or above their scene's count.  DSIM_E_ARG: a null ctx, scenes or out.
+ *
+ * dsim_scenes_move_twist: dsim_scenes_move — the same kernel, the same table bit for bit — that also writes the TWIST of every
+ * moving placement at that scene time, the derivative of the law off the same sine and cosine:
+ *     t'     = vel + amp omega cos(omega tau + phase)
+ *     theta' = rate + swing omega cos(omega tau + phase),   w = theta' axis     (the axis is fixed in the task frame: the
+ *                                                                                placement's angular velocity in task axes)
+ * in double, rounded to float once.  twist_out: caller-owned device memory, [K G][8] floats, 16-byte aligned: (t'.xyz, 0, w.xyz, 0)
+ * per slot.  Only moving slots are written; static and unused slots are never touched, so the caller zeroes the table once, and
+ * again after a new dsim_scenes_motion_set.  A material point of the placement at task-frame position x moves with
+ * t' + w x (x - t(tau)): dsim_obstacle_witness_scenes_vel below.  The promises of dsim_scenes_move hold; DSIM_E_ARG, nothing
+ * enqueued: what dsim_scenes_move refuses (scenes without a motion among it), a null twist_out. */
 typedef struct dsim_scene_motion {
   float vel[3];    /* [m/s]                                                    */
   float amp[3];    /* [m]                                                      */
@@ -1125,6 +1137,8 @@ typedef struct dsim_scene_motion {
 } dsim_scene_motion;
 int dsim_scenes_motion_set(dsim_ctx* ctx, dsim_scenes* scenes, const dsim_scene_motion* motion_host);
 int dsim_scenes_move(dsim_ctx* ctx, void* stream, dsim_scenes* scenes, const uint64_t* clock, double dt, double t_start);
+int dsim_scenes_move_twist(dsim_ctx* ctx, void* stream, dsim_scenes* scenes, const uint64_t* clock, double dt, double t_start,
+                           float* twist_out);
 int dsim_scenes_read(dsim_ctx* ctx, void* stream, const dsim_scenes* scenes, float* place_host_out);
 
 /* The obstacle witness: the point watch's answer and WHERE the closest point lies.  A watch gives one scalar per drone and no
@@ -1148,7 +1162,22 @@ int dsim_scenes_read(dsim_ctx* ctx, void* stream, const dsim_scenes* scenes, flo
  * distance, the witness may sit on either, up to sqrt(2 d E) apart.
  * Stream-ordered, allocates nothing, never synchronises (may be captured).  DSIM_E_ARG, nothing enqueued: everything
  * dsim_obstacle_clearance (_scenes) refuses, a null args or rel_out, an unknown flag; DSIM_E_LAYOUT: DSIM_WITNESS_BODY_FRAME on a
- * view of fewer than 7 fields. */
+ * view of fewer than 7 fields.
+ *
+ * dsim_obstacle_witness_scenes_vel: the witness on MOVING scenes, with the velocity of the closest point.  Against a moving
+ * obstacle the filters above need h' = n . (v_drone - v_obstacle); differencing two witnesses mixes in the drone's own motion and
+ * jumps when the winning triangle changes, while the device knows the answer.  It writes everything
+ * dsim_obstacle_witness_scenes writes, bit for bit, and
+ *     vel_out[k][i]    = (t'_g + w_g x r)_k            SoA [3][n_pad] (device), required: the velocity of w* as a material point of
+ *                                                      the placement g that holds it, from that slot of `twist`, the table
+ *                                                      dsim_scenes_move_twist wrote ([K G][8] floats, device).  r = R_g (l + v_l), with
+ *                                                      l the query point and v_l the closest-point vector in the placement's
+ *                                                      frame: relative quantities, so offsets of 128 m cost it no digits.  World axes;
+ *                                                      with DSIM_WITNESS_BODY_FRAME R(quat_i)^T of it.  The obstacle point's OWN
+ *                                                      velocity, not the velocity relative to the drone.
+ * A drone without a witness gets zeros, as in rel_out; a witness on a static placement (a zeroed slot of `twist`) reads 0 in
+ * every component.  The two twist quarters of the winner are read once, behind the search, by the drones that have a witness.
+ * DSIM_E_ARG, nothing enqueued and nothing written: what dsim_obstacle_witness_scenes refuses, a null twist or vel_out. */
 enum { DSIM_WITNESS_BODY_FRAME = 1 };   /* rel_out in the drone's body axes */
 typedef struct dsim_witness_args {
   const float*   offset;        /* SoA [3][n_pad] or NULL, as dsim_obstacle_clearance                      */
@@ -1165,6 +1194,8 @@ int dsim_obstacle_witness(dsim_ctx* ctx, void* stream, int64_t n, dsim_view stat
                           const dsim_witness_args* args);
 int dsim_obstacle_witness_scenes(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, const dsim_scenes* scenes,
                                  const int32_t* scene_id, const dsim_witness_args* args);
+int dsim_obstacle_witness_scenes_vel(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, const dsim_scenes* scenes,
+                                     const int32_t* scene_id, const dsim_witness_args* args, const float* twist, float* vel_out);
 
 /* Range scanner: a fan of range beams per drone, for EVERY drone — the sensor real vehicles carry (a ToF ring, a downward altimeter,
  * a small lidar fan).  A watch gives one scalar per drone and no direction; the camera gives direction at thousands of rays per

@@ -6,9 +6,10 @@ law on (velocity, oscillation, spin and swing).  Device events around batches of
 interleaved round by round (tools/bench_camera.py's protocol); one JSON line per case, the float4-copy rate of the same box
 (tools/membench) beside it.
 
-    python tools/bench_motion.py [--iters 200] [--warmup 50] [--rounds 7] [--lib PATH]
+    python tools/bench_motion.py [--iters 200] [--warmup 50] [--rounds 7] [--lib PATH] [--twist]
 
 The bytes a slot must move: a moving one reads 64 (motion record) + 48 (base pose) and writes 64 = 176; a static one reads 16.
+With --twist the call is dsim_scenes_move_twist, which writes 32 more per moving slot (its twist): 208.
 Each case is timed at clock 7 and at clock 2^33: the bytes are the same, but at 2^33 the phase is ~1e9 rad and the fp64 sin/cos
 take their large-argument reduction.  Equal times say the bytes bound the kernel; a slower 2^33 says the sin/cos show.
 """
@@ -41,6 +42,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--lib", default=None, help="another build of the library (an A/B against the one in the tree)")
+    ap.add_argument("--twist", action="store_true", help="time dsim_scenes_move_twist: the move that also writes the twist table")
     a = ap.parse_args()
     import torch
     from dronesim_amd import _native as nat
@@ -81,7 +83,10 @@ def main():
                                 axis=np.where(on[..., None], axis, 0.0), rate=np.where(on, rng.uniform(2.0, 4.0, (K, G)), 0.0),
                                 swing=np.where(on, rng.uniform(0.3, 0.9, (K, G)), 0.0))
             assert int(m.moving.sum()) == int(on.sum())
-            dev = scenes.to_device(ctx, prototype_dev=proto).set_motion(m)
+            dev = scenes.to_device(ctx, prototype_dev=proto)
+            if a.twist:
+                dev.enable_twist()
+            dev.set_motion(m)
             for clock in (7, 2 ** 33):
                 c = torch.tensor([clock], dtype=torch.int64, device=ctx.device)
                 cases[(share, clock)] = (dev, c, int(on.sum()), K * G - int(on.sum()))
@@ -96,9 +101,9 @@ def main():
                 t[key].append(timed(fn))
         for (share, clock), (dev, c, moving, static) in cases.items():
             us = np.array(t[(share, clock)])
-            nbytes = 176 * moving + 16 * static
+            nbytes = (208 if a.twist else 176) * moving + 16 * static
             print(json.dumps({
-                "what": "dsim_scenes_move", "lib": a.lib or "tree", "K": K, "G": G, "slots": K * G, "moving_one_in": share, "clock": clock,
+                "what": "dsim_scenes_move_twist" if a.twist else "dsim_scenes_move", "lib": a.lib or "tree", "K": K, "G": G, "slots": K * G, "moving_one_in": share, "clock": clock,
                 "us_median": round(float(np.median(us)), 2), "us_min_max": [round(float(us.min()), 2), round(float(us.max()), 2)],
                 "algorithmic_bytes": nbytes, "GBps_at_median": round(nbytes / float(np.median(us)) / 1e3, 1),
                 "float4_copy_GBps": copy, "iters": a.iters, "rounds": a.rounds}), flush=True)

@@ -11,6 +11,13 @@ interleaved round by round; prints one JSON line per case with the median and th
 
 The bytes a far drone must move: the point watch reads 12 (position) and writes 8; the witness writes 12 more (rel = 0).  A drone in
 reach reads one 64-byte record again (from LDS, or through L2) and, in the body frame, its quaternion (16).
+
+Moving ("moving_G3"): the same 64 scenes under a motion of every term (dsim_scenes_motion_set), the clock at 7.  D = dsim_scenes_move
++ dsim_obstacle_witness_scenes, what an env with obstacle_motion and obstacle_witness launches behind a step; E =
+dsim_scenes_move_twist + dsim_obstacle_witness_scenes_vel, the same with obstacle_witness_velocity; F and G the two moves alone.
+E costs 32 bytes written per moving slot, and 32 read and 12 written per drone in reach (12 written per far drone: vel = 0).  A
+build without the twist entries (an older library's tree) prints D and F only: run the tool from both trees in alternation for
+an A/B against it.
 """
 import argparse
 import json
@@ -48,6 +55,19 @@ def main():
     rpy3 = rng.uniform([-0.5, -0.5, -np.pi], [0.5, 0.5, np.pi], (K, 3, 3))
     dev = gate.to_device(ctx, obs.watch_reach(ctx.types, a.margin))
     three = obs.ObstacleScenes(gate, pos3, rpy3).to_device(ctx, prototype_dev=dev)
+    # the same scenes twice more, moving: one moved plainly, one with its twist table (where the build has one)
+    mrng = np.random.default_rng(13)
+    axis = mrng.normal(size=(K, 3, 3))
+    axis /= np.linalg.norm(axis, axis=-1, keepdims=True)
+    scenes_m = obs.ObstacleScenes(gate, pos3, rpy3)
+    motion = obs.SceneMotion(scenes_m, velocity=mrng.uniform(-1.5, 1.5, (K, 3, 3)), amplitude=mrng.uniform(-0.4, 0.4, (K, 3, 3)),
+                             omega=mrng.uniform(3.0, 6.0, (K, 3)), phase=mrng.uniform(-1.0, 1.0, (K, 3)), axis=axis,
+                             rate=mrng.uniform(2.0, 4.0, (K, 3)), swing=mrng.uniform(0.3, 0.9, (K, 3)))
+    moved = scenes_m.to_device(ctx, prototype_dev=dev).set_motion(motion)
+    has_twist = hasattr(obs.DeviceScenes, "enable_twist")
+    twisted = scenes_m.to_device(ctx, prototype_dev=dev).enable_twist().set_motion(motion) if has_twist else None
+    clock = torch.full((1,), 7, dtype=torch.int64, device=ctx.device)
+    dt = 1.0 / 48.0
     r = lambda x: round(float(x), 2)
 
     def timed(fn):
@@ -109,7 +129,27 @@ def main():
                 report({"what": what, "case": case, "drones": n, "n_tri": gate.n_tri, "margin": a.margin, "in_reach_share": share,
                         "far_bytes_per_drone_A_B": [20, 32] if what == "unplaced" else [72, 84]},
                        ["A_point", "B_witness", "C_witness_body"], t)
-            del st, clr, near, rel, id3
+            vel = torch.empty((3, st.n_pad), dtype=torch.float32, device=ctx.device)
+
+            def plain_pair():
+                moved.move(clock, dt)
+                obs.witness_scenes(ctx, st, moved, id3, a.margin, clr, near, rel)
+
+            def twist_pair():
+                twisted.move(clock, dt)
+                obs.witness_scenes_vel(ctx, st, twisted, id3, a.margin, clr, near, rel, vel)
+            fns, names = [plain_pair, lambda: moved.move(clock, dt)], ["D_move_witness", "F_move"]
+            if has_twist:
+                fns, names = fns + [twist_pair, lambda: twisted.move(clock, dt)], names + ["E_movetwist_witnessvel", "G_move_twist"]
+            t = rounds(fns)
+            plain_pair()
+            share = round(float((near[:n] >= 0).float().mean().item()), 4)
+            report({"what": "moving_G3", "case": case, "drones": n, "n_tri": gate.n_tri, "margin": a.margin, "in_reach_share": share,
+                    "moving_slots": int(motion.moving.sum())}, names, t)
+            del st, clr, near, rel, vel, id3
+    moved.close()
+    if twisted is not None:
+        twisted.close()
     three.close()
     dev.close()
     ctx.close()
