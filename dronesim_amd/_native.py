@@ -36,6 +36,7 @@ EXPORTS = (
     "dsim_line_of_sight",
     "dsim_scenes_motion_set", "dsim_scenes_move", "dsim_scenes_read",
     "dsim_scenes_move_twist", "dsim_obstacle_witness_scenes_vel",
+    "dsim_obstacle_witnesses", "dsim_obstacle_witnesses_scenes",
 )
 
 ABI_VERSION = 11
@@ -232,6 +233,28 @@ class WitnessArgs(ctypes.Structure):
         ("rel_out", ctypes.c_void_p),
         ("triangle_out", ctypes.c_void_p),
         ("contacts_out", ctypes.c_void_p),
+    ]
+
+
+WITNESSES_MAX = 8                       # DSIM_WITNESSES_MAX: slots per drone of dsim_obstacle_witnesses
+
+
+class WitnessesArgs(ctypes.Structure):
+    """dsim_witnesses_args (dsim_obstacle_witnesses, dsim_obstacle_witnesses_scenes)."""
+    _fields_ = [
+        ("offset", ctypes.c_void_p),
+        ("type_id", ctypes.c_void_p),
+        ("margin", ctypes.c_float),
+        ("m", ctypes.c_int32),
+        ("flags", ctypes.c_int32),
+        ("clearance_out", ctypes.c_void_p),
+        ("body_out", ctypes.c_void_p),
+        ("rel_out", ctypes.c_void_p),
+        ("triangle_out", ctypes.c_void_p),
+        ("count_out", ctypes.c_void_p),
+        ("contacts_out", ctypes.c_void_p),
+        ("twist", ctypes.c_void_p),
+        ("vel_out", ctypes.c_void_p),
     ]
 
 
@@ -498,6 +521,8 @@ def load(path: str = None) -> ctypes.CDLL:
     lib.dsim_obstacle_witness.argtypes = [vp, vp, i64, View, vp, ctypes.POINTER(WitnessArgs)]
     lib.dsim_obstacle_witness_scenes.argtypes = [vp, vp, i64, View, vp, vp, ctypes.POINTER(WitnessArgs)]
     lib.dsim_obstacle_witness_scenes_vel.argtypes = [vp, vp, i64, View, vp, vp, ctypes.POINTER(WitnessArgs), vp, vp]
+    lib.dsim_obstacle_witnesses.argtypes = [vp, vp, i64, View, vp, ctypes.POINTER(WitnessesArgs)]
+    lib.dsim_obstacle_witnesses_scenes.argtypes = [vp, vp, i64, View, vp, vp, ctypes.POINTER(WitnessesArgs)]
     lib.dsim_range_scan.argtypes = [vp, vp, i64, View, vp, ctypes.POINTER(ScanArgs)]
     lib.dsim_line_of_sight.argtypes = [vp, vp, i64, View, vp, ctypes.POINTER(SightArgs)]
     lib.dsim_gate_passage.argtypes = [vp, vp, i64, View, vp, vp, ctypes.POINTER(GateArgs)]

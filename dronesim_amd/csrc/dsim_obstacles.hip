@@ -395,3 +395,7 @@ int dsim_obstacle_clearance(dsim_ctx* ctx, void* stream, int64_t n, dsim_view st
 // the obstacle witness: the point watch with the vector to the closest point (both point kernels above are its kernels too; the
 // file holds the tail they call, its arguments and its entry points)
 #include "dsim_witness.hip"
+
+// obstacle witnesses: the m closest bodies per drone, each with its vector (it shares the tile frame, the scenes' cull and the
+// witness's tail steps; its kernels keep a sorted list of per-body minima where the point kernels keep one)
+#include "dsim_witnesses.hip"

@@ -165,6 +165,7 @@ class CtrlAviary(PlacedFleetArrays, FleetObservation, StepWatches):
         neighbor_sight_scene=None,
         obstacle_motion=None,
         obstacle_witness_velocity: bool = False,
+        obstacle_witnesses: int = 0,
     ):
         if gui or record or obstacles:
             raise NotImplementedError("gui/record/obstacles are rendering features outside the hot path")
@@ -182,7 +183,8 @@ class CtrlAviary(PlacedFleetArrays, FleetObservation, StepWatches):
                             neighbor_obs=neighbor_obs, neighbor_radius=neighbor_radius, neighbor_vel=neighbor_vel,
                             neighbourhood_radius=neighbourhood_radius, obstacle_witness=obstacle_witness,
                             neighbor_sight=neighbor_sight, neighbor_sight_scene=neighbor_sight_scene,
-                            obstacle_motion=obstacle_motion, obstacle_witness_velocity=obstacle_witness_velocity)
+                            obstacle_motion=obstacle_motion, obstacle_witness_velocity=obstacle_witness_velocity,
+                            obstacle_witnesses=obstacle_witnesses)
         # the add-on terms of the PYB_* modes (dead code in the reference fork, intended formulas); Physics.DYN: the
         # reference's own explicit model, BaseAviary._dynamics (BaseAviary.py:1767-1828; DSIM_OPT_DYN)
         self._phys_options = {Physics.PYB: 0, Physics.PYB_DW: 0, Physics.PYB_GND: nat.OPT_GROUND,

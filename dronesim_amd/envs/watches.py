@@ -26,6 +26,8 @@ class StepWatches:
     _obst_rel = None              # ... and the vector it writes behind every launch (set by _obstacle_setup)
     _obst_vel = None              # ... and, with obstacle_witness_velocity=True, the velocity of that point behind every launch
     _wit_vel = False
+    _obst_m = 0                   # ... with the witnesses query in the witness's place: slots per drone (obstacle_witnesses=m)
+    _obst_wits = None             # ... and what it writes behind every launch, slot-major (set by _obstacle_setup)
     _motion = None                # the SceneMotion of the watch's scenes (obstacle_motion=; attached by _obstacle_setup)
     _scene_clock = None           # ... and the Env.steps since reset() its scene time counts, on the device
     _vision = None                # the depth camera of vision_attributes=True (set by _watch_setup)
@@ -50,7 +52,8 @@ class StepWatches:
                        range_drone_range=None, gate_watch=None, gate_scenes=None, gate_start=0, gate_laps=False,
                        gate_travel=None, neighbor_obs=None, neighbor_radius=None, neighbor_vel=None,
                        neighbourhood_radius=np.inf, obstacle_witness=None, neighbor_sight=False,
-                       neighbor_sight_scene=None, obstacle_motion=None, obstacle_witness_velocity=False) -> None:
+                       neighbor_sight_scene=None, obstacle_motion=None, obstacle_witness_velocity=False,
+                       obstacle_witnesses=0) -> None:
         """The services' keywords of ``CtrlAviary.__init__``: checked and stashed (the set-up follows in _watch_setup, when the
         context and the storage order exist)."""
         # The reference's Bullet world lets the vehicles' collision shapes act on each other; here every drone is integrated
@@ -243,6 +246,18 @@ class StepWatches:
             if obstacle_motion is None:
                 raise ValueError("obstacle_witness_velocity without obstacle_motion=SceneMotion: a static world's points stand still")
         self._wit_vel = bool(obstacle_witness_velocity)
+        # obstacle_witnesses=m (1..8, with obstacle_witness): the query behind a launch is dsim_obstacle_witnesses (_scenes) in the
+        # witness's place — still one watch launch: per drone the m closest BODIES within the margin, sorted, each with its
+        # clearance, its vector and (with obstacle_witness_velocity) its velocity.  last_obstacle_witnesses holds the record in the
+        # caller's numbering (None before the first step), obstacle_witnesses() asks on demand.  Slot 0 is the witness bit for
+        # bit: last_obstacle_clearance, last_obstacle_witness, last_obstacle_witness_velocity and obstacle_contacts() read row 0
+        # of the new buffers and keep their values.  0 by default: nothing new is allocated or launched.
+        if isinstance(obstacle_witnesses, bool) or not isinstance(obstacle_witnesses, (int, np.integer)) \
+                or not 0 <= int(obstacle_witnesses) <= nat.WITNESSES_MAX:
+            raise ValueError(f"obstacle_witnesses must be an int in 0..{nat.WITNESSES_MAX}, got {obstacle_witnesses!r}")
+        if obstacle_witnesses and obstacle_witness is None:
+            raise ValueError("obstacle_witnesses without obstacle_witness='world' or 'body'")
+        self._obst_m = int(obstacle_witnesses)
         # BaseAviary(vision_attributes=True) keeps self.rgb / self.dep / self.seg per drone at IMG_RES = [64, 48] and refreshes them
         # from _getDroneImages whenever step_counter % IMG_CAPTURE_FREQ == 0 (BaseAviary.py:236-261, 453-502, 794-853).  Here:
         # env.dep / env.seg ([n, H, W] device tensors; no rgb) of the static world `vision_scene` (default: the obstacle_watch
@@ -368,6 +383,15 @@ class StepWatches:
         self._obst_sampled = False
         # the witness behind every launch (storage order, fixed address: a captured sequence holds it)
         self._obst_rel = torch.zeros((3, n_pad), dtype=torch.float32, device=dev) if self._obst_wit is not None else None
+        m = self._obst_m
+        if m:
+            # the witnesses behind every launch, slot-major; the single answers are row 0 of them (the same fixed addresses)
+            from ..obstacles import ObstacleWitnesses
+            self._obst_wits = ObstacleWitnesses(torch.empty((m, n_pad), dtype=torch.float32, device=dev),
+                                                torch.empty((m, n_pad), dtype=torch.int32, device=dev),
+                                                torch.zeros((m, 3, n_pad), dtype=torch.float32, device=dev), None,
+                                                torch.zeros((n_pad,), dtype=torch.int32, device=dev))
+            self._obst_clr, self._obst_near, self._obst_rel = self._obst_wits.clearance[0], self._obst_wits.body[0], self._obst_wits.rel[0]
         if self._motion is not None:
             # the scene clock (fixed address: a captured sequence holds it) and the motion's device copy; the table to scene time 0
             self._scene_clock = torch.zeros((1,), dtype=torch.int64, device=dev)
@@ -375,6 +399,9 @@ class StepWatches:
                 # the twist table every move then writes, and the velocity behind every launch (storage order, fixed addresses)
                 self._obst.enable_twist()
                 self._obst_vel = torch.zeros((3, n_pad), dtype=torch.float32, device=dev)
+                if m:
+                    self._obst_wits = self._obst_wits._replace(vel=torch.zeros((m, 3, n_pad), dtype=torch.float32, device=dev))
+                    self._obst_vel = self._obst_wits.vel[0]
             self._obst.set_motion(self._motion)
             self._obst.move(self._scene_clock, self._scene_dt())
         if self._obst_sweep:
@@ -620,16 +647,20 @@ class StepWatches:
                       self._obst_near, self._obst_off, self._type_id, None, self._obst_unswept)
             self._obst_sampled = True
             return
-        self._obst_query(self._obst_margin, self._obst_clr, self._obst_near, None, self._obst_rel, self._obst_wit, self._obst_vel)
+        if self._obst_m:
+            w = self._obst_wits
+            self._obst_query(self._obst_margin, w.clearance, w.body, None, w.rel, self._obst_wit, w.vel, self._obst_m, w.count)
+        else:
+            self._obst_query(self._obst_margin, self._obst_clr, self._obst_near, None, self._obst_rel, self._obst_wit, self._obst_vel)
         self._obst_sampled = True
 
-    def _obst_query(self, margin, clr, near, contacts_out, rel=None, frame=None, vel=None) -> None:
+    def _obst_query(self, margin, clr, near, contacts_out, rel=None, frame=None, vel=None, m=None, count=None) -> None:
         """The point query of the watch's world: dsim_obstacle_clearance, or dsim_obstacle_clearance_scenes on scenes; with
         ``rel`` the witness query in its place (dsim_obstacle_witness / _scenes: the same answers and the vector beside them);
-        with ``vel`` too dsim_obstacle_witness_scenes_vel."""
+        with ``vel`` too dsim_obstacle_witness_scenes_vel; with ``m`` dsim_obstacle_witnesses (_scenes) into slot-major tensors."""
         from .. import obstacles as obs
         obs.point_query(self.ctx, self.state, self._obst, self._obst_ids, margin, clr, near, rel, self._obst_off, self._type_id,
-                        contacts_out, body_frame=frame == "body", vel=vel)
+                        contacts_out, body_frame=frame == "body", vel=vel, m=m, count=count)
 
     def _scan_now(self):
         """One dsim_range_scan on the state the launch just left, on the env's stream (also under capture)."""
@@ -657,7 +688,9 @@ class StepWatches:
             self._obst.move(self._scene_clock, self._scene_dt())
         if self._obst is not None:
             # (eager, not an Env.step: the watch's kernel is loaded before the capture starts)
-            if self._obst_vel is not None:
+            if self._obst_m:
+                self.obstacle_witnesses()
+            elif self._obst_vel is not None:
                 self.obstacle_witness_velocity()
             elif self._obst_wit is not None:
                 self.obstacle_witness()
@@ -989,6 +1022,45 @@ class StepWatches:
         if frame not in ("world", "body"):
             raise ValueError(f"frame must be 'world' or 'body', got {frame!r}")
         return self._obst_now(margin, frame, velocity=True)
+
+    @property
+    def last_obstacle_witnesses(self):
+        """The :class:`~dronesim_amd.obstacles.ObstacleWitnesses` behind the last step of an ``obstacle_witnesses=m`` env, in the
+        caller's numbering: ``clearance`` / ``body`` [m, N], ``rel`` [m, 3, N] (the env's witness axes), ``vel`` [m, 3, N] with
+        ``obstacle_witness_velocity`` else None, ``count`` [N] — per drone the m closest bodies within the margin, ascending;
+        (margin, -1, zeros) in an unfilled slot; ``count == m`` may hide further bodies.  Slot 0 is last_obstacle_clearance /
+        last_obstacle_witness / last_obstacle_witness_velocity.  None before the first step."""
+        if self._obst_wits is None or not self._obst_sampled:
+            return None
+        return self._wits_to_caller(self._obst_wits)
+
+    def _wits_to_caller(self, w):
+        n = self.NUM_DRONES
+        to = (lambda t: self.order.to_caller(t[..., :n], -1)) if self.order is not None else (lambda t: t[..., :n])
+        return type(w)(to(w.clearance), to(w.body), to(w.rel), to(w.vel) if w.vel is not None else None, to(w.count))
+
+    def obstacle_witnesses(self, margin: Optional[float] = None, frame: Optional[str] = None, m: Optional[int] = None):
+        """The :class:`~dronesim_amd.obstacles.ObstacleWitnesses` of the CURRENT state, in the caller's numbering
+        (dsim_obstacle_witnesses / _scenes): per drone the ``m`` (default: the env's obstacle_witnesses, else 1) closest bodies of
+        the ``obstacle_watch`` world within ``margin``; ``vel`` on an ``obstacle_witness_velocity`` env, from the twist table as
+        the last launch left it.  Not counted as an Env.step: the contacts it sees go where obstacle_clearance()'s go."""
+        if self._obst is None:
+            raise ValueError("obstacle_witnesses() needs an env made with obstacle_watch=ObstacleSet")
+        frame = (self._obst_wit or "world") if frame is None else frame
+        if frame not in ("world", "body"):
+            raise ValueError(f"frame must be 'world' or 'body', got {frame!r}")
+        m = (self._obst_m or 1) if m is None else m
+        if isinstance(m, bool) or not isinstance(m, (int, np.integer)) or not 1 <= int(m) <= nat.WITNESSES_MAX:
+            raise ValueError(f"m must be an int in 1..{nat.WITNESSES_MAX}, got {m!r}")
+        from ..obstacles import ObstacleWitnesses
+        margin = self._obst_margin if margin is None else float(margin)
+        dev, n_pad, m = self.ctx.device, self.state.n_pad, int(m)
+        w = ObstacleWitnesses(torch.empty((m, n_pad), dtype=torch.float32, device=dev), torch.empty((m, n_pad), dtype=torch.int32, device=dev),
+                              torch.zeros((m, 3, n_pad), dtype=torch.float32, device=dev),
+                              torch.zeros((m, 3, n_pad), dtype=torch.float32, device=dev) if self._obst_vel is not None else None,
+                              torch.zeros((n_pad,), dtype=torch.int32, device=dev))
+        self._obst_query(margin, w.clearance, w.body, self._obst_on_demand, w.rel, frame, w.vel, m, w.count)
+        return self._wits_to_caller(w)
 
     def scene_twists(self) -> np.ndarray:
         """float32 [K, G, 6]: (t', w) of the watch's placements as the device holds them now, the last launch's scene time; zeros

@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+import typing
 import xml.etree.ElementTree as etxml
 
 import numpy as np
@@ -582,13 +583,74 @@ def witness_scenes_vel(ctx, state, dev_scenes: DeviceScenes, scene_id, margin: f
                                                        vel.data_ptr()))
 
 
+class ObstacleWitnesses(typing.NamedTuple):
+    """What :func:`witnesses` / :func:`witnesses_scenes` answer, slot-major: ``clearance`` and ``body`` [m, N], ``rel`` [m, 3, N],
+    ``vel`` [m, 3, N] or None, ``count`` [N] — the slots filled, min(bodies within the margin, m): ``count == m`` may hide
+    further bodies."""
+    clearance: object
+    body: object
+    rel: object
+    vel: object
+    count: object
+
+
+def _witnesses_args(m, margin, clearance, body, rel, triangle, count, offset, type_id, contacts_out, body_frame, twist=None,
+                    vel=None) -> "nat.WitnessesArgs":
+    if isinstance(m, bool) or not isinstance(m, (int, np.integer)) or not 1 <= int(m) <= nat.WITNESSES_MAX:
+        raise ValueError(f"m must be an int in 1..{nat.WITNESSES_MAX}, got {m!r}")
+    if clearance is None or body is None or rel is None:
+        raise ValueError("clearance, body ([m, n_pad]) and rel ([m, 3, n_pad] float32) are required")
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    return nat.WitnessesArgs(ptr(offset), ptr(type_id), float(margin), int(m), nat.WITNESS_BODY_FRAME if body_frame else 0,
+                             clearance.data_ptr(), body.data_ptr(), rel.data_ptr(), ptr(triangle), ptr(count), ptr(contacts_out),
+                             ptr(twist), ptr(vel))
+
+
+def witnesses(ctx, state, dev: DeviceObstacles, margin: float, m: int, clearance, body, rel, triangle=None, count=None, offset=None,
+              type_id=None, contacts_out=None, body_frame: bool = False) -> None:
+    """dsim_obstacle_witnesses on the current stream: per drone the ``m`` (1..8) closest BODIES of the set within the margin,
+    ascending in distance, slot-major: ``clearance`` [m, n_pad] float32 (``margin`` in an unfilled slot), ``body`` [m, n_pad]
+    int32 (-1), ``rel`` [m, 3, n_pad] float32, the vector from the query point to the closest point of that body — world axes, or
+    the drone's body axes with ``body_frame`` — exact zeros unfilled; ``triangle`` [m, n_pad] int32 and ``count`` [n_pad] int32
+    may be None.  Slot 0 is :func:`witness`, bit for bit; ties keep what the walk met first."""
+    a = _witnesses_args(m, margin, clearance, body, rel, triangle, count, offset, type_id, contacts_out, body_frame)
+    nat.check(ctx.lib.dsim_obstacle_witnesses(ctx.handle, ctx.stream_ptr(), state.n, state.view(), dev.handle, ctypes.byref(a)))
+
+
+def witnesses_scenes(ctx, state, dev_scenes: DeviceScenes, scene_id, margin: float, m: int, clearance, body, rel, triangle=None,
+                     count=None, offset=None, type_id=None, contacts_out=None, body_frame: bool = False, vel=None) -> None:
+    """dsim_obstacle_witnesses_scenes on the current stream: :func:`witnesses` over the instance-major bodies g n_bodies + body of
+    the placements of each drone's scene (``scene_id`` as in :func:`query_scenes`; ``triangle`` is g n_tri + t).  With ``vel``
+    ([m, 3, n_pad] float32) the velocity of every witness as a material point of its own placement, from ``dev_scenes.twist`` as
+    the last :meth:`DeviceScenes.move` left it: what :func:`witness_scenes_vel` gives for the one, zeros unfilled and static."""
+    if scene_id is None:
+        raise ValueError("scene_id is required")
+    if vel is not None and dev_scenes.twist is None:
+        raise ValueError("vel needs the scenes' twist table: DeviceScenes.enable_twist()")
+    a = _witnesses_args(m, margin, clearance, body, rel, triangle, count, offset, type_id, contacts_out, body_frame,
+                        dev_scenes.twist if vel is not None else None, vel)
+    nat.check(ctx.lib.dsim_obstacle_witnesses_scenes(ctx.handle, ctx.stream_ptr(), state.n, state.view(), dev_scenes.handle,
+                                                     scene_id.data_ptr(), ctypes.byref(a)))
+
+
 def point_query(ctx, state, dev, scene_id, margin: float, clearance, nearest, rel=None, offset=None, type_id=None, contacts_out=None,
-                body_frame: bool = False, vel=None) -> None:
+                body_frame: bool = False, vel=None, m=None, count=None) -> None:
     """The point query of a device world, whichever it is: :func:`query` on a :class:`DeviceObstacles`, :func:`query_scenes` on a
     :class:`DeviceScenes` (``scene_id`` is theirs and is not looked at otherwise); with ``rel`` the witness query in its place
     (:func:`witness` / :func:`witness_scenes`: the same answers and the vector beside them, no ``triangle``); with ``vel`` too,
-    on scenes, :func:`witness_scenes_vel`."""
+    on scenes, :func:`witness_scenes_vel`.  With ``m`` the witnesses query in the witness's place (:func:`witnesses` /
+    :func:`witnesses_scenes`): ``clearance`` / ``nearest`` [m, n_pad], ``rel`` / ``vel`` [m, 3, n_pad], ``count`` [n_pad]."""
     ids = (scene_id,) if isinstance(dev, DeviceScenes) else ()
+    if m is not None:
+        if rel is None or (vel is not None and not ids):
+            raise ValueError("m needs rel, and vel a DeviceScenes")
+        if ids:
+            witnesses_scenes(ctx, state, dev, scene_id, margin, m, clearance, nearest, rel, None, count, offset, type_id, contacts_out,
+                             body_frame=body_frame, vel=vel)
+        else:
+            witnesses(ctx, state, dev, margin, m, clearance, nearest, rel, None, count, offset, type_id, contacts_out,
+                      body_frame=body_frame)
+        return
     if vel is not None:
         if not ids or rel is None:
             raise ValueError("vel needs a DeviceScenes and rel")

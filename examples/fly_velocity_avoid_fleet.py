@@ -9,8 +9,12 @@ With --moving --lead a third flight adds env.last_obstacle_witness_velocity (obs
 closest point as a point of its moving gate, from dsim_obstacle_witness_scenes_vel), weighted by the repulsion's own falloff: the
 drone is carried along with the gate that closes on it, so the repulsion leads the gate instead of answering where it was.  The
 least clearance of each flight is printed; no figure is promised for it.
+With --witnesses M (1..8) the env answers with the M closest gates of every drone (obstacle_witnesses=M:
+env.last_obstacle_witnesses, dsim_obstacle_witnesses_scenes in the witness's place) and the repulsion is summed over the filled
+slots: a drone between two gates is pushed by both, and nothing jumps when the nearer one changes.  With --moving --lead each slot
+is led by its own gate's velocity.
 
-    python examples/fly_velocity_avoid_fleet.py --num_drones 4096 --duration_sec 6 [--moving [--lead]]
+    python examples/fly_velocity_avoid_fleet.py --num_drones 4096 --duration_sec 6 [--moving [--lead]] [--witnesses 3]
 """
 import argparse
 import os
@@ -65,26 +69,38 @@ def fly(A, avoid: bool, lead: bool = False):
     xyz = off + np.array([0.0, 0.0, 2.0]) + rng.uniform(-0.5, 0.5, (n, 3))
     env = VelocityAviary([A.drone], n, initial_xyzs=xyz, aggregate_phy_steps=AGGR, freq=FREQ, dict_io=False, obstacle_watch=scenes,
                          obstacle_scene_id=np.arange(n) % K, obstacle_offsets=off, obstacle_margin=A.margin,
-                         obstacle_witness="world", obstacle_witness_velocity=lead, **moving)
+                         obstacle_witness="world", obstacle_witness_velocity=lead, obstacle_witnesses=A.witnesses, **moving)
     dev = env.ctx.device
     radius = float(np.float32(env.ctx.types[0].collision_sphere))
     goal = torch.tensor([A.speed, 0.0, 0.0], device=dev)[:, None].expand(3, n)
     limit = float(env.SPEED_LIMIT[0])
-    clr, _, rel = env.obstacle_witness()
+    if A.witnesses:
+        w = env.obstacle_witnesses()                                 # [M, N], [M, 3, N]: unfilled slots push by nothing
+        clr, rel = w.clearance, w.rel
+    else:
+        clr, _, rel = env.obstacle_witness()
     vel = torch.zeros_like(rel)
     steps = int(A.duration_sec * FREQ / AGGR)
     closest = float("inf")
     START = time.time()
     for _ in range(steps):
-        wish = goal + repulsion(rel, clr, radius, A.margin, A.gain) if avoid else goal
+        # (with --witnesses the terms are [M, 3, N] against clearances [M, 1, N]: summed over the slots)
+        c = clr[:, None, :] if A.witnesses else clr
+        push = repulsion(rel, c, radius, A.margin, A.gain)
+        wish = goal + (push.sum(0) if A.witnesses else push) if avoid else goal
         if lead:
-            wish = wish + lead_term(vel, clr, A.margin)
+            carry = lead_term(vel, c, A.margin)
+            wish = wish + (carry.sum(0) if A.witnesses else carry)
         speed = wish.norm(dim=0)
         action = torch.cat([wish / speed.clamp(min=1e-6), (speed / limit).clamp(max=1.0)[None, :]], 0).T.contiguous()
         env.step(action)
-        (clr, _), rel = env.last_obstacle_clearance, env.last_obstacle_witness
-        if lead:
-            vel = env.last_obstacle_witness_velocity
+        if A.witnesses:
+            w = env.last_obstacle_witnesses
+            clr, rel, vel = w.clearance, w.rel, w.vel if lead else vel
+        else:
+            (clr, _), rel = env.last_obstacle_clearance, env.last_obstacle_witness
+            if lead:
+                vel = env.last_obstacle_witness_velocity
         closest = min(closest, float(clr.min().item()))
     contacts = env.obstacle_contacts()
     print(f"{'with' if avoid else 'without'} the repulsion term{' and the lead term' if lead else ''}{', swinging gates' if A.moving else ''}: {n} drones x {steps} env steps in {time.time() - START:.2f} s wall; "
@@ -104,6 +120,8 @@ def main(argv=None):
     ap.add_argument("--moving", action="store_true", help="the gates swing across the course (obstacle_motion=SceneMotion)")
     ap.add_argument("--lead", action="store_true", help="with --moving: a third flight adds the closest point's own velocity "
                                                         "(obstacle_witness_velocity=True), weighted by the repulsion's falloff")
+    ap.add_argument("--witnesses", type=int, default=0, help="the M closest gates per drone (obstacle_witnesses=M, 1..8): the "
+                                                             "repulsion is summed over the filled slots; 0: the one witness")
     A = ap.parse_args(argv)
     if A.lead and not A.moving:
         ap.error("--lead needs --moving: a static world's points stand still")

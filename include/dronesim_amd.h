@@ -57,7 +57,8 @@ extern "C" {
                               dsim_obstacle_witness, dsim_obstacle_witness_scenes, dsim_witness_args, DSIM_WITNESS_BODY_FRAME; line
                               of sight, dsim_line_of_sight, dsim_sight_args, DSIM_SIGHT_GROUND; moving scenes,
                               dsim_scenes_motion_set, dsim_scenes_move, dsim_scenes_read, dsim_scene_motion; the velocity of the
-                              witness on moving scenes, dsim_scenes_move_twist, dsim_obstacle_witness_scenes_vel */
+                              witness on moving scenes, dsim_scenes_move_twist, dsim_obstacle_witness_scenes_vel; obstacle witnesses,
+                              dsim_obstacle_witnesses, dsim_obstacle_witnesses_scenes, dsim_witnesses_args, DSIM_WITNESSES_MAX */
 #define DSIM_MAX_ACT 6     /* actuators per vehicle (quad 4, morphing hexa 6) */
 #define DSIM_MAX_TYPES 8
 
@@ -1196,6 +1197,58 @@ int dsim_obstacle_witness_scenes(dsim_ctx* ctx, void* stream, int64_t n, dsim_vi
                                  const int32_t* scene_id, const dsim_witness_args* args);
 int dsim_obstacle_witness_scenes_vel(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, const dsim_scenes* scenes,
                                      const int32_t* scene_id, const dsim_witness_args* args, const float* twist, float* vel_out);
+
+/* Obstacle witnesses: the m closest BODIES of every drone, each with its vector.  The witness above answers for the one closest
+ * point of the whole world; a drone between two gates, or between a wall and a moving gate, has two active constraints, and a
+ * repulsion built on the nearer one alone jumps when the winner changes.  With q_i, R_i and margin as above, d_b the least distance
+ * from q_i to a triangle of body b (dsim_obstacle_witnesses: the bodies of the set; dsim_obstacle_witnesses_scenes: the
+ * instance-major bodies g n_bodies + body of the placements g < count of scene scene_id[i]) and c_b = d_b - R_i: the witnesses of
+ * drone i are the bodies with c_b < margin, ascending in d_b, the first m of them, 1 <= m <= DSIM_WITNESSES_MAX.  Slot-major, so that
+ * every store of a wave is contiguous, for slot s < m:
+ *     clearance_out[s][i]                              [m][n_pad] (device), required; c_b, or margin for an unfilled slot
+ *     body_out[s][i]                                   [m][n_pad], required; b, or -1
+ *     rel_out[s][k][i]                                 [m][3][n_pad], required; the vector from q_i to the closest point of b, in
+ *                                                      world axes or with DSIM_WITNESS_BODY_FRAME in the drone's body axes (the
+ *                                                      quaternion is read once per drone); exact zeros for an unfilled slot
+ *     triangle_out[s][i]                               [m][n_pad], nullable; the triangle of b that holds the point, on scenes
+ *                                                      instance-major g n_tri + t; -1
+ *     count_out[i]                                     [n_pad], nullable; the number of slots filled, min(bodies within the margin, m).
+ *                                                      count == m may hide further bodies: an exact count beyond m would need a
+ *                                                      memory of the bodies the walk evicted, which it does not keep
+ *     vel_out[s][k][i]                                 [m][3][n_pad], nullable, on scenes with `twist` (the table
+ *                                                      dsim_scenes_move_twist wrote) and only with it: the velocity of each
+ *                                                      witness as a material point of its OWN placement, what
+ *                                                      dsim_obstacle_witness_scenes_vel gives for the one, in the witness's axes;
+ *                                                      zeros for an unfilled slot and on a static placement
+ * Ties.  A candidate enters the list or moves up in it only on a strict <: an exact tie between two bodies keeps the one the walk
+ * met first, an exact tie between two triangles of one body keeps the first triangle, and placements are walked in slot order.
+ * Hence, for every m, slot 0 IS the witness: clearance_out[0], body_out[0], rel_out[0], triangle_out[0] and vel_out[0] are what
+ * dsim_obstacle_witness / _scenes / _scenes_vel write on the same inputs.  The counters keep their meaning: one per drone whose
+ * slot-0 clearance is negative, added to the ctx's shards (DSIM_Q_OBSTACLE_CONTACTS) and to contacts_out.
+ * Stream-ordered, allocates nothing, never synchronises (may be captured).  DSIM_E_ARG, nothing enqueued and every output
+ * untouched: a null args, clearance_out, body_out or rel_out; m outside 1 .. DSIM_WITNESSES_MAX; an unknown flag; twist and vel_out
+ * not both given or both null, or either given to dsim_obstacle_witnesses; everything the witness refuses.  DSIM_E_LAYOUT:
+ * DSIM_WITNESS_BODY_FRAME on a view of fewer than 7 fields. */
+enum { DSIM_WITNESSES_MAX = 8 };
+typedef struct dsim_witnesses_args {
+  const float*   offset;        /* SoA [3][n_pad] or NULL, as dsim_obstacle_clearance                      */
+  const uint8_t* type_id;       /* [n_pad]; required with more than one type                               */
+  float          margin;        /* > 0                                                                      */
+  int32_t        m;             /* 1 .. DSIM_WITNESSES_MAX                                                  */
+  int32_t        flags;         /* DSIM_WITNESS_BODY_FRAME                                                  */
+  float*         clearance_out; /* [m][n_pad]; required                                                     */
+  int32_t*       body_out;      /* [m][n_pad]; required                                                     */
+  float*         rel_out;       /* [m][3][n_pad]; required                                                  */
+  int32_t*       triangle_out;  /* [m][n_pad], nullable                                                     */
+  int32_t*       count_out;     /* [n_pad], nullable                                                        */
+  uint64_t*      contacts_out;  /* device counter, nullable                                                 */
+  const float*   twist;         /* [K G][8] (device), nullable; scenes only, with vel_out                   */
+  float*         vel_out;       /* [m][3][n_pad], nullable; with twist                                      */
+} dsim_witnesses_args;
+int dsim_obstacle_witnesses(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, const dsim_obstacles* set,
+                            const dsim_witnesses_args* args);
+int dsim_obstacle_witnesses_scenes(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, const dsim_scenes* scenes,
+                                   const int32_t* scene_id, const dsim_witnesses_args* args);
 
 /* Range scanner: a fan of range beams per drone, for EVERY drone — the sensor real vehicles carry (a ToF ring, a downward altimeter,
  * a small lidar fan).  A watch gives one scalar per drone and no direction; the camera gives direction at thousands of rays per
