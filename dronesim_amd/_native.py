@@ -37,6 +37,7 @@ EXPORTS = (
     "dsim_scenes_motion_set", "dsim_scenes_move", "dsim_scenes_read",
     "dsim_scenes_move_twist", "dsim_obstacle_witness_scenes_vel",
     "dsim_obstacle_witnesses", "dsim_obstacle_witnesses_scenes",
+    "dsim_velocity_filter",
 )
 
 ABI_VERSION = 11
@@ -344,6 +345,37 @@ class KnnArgs(ctypes.Structure):
     ]
 
 
+FILTER_FLOOR_BIT, FILTER_OBSTACLE_BIT, FILTER_NEIGHBOR_BIT, FILTER_ROWS = 0, 1, 9, 25      # DSIM_FILTER_*: the bits of dropped_out
+
+
+class FilterArgs(ctypes.Structure):
+    """dsim_filter_args (dsim_velocity_filter): the wished velocity, the barrier's constants and the records the rows are built from."""
+    _fields_ = [
+        ("u", ctypes.c_void_p),
+        ("offset", ctypes.c_void_p),
+        ("type_id", ctypes.c_void_p),
+        ("alpha", ctypes.c_float),
+        ("share", ctypes.c_float),
+        ("buffer_drone", ctypes.c_float),
+        ("buffer_obstacle", ctypes.c_float),
+        ("floor", ctypes.c_float),
+        ("has_floor", ctypes.c_int32),
+        ("k", ctypes.c_int32),
+        ("m", ctypes.c_int32),
+        ("nb_index", ctypes.c_void_p),
+        ("nb_dist", ctypes.c_void_p),
+        ("nb_rel_pos", ctypes.c_void_p),
+        ("nb_rel_vel", ctypes.c_void_p),
+        ("wit_clearance", ctypes.c_void_p),
+        ("wit_body", ctypes.c_void_p),
+        ("wit_rel", ctypes.c_void_p),
+        ("wit_vel", ctypes.c_void_p),
+        ("v_out", ctypes.c_void_p),
+        ("dropped_out", ctypes.c_void_p),
+        ("counters", ctypes.c_void_p),
+    ]
+
+
 class View(ctypes.Structure):
     _fields_ = [
         ("base", ctypes.c_void_p),
@@ -529,6 +561,7 @@ def load(path: str = None) -> ctypes.CDLL:
     lib.dsim_knn_workspace.restype = ctypes.c_int64
     lib.dsim_knn_workspace.argtypes = [i64, i32, i32]
     lib.dsim_knn.argtypes = [vp, vp, i64, View, ctypes.POINTER(KnnArgs)]
+    lib.dsim_velocity_filter.argtypes = [vp, vp, i64, View, ctypes.POINTER(FilterArgs)]
     lib.dsim_trajgen_workspace.restype = ctypes.c_int64
     lib.dsim_trajgen_workspace.argtypes = [i64, i32]
     lib.dsim_trajgen.argtypes = [vp, vp, ctypes.POINTER(TrajBank), ctypes.POINTER(TrajGenArgs)]

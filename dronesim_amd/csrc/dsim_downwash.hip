@@ -1744,3 +1744,5 @@ int dsim_sphere_grid_build(dsim_ctx* ctx, hipStream_t st_, int64_t n, const dsim
 #include "dsim_clearance_sweep.hip"
 // the nearest-neighbour observation (dsim_knn): part of this translation unit, it shares DwK, grid_build and the adjacency's sorted entry
 #include "dsim_knn.hip"
+// the velocity safety filter (dsim_velocity_filter): likewise part of this translation unit, it reads the state block and the type table as dsim_knn does
+#include "dsim_avoid.hip"

@@ -81,6 +81,29 @@ class VelocityAviary(_AdaptorAviary):
     def __init__(self, *a, **k):
         super().__init__(*a, **k)
         self.SPEED_LIMIT = [t.max_speed_kmh * (1000 / 3600) for t in (self.drones or self.types)]
+        self._vel_action = self._vel_limit = None      # step_velocity's action buffer and per-drone speed limits, made on first use
+
+    def step_velocity(self, u, filter: bool = True):
+        """``step`` on a wished velocity ``u`` [3, N] (world axes, m/s, the caller's numbering): with ``filter`` it first goes
+        through filter_velocity() (an env made with velocity_filter=dict(...)), then v is encoded as the action
+        (unit(v), min(|v| / SPEED_LIMIT, 1)) into an env-owned [N, 4] buffer at a fixed address, and step() runs on that buffer.
+        The clamp at the speed limit is outside the filter's program and can undo a row."""
+        import numpy as np
+        n, dev = self.NUM_DRONES, self.ctx.device
+        if self._vel_action is None:
+            lim = np.array([t.max_speed_kmh * (1000 / 3600) for t in self.types])[np.asarray(self.type_ids_caller, dtype=np.int64)]
+            self._vel_limit = torch.from_numpy(lim.astype(np.float32)).to(dev)
+            self._vel_action = torch.zeros((n, 4), dtype=torch.float32, device=dev)
+        if filter:
+            v = self.filter_velocity(u)
+        else:
+            v = torch.as_tensor(u, dtype=torch.float32, device=dev)
+            if tuple(v.shape) != (3, n):
+                raise ValueError(f"u must be [3, {n}]")
+        speed = v.norm(dim=0)
+        self._vel_action[:, :3] = (v / speed.clamp(min=1e-6)).T
+        self._vel_action[:, 3] = (speed / self._vel_limit).clamp(max=1.0)
+        return self.step(self._vel_action)
 
 
 class RPYTAviary(_AdaptorAviary):

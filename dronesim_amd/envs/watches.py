@@ -1,6 +1,7 @@
 """The services that follow every step of the fleet env on its stream: the drone-drone contact watch (``drone_watch``), the
 static-obstacle watch (``obstacle_watch``), the depth camera (``vision_attributes``), the range scanner (``range_scan``), the gate
-passage watch (``gate_watch``), the nearest-neighbour observation (``neighbor_obs``) and its line of sight (``neighbor_sight``).  Their keywords, set-up, state and public
+passage watch (``gate_watch``), the nearest-neighbour observation (``neighbor_obs``) and its line of sight (``neighbor_sight``), and
+the velocity safety filter that consumes their records on demand (``velocity_filter``).  Their keywords, set-up, state and public
 calls, the one epilogue of a launch (``_stepped``) and the four hooks a captured sequence goes through (``_capture_prepare``,
 ``_captured_step``, ``_capture_keepalive``, ``_replayed``).  A mix-in of ``CtrlAviary``: it uses the env's attributes as they are."""
 from __future__ import annotations
@@ -42,6 +43,10 @@ class StepWatches:
     _sight = None                 # ... its LineOfSight (set by _watch_setup)
     _sight_demand = None          # ... and those of the on-demand queries, by k
     last_neighbor_sight = None    # ... and what it saw behind the last step
+    _filter_opts = None           # the velocity safety filter's constants (velocity_filter=dict(...); set by _watch_options)
+    _filter = None                # ... its VelocityFilter (set by _watch_setup)
+    _filter_fresh = False         # ... whether the records behind the last launch describe the current state
+    _filter_sampled = False
 
     # ------------------------------------------------------------------ construction
     def _watch_options(self, *, num_drones, freq, aggregate_phy_steps, dist, drone_watch, drone_watch_margin, obstacle_watch,
@@ -53,7 +58,7 @@ class StepWatches:
                        gate_travel=None, neighbor_obs=None, neighbor_radius=None, neighbor_vel=None,
                        neighbourhood_radius=np.inf, obstacle_witness=None, neighbor_sight=False,
                        neighbor_sight_scene=None, obstacle_motion=None, obstacle_witness_velocity=False,
-                       obstacle_witnesses=0) -> None:
+                       obstacle_witnesses=0, velocity_filter=None) -> None:
         """The services' keywords of ``CtrlAviary.__init__``: checked and stashed (the set-up follows in _watch_setup, when the
         context and the storage order exist)."""
         # The reference's Bullet world lets the vehicles' collision shapes act on each other; here every drone is integrated
@@ -258,6 +263,30 @@ class StepWatches:
         if obstacle_witnesses and obstacle_witness is None:
             raise ValueError("obstacle_witnesses without obstacle_witness='world' or 'body'")
         self._obst_m = int(obstacle_witnesses)
+        # velocity_filter=dict(alpha=..., buffer_drone=0, buffer_obstacle=0, share=0.5, floor=None): the consumer of the records
+        # above.  filter_velocity(u) turns a wished velocity [3, N] into the closest one that meets the control-barrier rows of
+        # every drone's floor, obstacle witnesses (obstacle_witnesses=m with obstacle_witness="world"; their velocities with
+        # obstacle_witness_velocity=True) and neighbours (neighbor_obs=k with the relative velocities), in one dsim_velocity_filter
+        # on the storage-order records the env keeps behind each launch; last_filter_dropped says which rows could not be kept,
+        # filter_counts() how many drones were changed and how many lost a row; VelocityAviary.step_velocity(u) filters, encodes
+        # and steps.  It runs when asked, outside the launch: a captured sequence neither captures nor refuses it.  On a sharded
+        # fleet it works with the witnesses alone.  None by default: nothing is allocated or launched.
+        if velocity_filter is not None:
+            from ..avoid import check_options
+            if not isinstance(velocity_filter, dict) or "alpha" not in velocity_filter:
+                raise ValueError("velocity_filter takes a dict(alpha=..., buffer_drone=, buffer_obstacle=, share=, floor=)")
+            unknown = set(velocity_filter) - {"alpha", "buffer_drone", "buffer_obstacle", "share", "floor"}
+            if unknown:
+                raise ValueError(f"velocity_filter: unknown keys {sorted(unknown)}")
+            opts = check_options(**velocity_filter)
+            if obstacle_witness == "body":
+                raise ValueError("velocity_filter needs the witnesses in world axes: obstacle_witness='world', not 'body'")
+            if neighbor_obs is not None and neighbor_vel is False:
+                raise ValueError("velocity_filter needs the neighbours' relative velocities: neighbor_vel=False leaves them out")
+            if neighbor_obs is None and not obstacle_witnesses:
+                raise ValueError("velocity_filter needs a source of rows: neighbor_obs=k (with neighbor_vel) or obstacle_witnesses=m "
+                                 "with obstacle_witness='world'")
+            self._filter_opts = dict(zip(("alpha", "buffer_drone", "buffer_obstacle", "share", "floor"), opts))
         # BaseAviary(vision_attributes=True) keeps self.rgb / self.dep / self.seg per drone at IMG_RES = [64, 48] and refreshes them
         # from _getDroneImages whenever step_counter % IMG_CAPTURE_FREQ == 0 (BaseAviary.py:236-261, 453-502, 794-853).  Here:
         # env.dep / env.seg ([n, H, W] device tensors; no rgb) of the static world `vision_scene` (default: the obstacle_watch
@@ -350,6 +379,20 @@ class StepWatches:
         self._scan_setup(offsets)
         self._gate_setup(offsets)
         self._sight_setup(offsets)
+        self._filter_setup(offsets)
+
+    def _filter_setup(self, offsets) -> None:
+        """velocity_filter=dict(...): the VelocityFilter and the tensors every call reads and writes (storage order, fixed addresses)."""
+        if self._filter_opts is None:
+            return
+        from ..avoid import Filtered, VelocityFilter
+        dev, n_pad = self.ctx.device, self.state.n_pad
+        self._filter = VelocityFilter(self.ctx, self.state, offsets=offsets, type_id=self._type_id, **self._filter_opts)
+        self._filter_u = torch.zeros((3, n_pad), dtype=torch.float32, device=dev)
+        self._filter_out = Filtered(torch.zeros((3, n_pad), dtype=torch.float32, device=dev),
+                                    torch.zeros((n_pad,), dtype=torch.int32, device=dev))
+        self._filter_wits = None      # the on-demand witnesses of a call before the first step
+        self._filter_fresh = self._filter_sampled = False
 
     def _obstacle_setup(self, offsets) -> None:
         """obstacle_watch: the device set for reach = R_max + margin, the offsets in storage order and the tensors every
@@ -521,6 +564,7 @@ class StepWatches:
 
     def _watch_placed(self) -> None:
         """_housekeeping placed every drone: the swept watch's chords start there (the first step is swept from the start)."""
+        self._filter_fresh = False         # (the records behind the last launch describe a state that is gone)
         if self._obst is not None and self._obst_sweep:
             from .. import obstacles as obs
             obs.prime(self.ctx, self.state, self._obst, self._obst_prev)
@@ -584,6 +628,7 @@ class StepWatches:
             self._scan_now()
         if self._gate is not None:
             self._watch_gates()
+        self._filter_fresh = True
 
     def _scene_dt(self) -> float:
         """One Env.step in seconds: the unit of the scene clock."""
@@ -1061,6 +1106,56 @@ class StepWatches:
                               torch.zeros((n_pad,), dtype=torch.int32, device=dev))
         self._obst_query(margin, w.clearance, w.body, self._obst_on_demand, w.rel, frame, w.vel, m, w.count)
         return self._wits_to_caller(w)
+
+    # ---- the velocity safety filter
+    def filter_velocity(self, u):
+        """[3, N] float32 in the caller's numbering: the wished velocity ``u`` [3, N] (world axes, m/s) changed as little as the
+        control-barrier rows of every drone allow (dsim_velocity_filter; the rows and the drop rule are in
+        include/dronesim_amd.h), on the records the env keeps behind the last launch — last_neighbors and
+        last_obstacle_witnesses as the queries wrote them, in storage order.  Before the first step (and after a reset) the
+        records are asked for on demand, which leaves last_* alone.  The answer lives in the env's own tensor: the next call
+        writes it again.  There is no speed cap: step_velocity clamps the speed fraction at 1, which can undo a row."""
+        if self._filter is None:
+            raise ValueError("filter_velocity() needs an env made with velocity_filter=dict(alpha=...)")
+        n = self.NUM_DRONES
+        u = torch.as_tensor(u, dtype=torch.float32, device=self.ctx.device)
+        if tuple(u.shape) != (3, n):
+            raise ValueError(f"u must be [3, {n}]")
+        self._filter_u[:, :n].copy_(self.order.to_storage(u, 1) if self.order is not None else u)
+        nb = wit = None
+        if self._knn_k:
+            nb = self._knn_out if self._filter_fresh else self._neighbor_raw(self._knn_k, self._knn_radius, True, None)
+        if self._obst_m:
+            wit = self._obst_wits
+            if not self._filter_fresh:
+                from ..obstacles import ObstacleWitnesses
+                if self._filter_wits is None:
+                    dev, n_pad, m = self.ctx.device, self.state.n_pad, self._obst_m
+                    f32 = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)
+                    i32 = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=dev)
+                    self._filter_wits = ObstacleWitnesses(f32(m, n_pad), i32(m, n_pad), f32(m, 3, n_pad),
+                                                          f32(m, 3, n_pad) if self._obst_vel is not None else None, i32(n_pad))
+                wit = self._filter_wits
+                self._obst_query(self._obst_margin, wit.clearance, wit.body, self._obst_on_demand, wit.rel, "world", wit.vel,
+                                 self._obst_m, wit.count)
+        out = self._filter.apply(self._filter_u, nb, wit, out=self._filter_out)
+        self._filter_sampled = True
+        return self.order.to_caller(out.vel, 1) if self.order is not None else out.vel
+
+    @property
+    def last_filter_dropped(self):
+        """[N] int32 in the caller's numbering: the rows the last filter_velocity() could not keep, one bit per row — bit 0 the
+        floor, 1 + s obstacle slot s, 9 + t neighbour slot t; None before the first call."""
+        if self._filter is None or not self._filter_sampled:
+            return None
+        d = self._filter_out.dropped[: self.NUM_DRONES]
+        return self.order.to_caller(d, 0) if self.order is not None else d
+
+    def filter_counts(self):
+        """(drones x calls whose velocity the filter changed, drones x calls with a dropped row), cumulative (synchronises the stream)."""
+        if self._filter is None:
+            raise ValueError("filter_counts() needs an env made with velocity_filter=dict(alpha=...)")
+        return self._filter.counters()
 
     def scene_twists(self) -> np.ndarray:
         """float32 [K, G, 6]: (t', w) of the watch's placements as the device holds them now, the last launch's scene time; zeros

@@ -13,8 +13,16 @@ With --witnesses M (1..8) the env answers with the M closest gates of every dron
 env.last_obstacle_witnesses, dsim_obstacle_witnesses_scenes in the witness's place) and the repulsion is summed over the filled
 slots: a drone between two gates is pushed by both, and nothing jumps when the nearer one changes.  With --moving --lead each slot
 is led by its own gate's velocity.
+With --filter one more flight replaces the repulsion by the velocity safety filter (velocity_filter=dict(alpha=...),
+env.step_velocity: dsim_velocity_filter on the witnesses the env keeps behind each step, M = --witnesses or 3 of them, with their
+velocities when the gates swing): the goal velocity is changed only where a control-barrier row h' + alpha h >= 0 is violated, and
+then as little as the rows allow.  It prints the same two figures and env.filter_counts().  The filter certifies the velocity it
+returns, not the flight: the vehicle follows a velocity command with a lag, which --buffer has to cover, and the speed fraction is
+clamped at 1 after the filter, which can undo a row.  A drone whose goal points straight into a bar stops in front of it (the
+projection has nowhere to slide), and obstacle_contacts() counts drone x steps, so a drone that stands close counts for long: no
+figure is promised for it.
 
-    python examples/fly_velocity_avoid_fleet.py --num_drones 4096 --duration_sec 6 [--moving [--lead]] [--witnesses 3]
+    python examples/fly_velocity_avoid_fleet.py --num_drones 4096 --duration_sec 6 [--moving [--lead]] [--witnesses 3] [--filter]
 """
 import argparse
 import os
@@ -48,7 +56,7 @@ def lead_term(vel, clearance, margin):
     return weight * vel
 
 
-def fly(A, avoid: bool, lead: bool = False):
+def fly(A, avoid: bool, lead: bool = False, filtered: bool = False):
     n, AGGR, FREQ, K, G = A.num_drones, 5, 240, 64, 6
     rng = np.random.default_rng(0)
     gate = ObstacleSet.from_urdf(GATE, (0, 0, 0), (0, 0, 0))
@@ -67,13 +75,31 @@ def fly(A, avoid: bool, lead: bool = False):
     side = int(np.ceil(np.sqrt(n)))
     off = np.stack([(np.arange(n) % side) * 40.0, (np.arange(n) // side) * 40.0, np.zeros(n)], 1)      # a frame per drone
     xyz = off + np.array([0.0, 0.0, 2.0]) + rng.uniform(-0.5, 0.5, (n, 3))
+    if filtered:
+        # the filter's rows come from the witnesses record (and its velocities on moving gates); the floor is the plane z = 0
+        moving.update(velocity_filter=dict(alpha=A.alpha, buffer_obstacle=A.buffer, floor=0.0))
+        lead = A.moving
     env = VelocityAviary([A.drone], n, initial_xyzs=xyz, aggregate_phy_steps=AGGR, freq=FREQ, dict_io=False, obstacle_watch=scenes,
                          obstacle_scene_id=np.arange(n) % K, obstacle_offsets=off, obstacle_margin=A.margin,
-                         obstacle_witness="world", obstacle_witness_velocity=lead, obstacle_witnesses=A.witnesses, **moving)
+                         obstacle_witness="world", obstacle_witness_velocity=lead,
+                         obstacle_witnesses=(A.witnesses or 3) if filtered else A.witnesses, **moving)
     dev = env.ctx.device
     radius = float(np.float32(env.ctx.types[0].collision_sphere))
     goal = torch.tensor([A.speed, 0.0, 0.0], device=dev)[:, None].expand(3, n)
     limit = float(env.SPEED_LIMIT[0])
+    if filtered:
+        steps = int(A.duration_sec * FREQ / AGGR)
+        closest = float("inf")
+        START = time.time()
+        for _ in range(steps):
+            env.step_velocity(goal)
+            closest = min(closest, float(env.last_obstacle_clearance[0].min().item()))
+        contacts, (changed, lost) = env.obstacle_contacts(), env.filter_counts()
+        print(f"with the velocity filter{', swinging gates' if A.moving else ''}: {n} drones x {steps} env steps in {time.time() - START:.2f} s wall; "
+              f"obstacle_contacts() = {contacts} drone x steps, least clearance {closest:.3f} m; filter_counts() = {changed} drone x steps "
+              f"changed, {lost} with a dropped row")
+        env.close()
+        return contacts
     if A.witnesses:
         w = env.obstacle_witnesses()                                 # [M, N], [M, 3, N]: unfilled slots push by nothing
         clr, rel = w.clearance, w.rel
@@ -122,11 +148,17 @@ def main(argv=None):
                                                         "(obstacle_witness_velocity=True), weighted by the repulsion's falloff")
     ap.add_argument("--witnesses", type=int, default=0, help="the M closest gates per drone (obstacle_witnesses=M, 1..8): the "
                                                              "repulsion is summed over the filled slots; 0: the one witness")
+    ap.add_argument("--filter", action="store_true", help="one more flight with the velocity safety filter in the repulsion's place "
+                                                          "(velocity_filter=dict(alpha=...), env.step_velocity)")
+    ap.add_argument("--alpha", type=float, default=1.5, help="with --filter: the barrier's rate [1/s]")
+    ap.add_argument("--buffer", type=float, default=0.2, help="with --filter: metres kept between the bounding sphere and the gates; it "
+                                                              "has to cover the lag with which the vehicle follows a velocity")
     A = ap.parse_args(argv)
     if A.lead and not A.moving:
         ap.error("--lead needs --moving: a static world's points stand still")
     out = fly(A, False), fly(A, True)
-    return out + (fly(A, True, True),) if A.lead else out
+    out = out + (fly(A, True, True),) if A.lead else out
+    return out + (fly(A, False, filtered=True),) if A.filter else out
 
 
 if __name__ == "__main__":

@@ -58,7 +58,8 @@ extern "C" {
                               of sight, dsim_line_of_sight, dsim_sight_args, DSIM_SIGHT_GROUND; moving scenes,
                               dsim_scenes_motion_set, dsim_scenes_move, dsim_scenes_read, dsim_scene_motion; the velocity of the
                               witness on moving scenes, dsim_scenes_move_twist, dsim_obstacle_witness_scenes_vel; obstacle witnesses,
-                              dsim_obstacle_witnesses, dsim_obstacle_witnesses_scenes, dsim_witnesses_args, DSIM_WITNESSES_MAX */
+                              dsim_obstacle_witnesses, dsim_obstacle_witnesses_scenes, dsim_witnesses_args, DSIM_WITNESSES_MAX; the
+                              velocity safety filter, dsim_velocity_filter, dsim_filter_args, DSIM_FILTER_* */
 #define DSIM_MAX_ACT 6     /* actuators per vehicle (quad 4, morphing hexa 6) */
 #define DSIM_MAX_TYPES 8
 
@@ -1249,6 +1250,61 @@ int dsim_obstacle_witnesses(dsim_ctx* ctx, void* stream, int64_t n, dsim_view st
                             const dsim_witnesses_args* args);
 int dsim_obstacle_witnesses_scenes(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, const dsim_scenes* scenes,
                                    const int32_t* scene_id, const dsim_witnesses_args* args);
+
+/* Velocity safety filter: the consumer of dsim_knn's and dsim_obstacle_witnesses' records.  Per drone i < n of `state` the input is
+ * a wished velocity u_i (world axes, m/s) and the output
+ *     v_i = argmin |v - u_i|^2   subject to   a_j . v >= b_j   for every row j the drone keeps,
+ * the control-barrier half-spaces h' + alpha h >= 0 of at most 25 rows, built from the records in this priority order, which is
+ * also the bit order of dropped_out:
+ *     bit 0          the floor (has_floor): a = (0, 0, 1), b = -alpha (p_z - offset_z - floor - R_i)
+ *     bit 1 + s      obstacle slot s < m <= 8 with wit_body[s][i] >= 0: a = -wit_rel[s][:][i] / (wit_clearance[s][i] + R_i),
+ *                    b = a . wit_vel[s][:][i] - alpha (wit_clearance[s][i] - buffer_obstacle)      (wit_vel NULL: a static world)
+ *     bit 9 + t      neighbour slot t < k <= 16 with 0 <= nb_index[t][i] < n: a = -nb_rel_pos[t][:][i] / nb_dist[t][i],
+ *                    h = nb_dist[t][i] - (R_i + R_j) - buffer_drone with j = nb_index[t][i],
+ *                    b = a . v_i + share (a . nb_rel_vel[t][:][i] - alpha h), v_i the drone's velocity in the state block
+ * R is dsim_type_params.collision_sphere of the drone's type (type_id, required with more than one type; R_j through type_id[j]).  The
+ * neighbour row is reciprocal: the pair's relative normal velocity has to change by c = a . rel_vel - alpha h, drone i takes
+ * `share` of it, and two drones that see each other and both apply the filter with share = 1/2 meet h' + alpha h >= 0 between
+ * them.  The floor and the obstacles give way to nobody: their rows take the whole change.  The records are slot-major as
+ * dsim_knn and dsim_obstacle_witnesses (world axes, not DSIM_WITNESS_BODY_FRAME) write them, in storage order.
+ * A slot is no row when its index or body is unused, when an entry of it is not finite, or when nb_dist or wit_clearance + R_i is
+ * at or below 1e-6 m.  A drone whose u, position, velocity or offset is not finite has no rows.
+ * Rows that cannot all be met: the rows are taken in the order above; a row that is infeasible together with the rows already kept
+ * is skipped and its bit set in dropped_out[i]; v is the exact projection of u onto the rows kept.  Deterministic; what cannot
+ * yield comes first.  A drone with no rows, and a drone whose u meets every row, gets v == u bit for bit.  There is no speed
+ * cap in the program: whoever turns v into a command clamps it, and that clamp can undo a row.
+ * counters (nullable, device): [0] += drones with v != u, [1] += drones with a dropped row; at most one atomic per wave and counter.
+ * Stream-ordered, allocates nothing, never synchronises (may be captured); one drone per lane, every store coalesced; lanes
+ * i >= n are not written.  DSIM_E_ARG, nothing enqueued: a null ctx, args, u, v_out or dropped_out; n <= 0 or > n_pad; k outside
+ * 0 .. 16 or m outside 0 .. DSIM_WITNESSES_MAX; k == 0 and m == 0 without the floor; a null nb_* with k > 0; a null wit_clearance,
+ * wit_body or wit_rel with m > 0; alpha not finite or <= 0; share outside (0, 1]; a buffer that is negative or not finite; a floor
+ * that is not finite; more than one type without type_id.  DSIM_E_LAYOUT: a view of fewer than 10 fields. */
+enum { DSIM_FILTER_FLOOR_BIT = 0, DSIM_FILTER_OBSTACLE_BIT = 1, DSIM_FILTER_NEIGHBOR_BIT = 9, DSIM_FILTER_ROWS = 25 };
+typedef struct dsim_filter_args {
+  const float*   u;               /* SoA [3][n_pad] wished velocity; required                                  */
+  const float*   offset;          /* SoA [3][n_pad] or NULL, as dsim_obstacle_clearance (the floor reads z)    */
+  const uint8_t* type_id;         /* [n_pad]; required with more than one type                                 */
+  float          alpha;           /* > 0 [1/s]: the barrier's rate                                             */
+  float          share;           /* (0, 1]: the part of a pair's change this drone takes                      */
+  float          buffer_drone;    /* >= 0 [m], kept between two bounding spheres                               */
+  float          buffer_obstacle; /* >= 0 [m], kept between a bounding sphere and the world                    */
+  float          floor;           /* [m] height of the floor in the task frame, with has_floor                 */
+  int32_t        has_floor;       /* 0: no floor row                                                           */
+  int32_t        k;               /* 0 .. 16 neighbour slots                                                   */
+  int32_t        m;               /* 0 .. DSIM_WITNESSES_MAX obstacle slots                                    */
+  const int32_t* nb_index;        /* [k][n_pad]     dsim_knn_args.index_out                                    */
+  const float*   nb_dist;         /* [k][n_pad]     ... dist_out                                               */
+  const float*   nb_rel_pos;      /* [k][3][n_pad]  ... rel_pos_out                                            */
+  const float*   nb_rel_vel;      /* [k][3][n_pad]  ... rel_vel_out                                            */
+  const float*   wit_clearance;   /* [m][n_pad]     dsim_witnesses_args.clearance_out                          */
+  const int32_t* wit_body;        /* [m][n_pad]     ... body_out                                               */
+  const float*   wit_rel;         /* [m][3][n_pad]  ... rel_out, world axes                                    */
+  const float*   wit_vel;         /* [m][3][n_pad]  ... vel_out, nullable                                      */
+  float*         v_out;           /* SoA [3][n_pad]; required (may be u: a lane reads its u before it writes)  */
+  int32_t*       dropped_out;     /* [n_pad]; required                                                         */
+  uint64_t*      counters;        /* device [2], nullable: += drones changed, += drones with a dropped row     */
+} dsim_filter_args;
+int dsim_velocity_filter(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, const dsim_filter_args* args);
 
 /* Range scanner: a fan of range beams per drone, for EVERY drone — the sensor real vehicles carry (a ToF ring, a downward altimeter,
  * a small lidar fan).  A watch gives one scalar per drone and no direction; the camera gives direction at thousands of rays per
