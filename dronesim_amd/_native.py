@@ -38,6 +38,7 @@ EXPORTS = (
     "dsim_scenes_move_twist", "dsim_obstacle_witness_scenes_vel",
     "dsim_obstacle_witnesses", "dsim_obstacle_witnesses_scenes",
     "dsim_velocity_filter",
+    "dsim_line_of_sight_drones",
 )
 
 ABI_VERSION = 11
@@ -557,6 +558,7 @@ def load(path: str = None) -> ctypes.CDLL:
     lib.dsim_obstacle_witnesses_scenes.argtypes = [vp, vp, i64, View, vp, vp, ctypes.POINTER(WitnessesArgs)]
     lib.dsim_range_scan.argtypes = [vp, vp, i64, View, vp, ctypes.POINTER(ScanArgs)]
     lib.dsim_line_of_sight.argtypes = [vp, vp, i64, View, vp, ctypes.POINTER(SightArgs)]
+    lib.dsim_line_of_sight_drones.argtypes = [vp, vp, i64, View, vp, ctypes.POINTER(SightArgs), vp, ctypes.POINTER(CameraDrones)]
     lib.dsim_gate_passage.argtypes = [vp, vp, i64, View, vp, vp, ctypes.POINTER(GateArgs)]
     lib.dsim_knn_workspace.restype = ctypes.c_int64
     lib.dsim_knn_workspace.argtypes = [i64, i32, i32]

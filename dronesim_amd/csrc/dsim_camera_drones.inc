@@ -7,7 +7,11 @@
 // to is the grid's grown by one ring of (empty) cells: a sphere of a border cell reaches outside the grid's box.  Then the outside
 // list.  The includer defines CD_GATE (the lanes that cast); `a.far`, `a.dr` (CamDr), `i` (the lane's drone in storage order: it is
 // never hit), `wx` .. `wz`, `dx` .. `dz`, `near`, `best` and `body` are the kernel's (and `n_tests` in the counting build).  A block
-// of its own, as the triangle walk is.
+// of its own, as the triangle walk is.  The sphere test is CD_SPHERE(p, idx, k): cam_sphere on the walk's own names unless the
+// includer defines another (line of sight: a solid ball and the slot's target left out, dsim_sight.hip).
+#ifndef CD_SPHERE
+#define CD_SPHERE(p, idx, k) cam_sphere(p, idx, k, own, wx, wy, wz, dx, dy, dz, inv_a, near, tmax, best, body)
+#endif
 {
   const SphereGrid& g = a.dr.g;
   const float tmax = fminf(a.far, a.dr.range);
@@ -41,7 +45,7 @@
         for (int yy = max(by0, 0); yy <= yhi; ++yy) {                      // a row of the block is one run of sorted[]
           const int end = g.cell_start[yy * g.nx + xhi + 1];
           for (int k = g.cell_start[yy * g.nx + xlo]; k < end; ++k) {
-            cam_sphere(g.sorted[k], g.sidx, k, own, wx, wy, wz, dx, dy, dz, inv_a, near, tmax, best, body);
+            CD_SPHERE(g.sorted[k], g.sidx, k);
 #ifdef DSIM_CAM_COUNT
             ++n_tests;
 #endif
@@ -61,7 +65,8 @@
   if (CD_GATE) {                                             // drones outside the grid's box: every ray, the list is short
     const int n_out = *g.outside_n;
     for (int k = 0; k < n_out; ++k)
-      cam_sphere(g.outside[k], g.outside_idx, k, own, wx, wy, wz, dx, dy, dz, inv_a, near, tmax, best, body);
+      CD_SPHERE(g.outside[k], g.outside_idx, k);
   }
 }
 #undef CD_GATE
+#undef CD_SPHERE

@@ -42,6 +42,8 @@ class StepWatches:
     _sight_on = False             # line of sight behind every step's neighbour query (neighbor_sight=True; set by _watch_options)
     _sight = None                 # ... its LineOfSight (set by _watch_setup)
     _sight_demand = None          # ... and those of the on-demand queries, by k
+    _sight_drones = False         # ... with the other drones hiding too (neighbor_sight_drones=True)
+    _sight_box = None
     last_neighbor_sight = None    # ... and what it saw behind the last step
     _filter_opts = None           # the velocity safety filter's constants (velocity_filter=dict(...); set by _watch_options)
     _filter = None                # ... its VelocityFilter (set by _watch_setup)
@@ -58,7 +60,8 @@ class StepWatches:
                        gate_travel=None, neighbor_obs=None, neighbor_radius=None, neighbor_vel=None,
                        neighbourhood_radius=np.inf, obstacle_witness=None, neighbor_sight=False,
                        neighbor_sight_scene=None, obstacle_motion=None, obstacle_witness_velocity=False,
-                       obstacle_witnesses=0, velocity_filter=None) -> None:
+                       obstacle_witnesses=0, velocity_filter=None, neighbor_sight_drones=False,
+                       neighbor_sight_drone_box=None) -> None:
         """The services' keywords of ``CtrlAviary.__init__``: checked and stashed (the set-up follows in _watch_setup, when the
         context and the storage order exist)."""
         # The reference's Bullet world lets the vehicles' collision shapes act on each other; here every drone is integrated
@@ -122,14 +125,26 @@ class StepWatches:
         # caller's numbering on the drone axis, None before the first step; unused slots read 0 / -1 / +inf.  neighbor_sight()
         # asks on demand.  The world lies in the frame of obstacle_offsets, and the segment of drone i in ITS task frame, from
         # p_i - offset_i to p_j - offset_i: two drones of different replicas (different offsets) may disagree on whether they see
-        # each other.  The other drones hide nobody.  A sharded fleet and graph capture are refused by neighbor_obs itself.  Off
-        # by default: nothing is allocated or launched.
+        # each other.  The other drones hide nobody unless neighbor_sight_drones=True: then the query is
+        # dsim_line_of_sight_drones, every other drone hides too as its bounding sphere about its stored position (never drone i
+        # itself, never the slot's own neighbour; blocker names drone j of the caller's numbering as -3 - j,
+        # LineOfSight.seg_drone), the fleet is binned per query on a grid over its bounding box or neighbor_sight_drone_box =
+        # (xmin, ymin, xmax, ymax), and a world becomes optional (open air).  A sharded fleet and graph capture are refused by
+        # neighbor_obs itself.  Off by default: nothing is allocated or launched.
         if neighbor_sight and neighbor_obs is None:
             raise ValueError("neighbor_sight=True without neighbor_obs=k")
         if neighbor_sight_scene is not None and not neighbor_sight:
             raise ValueError("neighbor_sight_scene without neighbor_sight=True")
-        if neighbor_sight and neighbor_sight_scene is None and obstacle_watch is None:
-            raise ValueError("neighbor_sight=True needs a world to look at: neighbor_sight_scene=ObstacleSet (or obstacle_watch)")
+        if (neighbor_sight_drones or neighbor_sight_drone_box is not None) and not neighbor_sight:
+            raise ValueError("neighbor_sight_drones / neighbor_sight_drone_box without neighbor_sight=True")
+        if neighbor_sight_drone_box is not None and not neighbor_sight_drones:
+            raise ValueError("neighbor_sight_drone_box without neighbor_sight_drones=True")
+        if neighbor_sight and neighbor_sight_scene is None and obstacle_watch is None and not neighbor_sight_drones:
+            raise ValueError("neighbor_sight=True needs a world to look at: neighbor_sight_scene=ObstacleSet (or obstacle_watch), "
+                             "or neighbor_sight_drones=True")
+        from ..drone_targets import check_drone_args
+        self._sight_drones = bool(neighbor_sight_drones)
+        self._sight_box = check_drone_args(self._sight_drones, None, neighbor_sight_drone_box)
         self._sight_on, self._sight_scene = bool(neighbor_sight), neighbor_sight_scene
         self.last_neighbor_sight = None
         # The reference's Bullet world also holds static bodies (p.loadURDF of a gate); here they act on nothing.
@@ -498,11 +513,21 @@ class StepWatches:
     def _sight_make(self, world, k: int):
         from ..obstacles import DeviceScenes, ObstacleScenes
         from ..sight import LineOfSight
+        # (one DroneTargets — one grid, one workspace, one outside count — serves the per-launch object and the on-demand ones)
         return LineOfSight(self.ctx, self.state, world, k, offsets=self._sight_offsets,
-                           scene_id=self._scene_ids if isinstance(world, (ObstacleScenes, DeviceScenes)) else None)
+                           scene_id=self._scene_ids if isinstance(world, (ObstacleScenes, DeviceScenes)) else None,
+                           drones=self._sight_drones, drone_box=self._sight_box, type_id=self._type_id if self._sight_drones else None,
+                           targets=self._sight._targets if self._sight is not None else None)
+
+    def _sight_query(self, sight, rel, index):
+        """One query of ``sight`` on a record in storage order, on the env's stream."""
+        if sight.drones and self._downwash is not None:
+            self._downwash.invalidate_prebin()            # the drones' binning drops the ctx's grid bookkeeping
+        return sight.query(rel, index)
 
     def _sight_caller(self, s):
-        """A Sight in storage order in the caller's numbering on the drone axis."""
+        """A Sight in storage order in the caller's numbering on the drone axis (the drone axis only: a drone that blocks is
+        already named in the caller's numbering, through the label table of the query)."""
         if self.order is None:
             return s
         from ..sight import Sight
@@ -613,7 +638,7 @@ class StepWatches:
             self.last_neighbors = self._neighbor_query(self._knn_k, self._knn_radius, self._knn_vel, self._knn_out)
             if self._sight is not None:
                 # (on the record the query just wrote, in storage order: the vectors last_neighbors reports, bit for bit)
-                self.last_neighbor_sight = self._sight_caller(self._sight.query(self._knn_out.rel_pos, self._knn_out.index))
+                self.last_neighbor_sight = self._sight_caller(self._sight_query(self._sight, self._knn_out.rel_pos, self._knn_out.index))
         if self._obst is not None:
             self._watch_obstacles()
         if self._vision is not None:
@@ -937,7 +962,9 @@ class StepWatches:
         nb = self._neighbor_raw(k, radius, True, None)
         if k not in self._sight_demand:
             self._sight_demand[k] = self._sight_make(self._sight.set, k)
-        return self._neighbors_caller(nb), self._sight_caller(self._sight_demand[k].query_neighbors(nb))
+        if nb.rel_pos is None:
+            raise ValueError("the record has no rel_pos")
+        return self._neighbors_caller(nb), self._sight_caller(self._sight_query(self._sight_demand[k], nb.rel_pos, nb.index))
 
     def drone_contacts(self) -> int:
         """Pairs of drones x Env.steps so far whose bounding spheres (DroneType.collision_sphere) overlapped behind a step

@@ -8,7 +8,8 @@ drone's state, and nothing leaves the device: the rules are a few torch ops on [
 
 --sight stands the committed gate (tests/golden/gate_50_curved.urdf) in the flock's way and lets a drone flock only with the
 neighbours it can SEE: env.last_neighbor_sight (dsim_line_of_sight behind every step's dsim_knn) says, per slot, whether the gate's
-frame hides that neighbour, and hidden ones are dropped from the three sums.
+frame hides that neighbour, and hidden ones are dropped from the three sums.  --sight-drones lets the other drones hide
+neighbours too, as their bounding spheres (dsim_line_of_sight_drones): in open air, or together with --sight's gate.
 """
 import argparse
 import os
@@ -48,6 +49,7 @@ def main(argv=None):
     ap.add_argument("--k", type=int, default=8)
     ap.add_argument("--radius", type=float, default=3.0)
     ap.add_argument("--sight", action="store_true", help="stand the gate in the flock and drop the neighbours it hides")
+    ap.add_argument("--sight-drones", action="store_true", help="the other drones hide neighbours too (alone: open air, no gate)")
     A = ap.parse_args(argv)
     n, AGGR, FREQ = A.num_drones, 5, 240
     rng = np.random.default_rng(0)
@@ -59,13 +61,16 @@ def main(argv=None):
         from dronesim_amd.obstacles import ObstacleSet
         mid = 0.75 * (side - 1)
         kw = dict(neighbor_sight=True, neighbor_sight_scene=ObstacleSet.from_urdf(GATE, (mid + 1.0, mid + 0.3, 2.0), (0, 0, 0)))
+    if A.sight_drones:
+        kw.update(neighbor_sight=True, neighbor_sight_drones=True)
+    see = A.sight or A.sight_drones
     env = VelocityAviary([A.drone], n, initial_xyzs=xyz, initial_vels=rng.uniform(-0.5, 0.5, (n, 3)), aggregate_phy_steps=AGGR,
                          freq=FREQ, dict_io=False, neighbor_obs=A.k, neighbor_radius=A.radius, drone_watch=True, **kw)
     cruise = torch.tensor([0.6, 0.2, 0.0], device=env.ctx.device)
     limit = float(env.SPEED_LIMIT[0])
     steps = int(A.duration_sec * FREQ / AGGR)
-    nb, sight = env.neighbor_sight() if A.sight else (env.nearest_neighbors(), None)
-    hidden = 0
+    nb, sight = env.neighbor_sight() if see else (env.nearest_neighbors(), None)
+    hidden = by_drones = 0
     START = time.time()
     for _ in range(steps):
         wish = reynolds(nb, cruise, sight=sight)
@@ -73,17 +78,18 @@ def main(argv=None):
         action = torch.cat([wish / speed.clamp(min=1e-6), (speed / limit).clamp(max=1.0)[None, :]], 0).T.contiguous()
         env.step(action)
         nb = env.last_neighbors
-        if A.sight:
+        if see:
             sight = env.last_neighbor_sight
             hidden += int(((sight.visible == 0) & (nb.index >= 0)).sum().item())
+            by_drones += int((sight.blocker <= -3).sum().item())
     nearest = nb.dist[0][torch.isfinite(nb.dist[0])]
     q = torch.quantile(nearest, torch.tensor([0.0, 0.05, 0.5, 0.95], device=nearest.device)).cpu().numpy()
     contacts = env.drone_contacts()
     print(f"{n} drones x {steps} env steps in {time.time() - START:.2f} s wall; nearest neighbour at min / 5 % / median / 95 % = "
           f"{q.round(3)} m, {int(nb.count.float().mean().item() * 10) / 10} drones within {A.radius} m on average; "
           f"drone_contacts() = {contacts}")
-    if A.sight:
-        print(f"neighbour slots hidden by the gate, summed over the steps: {hidden}")
+    if see:
+        print(f"neighbour slots hidden, summed over the steps: {hidden}" + (f", {by_drones} of them by another drone" if A.sight_drones else " (by the gate)"))
     env.close()
     return q, contacts
 

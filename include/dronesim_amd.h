@@ -59,7 +59,8 @@ extern "C" {
                               dsim_scenes_motion_set, dsim_scenes_move, dsim_scenes_read, dsim_scene_motion; the velocity of the
                               witness on moving scenes, dsim_scenes_move_twist, dsim_obstacle_witness_scenes_vel; obstacle witnesses,
                               dsim_obstacle_witnesses, dsim_obstacle_witnesses_scenes, dsim_witnesses_args, DSIM_WITNESSES_MAX; the
-                              velocity safety filter, dsim_velocity_filter, dsim_filter_args, DSIM_FILTER_* */
+                              velocity safety filter, dsim_velocity_filter, dsim_filter_args, DSIM_FILTER_*; line of sight
+                              among the drones, dsim_line_of_sight_drones */
 #define DSIM_MAX_ACT 6     /* actuators per vehicle (quad 4, morphing hexa 6) */
 #define DSIM_MAX_TYPES 8
 
@@ -1364,7 +1365,8 @@ int dsim_range_scan(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, con
  * the segment taken into the placement's frame (subtract first, then rotate; an id outside [0, K): no obstacles); with
  * DSIM_SIGHT_GROUND the plane z = 0 of the task frame, analytic.  d is `rel` as given (world axes, the layout of dsim_knn's
  * rel_pos_out) and is NOT recomputed from positions: a knn record is tested on exactly the vectors it reports, a gathered world of
- * a sharded rank works at this level, and so does any target point (a goal: rel = goal - p).  The other drones hide nobody.
+ * a sharded rank works at this level, and so does any target point (a goal: rel = goal - p).  For dsim_line_of_sight the other
+ * drones hide nobody; dsim_line_of_sight_drones (below) lets them.
  *
  * A slot is CAST when its index is not negative (or `index` is NULL), e is finite, and d is finite, not zero, and of a squared
  * length that is finite in float32 (shorter than about 1.8e19).  The hit test is the triangle walk's of the camera and the scanner
@@ -1400,6 +1402,35 @@ typedef struct dsim_sight_args {
 } dsim_sight_args;
 int dsim_line_of_sight(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, const dsim_obstacles* set,
                        const dsim_sight_args* args);
+
+/* Line of sight among the drones: dsim_line_of_sight with the other drones hiding too, as their bounding spheres.  The segment,
+ * the cast rule, the world of triangles and the plane, and the outputs are those above; the segment is ALSO tested against the
+ * sphere of radius R_m = collision_sphere of its type (or radius_all[m]) about the STORED position of every other drone m of the
+ * world with R_m > 0.
+ *   Frame.  The spheres stand at the stored world positions and are met from the stored p_i with the same d = rel[t][:][i]; the
+ *     triangles and the plane keep e = p_i - offset_i: the scanner's split.  s is shared, so the nearest of the triangle, plane
+ *     and sphere hits wins.
+ *   Who never blocks.  Drone i itself, and, when `index` is given, the slot's own target index[t][i]: a WORLD index, as dsim_knn
+ *     writes it, compared before any label is applied (the segment ends at the target's centre: without this every neighbour would
+ *     hide itself).  With index == NULL (goal segments) only i is left out.
+ *   Solid balls, both ends closed, as for triangles.  m blocks when its closed ball meets the closed segment: rho^2 <= R^2,
+ *     t0 <= min(1, range) and t1 >= 0, with t0, t1 = tc -+ h in the cancellation-free form of the camera's sphere test;
+ *     frac = max(t0, 0).  The camera and the scanner hit a SURFACE (the first root, else the second); the solid ball differs only
+ *     for a segment that starts inside another drone's ball: such a drone, already in contact, has all its slots blocked at
+ *     frac = 0 (all but a slot whose own target that very drone is).
+ *   blocker_out names the drone as DSIM_SEG_DRONE(k) = -3 - k, k the world index or label[world index], as the camera and the
+ *     scanner apply the label table.
+ *   drones->range bounds s, not metres: a sphere hit needs s <= min(1, range) (1 or more: the whole segment).
+ *   A drone whose position is not finite is binned nowhere and hides nobody; a type of radius 0 is no target and still looks.
+ * Worlds combine freely: set or scenes, plane, drones; drones alone (no set, no scenes, no ground flag) is a valid world.
+ * type_id [n_pad] is what the drones' grid is binned with: required with more than one type.  The fleet is binned per call, on
+ * the stream, through drones->grid (dsim_depth_image_drones has the rules: workspace, outside_out, the box that need not hold every
+ * drone), and the call drops the context's record of the downwash grid, as that call does.  Stream-ordered, allocates nothing,
+ * never synchronises; may be captured.  DSIM_E_ARG, nothing enqueued: what dsim_line_of_sight refuses ("no world at all"
+ * excepted), a null drones, several types and no type_id, everything dsim_depth_image_drones refuses about `drones` (a halo plan:
+ * DSIM_E_UNSUPPORTED).  dsim_sight_args and dsim_line_of_sight are unchanged. */
+int dsim_line_of_sight_drones(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, const dsim_obstacles* set,
+                              const dsim_sight_args* args, const uint8_t* type_id, const dsim_camera_drones* drones);
 
 /* Gate passage watch: which drones flew THROUGH the gates of their scene, in order.  The clearance watches say how close a
  * vehicle came to a gate's frame; a drone that flies round its gate, goes through backwards or never reaches it has a perfect

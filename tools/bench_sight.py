@@ -7,9 +7,12 @@ The fleet is N / 16 replicas of one task by offsets: 16 drones about the gate at
 it, so that neighbours are hidden —, stored at that place plus the replica's offset, 12 m apart on a square lattice: every drone
 has its replica's 15 others within reach and nobody else.  World "set": the gate scene (tests/camera_ref.scene).  World "scenes":
 per-drone scenes, 64 scenes of 3 placements of the gate prototype (tests/scenes_ref.random_placements), replica r in scene r mod 64.
-One JSON line per world and fleet size.
+One JSON line per world and fleet size.  --drones: beside them the same query with the other drones hiding too
+(dsim_line_of_sight_drones, on the same record and the same device set), the share of it that the per-call binning of the fleet
+takes (the same call with every index at -1: it bins and casts nothing) and, for scale, the scanner with drones=True.
 
     python tools/bench_sight.py [--sizes 65536 1048576] [--k 8] [--radius 3.0] [--subdiv 0] [--iters 200] [--warmup 50] [--lib PATH]
+                                [--drones]
 """
 import argparse
 import json
@@ -48,6 +51,7 @@ def main():
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--drones", action="store_true", help="also time the query with the other drones hiding (and its binning)")
     ap.add_argument("--lib", default=None, help="another build of the library (an A/B against the one in the tree)")
     a = ap.parse_args()
     from dronesim_amd import _native as nat
@@ -93,7 +97,25 @@ def main():
             t_knn, all_knn = timed(torch, knn, a)
             s = los.query(out.rel_pos, out.index)
             used = out.index[:, :n] >= 0
-            print(json.dumps({"world": world, "drones": n, "k": a.k, "radius": a.radius, "n_tri": int(n_tri),
+            extra = {}
+            if a.drones:
+                lod = LineOfSight(env.ctx, env.state, los.set, a.k, offsets=off, scene_id=sid, drones=True)
+                scan_d = RangeScanner(env.ctx, env.state, los.set, RangeScanner.fan(a.k), t_min=0.0, t_max=a.radius, ground=False,
+                                      offsets=off, scene_id=sid, drones=True)
+                nobody = torch.full_like(out.index, -1)
+                t_d, all_d = timed(torch, lambda: lod.query(out.rel_pos, out.index), a)
+                t_bin, all_bin = timed(torch, lambda: lod.query(out.rel_pos, nobody), a)
+                t_sd, all_sd = timed(torch, scan_d.scan, a)
+                sd_ = lod.query(out.rel_pos, out.index)
+                extra = {"us_per_sight_drones_median": round(t_d, 2), "us_per_sight_drones_all": all_d,
+                         "us_per_binning_median": round(t_bin, 2), "us_per_binning_all": all_bin,
+                         "binning_share_of_sight_drones": round(t_bin / t_d, 4), "sight_drones_over_sight": round(t_d / t_sight, 4),
+                         "us_per_scan_drones_median": round(t_sd, 2), "us_per_scan_drones_all": all_sd,
+                         "blocked_by_drones_share_of_used": round(float(((sd_.blocker <= -3) & used).sum().item()) / max(float(used.sum().item()), 1.0), 4),
+                         "drones_outside": lod.drones_outside()}
+                scan_d.close()
+                lod.close()
+            print(json.dumps({**extra, "world": world, "drones": n, "k": a.k, "radius": a.radius, "n_tri": int(n_tri),
                               "us_per_sight_median": round(t_sight, 2), "us_per_sight_all": all_sight,
                               "us_per_scan_median": round(t_scan, 2), "us_per_scan_all": all_scan,
                               "us_per_knn_median": round(t_knn, 2), "us_per_knn_all": all_knn,
