@@ -39,6 +39,7 @@ EXPORTS = (
     "dsim_obstacle_witnesses", "dsim_obstacle_witnesses_scenes",
     "dsim_velocity_filter",
     "dsim_line_of_sight_drones",
+    "dsim_corridor_clearance",
 )
 
 ABI_VERSION = 11
@@ -202,6 +203,30 @@ class ObstacleGrid(ctypes.Structure):
 
 
 SWEEP_KEEP_PREV, SWEEP_PRIME = 1, 2     # dsim_sweep_args.flags
+
+
+CORRIDOR_GROUND = 1              # dsim_corridor_args.flags
+CORRIDOR_MAX_K = 32              # dsim_corridor_args.k: 1 .. 32
+CORRIDOR_MAX_PIECES = 32         # a slot that needs more pieces is unserved
+
+
+class CorridorArgs(ctypes.Structure):
+    """dsim_corridor_args (dsim_corridor_clearance)."""
+    _fields_ = [
+        ("rel", ctypes.c_void_p),
+        ("index", ctypes.c_void_p),
+        ("k", ctypes.c_int32),
+        ("flags", ctypes.c_uint32),
+        ("offset", ctypes.c_void_p),
+        ("type_id", ctypes.c_void_p),
+        ("scenes", ctypes.c_void_p),
+        ("scene_id", ctypes.c_void_p),
+        ("margin", ctypes.c_float),
+        ("sag", ctypes.c_float),
+        ("clearance_out", ctypes.c_void_p),
+        ("body_out", ctypes.c_void_p),
+        ("unserved_out", ctypes.c_void_p),
+    ]
 
 
 class SweepArgs(ctypes.Structure):
@@ -559,6 +584,7 @@ def load(path: str = None) -> ctypes.CDLL:
     lib.dsim_range_scan.argtypes = [vp, vp, i64, View, vp, ctypes.POINTER(ScanArgs)]
     lib.dsim_line_of_sight.argtypes = [vp, vp, i64, View, vp, ctypes.POINTER(SightArgs)]
     lib.dsim_line_of_sight_drones.argtypes = [vp, vp, i64, View, vp, ctypes.POINTER(SightArgs), vp, ctypes.POINTER(CameraDrones)]
+    lib.dsim_corridor_clearance.argtypes = [vp, vp, i64, View, vp, ctypes.POINTER(CorridorArgs)]
     lib.dsim_gate_passage.argtypes = [vp, vp, i64, View, vp, vp, ctypes.POINTER(GateArgs)]
     lib.dsim_knn_workspace.restype = ctypes.c_int64
     lib.dsim_knn_workspace.argtypes = [i64, i32, i32]

@@ -392,6 +392,10 @@ int dsim_obstacle_clearance(dsim_ctx* ctx, void* stream, int64_t n, dsim_view st
 // moving scenes: per-placement motion that rewrites the scenes' table in stream order (every placed kernel above reads it per launch)
 #include "dsim_scene_motion.hip"
 
+// corridor clearance: k candidate segments per drone as swept spheres against the set, the scenes where they stand and the ground
+// (it shares the swept watch's segment arithmetic and pieces, the scenes' frames and line of sight's per-slot mapping)
+#include "dsim_corridor.hip"
+
 // the obstacle witness: the point watch with the vector to the closest point (both point kernels above are its kernels too; the
 // file holds the tail they call, its arguments and its entry points)
 #include "dsim_witness.hip"

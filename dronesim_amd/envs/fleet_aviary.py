@@ -169,6 +169,7 @@ class CtrlAviary(PlacedFleetArrays, FleetObservation, StepWatches):
         velocity_filter: Optional[dict] = None,
         neighbor_sight_drones: bool = False,
         neighbor_sight_drone_box=None,
+        corridor: Optional[dict] = None,
     ):
         if gui or record or obstacles:
             raise NotImplementedError("gui/record/obstacles are rendering features outside the hot path")
@@ -188,7 +189,8 @@ class CtrlAviary(PlacedFleetArrays, FleetObservation, StepWatches):
                             neighbor_sight=neighbor_sight, neighbor_sight_scene=neighbor_sight_scene,
                             obstacle_motion=obstacle_motion, obstacle_witness_velocity=obstacle_witness_velocity,
                             obstacle_witnesses=obstacle_witnesses, velocity_filter=velocity_filter,
-                            neighbor_sight_drones=neighbor_sight_drones, neighbor_sight_drone_box=neighbor_sight_drone_box)
+                            neighbor_sight_drones=neighbor_sight_drones, neighbor_sight_drone_box=neighbor_sight_drone_box,
+                            corridor=corridor)
         # the add-on terms of the PYB_* modes (dead code in the reference fork, intended formulas); Physics.DYN: the
         # reference's own explicit model, BaseAviary._dynamics (BaseAviary.py:1767-1828; DSIM_OPT_DYN)
         self._phys_options = {Physics.PYB: 0, Physics.PYB_DW: 0, Physics.PYB_GND: nat.OPT_GROUND,

@@ -49,6 +49,8 @@ class StepWatches:
     _filter = None                # ... its VelocityFilter (set by _watch_setup)
     _filter_fresh = False         # ... whether the records behind the last launch describe the current state
     _filter_sampled = False
+    _corr_opts = None             # corridor clearance's constants (corridor=dict(...); set by _watch_options)
+    _corr = None                  # ... its Corridor (set by _watch_setup)
 
     # ------------------------------------------------------------------ construction
     def _watch_options(self, *, num_drones, freq, aggregate_phy_steps, dist, drone_watch, drone_watch_margin, obstacle_watch,
@@ -61,7 +63,7 @@ class StepWatches:
                        neighbourhood_radius=np.inf, obstacle_witness=None, neighbor_sight=False,
                        neighbor_sight_scene=None, obstacle_motion=None, obstacle_witness_velocity=False,
                        obstacle_witnesses=0, velocity_filter=None, neighbor_sight_drones=False,
-                       neighbor_sight_drone_box=None) -> None:
+                       neighbor_sight_drone_box=None, corridor=None) -> None:
         """The services' keywords of ``CtrlAviary.__init__``: checked and stashed (the set-up follows in _watch_setup, when the
         context and the storage order exist)."""
         # The reference's Bullet world lets the vehicles' collision shapes act on each other; here every drone is integrated
@@ -372,6 +374,35 @@ class StepWatches:
                                  "range_ground=True or range_see_drones=True")
             self._scan_args = (beams, range_scene, float(range_min), float(range_max), bool(range_ground), bool(range_clamp),
                                bool(range_see_drones), range_drone_range)
+        # corridor=dict(k, piece, sag=0.0, margin=None, ground=False): the planner's question, on demand.  corridor_clearance(rel)
+        # gives, for k candidate segments per drone, the clearance of its bounding sphere (+ sag) swept along each
+        # (dsim_corridor_clearance) against the obstacle_watch world where it stands now — the watch's device set or scenes, its
+        # obstacle_offsets and obstacle_scene_id, so it sees obstacle_motion — and, with ground, the half-space z <= 0.  piece [m]:
+        # the length one cell lookup serves; the shared set is made with the larger of the watch's reach and
+        # corridor_reach(types, margin, sag, piece), and a segment of up to 32 pieces is served (corridor_unserved() counts the
+        # others).  margin None: obstacle_margin.  It runs when asked, outside the launch: a captured sequence neither captures nor
+        # refuses it, and it needs nothing of other ranks.  None by default: nothing is allocated or launched, and the set keeps
+        # the reach it has without it.
+        if corridor is not None:
+            if not isinstance(corridor, dict) or "k" not in corridor or "piece" not in corridor:
+                raise ValueError("corridor takes a dict(k=..., piece=..., sag=0.0, margin=None, ground=False)")
+            unknown = set(corridor) - {"k", "piece", "sag", "margin", "ground"}
+            if unknown:
+                raise ValueError(f"corridor: unknown keys {sorted(unknown)}")
+            if obstacle_watch is None:
+                raise ValueError("corridor without obstacle_watch=ObstacleSet (or ObstacleScenes)")
+            k, piece, sag = corridor["k"], corridor["piece"], corridor.get("sag", 0.0)
+            margin = corridor.get("margin")
+            if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= nat.CORRIDOR_MAX_K:
+                raise ValueError(f"corridor: k must be a whole number of slots in 1 .. {nat.CORRIDOR_MAX_K}")
+            if isinstance(piece, bool) or not np.isfinite(float(piece)) or not float(piece) >= 1e-3:
+                raise ValueError("corridor: piece must be at least a millimetre")
+            if isinstance(sag, bool) or not np.isfinite(float(sag)) or float(sag) < 0.0:
+                raise ValueError("corridor: sag must be >= 0")
+            margin = float(obstacle_margin) if margin is None else float(margin)
+            if not (np.isfinite(margin) and margin > 0.0):
+                raise ValueError("corridor: margin must be positive")
+            self._corr_opts = dict(k=int(k), piece=float(piece), sag=float(sag), margin=margin, ground=bool(corridor.get("ground", False)))
 
     def _watch_setup(self, offsets) -> None:
         """At the end of __init__: the obstacle set first, because the camera shares its device set."""
@@ -395,6 +426,20 @@ class StepWatches:
         self._gate_setup(offsets)
         self._sight_setup(offsets)
         self._filter_setup(offsets)
+        self._corridor_setup(offsets)
+
+    def _corridor_setup(self, offsets) -> None:
+        """corridor=dict(...): the Corridor on the watch's device world, and the tensors every call reads (storage order, fixed
+        addresses)."""
+        if self._corr_opts is None:
+            return
+        from ..corridor import Corridor
+        c = self._corr_opts
+        dev, n_pad, k = self.ctx.device, self.state.n_pad, c["k"]
+        self._corr = Corridor(self.ctx, self.state, self._obst, k, c["margin"], sag=c["sag"], ground=c["ground"], offsets=offsets,
+                              scene_id=self._scene_ids if self._obst_placed else None, type_id=self._type_id)
+        self._corr_rel = torch.zeros((k, 3, n_pad), dtype=torch.float32, device=dev)
+        self._corr_index = torch.full((k, n_pad), -1, dtype=torch.int32, device=dev)
 
     def _filter_setup(self, offsets) -> None:
         """velocity_filter=dict(...): the VelocityFilter and the tensors every call reads and writes (storage order, fixed addresses)."""
@@ -431,6 +476,9 @@ class StepWatches:
             self._obst_off = self._soa3(offsets)
         reach = (obs.sweep_reach(self.ctx.types, self._obst_margin, self._obst_sag, self._obst_travel) if self._obst_sweep
                  else obs.watch_reach(self.ctx.types, self._obst_margin))
+        if self._corr_opts is not None:              # (the corridor's pieces need their half cell: results of the watches do not depend on reach)
+            c = self._corr_opts
+            reach = max(reach, obs.corridor_reach(self.ctx.types, c["margin"], c["sag"], c["piece"]))
         self._obst = self._obst_set.to_device(self.ctx, reach)
         # the scene of every drone in storage order (a type-major fleet and a sharded rank's slice see their own ids)
         self._obst_ids = (obs.scene_ids_tensor(self._scene_ids, self.NUM_DRONES, n_pad, dev, self.order) if self._obst_placed
@@ -620,6 +668,8 @@ class StepWatches:
             self._sight.close()
         if self._gate is not None and not self._gate_shared:
             self._gate.close()
+        if self._corr is not None:
+            self._corr.close()
         if self._obst is not None:
             self._obst.close()
 
@@ -1183,6 +1233,42 @@ class StepWatches:
         if self._filter is None:
             raise ValueError("filter_counts() needs an env made with velocity_filter=dict(alpha=...)")
         return self._filter.counters()
+
+    # ---- corridor clearance
+    def corridor_clearance(self, rel, index=None):
+        """CorridorClearance(clearance [k, N] float32, body [k, N] int32) in the caller's numbering: for slot t of drone i the
+        clearance of its bounding sphere (+ sag) swept from p_i - offset_i along ``rel[t, :, i]`` ([k, 3, N], world axes, m)
+        against the ``obstacle_watch`` world as it stands now and, with ground, the half-space z <= 0 (dsim_corridor_clearance;
+        include/dronesim_amd.h), cut at the corridor's margin; ``body`` the body that attains it (-2 the ground, -1 none within
+        the margin).  ``index`` [k, N] ints or None: a slot whose index is negative is not evaluated.  A slot that is not
+        evaluated (also: a non-finite rel or position) or not served (longer than 32 pieces: corridor_unserved()) reads -inf / -1
+        — never "free".  The answer lives in the env's own tensors: the next call writes them again.  Not counted as an
+        Env.step, and no contact counter moves."""
+        if self._corr is None:
+            raise ValueError("corridor_clearance() needs an env made with corridor=dict(k=..., piece=...)")
+        n, k, dev = self.NUM_DRONES, self._corr.k, self.ctx.device
+        rel = torch.as_tensor(rel, dtype=torch.float32, device=dev)
+        if tuple(rel.shape) != (k, 3, n):
+            raise ValueError(f"rel must be [{k}, 3, {n}]")
+        self._corr_rel[:, :, :n].copy_(self.order.to_storage(rel, 2) if self.order is not None else rel)
+        if index is not None:
+            index = torch.as_tensor(index, device=dev)
+            if tuple(index.shape) != (k, n) or index.dtype.is_floating_point or index.dtype == torch.bool:
+                raise ValueError(f"index must be [{k}, {n}] ints")
+            index = index.clamp(min=-1, max=2 ** 31 - 1).to(torch.int32)
+            self._corr_index[:, :n].copy_(self.order.to_storage(index, 1) if self.order is not None else index)
+        out = self._corr.query(self._corr_rel, self._corr_index if index is not None else None)
+        if self.order is None:
+            return out
+        from ..corridor import CorridorClearance
+        return CorridorClearance(*(self.order.to_caller(t, 1) for t in out))
+
+    def corridor_unserved(self) -> int:
+        """Slots x corridor_clearance() calls so far whose segment needed more than 32 pieces (longer than the Corridor's
+        max_length; synchronises the stream): they read -inf."""
+        if self._corr is None:
+            raise ValueError("corridor_unserved() needs an env made with corridor=dict(k=..., piece=...)")
+        return self._corr.unserved()
 
     def scene_twists(self) -> np.ndarray:
         """float32 [K, G, 6]: (t', w) of the watch's placements as the device holds them now, the last launch's scene time; zeros

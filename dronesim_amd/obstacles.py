@@ -689,6 +689,13 @@ def sweep_reach(types, margin: float, sag: float, travel: float) -> float:
     return float(np.float32(s * (1.0 + 2.0 ** -10)))
 
 
+def corridor_reach(types, margin: float, sag: float, piece: float) -> float:
+    """The ``reach`` of a set for corridor queries (dsim_corridor_clearance, corridor.Corridor) of ``margin`` and ``sag`` over these
+    drone types whose segments are cut into pieces of ``piece`` metres: :func:`sweep_reach`, the same pieces under the name the
+    query's callers look for.  A segment of up to 32 pieces is served, so ``piece`` decides speed and the longest segment."""
+    return sweep_reach(types, margin, sag, piece)
+
+
 def sweep_sag(a_max: float, T: float) -> float:
     """a_max T^2 / 8: how far a path whose acceleration never exceeds ``a_max`` [m/s^2] can leave the chord between its positions
     a time ``T`` [s] apart (x(t) minus the chord vanishes at both ends and has a second derivative bounded by a_max: the

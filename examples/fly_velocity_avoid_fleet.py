@@ -21,8 +21,13 @@ returns, not the flight: the vehicle follows a velocity command with a lag, whic
 clamped at 1 after the filter, which can undo a row.  A drone whose goal points straight into a bar stops in front of it (the
 projection has nowhere to slide), and obstacle_contacts() counts drone x steps, so a drone that stands close counts for long: no
 figure is promised for it.
+With --plan B (2..32) one more flight plans before it steps: every control step each drone forms B candidate velocities — the goal
+direction and B - 1 yawed or pitched about it —, asks env.corridor_clearance (corridor=dict(k=B, ...): dsim_corridor_clearance,
+its bounding sphere swept along v_c x --horizon against the gates where they stand and the ground) and takes the candidate nearest
+the goal direction whose corridor is free, or, where none is, the one with the largest clearance.  With --filter the chosen
+velocity goes through the velocity filter.  The corridor is a straight one over a short horizon: no figure is promised for it.
 
-    python examples/fly_velocity_avoid_fleet.py --num_drones 4096 --duration_sec 6 [--moving [--lead]] [--witnesses 3] [--filter]
+    python examples/fly_velocity_avoid_fleet.py --num_drones 4096 --duration_sec 6 [--moving [--lead]] [--witnesses 3] [--filter] [--plan 9]
 """
 import argparse
 import os
@@ -56,8 +61,61 @@ def lead_term(vel, clearance, margin):
     return weight * vel
 
 
-def fly(A, avoid: bool, lead: bool = False, filtered: bool = False):
-    n, AGGR, FREQ, K, G = A.num_drones, 5, 240, 64, 6
+def candidates(B, spread):
+    """[B, 3] unit directions about +x, nearest the goal direction first: +x itself, then pairs yawed and pitched by growing
+    angles up to ``spread`` [rad]."""
+    out = [np.array([1.0, 0.0, 0.0])]
+    rings = max((B - 1 + 3) // 4, 1)
+    for j in range(B - 1):
+        ang = spread * (j // 4 + 1) / rings
+        c, sn = np.cos(ang), np.sin(ang) * (1.0 if j % 2 == 0 else -1.0)
+        out.append(np.array([c, sn, 0.0]) if (j // 2) % 2 == 0 else np.array([c, 0.0, sn]))
+    return np.stack(out)
+
+
+def fly_planned(A, filtered: bool):
+    """The planned flight: corridor_clearance on a fan of candidate velocities, then a step (through the filter with --filter)."""
+    n, AGGR, FREQ, K, B = A.num_drones, 5, 240, 64, A.plan
+    scenes, moving, off, xyz = world(A)
+    if filtered:
+        moving.update(velocity_filter=dict(alpha=A.alpha, buffer_obstacle=A.buffer, floor=0.0))
+    env = VelocityAviary([A.drone], n, initial_xyzs=xyz, aggregate_phy_steps=AGGR, freq=FREQ, dict_io=False, obstacle_watch=scenes,
+                         obstacle_scene_id=np.arange(n) % K, obstacle_offsets=off, obstacle_margin=A.margin,
+                         obstacle_witness="world" if filtered else None, obstacle_witness_velocity=filtered and A.moving,
+                         obstacle_witnesses=(A.witnesses or 3) if filtered else 0,
+                         corridor=dict(k=B, piece=0.5, sag=A.buffer, ground=True), **moving)
+    dev = env.ctx.device
+    limit = float(env.SPEED_LIMIT[0])
+    cand = torch.from_numpy(candidates(B, np.radians(A.spread)).astype(np.float32)).to(dev) * A.speed      # [B, 3] velocities
+    rel = (cand * A.horizon)[:, :, None].expand(B, 3, n).contiguous()
+    rank = torch.arange(B, device=dev)[:, None]
+    steps = int(A.duration_sec * FREQ / AGGR)
+    closest, blocked = float("inf"), 0
+    START = time.time()
+    for _ in range(steps):
+        c = env.corridor_clearance(rel).clearance                        # [B, N]
+        free = c > 0.0
+        first_free = torch.where(free, rank, B).min(0).values           # the candidate nearest the goal whose corridor is free
+        pick = torch.where(first_free < B, first_free, c.argmax(0))
+        blocked += int((first_free == B).sum().item())
+        wish = cand[pick].T                                              # [3, N]
+        if filtered:
+            env.step_velocity(wish)
+        else:
+            speed = wish.norm(dim=0)
+            env.step(torch.cat([wish / speed.clamp(min=1e-6), (speed / limit).clamp(max=1.0)[None, :]], 0).T.contiguous())
+        closest = min(closest, float(env.last_obstacle_clearance[0].min().item()))
+    contacts = env.obstacle_contacts()
+    print(f"planned on {B} corridors of {A.horizon:.2f} s{' through the velocity filter' if filtered else ''}{', swinging gates' if A.moving else ''}: "
+          f"{n} drones x {steps} env steps in {time.time() - START:.2f} s wall; obstacle_contacts() = {contacts} drone x steps, "
+          f"least clearance {closest:.3f} m; {blocked} drone x steps with no free corridor, corridor_unserved() = {env.corridor_unserved()}")
+    env.close()
+    return contacts
+
+
+def world(A):
+    """(scenes, the motion keywords, offsets, initial positions) of every flight."""
+    n, K, G = A.num_drones, 64, 6
     rng = np.random.default_rng(0)
     gate = ObstacleSet.from_urdf(GATE, (0, 0, 0), (0, 0, 0))
     # G gates per scene, strung along the course with a sideways scatter and any yaw: some stand in the way
@@ -75,6 +133,12 @@ def fly(A, avoid: bool, lead: bool = False, filtered: bool = False):
     side = int(np.ceil(np.sqrt(n)))
     off = np.stack([(np.arange(n) % side) * 40.0, (np.arange(n) // side) * 40.0, np.zeros(n)], 1)      # a frame per drone
     xyz = off + np.array([0.0, 0.0, 2.0]) + rng.uniform(-0.5, 0.5, (n, 3))
+    return scenes, moving, off, xyz
+
+
+def fly(A, avoid: bool, lead: bool = False, filtered: bool = False):
+    n, AGGR, FREQ, K = A.num_drones, 5, 240, 64
+    scenes, moving, off, xyz = world(A)
     if filtered:
         # the filter's rows come from the witnesses record (and its velocities on moving gates); the floor is the plane z = 0
         moving.update(velocity_filter=dict(alpha=A.alpha, buffer_obstacle=A.buffer, floor=0.0))
@@ -152,13 +216,21 @@ def main(argv=None):
                                                           "(velocity_filter=dict(alpha=...), env.step_velocity)")
     ap.add_argument("--alpha", type=float, default=1.5, help="with --filter: the barrier's rate [1/s]")
     ap.add_argument("--buffer", type=float, default=0.2, help="with --filter: metres kept between the bounding sphere and the gates; it "
-                                                              "has to cover the lag with which the vehicle follows a velocity")
+                                                              "has to cover the lag with which the vehicle follows a velocity "
+                                                              "(with --plan: the corridor's sag)")
+    ap.add_argument("--plan", type=int, default=0, help="one more flight that picks among B candidate velocities by their corridor "
+                                                        "clearance (corridor=dict(k=B, ...), env.corridor_clearance); 0: none")
+    ap.add_argument("--horizon", type=float, default=0.75, help="with --plan: the corridor of a candidate is v x horizon [s] long")
+    ap.add_argument("--spread", type=float, default=60.0, help="with --plan: the widest yaw or pitch of a candidate [deg]")
     A = ap.parse_args(argv)
     if A.lead and not A.moving:
         ap.error("--lead needs --moving: a static world's points stand still")
+    if A.plan and not 2 <= A.plan <= 32:
+        ap.error("--plan takes 2 .. 32 candidates")
     out = fly(A, False), fly(A, True)
     out = out + (fly(A, True, True),) if A.lead else out
-    return out + (fly(A, False, filtered=True),) if A.filter else out
+    out = out + (fly(A, False, filtered=True),) if A.filter else out
+    return out + (fly_planned(A, A.filter),) if A.plan else out
 
 
 if __name__ == "__main__":

@@ -60,7 +60,8 @@ extern "C" {
                               witness on moving scenes, dsim_scenes_move_twist, dsim_obstacle_witness_scenes_vel; obstacle witnesses,
                               dsim_obstacle_witnesses, dsim_obstacle_witnesses_scenes, dsim_witnesses_args, DSIM_WITNESSES_MAX; the
                               velocity safety filter, dsim_velocity_filter, dsim_filter_args, DSIM_FILTER_*; line of sight
-                              among the drones, dsim_line_of_sight_drones */
+                              among the drones, dsim_line_of_sight_drones; corridor clearance, dsim_corridor_clearance,
+                              dsim_corridor_args, DSIM_CORRIDOR_GROUND */
 #define DSIM_MAX_ACT 6     /* actuators per vehicle (quad 4, morphing hexa 6) */
 #define DSIM_MAX_TYPES 8
 
@@ -1431,6 +1432,57 @@ int dsim_line_of_sight(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, 
  * DSIM_E_UNSUPPORTED).  dsim_sight_args and dsim_line_of_sight are unchanged. */
 int dsim_line_of_sight_drones(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, const dsim_obstacles* set,
                               const dsim_sight_args* args, const uint8_t* type_id, const dsim_camera_drones* drones);
+
+/* Corridor clearance: is the way there free for a vehicle of my size?  Line of sight casts a segment of zero thickness and the
+ * swept watch serves one fixed chord; a local planner asks, for k candidate segments per drone, the clearance of the drone's
+ * bounding sphere swept along each.  For every drone i < n and slot t < k:
+ *     e  = p_i - offset_i                       (formed in float32, as the watches form it)
+ *     d  = rel[t][:][i]                         (world axes, the layout of dsim_knn's rel_pos_out: used as given)
+ *     Rs = collision_sphere of its type + sag   (sag >= 0; a type with R = 0 still asks, with the radius sag)
+ *     c  = min over the world of dist(segment e -> e + d, .) - Rs
+ * The world is the watches': both faces of every triangle of `set`; with `scenes`, every placement of scene scene_id[i] where the
+ * table stands at this launch (a table dsim_scenes_move rewrites is seen as it is now), both ends of the segment taken into the
+ * placement's frame, the subtraction first (an id outside [0, K): no obstacles); with DSIM_CORRIDOR_GROUND the half-space z <= 0
+ * of the task frame, at the distance max(0, min(e.z, e.z + d.z)), as body DSIM_SEG_GROUND.
+ *     clearance_out[t][i] = min(margin, c)
+ *     body_out[t][i]      = the BODY that attains the minimum (instance-major g n_bodies + body on scenes), -1 when c >= margin.
+ *                           Nullable.  Strict <: the ground first, then the placements in slot order, then the lists' order.
+ * Both are slot-major [k][n_pad] (device, storage order), written with plain vector stores; lanes i >= n are not written.
+ *
+ * A slot is NOT EVALUATED when `index` is given and index[t][i] < 0, or when a component of e or d is not finite: it reads
+ * clearance = -inf, body = -1 (a slot nobody looked at is never free, as line of sight reads visible = 0 for a slot it did not
+ * cast).  A zero d is a valid segment: the point query at the radius Rs.
+ *
+ * The pieces are dsim_obstacle_sweep's: half = reach - (R_max + sag + margin), K = ceil(|d| / (2 half (1 - 2^-10))), each piece
+ * looked up in the cell of its own midpoint, a piece whose midpoint lies outside the grown box reading no list; what a lane
+ * stages and walks follows from the segment's bounding box (per placement: from the distance of its cull sphere to the segment),
+ * not from its ends.  A slot with K > 32 (or a length float32 does not hold) is UNSERVED: it reads -inf, -1 and adds one to
+ * *unserved_out (a device counter, nullable; one atomic per wave and tile at most).  The longest segment served is
+ * 64 half (1 - 2^-10).  With the ground alone every finite segment is one piece.
+ *
+ * A query, not a watch: DSIM_Q_OBSTACLE_CONTACTS is not touched.  Stream-ordered, allocates nothing, never synchronises; may be
+ * captured.  DSIM_E_ARG, nothing enqueued: a null ctx, args, rel or clearance_out; n <= 0 or n > n_pad; k outside 1 .. 32; an
+ * unknown flag; margin <= 0, sag < 0, either not finite; several types and no type_id; scenes without scene_id or the reverse;
+ * scenes together with a non-NULL set; no world at all (no set, no scenes, no ground flag); half < reach / 1024 (make the set
+ * with reach >= R_max + sag + margin + half the length one lookup should serve). */
+enum { DSIM_CORRIDOR_GROUND = 1u << 0 };  /* the half-space z <= 0 of the task frame counts too, body DSIM_SEG_GROUND */
+typedef struct dsim_corridor_args {
+  const float*   rel;           /* device [k][3][n_pad]: the segment of slot t of drone i is e_i -> e_i + rel[t][:][i]  */
+  const int32_t* index;         /* device [k][n_pad] or NULL: a slot with index < 0 is not evaluated                      */
+  int32_t        k;             /* 1 .. 32                                                                                 */
+  uint32_t       flags;         /* DSIM_CORRIDOR_GROUND (unknown bits: DSIM_E_ARG)                                         */
+  const float*   offset;        /* SoA [3][n_pad] or NULL: e_i = p_i - offset_i, as the watches                            */
+  const uint8_t* type_id;       /* [n_pad]; required with more than one type                                               */
+  const dsim_scenes* scenes;    /* nullable: the placed world; then `set` must be NULL (the prototype is its)              */
+  const int32_t* scene_id;      /* [n_pad] storage order; with `scenes`, and only with it                                  */
+  float          margin;        /* > 0                                                                                     */
+  float          sag;           /* >= 0 [m]: added to every radius                                                         */
+  float*         clearance_out; /* [k][n_pad], required                                                                    */
+  int32_t*       body_out;      /* [k][n_pad] or NULL                                                                      */
+  uint64_t*      unserved_out;  /* device counter, nullable                                                                */
+} dsim_corridor_args;
+int dsim_corridor_clearance(dsim_ctx* ctx, void* stream, int64_t n, dsim_view state, const dsim_obstacles* set,
+                            const dsim_corridor_args* args);
 
 /* Gate passage watch: which drones flew THROUGH the gates of their scene, in order.  The clearance watches say how close a
  * vehicle came to a gate's frame; a drone that flies round its gate, goes through backwards or never reaches it has a perfect
