@@ -135,3 +135,251 @@ def test_nothing_on_nothing_launched():
     assert log == ["dsim_step"] * len(CALLS)
     assert (e.step_counter, e._env_steps) == (STEP_COUNTER[-1], ENV_STEPS[-1])
     assert e.last_obstacle_clearance is None
+
+
+# ---- every service on one env: the order behind a launch, the captured step, and what reads None when -----------------------------------
+# The rule of StepWatches._stepped's docstring and of the obstacle_motion= comment ("every launch first advances the clock, then one
+# dsim_scenes_move ..., then the watches run"), the neighbour query with its line of sight on the record it just wrote, the camera when
+# due, the scan, the gates (whose clock moves on after their query).  Written from that rule:
+CLOCK, MOVE, DRONES, KNN, SIGHT, OBST, CAMERA, SCAN, GATES = ("dsim_counter_add", "move", "clearance", "knn", "sight",
+                                                               "dsim_obstacle_clearance", "camera", "scan", "dsim_gate_passage")
+LAUNCH = [CLOCK, MOVE, DRONES, KNN, SIGHT, OBST, CAMERA, SCAN, GATES, CLOCK]        # (the last: the gates' own query clock)
+CAPTURED = [x for x in LAUNCH if x not in (DRONES, KNN, SIGHT)]                    # what a graph cannot hold is refused before it
+
+
+class _World:
+    """The obstacle watch's device scenes: only the move is recorded (the queries go through the library)."""
+    handle, G = None, 3
+
+    def __init__(self, log):
+        self._log = log
+
+    def move(self, clock, dt):
+        self._log.append(MOVE)
+
+
+class _Knn:
+    def __init__(self, log):
+        self._log = log
+
+    def nearest(self, radius, k, out=None, rel_vel=True):
+        self._log.append(KNN)
+        return out
+
+
+class _Sight:
+    drones = True
+
+    def __init__(self, log):
+        self._log = log
+
+    def query(self, rel, index):
+        from dronesim_amd.sight import Sight
+        self._log.append(SIGHT)
+        return Sight(None, None, None)
+
+
+class _Scanner:
+    drones = True
+    ranges, hits = torch.zeros((4, N)), torch.zeros((4, N), dtype=torch.int32)
+
+    def __init__(self, log):
+        self._log = log
+
+    def scan(self):
+        self._log.append(SCAN)
+
+
+def _full_env(uncapturable=True):
+    from dronesim_amd.downwash import Neighbors
+    from dronesim_amd.obstacles import Aperture
+    e, tg, log = _env(obstacles=True, camera=True, drone_watch=uncapturable)
+    n_pad = e.state.n_pad
+    e._obst, e._scene_clock = _World(log), torch.zeros((1,), dtype=torch.int64)
+    e.SIM_FREQ = 240
+    if uncapturable:
+        e._knn_k, e._knn_radius, e._knn_vel, e._knn = 4, 1.5, True, _Knn(log)
+        e._knn_out = Neighbors(torch.zeros((4, n_pad), dtype=torch.int32), None, torch.zeros((4, 3, n_pad)), None, None)
+        e._sight, e._sight_on = _Sight(log), True
+    e._scan, e._scan_sampled, e._gate_sampled = _Scanner(log), False, False
+    i32 = lambda: torch.zeros((n_pad,), dtype=torch.int32)
+    e._gate, e._gate_ids, e._gate_off = e._obst, i32(), None
+    e._gate_ap = Aperture((0, 0, 0), (1, 0, 0), (0, 1, 0), (0.3, 0.2))
+    e._gate_travel, e._gate_wrap, e._gate_start = 0.2, False, 0
+    e._gate_prev, e._gate_due, e._gate_lap = torch.zeros((3, n_pad)), i32(), i32()
+    e._gate_time = torch.zeros((3, n_pad), dtype=torch.float64)
+    e._gate_fwd, e._gate_back, e._gate_miss = i32(), i32(), i32()
+    e._gate_clock, e._gate_counts = torch.zeros((1,), dtype=torch.int64), torch.zeros((5,), dtype=torch.int64)
+    return e, tg, log
+
+
+def _records(e):
+    return dict(clearance=e.last_clearance, neighbors=e.last_neighbors, sight=e.last_neighbor_sight, obstacle=e.last_obstacle_clearance,
+                ranges=e.ranges, hits=e.range_hits, gates=e.last_gate_events)
+
+
+def test_every_service_on_the_order_behind_a_launch():
+    e, tg, log = _full_env()
+    assert all(v is None for v in _records(e).values()), _records(e)                # a fresh env: nothing seen yet
+    for n, capture in zip(CALLS, CAPTURE):
+        del log[:]
+        e.step_fused(tg, n_steps=n)
+        assert log == ["dsim_step"] + [x for x in LAUNCH if capture or x != CAMERA], (n, log)
+        assert all(v is not None for v in _records(e).values())
+    assert e._filter_fresh
+
+
+def test_reset_starts_the_world_and_the_gates_again():
+    """What reset() does behind placing the drones: the world back at scene time 0 and the gates' chords primed, the gate watch's
+    record gone and the filter's records stale.  (The other last_* keep describing the flight before the reset: finding 2 of
+    tests/README_env_watches.md, not settled here.)"""
+    e, tg, log = _full_env()
+    e.step_fused(tg)
+    e.step_fused(tg)
+    del log[:]
+    e._watch_placed()                                          # (what _housekeeping calls once the drones stand where they start)
+    assert log == [MOVE, "dsim_gate_passage"]
+    assert e.last_gate_events is None and not e._filter_fresh and int(e._scene_clock.item()) == 0 and int(e._gate_clock.item()) == 0
+    e.step_fused(tg)
+    assert all(v is not None for v in _records(e).values()) and e._filter_fresh
+
+
+def test_captured_step_is_the_launch_without_what_cannot_be_captured():
+    e, tg, log = _full_env(uncapturable=False)
+    e._captured_step()
+    assert log == CAPTURED, log
+
+
+def test_capture_refuses_the_two_services_that_measure_on_the_host():
+    import pytest
+    for word, kw in (("drone_watch", dict(_drone_watch=True)), ("neighbor_obs", dict(_knn_k=4))):
+        e, tg, log = _full_env(uncapturable=False)
+        for k, v in kw.items():
+            setattr(e, k, v)
+        with pytest.raises(NotImplementedError, match=word):
+            e._capture_prepare()
+
+
+# ---- the refusals _watch_options documents ------------------------------------------------------------------------------------------------
+def _options(**kw):
+    """StepWatches._watch_options with CtrlAviary's defaults and ``kw`` over them, on an env that is nothing else."""
+    from dronesim_amd.envs import CtrlAviary
+    base = dict(num_drones=8, freq=240, aggregate_phy_steps=5, dist=None, drone_watch=False, drone_watch_margin=1.0, obstacle_watch=None,
+                obstacle_margin=1.0, obstacle_sweep=False, obstacle_sweep_sag=0.0, obstacle_sweep_travel=None, vision_attributes=False,
+                vision_scene=None, vision_drones=None, vision_res=(64, 48), vision_ground=True, vision_see_drones=False,
+                vision_drone_range=None)
+    base.update(kw)
+    e = CtrlAviary.__new__(CtrlAviary)
+    e._watch_options(**base)
+    return e
+
+
+def _worlds():
+    from tests import motion_ref as mr
+    from tests import scenes_ref as sr
+    motion = mr.small_motions()[0]
+    scenes = motion.scenes
+    return sr.gate(), scenes, motion, np.zeros(8, dtype=np.int64)
+
+
+def _refusals():
+    from dronesim_amd.obstacles import Aperture
+    from dronesim_amd.scanner import RangeScanner
+    gate, scenes, motion, ids = _worlds()
+    ap = Aperture((0, 0, 0), (1, 0, 0), (0, 1, 0), (0.3, 0.2))
+    placed = dict(obstacle_watch=scenes, obstacle_scene_id=ids)
+    filt = dict(alpha=2.0)
+    NI, VE = NotImplementedError, ValueError
+    return [
+        # the pairs that are not implemented
+        ("sweep with scenes", NI, "swept watch on scenes", dict(placed, obstacle_sweep=True)),
+        ("witness with sweep", NI, "another quantity", dict(obstacle_watch=gate, obstacle_sweep=True, obstacle_witness="world")),
+        ("see-drones with scenes", NI, "placed images", dict(placed, vision_attributes=True, vision_see_drones=True)),
+        ("see-drones with a vision_scene of scenes", NI, "placed images",
+         dict(vision_scene=scenes, obstacle_scene_id=ids, vision_attributes=True, vision_see_drones=True)),
+        ("gates on moved scenes", NI, "moving opening", dict(placed, obstacle_motion=motion, gate_watch=ap)),
+        ("gates on moved scenes, named", NI, "moving opening", dict(placed, obstacle_motion=motion, gate_watch=ap, gate_scenes=scenes)),
+        # the filter
+        ("filter with body", VE, "world axes", dict(obstacle_watch=gate, obstacle_witness="body", obstacle_witnesses=2, velocity_filter=filt)),
+        ("filter without a source", VE, "source of rows", dict(velocity_filter=filt)),
+        ("filter without relative velocities", VE, "leaves them out", dict(neighbor_obs=4, neighbor_radius=1.0, neighbor_vel=False,
+                                                                         velocity_filter=filt)),
+        ("filter without alpha", VE, "velocity_filter takes a dict", dict(neighbor_obs=4, neighbor_radius=1.0, velocity_filter=dict(share=0.5))),
+        # the corridor
+        ("corridor without a world", VE, "without obstacle_watch", dict(corridor=dict(k=4, piece=0.5))),
+        ("corridor without piece", VE, "corridor takes a dict", dict(obstacle_watch=gate, corridor=dict(k=4))),
+        # X without Y
+        ("drone_sweep without drone_watch", VE, "without drone_watch", dict(drone_sweep=True)),
+        ("drone_sweep_sag without drone_watch", VE, "without drone_watch", dict(drone_sweep_sag=0.01)),
+        ("drone_sweep_sag without drone_sweep", VE, "without drone_sweep", dict(drone_watch=True, drone_sweep_sag=0.01)),
+        ("drone_sweep_travel without drone_sweep", VE, "without drone_sweep", dict(drone_watch=True, drone_sweep_travel=0.5)),
+        ("neighbor_radius without neighbor_obs", VE, "without neighbor_obs", dict(neighbor_radius=1.0)),
+        ("neighbor_vel without neighbor_obs", VE, "without neighbor_obs", dict(neighbor_vel=True)),
+        ("neighbor_obs without a radius", VE, "must be finite and positive", dict(neighbor_obs=4)),
+        ("neighbor_sight without neighbor_obs", VE, "without neighbor_obs", dict(neighbor_sight=True)),
+        ("neighbor_sight_scene without neighbor_sight", VE, "without neighbor_sight", dict(neighbor_sight_scene=gate)),
+        ("neighbor_sight_drones without neighbor_sight", VE, "without neighbor_sight", dict(neighbor_sight_drones=True)),
+        ("neighbor_sight_drone_box without neighbor_sight", VE, "without neighbor_sight", dict(neighbor_sight_drone_box=(0, 0, 1, 1))),
+        ("neighbor_sight_drone_box without neighbor_sight_drones", VE, "without neighbor_sight_drones",
+         dict(obstacle_watch=gate, neighbor_obs=4, neighbor_radius=1.0, neighbor_sight=True, neighbor_sight_drone_box=(0, 0, 1, 1))),
+        ("neighbor_sight without a world", VE, "needs a world", dict(neighbor_obs=4, neighbor_radius=1.0, neighbor_sight=True)),
+        ("gate_scenes without gate_watch", VE, "without gate_watch", dict(gate_scenes=scenes, obstacle_scene_id=ids)),
+        ("gate_start without gate_watch", VE, "without gate_watch", dict(gate_start=1)),
+        ("gate_laps without gate_watch", VE, "without gate_watch", dict(gate_laps=True)),
+        ("gate_travel without gate_watch", VE, "without gate_watch", dict(gate_travel=1.0)),
+        ("gate_watch without placements", VE, "needs the gates' placements", dict(obstacle_watch=gate, gate_watch=ap)),
+        ("scenes without obstacle_scene_id", VE, "is required with an ObstacleScenes", dict(obstacle_watch=scenes)),
+        ("obstacle_scene_id without scenes", VE, "without an ObstacleScenes", dict(obstacle_watch=gate, obstacle_scene_id=ids)),
+        ("obstacle_motion without its scenes", VE, "must be made for", dict(obstacle_motion=motion)),
+        ("obstacle_motion beside a set", VE, "must be made for", dict(obstacle_watch=gate, obstacle_motion=motion)),
+        ("obstacle_sweep without obstacle_watch", VE, "without obstacle_watch", dict(obstacle_sweep=True)),
+        ("obstacle_sweep_sag without obstacle_sweep", VE, "without obstacle_sweep", dict(obstacle_watch=gate, obstacle_sweep_sag=0.01)),
+        ("obstacle_sweep_travel without obstacle_sweep", VE, "without obstacle_sweep", dict(obstacle_watch=gate, obstacle_sweep_travel=0.5)),
+        ("obstacle_witness without obstacle_watch", VE, "without obstacle_watch", dict(obstacle_witness="world")),
+        ("obstacle_witness_velocity without obstacle_witness", VE, "without obstacle_witness",
+         dict(placed, obstacle_motion=motion, obstacle_witness_velocity=True)),
+        ("obstacle_witness_velocity without obstacle_motion", VE, "without obstacle_motion",
+         dict(placed, obstacle_witness="world", obstacle_witness_velocity=True)),
+        ("obstacle_witnesses without obstacle_witness", VE, "without obstacle_witness", dict(obstacle_watch=gate, obstacle_witnesses=2)),
+        ("vision_see_drones without vision_attributes", VE, "without vision_attributes", dict(vision_see_drones=True)),
+        ("vision_drone_range without vision_attributes", VE, "without vision_attributes", dict(vision_drone_range=2.0)),
+        ("vision_drone_range without vision_see_drones", VE, "without vision_see_drones",
+         dict(obstacle_watch=gate, vision_attributes=True, vision_drone_range=2.0)),
+        ("vision_scene without vision_attributes", VE, "without vision_attributes", dict(vision_scene=gate)),
+        ("vision_drones without vision_attributes", VE, "without vision_attributes", dict(vision_drones=[0])),
+        ("vision_attributes without a world", VE, "needs a world", dict(vision_attributes=True)),
+        ("range_scene without range_scan", VE, "without range_scan", dict(range_scene=gate)),
+        ("range_see_drones without range_scan", VE, "without range_scan", dict(range_see_drones=True)),
+        ("range_max without range_scan", VE, "without range_scan", dict(range_max=5.0)),
+        ("range_drone_range without range_see_drones", VE, "without range_see_drones",
+         dict(range_scan=RangeScanner.fan(4), range_drone_range=2.0)),
+        ("range_scan without a world", VE, "needs a world", dict(range_scan=RangeScanner.fan(4), range_ground=False)),
+    ]
+
+
+def test_every_documented_refusal_refuses():
+    import pytest
+    cases = _refusals()
+    assert len({c[0] for c in cases}) == len(cases) >= 50
+    for what, exc, word, kw in cases:
+        with pytest.raises(exc, match=word):
+            _options(**kw)
+
+
+def test_what_is_not_refused_is_taken():
+    """The negative control of the list above: each refused pair, with the offending keyword taken out or its partner put in, passes."""
+    from dronesim_amd.obstacles import Aperture
+    from dronesim_amd.scanner import RangeScanner
+    gate, scenes, motion, ids = _worlds()
+    ap = Aperture((0, 0, 0), (1, 0, 0), (0, 1, 0), (0.3, 0.2))
+    placed = dict(obstacle_watch=scenes, obstacle_scene_id=ids)
+    e = _options(**placed, obstacle_motion=motion, obstacle_witness="world", obstacle_witness_velocity=True, obstacle_witnesses=3,
+                 drone_watch=True, neighbor_obs=6, neighbor_radius=1.5, neighbor_sight=True, neighbor_sight_drones=True,
+                 range_scan=RangeScanner.fan(4), range_see_drones=True, vision_attributes=True, vision_res=(16, 12), gate_watch=ap,
+                 gate_scenes=motion.snapshot(0.0), velocity_filter=dict(alpha=2.0, floor=0.0), corridor=dict(k=4, piece=0.5))
+    assert e._obst_m == 3 and e._knn_k == 6 and e._sight_drones and e._corr_opts["piece"] == 0.5 and e._filter_opts["alpha"] == 2.0
+    e = _options(obstacle_watch=gate, obstacle_sweep=True, obstacle_sweep_sag=0.01, drone_watch=True, drone_sweep=True, drone_sweep_sag=0.01,
+                 vision_attributes=True, vision_see_drones=True, range_scan=RangeScanner.fan(4), range_see_drones=True, neighbor_obs=4,
+                 neighbor_radius=1.0, neighbor_sight=True, neighbor_sight_drones=True, corridor=dict(k=2, piece=0.25),
+                 velocity_filter=dict(alpha=1.0))
+    assert e._obst_sweep and e._drone_sweep and e._filter_opts is not None
